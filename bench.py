@@ -20,7 +20,12 @@ The tail of step k runs on worker threads (own HIP streams; one page-range work 
 step k+1.  Before the W warm-up steps the process runs `--spinup` untimed steps (board out of its low-power state, host
 buffers settled; `config.spinup_steps`); the timed region is exactly K steps between barriers + synchronisations.
 
-The same JSON line carries, from short sub-runs on rank 0 at N=1 (skipped with --no-extras; in this process, reusing the
+A plain run sets up, warms up, times the K steps and prints the line (`metric`, `value`, `unit`, `higher_is_better`, `dtype`,
+`ms_per_step`, `config`).  `--dump-outputs DIR` then also writes what the last timed step computed as DIR/<name>.npy (the
+inputs are seeded: the same arguments give the same pages and checkpoint in every run).
+
+With `--full` the line also carries `serial_step` (one un-pipelined step), `roofline` (profiled forwards; `--dump-ops`
+implies `--full`) and, from short sub-runs on rank 0 at N=1 (skipped with --no-extras; in this process, reusing the
 headline's native tails -- see `inproc_bench` -- except the mixed-size stream and the MIOpen baseline, which are children):
   parity_exact   the EXACT engine (fp32s: fp32 tensors, split-operand products; identical lines / blocks / refined mask
                  to the oracle) end to end at the same batch size -- the rate the parity claim refers to
@@ -30,11 +35,12 @@ headline's native tails -- see `inproc_bench` -- except the mixed-size stream an
   rocm_baseline  the reference's own torch network on this GPU through PyTorch-ROCm / MIOpen
   cpu_baseline   the oracle (CPU fp32 port of the reference forward + the oracle tail) on the host cores
 
-    python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 [--dump-outputs DIR]
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python bench.py --gpus 8            (re-executes itself under torch.distributed.run when WORLD_SIZE is unset)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P bench.py --gpus N ...
 
-Rank 0 prints ONE JSON line.  `roofline` is measured live with hipEvents around every op of the engine
+Rank 0 prints ONE JSON line.  `roofline` (--full) is measured live with hipEvents around every op of the engine
 (ctd_engine_profile, on the stream the kernels run on).
 """
 from __future__ import annotations
@@ -166,6 +172,7 @@ class Pipeline:
         # N > 1: the tail builds every page's gather record natively (dist.pack_results then only stacks them)
         self.records = (D.CAP_BLK, D.CAP_LINE) if self.gather else None
         self.gathered = None                                 # the last gathered record tensor (checked by the caller)
+        self.last = None                                     # the results of the latest batch handed back
         self.gathers = deque()                               # record gathers handed to the communication thread (futures)
         self.handles = deque()                               # ... in flight on the device (dist.GatherHandle), that thread's
         self.cpool = ThreadPoolExecutor(max_workers=1, thread_name_prefix="ctd-comm") if self.gather else None
@@ -207,6 +214,7 @@ class Pipeline:
             # ... and off the launching thread: ONE communication thread enqueues the collectives in step order (every rank in
             # the same order) and resolves them; this thread only hands the batch over
             self.gathers.append(self.cpool.submit(self._gather, res))
+        self.last = res                                      # the latest batch's results (--dump-outputs)
         self.tfin.append(time.perf_counter())
         self.stats["pages"] += len(res)
         self.stats["blocks"] += sum(len(r[2]) for r in res)
@@ -316,6 +324,76 @@ def timed(run, steps, warmup, spinup, world, dev, stats=None):
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         dt = float(t.item())
     return dt
+
+
+# =====================================================================================================================
+# --dump-outputs: what the timed path computed in its last step
+# =====================================================================================================================
+
+DUMP_LIMIT_BYTES = 64 << 20     # all arrays of one dump together
+DUMP_MASK_PAGES = 4             # pages whose masks are written: a fixed, seeded sample of the batch
+DUMP_SEED = 0
+BLOCK_COLUMNS = ("page", "block", "x1", "y1", "x2", "y2", "vertical", "language", "font_size", "angle", "vec_x", "vec_y",
+                 "norm", "weight", "merged", "n_lines")
+LINE_COLUMNS = ("page", "block", "line", "x0", "y0", "x1", "y1", "x2", "y2", "x3", "y3", "distance")
+
+
+def _num(v) -> float:
+    return float("nan") if v is None else float(v)
+
+
+def e2e_output_arrays(res, mask_budget: int = DUMP_LIMIT_BYTES * 3 // 4) -> dict:
+    """The arrays a caller of the end-to-end step receives for one batch (`res`: one (mask, mask_refined, blk_list) per
+    page), in float32 / float64: every block and every line of every page (columns BLOCK_COLUMNS / LINE_COLUMNS;
+    language as `textblock.LANGCLS2IDX`, -1 for any other string), and the two masks of DUMP_MASK_PAGES pages drawn with
+    a fixed seed (`mask_pages`), strided by whole pixels when even those would exceed `mask_budget` bytes."""
+    TB = importlib.import_module("comic-text-detector_amd.textblock")
+    n = len(res)
+    pick = np.sort(np.random.RandomState(DUMP_SEED).choice(n, min(DUMP_MASK_PAGES, n), replace=False))
+    has_refined = all(res[i][1] is not None for i in pick)
+    planes = len(pick) * (2 if has_refined else 1)
+    h, w = np.asarray(res[pick[0]][0]).shape
+    stride = 1
+    while planes * -(-h // stride) * -(-w // stride) * 4 > mask_budget:
+        stride += 1
+    out = {"mask_pages": pick.astype(np.float64), "mask_stride": np.array([stride], np.float64),
+           "mask": np.stack([np.asarray(res[i][0], np.float32)[::stride, ::stride] for i in pick])}
+    if has_refined:
+        out["mask_refined"] = np.stack([np.asarray(res[i][1], np.float32)[::stride, ::stride] for i in pick])
+    blocks, lines = [], []
+    for p, r in enumerate(res):
+        for b, blk in enumerate(r[2]):
+            vec = [None, None] if blk.vec is None else list(np.asarray(blk.vec, np.float64).ravel()[:2])
+            blocks.append([p, b, *blk.xyxy, _num(blk.vertical), TB.LANGCLS2IDX.get(blk.language, -1), _num(blk.font_size),
+                           _num(blk.angle), _num(vec[0]), _num(vec[1]), _num(blk.norm), _num(blk.weight), _num(blk.merged),
+                           len(blk.lines)])
+            dist = None if blk.distance is None else np.asarray(blk.distance, np.float64).ravel()
+            for j, ln in enumerate(blk.lines):
+                d = dist[j] if dist is not None and len(dist) == len(blk.lines) else None
+                lines.append([p, b, j, *np.asarray(ln, np.float64).ravel()[:8], _num(d)])
+    out["blocks"] = np.asarray(blocks, np.float64).reshape(-1, len(BLOCK_COLUMNS))
+    out["lines"] = np.asarray(lines, np.float64).reshape(-1, len(LINE_COLUMNS))
+    out["blocks_per_page"] = np.bincount(out["blocks"][:, 0].astype(np.int64), minlength=n).astype(np.float64)
+    return out
+
+
+def net_output_arrays(dets, counts) -> dict:
+    """`--mode net`: the step's GPU NMS output (detections padded per page, and the kept count of every page)."""
+    return {"dets": dets.float().cpu().numpy(), "counts": counts.cpu().numpy().astype(np.float64)}
+
+
+def write_outputs(out_dir: str, arrays: dict) -> dict:
+    """Writes every array as `out_dir/<name>.npy` (float32 or float64 only, DUMP_LIMIT_BYTES in all); returns
+    name -> shape."""
+    total = sum(a.nbytes for a in arrays.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError(f"--dump-outputs: {total} bytes exceed the {DUMP_LIMIT_BYTES}-byte limit")
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in arrays.items():
+        if a.dtype not in (np.float32, np.float64):
+            raise TypeError(f"--dump-outputs: {name} is {a.dtype}, not float32 / float64")
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return {name: list(a.shape) for name, a in arrays.items()}
 
 
 # =====================================================================================================================
@@ -569,10 +647,10 @@ def rocm_baseline_subprocess(args, timeout_s: float):
 
 
 def sub_bench(argv, steps: int, warmup: int = 3, spinup: int = 40, timeout: float = 150.0, whole: bool = False) -> dict:
-    """One configuration of this script in a child process (`--no-cpu-baseline --no-extras`): value / ms_per_step /
+    """One configuration of this script in a child process (`--full --no-cpu-baseline --no-extras`): value / ms_per_step /
     blocks and lines per page / network ms of its JSON line (`whole`: the line itself)."""
     cmd = [sys.executable, os.path.abspath(__file__), "--steps", str(steps), "--warmup", str(warmup), "--spinup", str(spinup),
-           "--no-cpu-baseline", "--no-extras"] + list(argv)
+           "--full", "--no-cpu-baseline", "--no-extras"] + list(argv)
     env = dict(os.environ)
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
@@ -634,12 +712,12 @@ def inproc_bench(pkg, D, DET, TL, base_args, dev, steps: int, warmup: int = 3, s
 # BASELINE configs[4]: mixed-size stream
 # =====================================================================================================================
 
-def mixed_stream(pkg, D, BK, det, rank, world, dev, steps, warmup, with_tail=True, n_per_gpu=512) -> dict:
+def mixed_stream(pkg, D, BK, det, rank, world, dev, steps, warmup, with_tail=True, n_per_gpu=512, full=True) -> dict:
     """A seeded stream of pages of three sizes, batched dynamically per size bucket under a fixed pixel budget, every
     bucket's forward captured ONCE into a hipGraph (largest bucket first, so the arena never moves; two instances per
     bucket so that a replay never overwrites outputs a tail is still reading) and replayed in steady state; the native
     tail of every batch (per-page metas) on worker threads under the next replays.  A step = one pass over this rank's
-    shard of the stream."""
+    shard of the stream.  `full`: also the roofline of the conv family (profiled forwards of their own)."""
     be = det.net
     sizes = (640, 1024, 1536)
     budget = 32 * 1024 * 1024                     # pixels per batch: 81 -> 64 @ 640, 32 @ 1024, 14 @ 1536
@@ -718,24 +796,31 @@ def mixed_stream(pkg, D, BK, det, rank, world, dev, steps, warmup, with_tail=Tru
                         g["busy"] = None
 
     dt = timed(run_steps, steps, warmup, 0, world, dev, stats)
-    # roofline: algorithmic bytes / flops of the conv family per step from the engine's plan of every bucket, over the
-    # family's hipEvent time in one profiled forward per bucket
-    fam_ms = fam_bytes = fam_flops = 0.0
-    count = {}
-    for key in batches:
-        count[key] = count.get(key, 0) + 1
-    for (s, n), c in count.items():
-        prof = be.profile(pool_pages[s][:n])
-        cls = prof["cls"]
-        fam = (cls == 1) | (cls == 2)
-        fam_ms += c * float(prof["ms"][fam].sum())
-        fam_bytes += c * float(prof["bytes"][fam].sum())
-        fam_flops += c * float(prof["flops"][fam].sum())
+    prec = det.precision
+    roof = None
+    if full:
+        # roofline: algorithmic bytes / flops of the conv family per step from the engine's plan of every bucket, over the
+        # family's hipEvent time in one profiled forward per bucket
+        fam_ms = fam_bytes = fam_flops = 0.0
+        count = {}
+        for key in batches:
+            count[key] = count.get(key, 0) + 1
+        for (s, n), c in count.items():
+            prof = be.profile(pool_pages[s][:n])
+            cls = prof["cls"]
+            fam = (cls == 1) | (cls == 2)
+            fam_ms += c * float(prof["ms"][fam].sum())
+            fam_bytes += c * float(prof["bytes"][fam].sum())
+            fam_flops += c * float(prof["flops"][fam].sum())
+        ach_gbs, ach_tf = fam_bytes / (fam_ms * 1e-3) / 1e9, fam_flops / (fam_ms * 1e-3) / 1e12
+        roof = {"bound": "hbm", "achieved": round(ach_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
+                "frac": round(ach_gbs / HBM_PEAK_GBS, 4), "kernel": FAMILY[prec],
+                "family_ms_per_step": round(fam_ms, 3), "alg_bytes_per_step": fam_bytes,
+                "alg_flops_per_step": fam_flops, "tflops": round(ach_tf, 1),
+                "mfma_frac": round(ach_tf / PEAK_TF[prec], 4), "traffic": None}
     if pool is not None:
         pool.shutdown(wait=True)
     mpix = float(sum(s * s * n for s, n in batches)) / 1e6
-    prec = det.precision
-    ach_gbs, ach_tf = fam_bytes / (fam_ms * 1e-3) / 1e9, fam_flops / (fam_ms * 1e-3) / 1e12
     return {"metric": "pages/sec, mixed-size stream (640/1024/1536), hipGraph steady state"
                       + (" + native tail" if with_tail else " + GPU NMS"),
             "value": round(n_stream * steps / dt, 2), "unit": "pages/s", "steps": steps, "warmup": warmup,
@@ -751,11 +836,7 @@ def mixed_stream(pkg, D, BK, det, rank, world, dev, steps, warmup, with_tail=Tru
                        "blocks_per_page": round(stats["blocks"] / max(stats["pages"], 1), 2) if with_tail else None,
                        "lines_per_page": round(stats["lines"] / max(stats["pages"], 1), 2) if with_tail else None},
             "plan_and_capture_ms": setup,
-            "roofline": {"bound": "hbm", "achieved": round(ach_gbs, 1), "peak": HBM_PEAK_GBS, "unit": "GB/s",
-                         "frac": round(ach_gbs / HBM_PEAK_GBS, 4), "kernel": FAMILY[prec],
-                         "family_ms_per_step": round(fam_ms, 3), "alg_bytes_per_step": fam_bytes,
-                         "alg_flops_per_step": fam_flops, "tflops": round(ach_tf, 1),
-                         "mfma_frac": round(ach_tf / PEAK_TF[prec], 4), "traffic": None}}
+            "roofline": roof}
 
 
 # =====================================================================================================================
@@ -902,12 +983,21 @@ def main() -> None:
                          "objects (the default, and what the headline times since round 5)")
     ap.add_argument("--spinup", type=int, default=int(os.environ.get("BENCH_SPINUP", "100")),
                     help="untimed steps before the warm-up steps (clock / host-side spin-up of a fresh process)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-extras", action="store_true", help="skip parity_exact / extra_configs / rocm_baseline sub-runs")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure and check everything else the line can carry: serial_step, "
+                         "roofline (profiled forwards), and at N = 1 cpu_baseline / parity (unless --no-cpu-baseline) and "
+                         "parity_exact / extra_configs / rocm_baseline (e2e, unless --no-extras).  Off: the run only sets up, "
+                         "warms up, times the steps and prints the line")
+    ap.add_argument("--dump-outputs", default="", metavar="DIR",
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (float32 / "
+                         "float64, 64 MB at most): e2e -- every block and line of the batch and the masks of a seeded sample "
+                         "of its pages; net -- the NMS detections and counts")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip cpu_baseline / parity")
+    ap.add_argument("--no-extras", action="store_true", help="--full: skip parity_exact / extra_configs / rocm_baseline sub-runs")
     ap.add_argument("--rocm-timeout", type=float, default=float(os.environ.get("BENCH_ROCM_TIMEOUT", "100")),
                     help="wall-clock limit of the rocm_baseline child process (s); 0 skips it")
     ap.add_argument("--rocm-budget", type=float, default=240.0, help="(rocm-baseline mode) stop starting new cases after this many s")
-    ap.add_argument("--dump-ops", default="", help="write the per-op profile table to this file")
+    ap.add_argument("--dump-ops", default="", help="write the per-op profile table to this file (implies --full)")
     ap.add_argument("--cu-split", type=int, default=0,
                     help="e2e experiment: confine the tails' streams to this many CUs (mask bits 0..T-1, the same share of every "
                          "XCD) and run the forwards on a stream masked to the REST of the chip (hipExtStreamCreateWithCUMask)")
@@ -920,6 +1010,10 @@ def main() -> None:
     ap.add_argument("--no-pin", action="store_true",
                     help="N > 1: do NOT bind the rank's threads to the CPUs of its GPU's NUMA node (affinity.py; A/B knob)")
     args = ap.parse_args()
+    if args.dump_ops:
+        args.full = True
+    if args.dump_outputs and args.mode not in ("e2e", "net"):
+        ap.error("--dump-outputs: modes e2e and net")
 
     if args.mode == "rocm-baseline":
         return rocm_baseline_main(args)
@@ -988,7 +1082,7 @@ def main() -> None:
         ckpt = blob_checkpoint(pkg, args)
         det = DET.TextDetector(ckpt, input_size=1024, device=dev, precision=args.precision)
         join()
-        out = mixed_stream(pkg, D, BK, det, rank, world, dev, args.steps, args.warmup, with_tail=True)
+        out = mixed_stream(pkg, D, BK, det, rank, world, dev, args.steps, args.warmup, with_tail=True, full=args.full)
         if rank == 0:
             out.update({"n_gpus": n_gpus, "higher_is_better": True, "scaling": "weak", "vs_baseline": None,
                         "data": "synthetic", "cpu_baseline": None})
@@ -1040,6 +1134,7 @@ def main() -> None:
         pipe.fixed_job = fj
 
     net_k = [0]
+    net_last = [None]
 
     def run_steps_net(n):
         for _ in range(n):
@@ -1047,6 +1142,7 @@ def main() -> None:
             net_k[0] += 1
             blks, _, _ = be.forward_u8(x)
             dets, counts = BK.nms(blks, 0.4, 0.35)
+            net_last[0] = (dets, counts)
             if world > 1:
                 D.gather_records(D.pack_records(dets, counts), total_pages, rank, world)
 
@@ -1057,6 +1153,10 @@ def main() -> None:
     # process is in the second state; `config.spinup_steps` records it and `--spinup 0` gives the cold number.
     dt = timed(run_steps, args.steps, args.warmup, args.spinup, world, dev, pipe.stats)
     stats = dict(pipe.stats)
+    dumped = None
+    if args.dump_outputs and rank == 0:
+        arrays = e2e_output_arrays(pipe.last) if e2e else net_output_arrays(*net_last[0])
+        dumped = write_outputs(args.dump_outputs, arrays)
     # intervals between the timed steps' result deliveries: a 20-step region is 0.2 s, one late batch (a noisy host) is 5 % of it
     tf = list(pipe.tfin)[-args.steps:] if e2e else []
     gaps = sorted((b - a) * 1e3 for a, b in zip(tf, tf[1:]))
@@ -1064,94 +1164,95 @@ def main() -> None:
                  "steady_pages_per_s": round(nloc * world * 1e3 / gaps[len(gaps) // 2], 1)} if len(gaps) >= 3 else None)
 
     if rank == 0:
-        # ---- one un-pipelined step: where a batch's time goes.  The tail runs on one of the pipeline's own worker threads
-        # (no extra native tail / stream for the measurement: see tail._Lease), the second of two runs on that thread (the
-        # first one sizes its 32-page buffers: the pipelined steps used page-range work items)
-        def serial_tail(job_):                               # twice on ONE worker thread: the first run sizes its tail's buffers
-            for _ in range(2):
-                t0_ = time.perf_counter()
-                det._tail(job_, 0, args.keep_undetected, lazy=True)
-                ms_ = (time.perf_counter() - t0_) * 1e3
-            return ms_, TL.thread_tail(dev).timings()
-        torch.cuda.synchronize()
-        ta = time.perf_counter()
-        job = pipe.forward_job(0)
-        torch.cuda.synchronize()
-        tb_ = time.perf_counter()
-        tail_ms, stages = pipe.pool.submit(serial_tail, job).result()
-        serial = {"forward_ms": round((tb_ - ta) * 1e3, 3), "tail_ms": round(tail_ms, 3),
-                  "tail_ms_per_page": round(tail_ms / nloc, 4), "tail_stages_ms": stages}
-        roof = roofline_block(be, batches[0], args.precision, B, S, args.dump_ops)
-        page0 = batches[0][0].cpu().numpy()
-        cpu = parity = exact = extra = rocm = None
-        solo = n_gpus == 1
-        if solo and not args.no_cpu_baseline:
-            cpu = cpu_baseline(pkg, ckpt, S, batches[0][:16].cpu().numpy(), canned_sample)
-            try:
-                parity = parity_block(pkg, ckpt, det, batches[0], 0, S)
-            except Exception as e:                      # never lose the bench line to the extra check
-                parity = {"error": repr(e)[:400]}
-        real = canned is None
-        if solo and e2e and not args.no_extras:
-            # Sub-runs IN THIS PROCESS (`inproc_bench`: fresh checkpoint / pages / detector / worker pool each; the native
-            # tails are leased from the pool before).  Round 3 ran them as child processes because a second pipeline in one
-            # process measured 12-18 % low; the cause -- a second set of tail streams at the highest priority sharing
-            # hardware queues with the first -- is gone.  Only the mixed-size stream and MIOpen are children.
+        serial = roof = cpu = parity = exact = extra = rocm = None
+        if args.full:                                       # everything but the headline: --full
+            # ---- one un-pipelined step: where a batch's time goes.  The tail runs on one of the pipeline's own worker threads
+            # (no extra native tail / stream for the measurement: see tail._Lease), the second of two runs on that thread (the
+            # first one sizes its 32-page buffers: the pipelined steps used page-range work items)
+            def serial_tail(job_):                               # twice on ONE worker thread: the first run sizes its tail's buffers
+                for _ in range(2):
+                    t0_ = time.perf_counter()
+                    det._tail(job_, 0, args.keep_undetected, lazy=True)
+                    ms_ = (time.perf_counter() - t0_) * 1e3
+                return ms_, TL.thread_tail(dev).timings()
             torch.cuda.synchronize()
-            pipe.close()                                     # the headline's workers end: their tails go to the next pools
-            TL.release_thread_tail()                         # ... and so does the one the parity leg used on this thread
-            sub = lambda steps_, **ov: inproc_bench(pkg, D, DET, TL, args, dev, steps_, **ov)      # noqa: E731
-            ex = "fp32s" if args.precision != "fp32s" else "fp32"
-            c = sub(40, precision=ex)
-            exact = dict(c, engine=ex, batch=B, workload="the headline's (same pages, checkpoint, pipeline), in this process",
-                         acceptance="lines / blocks / refined mask identical to the oracle on the acceptance pages "
-                                    "(tests/test_gpu_accept.py; `parity.engines` here)")
-            extra = {}
-            c = sub(40, precision="fp32", batch=8, tail_input="forward")
-            extra["fp32_bs8_e2e"] = dict(c, config="BASELINE configs[1]: bs=8 1024x1024, fp32 (f32-operand MFMA engine), end to end "
-                                                   "with the native tail")
-            c = sub_bench(["--mode", "mixed", "--precision", args.precision], 3, warmup=1, spinup=0, timeout=240, whole=True)
-            extra["mixed_e2e"] = c
-            if real and not args.dense_blocks:
-                c = sub(40, dense_blocks=True)
-                extra["dense_blocks_e2e"] = dict(c, config="the headline's pages and pipeline on synth.make_blob_checkpoint(0) WITHOUT "
-                                                           "sparse_det: every cell of one Detect anchor fires (random weights), NMS "
-                                                           "packs the page with boxes (65 blocks / 67 lines per page)")
-                c = sub(40, line_density="r3")
-                extra["r3_density_e2e"] = dict(c, config="round 3's headline pages (sparse_det without the line-density calibration: 16 "
-                                                         "blocks / 16 lines per page; round 3's driver line: 2586 pages/s)")
-                c = sub(40, lazy_blocks=True)
-                extra["lazy_blocklists_e2e"] = dict(c, config="the headline with the tail workers handing over lazily materialised "
-                                                              "BlockLists (`detect_stream(lazy=True)`: the native records, "
-                                                              "TextBlock objects built when a consumer looks at them) instead "
-                                                              "of the reference's return type, a list of TextBlock objects per "
-                                                              "page, which the headline builds (rounds 3-4 timed this variant "
-                                                              "as the headline)")
-                c = sub(40, refine_mode=1, keep_undetected=True)
-                extra["reference_cli_config_e2e"] = dict(c, config="the headline with the reference CLI's arguments (inference.py:35, "
-                                                                   "`model2annotations`): refine_mode = REFINEMASK_ANNOTATION, "
-                                                                   "keep_undetected_mask = True (refine_undetected_mask runs too)")
-                c = sub(40, host_input=True)
-                extra["host_input_e2e"] = dict(c, config="the headline with the pages starting in HOST memory (numpy arrays, as the "
-                                                         "reference's callers hand them over): PCIe-inclusive, never the headline")
-            if real:
-                c = sub(40, tail_input="canned")
-                extra["canned_tail_inputs_e2e"] = dict(c, config="round 2's workload (`--tail-input canned`): random checkpoint, ONE "
-                                                                 "resident batch, the tail fed text-like maps of the same pages "
-                                                                 "instead of the forward's outputs (round 2 measured 2502 pages/s)")
-            if args.rocm_timeout > 0:
-                torch.cuda.synchronize()
-                rocm = rocm_baseline_subprocess(args, args.rocm_timeout)
+            ta = time.perf_counter()
+            job = pipe.forward_job(0)
+            torch.cuda.synchronize()
+            tb_ = time.perf_counter()
+            tail_ms, stages = pipe.pool.submit(serial_tail, job).result()
+            serial = {"forward_ms": round((tb_ - ta) * 1e3, 3), "tail_ms": round(tail_ms, 3),
+                      "tail_ms_per_page": round(tail_ms / nloc, 4), "tail_stages_ms": stages}
+            roof = roofline_block(be, batches[0], args.precision, B, S, args.dump_ops)
+            page0 = batches[0][0].cpu().numpy()
+            solo = n_gpus == 1
+            if solo and not args.no_cpu_baseline:
+                cpu = cpu_baseline(pkg, ckpt, S, batches[0][:16].cpu().numpy(), canned_sample)
                 try:
-                    rocm["hip_forward"] = {"engine": args.precision, "ms_per_forward": roof["net_ms_per_step"], "batch": B}
-                    if isinstance(exact, dict) and "net_ms_per_step" in exact:
-                        rocm["hip_forward_exact"] = {"engine": exact["engine"], "ms_per_forward": exact["net_ms_per_step"], "batch": B}
-                    for k, mine in (("fp16_bs32", roof["net_ms_per_step"]),
-                                    ("fp32_bs32", exact.get("net_ms_per_step") if isinstance(exact, dict) else None)):
-                        if mine and isinstance(rocm.get(k), dict) and "ms_per_forward" in rocm[k] and rocm[k].get("batch") == B:
-                            rocm[k]["hip_speedup"] = round(rocm[k]["ms_per_forward"] / mine, 2)
-                except Exception:
-                    pass
+                    parity = parity_block(pkg, ckpt, det, batches[0], 0, S)
+                except Exception as e:                      # never lose the bench line to the extra check
+                    parity = {"error": repr(e)[:400]}
+            real = canned is None
+            if solo and e2e and not args.no_extras:
+                # Sub-runs IN THIS PROCESS (`inproc_bench`: fresh checkpoint / pages / detector / worker pool each; the native
+                # tails are leased from the pool before).  Round 3 ran them as child processes because a second pipeline in one
+                # process measured 12-18 % low; the cause -- a second set of tail streams at the highest priority sharing
+                # hardware queues with the first -- is gone.  Only the mixed-size stream and MIOpen are children.
+                torch.cuda.synchronize()
+                pipe.close()                                     # the headline's workers end: their tails go to the next pools
+                TL.release_thread_tail()                         # ... and so does the one the parity leg used on this thread
+                sub = lambda steps_, **ov: inproc_bench(pkg, D, DET, TL, args, dev, steps_, **ov)      # noqa: E731
+                ex = "fp32s" if args.precision != "fp32s" else "fp32"
+                c = sub(40, precision=ex)
+                exact = dict(c, engine=ex, batch=B, workload="the headline's (same pages, checkpoint, pipeline), in this process",
+                             acceptance="lines / blocks / refined mask identical to the oracle on the acceptance pages "
+                                        "(tests/test_gpu_accept.py; `parity.engines` here)")
+                extra = {}
+                c = sub(40, precision="fp32", batch=8, tail_input="forward")
+                extra["fp32_bs8_e2e"] = dict(c, config="BASELINE configs[1]: bs=8 1024x1024, fp32 (f32-operand MFMA engine), end to end "
+                                                       "with the native tail")
+                c = sub_bench(["--mode", "mixed", "--precision", args.precision], 3, warmup=1, spinup=0, timeout=240, whole=True)
+                extra["mixed_e2e"] = c
+                if real and not args.dense_blocks:
+                    c = sub(40, dense_blocks=True)
+                    extra["dense_blocks_e2e"] = dict(c, config="the headline's pages and pipeline on synth.make_blob_checkpoint(0) WITHOUT "
+                                                               "sparse_det: every cell of one Detect anchor fires (random weights), NMS "
+                                                               "packs the page with boxes (65 blocks / 67 lines per page)")
+                    c = sub(40, line_density="r3")
+                    extra["r3_density_e2e"] = dict(c, config="round 3's headline pages (sparse_det without the line-density calibration: 16 "
+                                                             "blocks / 16 lines per page; round 3's driver line: 2586 pages/s)")
+                    c = sub(40, lazy_blocks=True)
+                    extra["lazy_blocklists_e2e"] = dict(c, config="the headline with the tail workers handing over lazily materialised "
+                                                                  "BlockLists (`detect_stream(lazy=True)`: the native records, "
+                                                                  "TextBlock objects built when a consumer looks at them) instead "
+                                                                  "of the reference's return type, a list of TextBlock objects per "
+                                                                  "page, which the headline builds (rounds 3-4 timed this variant "
+                                                                  "as the headline)")
+                    c = sub(40, refine_mode=1, keep_undetected=True)
+                    extra["reference_cli_config_e2e"] = dict(c, config="the headline with the reference CLI's arguments (inference.py:35, "
+                                                                       "`model2annotations`): refine_mode = REFINEMASK_ANNOTATION, "
+                                                                       "keep_undetected_mask = True (refine_undetected_mask runs too)")
+                    c = sub(40, host_input=True)
+                    extra["host_input_e2e"] = dict(c, config="the headline with the pages starting in HOST memory (numpy arrays, as the "
+                                                             "reference's callers hand them over): PCIe-inclusive, never the headline")
+                if real:
+                    c = sub(40, tail_input="canned")
+                    extra["canned_tail_inputs_e2e"] = dict(c, config="round 2's workload (`--tail-input canned`): random checkpoint, ONE "
+                                                                     "resident batch, the tail fed text-like maps of the same pages "
+                                                                     "instead of the forward's outputs (round 2 measured 2502 pages/s)")
+                if args.rocm_timeout > 0:
+                    torch.cuda.synchronize()
+                    rocm = rocm_baseline_subprocess(args, args.rocm_timeout)
+                    try:
+                        rocm["hip_forward"] = {"engine": args.precision, "ms_per_forward": roof["net_ms_per_step"], "batch": B}
+                        if isinstance(exact, dict) and "net_ms_per_step" in exact:
+                            rocm["hip_forward_exact"] = {"engine": exact["engine"], "ms_per_forward": exact["net_ms_per_step"], "batch": B}
+                        for k, mine in (("fp16_bs32", roof["net_ms_per_step"]),
+                                        ("fp32_bs32", exact.get("net_ms_per_step") if isinstance(exact, dict) else None)):
+                            if mine and isinstance(rocm.get(k), dict) and "ms_per_forward" in rocm[k] and rocm[k].get("batch") == B:
+                                rocm[k]["hip_speedup"] = round(rocm[k]["ms_per_forward"] / mine, 2)
+                    except Exception:
+                        pass
         where = "in HOST memory (H2D inside the timed region)" if (e2e and args.host_input) else "resident in HBM"
         real = canned is None
         workload = (f"BASELINE configs[2]: bs={B}/GPU {S}x{S} u8 pages {where}, {len(batches)} distinct batches rotated; "
@@ -1227,6 +1328,8 @@ def main() -> None:
             "extra_configs": extra,
             "rocm_baseline": rocm,
         }
+        if dumped is not None:
+            out["dumped_outputs"] = dumped
         print(json.dumps(out), flush=True)
     pipe.close()                                             # (idempotent)
     if dist.is_initialized():

@@ -2,7 +2,7 @@
 # A/B of an environment knob on the bench workload: bash scripts/bench_ab.sh VAR v1 v2 ...
 VAR=$1; shift
 for v in "$@"; do
-  env $VAR=$v timeout 250 python bench.py --steps 8 --warmup 3 --no-cpu-baseline 2>/dev/null > /tmp/ab.json
+  env $VAR=$v timeout 250 python bench.py --steps 8 --warmup 3 --full --no-cpu-baseline 2>/dev/null > /tmp/ab.json
   python - "$VAR=$v" <<'PY'
 import json, sys
 d = json.load(open("/tmp/ab.json"))

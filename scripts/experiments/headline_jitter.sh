@@ -9,7 +9,7 @@ mkdir -p "$O"
 thr() { awk '/nr_throttled/{n=$2} /throttled_usec/{u=$2} END{print n, u}' /sys/fs/cgroup/cpu.stat 2>/dev/null; }
 for i in $(seq 1 "$N"); do
   T0=$(thr)
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras "$@" > "$O/h$i.json" 2> "$O/h$i.err"
+  timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras "$@" > "$O/h$i.json" 2> "$O/h$i.err"
   python - "$O/h$i.json" <<'PY'
 import json, sys
 try:

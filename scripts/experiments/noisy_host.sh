@@ -11,7 +11,7 @@ for i in $(seq 1 "$L"); do ( while :; do :; done ) & PIDS="$PIDS $!"; done
 trap 'kill $PIDS 2>/dev/null' EXIT
 sleep 1
 one() {  # name, args
-  timeout 300 python bench.py --steps 20 --warmup 5 --no-cpu-baseline --no-extras $2 > "$O/$1.json" 2> "$O/$1.err"
+  timeout 300 python bench.py --steps 20 --warmup 5 --full --no-cpu-baseline --no-extras $2 > "$O/$1.json" 2> "$O/$1.err"
   python - "$O/$1.json" "$1" <<'PY'
 import json, sys
 try:

@@ -4,7 +4,7 @@
 export TMPDIR=/tmp
 O=${1:-gpurun_out/twlds_knobs}; mkdir -p "$O"
 run() {  # name tuning args
-  CTD_TUNING="$2" timeout 300 python bench.py --no-cpu-baseline --no-extras --steps ${STEPS:-60} --warmup 5 $3 > "$O/$1.json" 2> "$O/$1.err"
+  CTD_TUNING="$2" timeout 300 python bench.py --full --no-cpu-baseline --no-extras --steps ${STEPS:-60} --warmup 5 $3 > "$O/$1.json" 2> "$O/$1.err"
   python - "$O/$1.json" "$1" "$2" <<'PY'
 import json, sys
 try:

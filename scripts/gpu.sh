@@ -8,7 +8,7 @@
 #   suite[:<pytest -k expression>]      pytest -m gpu (the whole GPU suite, or a selection)
 #   smoke                               __graft_entry__.smoke()
 #   bench[:<name>[:<bench.py args>]]    the driver's line (--steps 20 --warmup 5) + per-op table; args are appended
-#   run:<name>:<bench.py args>          a sub-run line: bench.py --no-cpu-baseline --no-extras <args>; prints value / ms
+#   run:<name>:<bench.py args>          a sub-run line: bench.py --full --no-cpu-baseline --no-extras <args>; prints value / ms
 #   st:<name>:<batch>:<ENV=V,ENV=V>     ctd_selftest <batch> with the environment given (ST_CASES=..,ST_SPLIT=1,CTD_TUNING=a=1;b=2)
 #   prof:<name>:<bench.py args>         rocprofv3 --kernel-trace --stats of a sub-run (kernel stats CSV kept, trace dropped)
 #   trace:<name>:<bench.py args>        the same, keeping the kernel trace slimmed by scripts/timeline_summary.py
@@ -51,7 +51,7 @@ for STEP in "$@"; do
     smoke) timeout 400 python -c "import __graft_entry__ as g; g.smoke()" > "$O/smoke.txt" 2>&1; tail -3 "$O/smoke.txt" | cut -c1-300 ;;
     bench) N=${NAME:-bench_n1}; ( time timeout 1500 python bench.py --steps 20 --warmup 5 --dump-ops "$O/$N.per_op.tsv" $ARGS ) > "$O/$N.json" 2> "$O/$N.err"
            show "$O/$N.json"; tail -4 "$O/$N.err" | cut -c1-200 ;;
-    run)   timeout 600 python bench.py --no-cpu-baseline --no-extras $ARGS > "$O/$NAME.json" 2> "$O/$NAME.err"; show "$O/$NAME.json"; tail -2 "$O/$NAME.err" | cut -c1-200 ;;
+    run)   timeout 600 python bench.py --full --no-cpu-baseline --no-extras $ARGS > "$O/$NAME.json" 2> "$O/$NAME.err"; show "$O/$NAME.json"; tail -2 "$O/$NAME.err" | cut -c1-200 ;;
     st)    B=${ARGS%%:*}; ENVS=${ARGS#*:}; [ "$ENVS" = "$ARGS" ] && ENVS=""
            ( cd comic-text-detector_amd && env $(echo "$ENVS" | tr ',' ' ' | tr ';' ',') timeout 600 ./ctd_selftest "$B" ) > "$O/$NAME.txt" 2>&1; tail -${ST_TAIL:-25} "$O/$NAME.txt" | cut -c1-260 ;;
     prof|trace)

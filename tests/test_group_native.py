@@ -1,6 +1,6 @@
 """`ctd_group_output` (native host code, csrc/host_group.cpp; runs without a GPU) against the oracle's
-restatement of reference utils/textblock.py:421-508 -- and, in the build container, against the
-reference's own `group_output` -- on randomised pages: rotated / vertical / horizontal line quads in
+restatement of reference utils/textblock.py:421-508 -- and against the reference's own `group_output`
+(live where the reference tree is present, else its stored results: tests/refcode.py) -- on randomised pages: rotated / vertical / horizontal line quads in
 clusters, yolo blocks around some clusters (all three languages), lines outside every block, blocks
 without lines, boxes reaching outside the page, empty inputs.  Strict comparison: every detection
 field of the record, `distance` / `vec` / `norm` / `weight` bit for bit, Python type of `font_size`."""
@@ -11,7 +11,7 @@ import pytest
 
 from conftest import pkg
 from oracle import postproc_ref as R
-from oracle import ref_import as RI
+from refcode import reference_post, reference_results
 
 
 def random_page(seed, im_w=None, im_h=None):
@@ -148,18 +148,21 @@ def test_native_group_output_equals_oracle_on_tied_lines(seed):
     same_blocks(got, ref)
 
 
-@pytest.mark.skipif(not RI.reference_available(), reason="reference tree not present")
+def reference_group_output(name, blks, lines, im_w, im_h, mask):
+    def compute():
+        with np.errstate(all="ignore"):
+            return reference_post().TB.group_output(copy.deepcopy(blks), lines.copy(), im_w, im_h, mask)
+    return reference_results(name, compute)
+
+
 @pytest.mark.parametrize("seed", range(0, 40, 2))
 def test_native_group_output_equals_reference_code_on_tied_lines(seed):
     """... and against the reference's OWN group_output on the same grids (round 6, by hand: 300 of 300; with a stable sort and
     glibc's acos in the product it was 151 of 300)."""
-    from oracle import ref_post_import as RP
-    ref = RP.load_reference_post()
     p = pkg()
     blks, lines, im_w, im_h, mask = grid_page(seed)
     got = p.textblock.group_output(copy.deepcopy(blks), lines.copy(), im_w, im_h, mask)
-    with np.errstate(all="ignore"):
-        theirs = ref.TB.group_output(copy.deepcopy(blks), lines.copy(), im_w, im_h, mask)
+    theirs = reference_group_output(f"group_output_tied_{seed}", blks, lines, im_w, im_h, mask)
     same_blocks(got, theirs)
 
 
@@ -177,17 +180,13 @@ def test_native_group_output_empty_inputs():
                 R.group_output(copy.deepcopy(blks), lines.copy(), im_w, im_h, mask))
 
 
-@pytest.mark.skipif(not RI.reference_available(), reason="reference tree not present")
 @pytest.mark.parametrize("seed", range(0, 60, 3))
 def test_native_group_output_equals_reference_code(seed):
     """The reference's OWN group_output (shapely stand-in = the oracle's polygon predicate)."""
-    from oracle import ref_post_import as RP
-    ref = RP.load_reference_post()
     p = pkg()
     blks, lines, im_w, im_h, mask = random_page(seed)
     got = p.textblock.group_output(copy.deepcopy(blks), lines.copy(), im_w, im_h, mask)
-    with np.errstate(all="ignore"):
-        theirs = ref.TB.group_output(copy.deepcopy(blks), lines.copy(), im_w, im_h, mask)
+    theirs = reference_group_output(f"group_output_{seed}", blks, lines, im_w, im_h, mask)
     same_blocks(got, theirs)
     for a, b in zip(got, theirs):
         assert type(a.font_size) is type(b.font_size)
