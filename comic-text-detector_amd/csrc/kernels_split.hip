@@ -4,9 +4,11 @@
 //     w * x  ~=  wh*xh + wh*xl + wl*xh                 (the dropped term wl*xl is <= 2^-22 |w x|)
 //
 // and accumulated in fp32.  Every fp16 x fp16 product is exact in the fp32 accumulator (11 x 11 mantissa bits), so the
-// result carries the operands to ~22 bits -- below the rounding noise of an fp32 accumulation chain of the same
-// length (scripts/experiments/split_accuracy.py: K = 1152, representation error 1.0e-7 rms against 4.8e-7 rms of an
-// fp32 matmul).  `v_mfma_f32_32x32x16_f16` runs at 16x the rate of the f32-operand MFMA the exact-fp32 engine uses
+// result carries the operands to 22 bits RELATIVE while their halves stay in fp16's normal range -- below the rounding
+// noise of an fp32 accumulation chain of the same length (scripts/experiments/split_accuracy.py: K = 1152,
+// representation error 1.0e-7 rms against 4.8e-7 rms of an fp32 matmul).  Weights are scaled per output channel (below);
+// activations are NOT: once |x| < 2^-3 the low half x - xh falls into fp16's subnormal range, so an activation carries
+// an ABSOLUTE error floor of 2^-25 (half the subnormal spacing), max(2^-22 |x|, 2^-25) in all (tests/layer_ref.py).  `v_mfma_f32_32x32x16_f16` runs at 16x the rate of the f32-operand MFMA the exact-fp32 engine uses
 // (kernels_f32.hip), so three of them are a ~5x higher ceiling for the SAME activations in HBM (fp32 NHWC) and the
 // same op program.  This is the engine of `precision="fp32s"`: the reference runs fp32 (reference inference.py:129,
 // basemodel.py:222-244), and north_star's "identical boxes / mask bit-exact after threshold" is an fp32-level

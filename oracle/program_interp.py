@@ -19,9 +19,17 @@ L = importlib.import_module("comic-text-detector_amd._lib")
 _ACT = {0: lambda x: x, 1: F.silu, 2: lambda x: F.leaky_relu(x, 0.1), 3: F.relu, 4: torch.sigmoid}
 
 
-def run_program(prog, x: torch.Tensor, bitmap_thresh: float = 0.3):
-    """x: (B,3,H,W) f32 in [0,1].  Returns dict(blks, mask, lines, mask_u8, bitmap)."""
-    blob = torch.from_numpy(prog.blob())
+def run_program(prog, x: torch.Tensor, bitmap_thresh: float = 0.3, blob=None, hook=None, return_tensors: bool = False):
+    """x: (B,3,H,W) f32 in [0,1].  Returns dict(blks, mask, lines, mask_u8, bitmap).
+
+    Optional, for tests that use the interpreter as a stand-in engine (tests/test_layer_ref.py); none of them changes
+    the default result:
+      blob            replaces `prog.blob()` (e.g. fp16-rounded weights);
+      hook(i, o, stage, y, ctx) -> y
+                      stage "pre": a CONV / CONVT result before activation and residual, ctx = dict(a=input, w=, b=);
+                      stage "out": what op i stores into its destination tensor, ctx = dict(res=residual or None);
+      return_tensors  adds "tensors": {tensor id: (B,C,H,W)} as the program left them."""
+    blob = torch.from_numpy(prog.blob() if blob is None else np.asarray(blob, np.float32))
     B, _, H, W = x.shape
     T: Dict[int, torch.Tensor] = {}
 
@@ -53,37 +61,45 @@ def run_program(prog, x: torch.Tensor, bitmap_thresh: float = 0.3):
     out = dict(blks=torch.zeros(B, rows, no), mask=torch.zeros(B, 1, H, W), lines=torch.zeros(B, prog.meta.get("line_planes", 2), H, W),
                mask_u8=torch.zeros(B, H, W, dtype=torch.uint8), bitmap=torch.zeros(B, H, W, dtype=torch.uint8))
 
-    for o in prog.ops:
+    def hk(i, o, stage, y, **ctx):
+        return y if hook is None else hook(i, o, stage, y, ctx)
+
+    for i, o in enumerate(prog.ops):
         k = o["kind"]
         if k == L.OP_INPUT:
             tens(o["dst"])[:] = 0           # channels beyond the image's 3 are zero padding
             tens(o["dst"])[:, :3] = x
+            if hook is not None:
+                tens(o["dst"])[:] = hk(i, o, "out", tens(o["dst"]).clone(), res=None)
         elif k == L.OP_STEM:
             w = par(o["w_off"], o["cout"] * 3 * 36).view(o["cout"], 3, 6, 6)
             b = par(o["b_off"], o["cout"])
-            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["cout"]] = _ACT[o["act"]](F.conv2d(x, w, b, 2, 2))
+            y = _ACT[o["act"]](hk(i, o, "pre", F.conv2d(x, w, b, 2, 2), a=x, w=w, b=b))
+            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["cout"]] = hk(i, o, "out", y, res=None)
         elif k == L.OP_CONV:
             a = srcs(o)
             cin = a.shape[1]
             w = par(o["w_off"], o["cout"] * cin * o["k"] ** 2).view(o["cout"], cin, o["k"], o["k"])
             b = par(o["b_off"], o["cout"]) if o["b_off"] >= 0 else None
-            y = _ACT[o["act"]](F.conv2d(a, w, b, o["stride"], o["pad"]))
+            y = _ACT[o["act"]](hk(i, o, "pre", F.conv2d(a, w, b, o["stride"], o["pad"]), a=a, w=w, b=b))
+            r = None
             if o["res"] >= 0:
-                y = y + tens(o["res"])[:, o["res_coff"]: o["res_coff"] + o["cout"]]
-            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["cout"]] = y
+                r = tens(o["res"])[:, o["res_coff"]: o["res_coff"] + o["cout"]]
+                y = y + r
+            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["cout"]] = hk(i, o, "out", y, res=r)
         elif k == L.OP_CONVT:
             a = srcs(o)
             cin = a.shape[1]
             w = par(o["w_off"], o["cout"] * cin * o["k"] ** 2).view(cin, o["cout"], o["k"], o["k"])
             b = par(o["b_off"], o["cout"]) if o["b_off"] >= 0 else None
-            y = _ACT[o["act"]](F.conv_transpose2d(a, w, b, o["stride"], o["pad"]))
-            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["cout"]] = y
+            y = _ACT[o["act"]](hk(i, o, "pre", F.conv_transpose2d(a, w, b, o["stride"], o["pad"]), a=a, w=w, b=b))
+            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["cout"]] = hk(i, o, "out", y, res=None)
         elif k == L.OP_MAXPOOL:
             a = view(o, "src0")
-            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["src0_c"]] = F.max_pool2d(a, o["k"], 1, o["k"] // 2)
+            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["src0_c"]] = hk(i, o, "out", F.max_pool2d(a, o["k"], 1, o["k"] // 2), res=None)
         elif k == L.OP_AVGPOOL2:
             a = view(o, "src0")
-            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["src0_c"]] = F.avg_pool2d(a, 2, 2)
+            tens(o["dst"])[:, o["dst_coff"]: o["dst_coff"] + o["src0_c"]] = hk(i, o, "out", F.avg_pool2d(a, 2, 2), res=None)
         elif k == L.OP_DETECT:
             stride, row_unit, na, no_ = o["aux"][:4]
             raw = view(o, "src0")                       # (B, na*no, ny, nx)
@@ -131,4 +147,6 @@ def run_program(prog, x: torch.Tensor, bitmap_thresh: float = 0.3):
                     out["bitmap"] = (y[:, 0] > o["faux"][0]).to(torch.uint8)
         else:
             raise ValueError(f"unknown op kind {k}")
+    if return_tensors:
+        out["tensors"] = T
     return out
