@@ -34,7 +34,7 @@ int fail(int code, const std::string& msg) {
       return fail(CTD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                 \
   } while (0)
 
-int g_fuse_epoch = 0;   // bumped when a fusion threshold changes: cached plans are re-made
+int g_plan_epoch = 0;   // bumped by every tuning key but the tail's: cached plans are re-made
 int g_no_reuse = 0;     // engines created from now on: no arena reuse (debug: `read_tensor` of any activation); "no_reuse"
 int g_fwd_prio = 1;      // the network's big kernels raise their waves' issue priority (s_setprio 3): a co-running tail stretched the
                          // VALU-bound stem kernel from 0.42 to 2.1 ms (rocprofv3 timeline); "fwd_prio"
@@ -43,6 +43,19 @@ int g_split_planes = 1;  // fp32s engine: keep conv-to-conv tensors split in HBM
 int g_f32_mfma = 1;     // engines created from now on: fp32 convs on the f32 MFMA kernel (0: exact-order direct kernels); "f32_mfma"
 
 enum Impl { IMPL_POINT = 0, IMPL_IGEMM = 1, IMPL_IGEMM_T = 2, IMPL_DIRECT = 3, IMPL_FUSED = 4 };
+
+// how plan() has an op's work launched: by the op itself, by another op's launch, or as the head of a multi-layer launch
+enum Role {
+  ROLE_OWN,
+  ROLE_FUSED,   // another op's launch does this op's work
+  ROLE_C3,      // cv1+cv2 of a C3 block with 32 hidden channels: kernels_c3.hip for ops [i, i+3]
+  ROLE_C3B,     // m.cv1 of a 64 / 128-channel bottleneck: kernels_c3b.hip for [m.cv1, m.cv2 (+ cv3)]
+  ROLE_SPPF,    // first of SPPF's three chained max pools: one launch does all three
+  ROLE_STEM2,   // STEM op that also computes the following 3x3/s2 conv
+  ROLE_STEMSP,  // fp32s: first conv reads the network input itself (kernels_split_stem.hip) in place of the INPUT op
+  ROLE_POST,    // 128-channel ConvTranspose whose single consumer, the next op (a 1x1 conv), runs on its output tile
+  ROLE_SEGP,    // 64-channel ConvTranspose feeding only SEG_FINAL: also stores SEG_FINAL's 16 tap products per pixel
+};
 
 struct OpState {
   ctd_op op;
@@ -58,20 +71,12 @@ struct OpState {
   // filled by plan()
   ConvArgs args{};
   double flops = 0, bytes = 0;
-  bool c3_head = false;   // this op launches the fused C3 kernel for ops [i, i+3] ...
-  bool skip = false;      // ... and the other three launch nothing (also: pools 2, 3 of a fused SPPF)
-  bool sppf_head = false; // first of SPPF's three chained max pools: one launch does all three
-  bool stem2_head = false; // STEM op that also computes the following 3x3/s2 conv (which is `skip`)
-  bool stemsp_head = false; // fp32s: first conv reads the network input itself (kernels_split_stem.hip); its INPUT op is `skip`
-  bool segp_head = false; // 64-channel ConvTranspose feeding only SEG_FINAL: stores the 16 tap products per pixel instead (halo3 SEGP)
-  bool segp_ran = false;  // (on the SEG_FINAL op, set per launch) its source holds P (B,H,W,16) f32, not the 64-channel map
-  bool post_head = false; // 128-channel ConvTranspose whose single consumer, the next op (a 1x1 conv), runs on its output tile
-  ConvArgs post_args{};   // ... its arguments with post_* filled (kernels_halo3.hip)
-  bool c3b_head = false;  // m.cv1 of a 64 / 128-channel bottleneck: launches kernels_c3b.hip for [m.cv1, m.cv2 (+ cv3)]
-  int c3b_conv3 = -1;     // ... index of that bottleneck's 3x3 op (its dispatch decides the K walk, at launch time)
+  Role role = ROLE_OWN;
+  ConvArgs post_args{};   // ROLE_POST / ROLE_SEGP: the ConvTranspose's arguments with post_* filled (kernels_halo3.hip)
   Stem2Args st2{};
   C3Args c3{};
   C3bArgs c3b{};
+  std::string ran;        // filled by launch_op: the kernel the last forward / profile launched for this op
 };
 
 // A C3 block in the op list: [cv1+cv2 -> Y] ([m.j.cv1: Y[0:c] -> Tj] [m.j.cv2: Tj -> Y[0:c] (+ Y[0:c])]) x n [cv3: Y -> out]
@@ -101,7 +106,7 @@ struct ctd_engine {
   size_t arena_bytes = 0;
   int arena_gen = 0;           // bumped whenever the arena is reallocated: captured graphs hold the old addresses
   int pB = 0, pH = 0, pW = 0;  // current plan
-  int p_fuse = -1;             // value of g_fuse the current plan was made under
+  int p_epoch = -1;            // value of g_plan_epoch the current plan was made under
   bool no_reuse = false;
   bool w_tiled = true;   // tile-major MFMA weight packing (CTD_W_TILED=0 disables)
   bool f32_mfma = true;  // fp32 engine: f32-operand MFMA kernel (CTD_F32_MFMA=0: exact-order direct kernels only)
@@ -363,7 +368,6 @@ int pack_op(ctd_engine* e, OpState& s, const float* P, int64_t nP) {
 }
 
 int validate(ctd_engine* e) {
-  const int nT = (int)e->tensors.size();
   for (auto& t : e->tensors) {
     if (t.t.channels < 1 || t.t.log2_down < 0 || t.t.log2_down > 6)
       return fail(CTD_ERR_INVALID, "tensor: bad channels/log2_down");
@@ -407,17 +411,35 @@ int validate(ctd_engine* e) {
         return bad("unknown op kind");
     }
   }
-  (void)nT;
   return CTD_OK;
 }
 
 size_t align_up(size_t v, size_t a) { return (v + a - 1) / a * a; }
 
-// ---- arena planning -----------------------------------------------------------
-int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
-  if (B < 1 || H < 64 || W < 64 || H % 64 || W % 64)
-    return fail(CTD_ERR_INVALID, "H and W must be positive multiples of 64 and B >= 1");
-  const int nT = (int)e->tensors.size(), nO = (int)e->ops.size();
+// address of channel `coff` of tensor `id` in the arena of the current plan
+char* tensor_ptr(const ctd_engine* e, int id, int coff) {
+  const TensorState& t = e->tensors[id];
+  return e->arena + t.offset + (size_t)coff * t.esize;
+}
+
+// ---- plan(): the passes it runs, in its order --------------------------------------------------------------------
+
+// an MFMA conv on the 32-channel K step with tile-major weights: the layers the multi-layer fp16 kernels take over
+bool mfma16(const ctd_engine* e, const OpState& s) {
+  return s.op.kind == CTD_OP_CONV && s.impl == IMPL_IGEMM && s.bk == 32 && e->w_tiled;
+}
+
+// op `o`'s work is done by `head`'s launch: its work is booked there (the algorithmic bytes of the layers stay the
+// yardstick) and it launches nothing
+void fold_into(OpState& head, OpState& o) {
+  head.flops += o.flops;
+  head.bytes += o.bytes;
+  o.flops = o.bytes = 0;
+  o.role = ROLE_FUSED;
+}
+
+// every tensor's size at (B,H,W) and its lifetime [first_def, last_use] in op indices
+int liveness(ctd_engine* e, int B, int H, int W) {
   for (auto& t : e->tensors) {
     t.esize = (e->prec != CTD_PREC_F16 || t.t.dtype == 1) ? 4 : 2;
     t.H = H >> t.t.log2_down;
@@ -438,7 +460,7 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
       e->tensors[id].last_use = std::max(e->tensors[id].last_use, i);
     }
   };
-  for (int i = 0; i < nO; ++i) {
+  for (int i = 0; i < (int)e->ops.size(); ++i) {
     const ctd_op& o = e->ops[i].op;
     switch (o.kind) {
       case CTD_OP_INPUT:
@@ -451,32 +473,33 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
       default: use(o.src0, i); break;
     }
   }
-  for (int t = 0; t < nT; ++t)
+  for (int t = 0; t < (int)e->tensors.size(); ++t)
     if (e->tensors[t].last_use >= 0 && e->tensors[t].first_def < 0)
       return fail(CTD_ERR_INVALID, "tensor " + std::to_string(t) + " is read but never written");
+  return CTD_OK;
+}
 
-  // ---- C3 blocks with 64 / 128 hidden channels (kernels_c3b.hip): found here, BEFORE the arena is laid out, because the
-  // fused launches change what is alive when.  Bottleneck j < n - 1 becomes one launch at m.j.cv1's position that reads the
-  // block's running tensor and writes Tj (NOT Y[0:c] in place: neighbouring patches still read its halo), so Tj lives until
-  // the next bottleneck's launch has read it; the last bottleneck + cv3 become one launch at m.(n-1).cv1's position, so
-  // cv3's output exists from there on.  Both changes only lengthen lifetimes: a chain the kernel then declines (grid too
-  // small) runs layer per launch on the same arena.
+// C3 blocks with 64 / 128 hidden channels (kernels_c3b.hip).  Bottleneck j < n - 1 becomes one launch at m.j.cv1's
+// position that reads the block's running tensor and writes Tj (NOT Y[0:c] in place: neighbouring patches still read its
+// halo), so Tj lives until the next bottleneck's launch has read it; the last bottleneck + cv3 become one launch at
+// m.(n-1).cv1's position, so cv3's output exists from there on.  Both changes only lengthen lifetimes: a chain the kernel
+// then declines (grid too small) runs layer per launch on the same arena.  (Only under the pattern's fuse bit: with it off
+// the lifetimes -- and the 32-channel C3 matcher, which wants a cv1 | cv2 output that is still first defined by its own
+// op -- see the unfused program.)
+std::vector<C3Chain> match_c3b_chains(ctd_engine* e) {
   std::vector<C3Chain> chains;
-  // (only under the pattern's fuse bit: with it off the lifetimes -- and the 32-channel C3 matcher, which wants a cv1 | cv2
-  // output that is still first defined by its own op -- see the unfused program; a change of `fuse` re-plans)
+  const int nO = (int)e->ops.size();
   for (int i = 0; e->prec == CTD_PREC_F16 && (g_fuse & 8) && i + 3 < nO; ++i) {
     const OpState& A = e->ops[i];
     const ctd_op& a = A.op;
-    auto mfma16 = [&](const OpState& s) { return s.op.kind == CTD_OP_CONV && s.impl == IMPL_IGEMM && s.bk == 32 && e->w_tiled; };
-    if (!mfma16(A) || a.k != 1 || a.stride != 1 || a.res >= 0 || a.dst_coff != 0) continue;
+    if (!mfma16(e, A) || a.k != 1 || a.stride != 1 || a.res >= 0 || a.dst_coff != 0) continue;
     const int Y = a.dst, c = a.cout / 2;
     if (a.cout % 2 || !(c == 64 || c == 128) || e->tensors[Y].t.channels != 2 * c || e->tensors[Y].first_def != i) continue;
     int j = i + 1, n = 0;
-    bool ok = true;
-    while (ok && j + 1 < nO) {
+    while (j + 1 < nO) {
       const OpState &Bo = e->ops[j], &C = e->ops[j + 1];
       const ctd_op &b = Bo.op, &cc = C.op;
-      if (!mfma16(Bo) || !mfma16(C)) break;
+      if (!mfma16(e, Bo) || !mfma16(e, C)) break;
       const int T = b.dst;
       if (b.k != 1 || b.stride != 1 || b.src0 != Y || b.src0_coff != 0 || b.src0_c != c || b.src0_up || b.src1 >= 0 ||
           b.cout != c || b.res >= 0 || b.dst_coff != 0 || T == Y || e->tensors[T].t.channels != c || b.act != a.act)
@@ -492,16 +515,14 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     if (!n || j >= nO) continue;
     const OpState& D = e->ops[j];
     const ctd_op& d = D.op;
-    if (!mfma16(D) || d.k != 1 || d.stride != 1 || d.src0 != Y || d.src0_coff != 0 || d.src0_c != 2 * c || d.src0_up ||
+    if (!mfma16(e, D) || d.k != 1 || d.stride != 1 || d.src0 != Y || d.src0_coff != 0 || d.src0_c != 2 * c || d.src0_up ||
         d.src1 >= 0 || d.cout != 2 * c || d.res >= 0 || d.dst == Y || d.act != a.act)
       continue;
     if (e->tensors[Y].last_use != j || e->tensors[Y].esize != 2 || e->tensors[d.dst].esize != 2) continue;
     bool t_is_dst = false;
     for (int q = 0; q < n; ++q) t_is_dst = t_is_dst || e->ops[i + 1 + 2 * q].op.dst == d.dst;
     if (t_is_dst) continue;
-    C3Chain ch;
-    ch.a = i; ch.d = j; ch.n = n; ch.c = c;
-    chains.push_back(ch);
+    chains.push_back(C3Chain{i, j, n, c});
     for (int q = 0; q + 1 < n; ++q) {   // Tq is read by the launch of bottleneck q + 1
       TensorState& tq = e->tensors[e->ops[i + 1 + 2 * q].op.dst];
       tq.last_use = std::max(tq.last_use, i + 1 + 2 * (q + 1));
@@ -510,11 +531,15 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     td.first_def = std::min(td.first_def, i + 1 + 2 * (n - 1));
     i = j;
   }
-  // (after the C3 chains: their match wants the 1x1's output still defined by the 1x1)
-  // ---- a 128-channel ConvTranspose followed by its ONLY consumer, a 1x1 conv over it (or over [x ; it], x <= 64 channels):
-  // one launch of kernels_halo3.hip writes the 1x1's output, at the ConvTranspose's position -- so that tensor is alive
-  // from there on.  (UNet: upconv4.conv.1 -> upconv5.conv.0.cv1+cv2 over [f160 ; u160]; DB head: upconv4.conv.1 -> conv.0.)
+  return chains;
+}
+
+// a 128-channel ConvTranspose followed by its ONLY consumer, a 1x1 conv over it (or over [x ; it], x <= 64 channels):
+// one launch of kernels_halo3.hip writes the 1x1's output, at the ConvTranspose's position -- so that tensor is alive
+// from there on.  (UNet: upconv4.conv.1 -> upconv5.conv.0.cv1+cv2 over [f160 ; u160]; DB head: upconv4.conv.1 -> conv.0.)
+std::vector<int> match_convt_post(ctd_engine* e) {
   std::vector<int> posts;
+  const int nO = (int)e->ops.size();
   for (int i = 0; e->prec == CTD_PREC_F16 && (g_fuse & 16) && i + 1 < nO; ++i) {
     const OpState &T = e->ops[i], &P = e->ops[i + 1];
     const ctd_op &t = T.op, &p = P.op;
@@ -533,8 +558,11 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     TensorState& td = e->tensors[p.dst];
     td.first_def = std::min(td.first_def, i);
   }
+  return posts;
+}
 
-  // first-fit allocation over a free list, in op order
+// first-fit allocation over a free list, in op order; the arena grows when the plan needs more than it holds
+int layout_arena(ctd_engine* e, hipStream_t cap_stream) {
   struct Blk { size_t off, size; };
   std::vector<Blk> freel;
   size_t top = 0;
@@ -563,11 +591,9 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
       } else ++i;
     }
   };
-  for (int i = 0; i < nO; ++i) {
-    for (int t = 0; t < nT; ++t)
-      if (e->tensors[t].first_def == i) e->tensors[t].offset = alloc(e->tensors[t].bytes);
-    for (int t = 0; t < nT; ++t)
-      if (e->tensors[t].first_def >= 0 && e->tensors[t].last_use == i) release(e->tensors[t].offset, e->tensors[t].bytes);
+  for (int i = 0; i < (int)e->ops.size(); ++i) {
+    for (auto& t : e->tensors) if (t.first_def == i) t.offset = alloc(t.bytes);
+    for (auto& t : e->tensors) if (t.first_def >= 0 && t.last_use == i) release(t.offset, t.bytes);
   }
   if (top > e->arena_bytes) {
     // growing the arena frees the old one: illegal inside a stream capture, and it invalidates every graph
@@ -585,67 +611,61 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     if (me != hipSuccess) return fail(CTD_ERR_NOMEM, "arena hipMalloc of " + std::to_string(top) + " bytes failed");
     e->arena_bytes = top;
   }
+  return CTD_OK;
+}
 
-  // fp32s: which tensors live split-plane.  A tensor qualifies when every op that writes it and every op that reads it
-  // is a launch of the split kernel on 32-channel-aligned slices; the two sources of one launch must agree.
+// fp32s: which tensors live split-plane.  A tensor qualifies when every op that writes it and every op that reads it
+// is a launch of the split kernel on 32-channel-aligned slices; the two sources of one launch must agree.
+void mark_split_planes(ctd_engine* e) {
+  const int nT = (int)e->tensors.size(), nO = (int)e->ops.size();
   for (auto& t : e->tensors) t.sp = false;
-  if (e->prec == CTD_PREC_F32S && g_split_planes) {
-    std::vector<char> sp(nT, 0);
-    for (int t = 0; t < nT; ++t) sp[t] = e->tensors[t].esize == 4 && e->tensors[t].t.dtype != 1 && e->tensors[t].t.channels % 32 == 0;
-    auto split_conv = [&](const OpState& s) {
-      return s.split && ((s.op.kind == CTD_OP_CONV && s.impl == IMPL_IGEMM) || (s.op.kind == CTD_OP_CONVT && s.impl == IMPL_IGEMM_T));
-    };
-    for (int i = 0; i < nO; ++i) {
-      const OpState& s = e->ops[i];
-      const ctd_op& o = s.op;
-      const bool sc = split_conv(s);
-      switch (o.kind) {
-        case CTD_OP_CONV:
-        case CTD_OP_CONVT:
-          if (!(sc && o.src0_coff % 32 == 0 && o.src0_c % 32 == 0)) sp[o.src0] = 0;
-          if (o.src1 >= 0 && !(sc && o.src1_coff % 32 == 0 && o.src1_c % 32 == 0)) sp[o.src1] = 0;
-          if (o.res >= 0 && !(sc && o.res_coff % 32 == 0 && o.cout % 32 == 0)) sp[o.res] = 0;
-          if (!(sc && o.dst_coff % 32 == 0 && o.cout % 32 == 0)) sp[o.dst] = 0;
-          break;
-        case CTD_OP_INPUT:
-        case CTD_OP_STEM: sp[o.dst] = 0; break;
-        case CTD_OP_MAXPOOL:
-        case CTD_OP_AVGPOOL2: sp[o.src0] = 0; sp[o.dst] = 0; break;
-        default: if (o.src0 >= 0) sp[o.src0] = 0; break;
-      }
-    }
-    for (bool changed = true; changed;) {
-      changed = false;
-      for (int i = 0; i < nO; ++i) {
-        const ctd_op& o = e->ops[i].op;
-        if ((o.kind == CTD_OP_CONV || o.kind == CTD_OP_CONVT) && o.src1 >= 0 && sp[o.src0] != sp[o.src1]) {
-          sp[o.src0] = sp[o.src1] = 0;
-          changed = true;
-        }
-      }
-    }
-    for (int t = 0; t < nT; ++t) e->tensors[t].sp = sp[t] != 0;
-  }
-
-  // per-op launch arguments
-  const bool f16 = e->prec == CTD_PREC_F16;
+  if (e->prec != CTD_PREC_F32S || !g_split_planes) return;
+  std::vector<char> sp(nT, 0);
+  for (int t = 0; t < nT; ++t) sp[t] = e->tensors[t].esize == 4 && e->tensors[t].t.dtype != 1 && e->tensors[t].t.channels % 32 == 0;
   for (int i = 0; i < nO; ++i) {
+    const OpState& s = e->ops[i];
+    const ctd_op& o = s.op;
+    const bool sc = s.split && ((o.kind == CTD_OP_CONV && s.impl == IMPL_IGEMM) || (o.kind == CTD_OP_CONVT && s.impl == IMPL_IGEMM_T));
+    switch (o.kind) {
+      case CTD_OP_CONV:
+      case CTD_OP_CONVT:
+        if (!(sc && o.src0_coff % 32 == 0 && o.src0_c % 32 == 0)) sp[o.src0] = 0;
+        if (o.src1 >= 0 && !(sc && o.src1_coff % 32 == 0 && o.src1_c % 32 == 0)) sp[o.src1] = 0;
+        if (o.res >= 0 && !(sc && o.res_coff % 32 == 0 && o.cout % 32 == 0)) sp[o.res] = 0;
+        if (!(sc && o.dst_coff % 32 == 0 && o.cout % 32 == 0)) sp[o.dst] = 0;
+        break;
+      case CTD_OP_INPUT:
+      case CTD_OP_STEM: sp[o.dst] = 0; break;
+      case CTD_OP_MAXPOOL:
+      case CTD_OP_AVGPOOL2: sp[o.src0] = 0; sp[o.dst] = 0; break;
+      default: if (o.src0 >= 0) sp[o.src0] = 0; break;
+    }
+  }
+  for (bool changed = true; changed;) {
+    changed = false;
+    for (int i = 0; i < nO; ++i) {
+      const ctd_op& o = e->ops[i].op;
+      if ((o.kind == CTD_OP_CONV || o.kind == CTD_OP_CONVT) && o.src1 >= 0 && sp[o.src0] != sp[o.src1]) {
+        sp[o.src0] = sp[o.src1] = 0;
+        changed = true;
+      }
+    }
+  }
+  for (int t = 0; t < nT; ++t) e->tensors[t].sp = sp[t] != 0;
+}
+
+// per-op launch arguments and algorithmic work; every op starts as a launch of its own
+int op_args(ctd_engine* e, int B) {
+  const bool f16 = e->prec == CTD_PREC_F16;
+  for (int i = 0; i < (int)e->ops.size(); ++i) {
     OpState& s = e->ops[i];
     const ctd_op& o = s.op;
     ConvArgs a{};
     auto view = [&](int id, int coff, int c, int up) {
-      SrcView v{};
       const TensorState& t = e->tensors[id];
-      v.ptr = e->arena + t.offset + (size_t)coff * t.esize;
-      v.pitch = t.t.channels;
-      v.c = c;
-      v.up = up;
-      v.H = t.H;
-      v.W = t.W;
-      return v;
+      return SrcView{tensor_ptr(e, id, coff), t.t.channels, c, up, t.H, t.W};
     };
-    s.flops = 0;
-    s.bytes = 0;
+    s.flops = s.bytes = 0;
     if (o.kind == CTD_OP_CONV || o.kind == CTD_OP_CONVT) {
       const TensorState& td = e->tensors[o.dst];
       a.s0 = view(o.src0, o.src0_coff, o.src0_c, o.src0_up);
@@ -657,13 +677,13 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
         const int h1 = a.s1.H << (o.src1_up ? 1 : 0), w1 = a.s1.W << (o.src1_up ? 1 : 0);
         if (h1 != a.Hin || w1 != a.Win) return fail(CTD_ERR_INVALID, "op " + std::to_string(i) + ": source sizes differ");
       }
-      a.dst = e->arena + td.offset + (size_t)o.dst_coff * td.esize;
+      a.dst = tensor_ptr(e, o.dst, o.dst_coff);
       a.pitchD = td.t.channels;
       a.oH = td.H;
       a.oW = td.W;
       if (o.res >= 0) {
         const TensorState& tr = e->tensors[o.res];
-        a.res = e->arena + tr.offset + (size_t)o.res_coff * tr.esize;
+        a.res = tensor_ptr(e, o.res, o.res_coff);
         a.pitchR = tr.t.channels;
         if (tr.H != td.H || tr.W != td.W) return fail(CTD_ERR_INVALID, "residual size mismatch");
       }
@@ -675,7 +695,6 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
       a.bk = s.bk;
       a.zeros = e->zeros;
       a.w_tiled = e->w_tiled;
-      a.k_rot = 0;
       a.prio = g_fwd_prio;
       const int cin = o.src0_c + (o.src1 >= 0 ? o.src1_c : 0);
       a.nphase = 1;
@@ -731,11 +750,14 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
                 (double)a.N * o.k * o.k * cin * es;
     }
     s.args = a;
-    s.c3_head = s.skip = s.sppf_head = s.stem2_head = s.stemsp_head = s.c3b_head = s.post_head = s.segp_head = s.segp_ran = false;
-    s.c3b_conv3 = -1;
+    s.role = ROLE_OWN;
   }
-  // ---- fp32s: INPUT (page -> fp32 NHWC, zero 4th channel) + the 6x6/s2 first conv -> one launch that reads the page itself
-  for (int i = 0; e->prec == CTD_PREC_F32S && g_split_stem && i + 1 < nO; ++i) {
+  return CTD_OK;
+}
+
+// fp32s: INPUT (page -> fp32 NHWC, zero 4th channel) + the 6x6/s2 first conv -> one launch that reads the page itself
+void fuse_stem_split(ctd_engine* e, int B, int H, int W) {
+  for (int i = 0; e->prec == CTD_PREC_F32S && g_split_stem && i + 1 < (int)e->ops.size(); ++i) {
     OpState &S0 = e->ops[i], &S1 = e->ops[i + 1];
     const ctd_op &o0 = S0.op, &o1 = S1.op;
     if (o0.kind != CTD_OP_INPUT || o1.kind != CTD_OP_CONV || !S1.split || S1.impl != IMPL_IGEMM) continue;
@@ -743,13 +765,16 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     if (o1.src0 != T0 || o1.src0_coff != 0 || o1.src1 >= 0 || o1.res >= 0) continue;
     if (e->tensors[T0].first_def != i || e->tensors[T0].last_use != i + 1) continue;
     if (!stem_split_supported(S1.args)) continue;
-    S0.skip = true;
-    S1.stemsp_head = true;
+    S0.role = ROLE_FUSED;
+    S1.role = ROLE_STEMSP;
     // algorithmic bytes: the page (3 B per pixel as uint8; the float format is 12) in, the 32-channel map out, the weights
     S1.bytes = (double)B * H * W * 3 + (double)B * S1.args.oH * S1.args.oW * S1.args.N * 4 + (double)S1.args.N * 36 * 3 * 4;
   }
-  // ---- stem + layer 1: the stem's output has one consumer, a 3x3/s2 conv 32 -> 64 -> one launch, never stored
-  for (int i = 0; f16 && (g_fuse & 4) && i + 1 < nO; ++i) {
+}
+
+// stem + layer 1: the stem's output has one consumer, a 3x3/s2 conv 32 -> 64 -> one launch, never stored
+void fuse_stem2(ctd_engine* e, int B, int H, int W) {
+  for (int i = 0; e->prec == CTD_PREC_F16 && (g_fuse & 4) && i + 1 < (int)e->ops.size(); ++i) {
     OpState &S0 = e->ops[i], &S1 = e->ops[i + 1];
     const ctd_op &o0 = S0.op, &o1 = S1.op;
     if (o0.kind != CTD_OP_STEM || o1.kind != CTD_OP_CONV || S1.impl != IMPL_IGEMM || S1.bk != 32 || !e->w_tiled) continue;
@@ -766,14 +791,15 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     f.w1 = (const half_t*)S1.w_dev; f.bias1 = S1.b_dev; f.act1 = o1.act;
     f.dst = (half_t*)S1.args.dst; f.pitchD = S1.args.pitchD;
     if (S1.args.oH != H / 4 || S1.args.oW != W / 4 || !stem_conv2_supported(f)) continue;
-    S0.stem2_head = true;
+    S0.role = ROLE_STEM2;
     S0.st2 = f;
-    S1.skip = true;
-    S0.flops += S1.flops; S0.bytes += S1.bytes;
-    S1.flops = 0; S1.bytes = 0;
+    fold_into(S0, S1);
   }
-  // ---- SPPF: three chained stride-1 max pools over the slots of one cat tensor -> one launch
-  for (int i = 0; (g_fuse & 2) && i + 2 < nO; ++i) {   // every engine: max is exact in any precision
+}
+
+// SPPF: three chained stride-1 max pools over the slots of one cat tensor -> one launch
+void fuse_sppf(ctd_engine* e) {
+  for (int i = 0; (g_fuse & 2) && i + 2 < (int)e->ops.size(); ++i) {   // every engine: max is exact in any precision
     const ctd_op &p0 = e->ops[i].op, &p1 = e->ops[i + 1].op, &p2 = e->ops[i + 2].op;
     if (p0.kind != CTD_OP_MAXPOOL || p1.kind != CTD_OP_MAXPOOL || p2.kind != CTD_OP_MAXPOOL) continue;
     const int c = p0.src0_c, P = p0.src0;
@@ -783,19 +809,21 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
         p2.src0_coff != p1.dst_coff || p2.dst_coff != p2.src0_coff + c)
       continue;
     const TensorState& tp = e->tensors[P];
-    if (!sppf_pool3_supported(tp.t.channels, c, c, tp.H, tp.W, p0.k, e->arena + tp.offset + (size_t)p0.src0_coff * tp.esize, tp.esize))
+    if (!sppf_pool3_supported(tp.t.channels, c, c, tp.H, tp.W, p0.k, tensor_ptr(e, P, p0.src0_coff), tp.esize))
       continue;
-    e->ops[i].sppf_head = true;
-    e->ops[i + 1].skip = e->ops[i + 2].skip = true;
+    e->ops[i].role = ROLE_SPPF;
+    e->ops[i + 1].role = e->ops[i + 2].role = ROLE_FUSED;
     i += 2;
   }
-  // ---- C3 blocks with 32 hidden channels and one bottleneck: ops [cv1+cv2, m.cv1, m.cv2 (+shortcut), cv3] whose
-  // intermediates nobody else reads become one launch of kernels_c3.hip (same packed weights, same arithmetic)
-  for (int i = 0; f16 && (g_fuse & 1) && i + 3 < nO; ++i) {
+}
+
+// C3 blocks with 32 hidden channels and one bottleneck: ops [cv1+cv2, m.cv1, m.cv2 (+shortcut), cv3] whose
+// intermediates nobody else reads become one launch of kernels_c3.hip (same packed weights, same arithmetic)
+void fuse_c3(ctd_engine* e, int B) {
+  for (int i = 0; e->prec == CTD_PREC_F16 && (g_fuse & 1) && i + 3 < (int)e->ops.size(); ++i) {
     OpState &A = e->ops[i], &Bo = e->ops[i + 1], &C = e->ops[i + 2], &D = e->ops[i + 3];
     const ctd_op &a = A.op, &b = Bo.op, &c = C.op, &d = D.op;
-    auto mfma16 = [&](const OpState& s) { return s.op.kind == CTD_OP_CONV && s.impl == IMPL_IGEMM && s.bk == 32 && e->w_tiled; };
-    if (!mfma16(A) || !mfma16(Bo) || !mfma16(C) || !mfma16(D)) continue;
+    if (!mfma16(e, A) || !mfma16(e, Bo) || !mfma16(e, C) || !mfma16(e, D)) continue;
     const int Y = a.dst, T = b.dst;
     if (a.k != 1 || a.stride != 1 || a.cout != 64 || a.res >= 0 || a.dst_coff != 0 || e->tensors[Y].t.channels != 64) continue;
     if (b.k != 1 || b.stride != 1 || b.src0 != Y || b.src0_coff != 0 || b.src0_c != 32 || b.src1 >= 0 || b.cout != 32 ||
@@ -825,19 +853,18 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     f.act = a.act;
     f.zeros = e->zeros;
     if (D.args.oH != f.H || D.args.oW != f.W || !c3_fused_supported(f)) continue;
-    A.c3_head = true;
+    A.role = ROLE_C3;
     A.c3 = f;
-    Bo.skip = C.skip = D.skip = true;
-    // the block's work is booked on its first op (the algorithmic bytes of the four layers stay the yardstick)
-    A.flops += Bo.flops + C.flops + D.flops;
-    A.bytes += Bo.bytes + C.bytes + D.bytes;
-    Bo.flops = C.flops = D.flops = 0;
-    Bo.bytes = C.bytes = D.bytes = 0;
+    fold_into(A, Bo);
+    fold_into(A, C);
+    fold_into(A, D);
     i += 3;
   }
-  // ---- ConvTranspose + its 1x1 consumer (found above)
+}
+
+// ConvTranspose + its 1x1 consumer (matched by match_convt_post)
+void fuse_convt_post(ctd_engine* e, const std::vector<int>& posts) {
   for (int i : posts) {
-    if (!(g_fuse & 16)) break;
     OpState &T = e->ops[i], &P = e->ops[i + 1];
     ConvArgs a = T.args;
     a.post_w = P.w_dev;
@@ -849,16 +876,17 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     a.post_x = SrcView{};
     if (P.op.src1 >= 0) a.post_x = P.args.s0;
     if (P.args.oH != T.args.oH || P.args.oW != T.args.oW || !conv_halo3_post_supported(a)) continue;
-    T.post_head = true;
+    T.role = ROLE_POST;
     T.post_args = a;
-    P.skip = true;
-    T.flops += P.flops; T.bytes += P.bytes;
-    P.flops = P.bytes = 0;
+    fold_into(T, P);
   }
-  // ---- the UNet's last pair: ConvTranspose 128 -> 64 (+BN+ReLU) whose only reader is the 64 -> 1 ConvTranspose + sigmoid
-  // (SEG_FINAL): the first one's launch also forms the second one's 16 tap products per pixel and stores THOSE (64 B per
-  // pixel, in the 64-channel tensor's own arena slot, which is 128 B per pixel) -- kernels_halo3.hip SEGP
-  for (int i = 0; f16 && (g_fuse & 32) && i + 1 < nO; ++i) {
+}
+
+// the UNet's last pair: ConvTranspose 128 -> 64 (+BN+ReLU) whose only reader is the 64 -> 1 ConvTranspose + sigmoid
+// (SEG_FINAL): the first one's launch also forms the second one's 16 tap products per pixel and stores THOSE (64 B per
+// pixel, in the 64-channel tensor's own arena slot, which is 128 B per pixel) -- kernels_halo3.hip SEGP
+void fuse_convt_taps(ctd_engine* e) {
+  for (int i = 0; e->prec == CTD_PREC_F16 && (g_fuse & 32) && i + 1 < (int)e->ops.size(); ++i) {
     OpState &T = e->ops[i], &F = e->ops[i + 1];
     const ctd_op &t = T.op, &fo = F.op;
     if (t.kind != CTD_OP_CONVT || T.impl != IMPL_IGEMM_T || t.cout != 64 || t.dst_coff != 0 || T.bk != 32 || !e->w_tiled) continue;
@@ -870,14 +898,15 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     a.post_dst = T.args.dst;             // P takes the place of the map it replaces
     a.post_n = -16;
     if (!conv_halo3_segp_supported(a)) continue;
-    T.segp_head = true;
+    T.role = ROLE_SEGP;
     T.post_args = a;
   }
-  // ---- the wider C3 blocks found above: one launch per bottleneck, the last one with cv3 (kernels_c3b.hip)
+}
+
+// the wider C3 blocks (matched by match_c3b_chains): one launch per bottleneck, the last one with cv3 (kernels_c3b.hip)
+void fuse_c3b(ctd_engine* e, const std::vector<C3Chain>& chains, int B) {
   for (const C3Chain& ch : chains) {
-    if (!(g_fuse & 8)) break;
     OpState &A = e->ops[ch.a], &D = e->ops[ch.d];
-    const ctd_op& d = D.op;
     std::vector<C3bArgs> fs(ch.n);
     bool ok = true;
     for (int q = 0; q < ch.n && ok; ++q) {
@@ -893,6 +922,7 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
       f.add = C.op.res >= 0;
       f.act = Bo.op.act;
       f.zeros = e->zeros;
+      f.tap_major = conv_halo_supported(C.args, false) ? 0 : 1;   // the 3x3's K walk: the one its own dispatch takes
       if (last) {
         f.cv3 = 1;
         f.y2 = D.args.s0;
@@ -911,22 +941,35 @@ int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
     if (!ok) continue;
     for (int q = 0; q < ch.n; ++q) {
       OpState &Bo = e->ops[ch.a + 1 + 2 * q], &C = e->ops[ch.a + 2 + 2 * q];
-      Bo.c3b_head = true;
+      Bo.role = ROLE_C3B;
       Bo.c3b = fs[q];
-      Bo.c3b_conv3 = ch.a + 2 + 2 * q;
-      C.skip = true;
-      // the launch's work is booked on its first op (the algorithmic bytes of the layers stay the yardstick)
-      Bo.flops += C.flops; Bo.bytes += C.bytes;
-      C.flops = C.bytes = 0;
-      if (q + 1 == ch.n) {
-        D.skip = true;
-        Bo.flops += D.flops; Bo.bytes += D.bytes;
-        D.flops = D.bytes = 0;
-      }
+      fold_into(Bo, C);
+      if (q + 1 == ch.n) fold_into(Bo, D);
     }
-    (void)d;
   }
-  e->p_fuse = g_fuse + 64 * g_fuse_epoch;
+}
+
+// The plan for (B,H,W): the arena layout, every op's arguments and its launch role.
+int plan(ctd_engine* e, int B, int H, int W, hipStream_t cap_stream = nullptr) {
+  if (B < 1 || H < 64 || W < 64 || H % 64 || W % 64)
+    return fail(CTD_ERR_INVALID, "H and W must be positive multiples of 64 and B >= 1");
+  e->pB = 0;   // until this plan is complete: a failed one is made again by the next forward
+  if (int rc = liveness(e, B, H, W)) return rc;
+  // the fused launches change what is alive when, so the matches that lengthen lifetimes run BEFORE the arena is laid
+  // out; the C3b chains first: their match wants the 1x1's output still defined by the 1x1
+  const std::vector<C3Chain> chains = match_c3b_chains(e);
+  const std::vector<int> posts = match_convt_post(e);
+  if (int rc = layout_arena(e, cap_stream)) return rc;
+  mark_split_planes(e);
+  if (int rc = op_args(e, B)) return rc;
+  fuse_stem_split(e, B, H, W);
+  fuse_stem2(e, B, H, W);
+  fuse_sppf(e);
+  fuse_c3(e, B);
+  fuse_convt_post(e, posts);
+  fuse_convt_taps(e);
+  fuse_c3b(e, chains, B);
+  e->p_epoch = g_plan_epoch;
   e->pB = B; e->pH = H; e->pW = W;
   return CTD_OK;
 }
@@ -937,89 +980,77 @@ struct Outs {
   int blk_rows;
 };
 
-int launch_op(ctd_engine* e, int i, const Outs& x, hipStream_t st) {
+// Launches op i as planned and records in it the kernel that ran.  What stays decided here depends on the call itself:
+// whether the caller wants the mask (the SEGP producer's form) and the launchers' checks on the caller's buffers.
+void launch_op(ctd_engine* e, int i, const Outs& x, hipStream_t st) {
   OpState& s = e->ops[i];
   const ctd_op& o = s.op;
   const bool f16 = e->prec == CTD_PREC_F16;
   const int B = e->pB, H = e->pH, W = e->pW;
-  auto tptr = [&](int id, int coff) {
-    const TensorState& t = e->tensors[id];
-    return (void*)(e->arena + t.offset + (size_t)coff * t.esize);
-  };
+  switch (s.role) {
+    case ROLE_OWN: break;
+    case ROLE_FUSED: s.ran = "(fused)"; return;
+    case ROLE_C3: launch_c3_fused(s.c3, st); s.ran = "c3_fused_kernel"; return;
+    case ROLE_C3B: launch_c3b(s.c3b, st); s.ran = "c3b_kernel"; return;
+    case ROLE_SPPF: {
+      const TensorState& tp = e->tensors[o.src0];
+      launch_sppf_pool3(tensor_ptr(e, o.src0, o.src0_coff), tp.t.channels, o.src0_c, o.src0_c, B, tp.H, tp.W, o.k, st, tp.esize);
+      s.ran = "sppf_pool3_kernel";
+      return;
+    }
+    case ROLE_STEM2: {
+      Stem2Args f = s.st2;   // + this call's network input
+      f.in = x.input; f.in_fmt = x.in_fmt;
+      launch_stem_conv2(f, st);
+      s.ran = "stem_conv2_kernel";
+      return;
+    }
+    case ROLE_STEMSP: launch_stem_split(s.args, x.input, x.in_fmt, st); s.ran = "stem_split_kernel"; return;
+    case ROLE_POST: s.ran = std::string(launch_conv_igemm(s.post_args, false, st)) + "+1x1"; return;
+    case ROLE_SEGP:   // SEG_FINAL, the next op, runs only when the caller wants the mask: the tap products are for it
+      if (!x.mask && !x.mask_u8) s.ran = launch_conv_igemm(s.args, false, st);
+      else s.ran = std::string(launch_conv_igemm(s.post_args, false, st)) + "+taps";
+      return;
+  }
+  const char* k = "(none)";   // the caller passed no buffer for any of the op's outputs
   switch (o.kind) {
     case CTD_OP_INPUT: {
-      if (s.skip) break;
-      void* d = tptr(o.dst, 0);
+      void* d = tensor_ptr(e, o.dst, 0);
       const int pitch = e->tensors[o.dst].t.channels;
       if (x.in_fmt == CTD_IN_NCHW_F32) launch_input_nchw((const float*)x.input, d, pitch, B, H, W, f16, st);
       else launch_input_u8((const uint8_t*)x.input, d, pitch, B, H, W, f16, st);
+      k = "input_kernel";
       break;
     }
     case CTD_OP_STEM: {
-      if (s.stem2_head) {
-        Stem2Args f = s.st2;
-        f.in = x.input;
-        f.in_fmt = x.in_fmt;
-        launch_stem_conv2(f, st);
-        break;
-      }
       const TensorState& td = e->tensors[o.dst];
-      launch_stem(x.input, x.in_fmt, (half_t*)tptr(o.dst, o.dst_coff), td.t.channels, B, H, W, o.cout,
+      launch_stem(x.input, x.in_fmt, (half_t*)tensor_ptr(e, o.dst, o.dst_coff), td.t.channels, B, H, W, o.cout,
                   (const half_t*)s.w_dev, s.b_dev, o.act, st);
+      k = "stem_mfma_kernel";
       break;
     }
     case CTD_OP_CONV:
-      if (s.skip) break;
-      if (s.c3_head) { launch_c3_fused(s.c3, st); break; }
-      if (s.c3b_head) {   // the 3x3's K walk is the one its own dispatch would take NOW (a tuning key may have moved it)
-        C3bArgs f = s.c3b;
-        f.tap_major = conv_halo_supported(e->ops[s.c3b_conv3].args, false) ? 0 : 1;
-        launch_c3b(f, st);
-        break;
-      }
-      if (s.stemsp_head) { launch_stem_split(s.args, x.input, x.in_fmt, st); break; }
-      if (s.impl == IMPL_IGEMM && s.split) launch_conv_split(s.args, st);
-      else if (s.impl == IMPL_IGEMM && !f16) launch_conv_f32_mfma(s.args, st);
-      else if (s.impl == IMPL_IGEMM) launch_conv_igemm(s.args, e->tensors[o.dst].esize == 4, st);
-      else launch_conv_direct(s.args, f16, st);
-      break;
     case CTD_OP_CONVT:
-      if (s.segp_head) {   // decided per launch (a tuning key may have taken the big-tile kernel away): SEG_FINAL is told
-        const bool fused = conv_halo3_segp_supported(s.post_args) && (x.mask || x.mask_u8);
-        e->ops[i + 1].segp_ran = fused;
-        launch_conv_igemm(fused ? s.post_args : s.args, false, st);
-        break;
-      }
-      if (s.post_head) {
-        if (conv_halo3_post_supported(s.post_args)) { launch_conv_igemm(s.post_args, false, st); break; }
-        // a tuning key has taken the big-tile kernel away since the plan was made: the two layers, one launch each
-        launch_conv_igemm(s.args, false, st);
-        launch_conv_igemm(e->ops[i + 1].args, false, st);
-        break;
-      }
-      if (s.impl == IMPL_IGEMM_T && s.split) launch_conv_split(s.args, st);
-      else if (s.impl == IMPL_IGEMM_T && !f16) launch_conv_f32_mfma(s.args, st);
-      else if (s.impl == IMPL_IGEMM_T) launch_conv_igemm(s.args, false, st);
-      else launch_convt_direct(s.args, f16, st);
+      if (s.impl == IMPL_DIRECT && o.kind == CTD_OP_CONV) { launch_conv_direct(s.args, f16, st); k = "conv_direct_kernel"; }
+      else if (s.impl == IMPL_DIRECT) { launch_convt_direct(s.args, f16, st); k = "convt_direct_kernel"; }
+      else if (s.split) k = launch_conv_split(s.args, st);
+      else if (!f16) { launch_conv_f32_mfma(s.args, st); k = "conv_f32_mfma_kernel"; }
+      else k = launch_conv_igemm(s.args, e->tensors[o.dst].esize == 4, st);
       break;
     case CTD_OP_MAXPOOL: {
-      if (s.skip) break;
-      if (s.sppf_head) {
-        const TensorState& tp = e->tensors[o.src0];
-        launch_sppf_pool3(tptr(o.src0, o.src0_coff), tp.t.channels, o.src0_c, o.src0_c, B, tp.H, tp.W, o.k, st, tp.esize);
-        break;
-      }
       const TensorState& ts = e->tensors[o.src0];
       const TensorState& td = e->tensors[o.dst];
-      launch_maxpool(tptr(o.src0, o.src0_coff), ts.t.channels, tptr(o.dst, o.dst_coff), td.t.channels, o.src0_c, B,
+      launch_maxpool(tensor_ptr(e, o.src0, o.src0_coff), ts.t.channels, tensor_ptr(e, o.dst, o.dst_coff), td.t.channels, o.src0_c, B,
                      ts.H, ts.W, o.k, f16, st);
+      k = "maxpool_kernel";
       break;
     }
     case CTD_OP_AVGPOOL2: {
       const TensorState& ts = e->tensors[o.src0];
       const TensorState& td = e->tensors[o.dst];
-      launch_avgpool2(tptr(o.src0, o.src0_coff), ts.t.channels, tptr(o.dst, o.dst_coff), td.t.channels, o.src0_c, B,
+      launch_avgpool2(tensor_ptr(e, o.src0, o.src0_coff), ts.t.channels, tensor_ptr(e, o.dst, o.dst_coff), td.t.channels, o.src0_c, B,
                       td.H, td.W, f16, st);
+      k = "avgpool2_kernel";
       break;
     }
     case CTD_OP_DETECT: {
@@ -1027,8 +1058,9 @@ int launch_op(ctd_engine* e, int i, const Outs& x, hipStream_t st) {
       if (!x.blks) break;
       // aux[1] is the row offset for a 64x64 unit input scaled by (H/64)*(W/64)
       const int unit = (H / 64) * (W / 64);
-      launch_detect_decode(tptr(o.src0, o.src0_coff), ts.t.channels, ts.esize == 2, x.blks, x.blk_rows,
+      launch_detect_decode(tensor_ptr(e, o.src0, o.src0_coff), ts.t.channels, ts.esize == 2, x.blks, x.blk_rows,
                            o.aux[1] * unit, B, ts.H, ts.W, o.aux[2], o.aux[3], (float)o.aux[0], s.aux_dev, st);
+      k = "detect_decode_kernel";
       break;
     }
     case CTD_OP_EXPORT: {
@@ -1040,37 +1072,41 @@ int launch_op(ctd_engine* e, int i, const Outs& x, hipStream_t st) {
       if (o.aux[0] == CTD_OUT_MASK) { u8 = x.mask_u8; mode = 1; }
       else if (o.aux[1] == 0) { u8 = x.bitmap; mode = 2; }
       if (!out && !u8) break;                      // the f32 plane may be skipped while its u8 side output is wanted
-      launch_export_plane(tptr(o.src0, o.src0_coff), ts.t.channels, ts.esize == 2, out, nplanes, o.aux[1], u8, mode,
+      launch_export_plane(tensor_ptr(e, o.src0, o.src0_coff), ts.t.channels, ts.esize == 2, out, nplanes, o.aux[1], u8, mode,
                           o.faux[0], B, ts.H, ts.W, st);
+      k = "export_plane_kernel";
       break;
     }
     case CTD_OP_SEG_FINAL: {
       const TensorState& ts = e->tensors[o.src0];
       if (!x.mask && !x.mask_u8) break;
-      if (s.segp_ran)      // the producer stored the tap products: col2im + sigmoid + u8 from them
-        launch_seg_final_gather((const float*)tptr(o.src0, o.src0_coff), B, ts.H, ts.W, 0.f, x.mask, x.mask_u8, st);
-      else if (ts.esize == 4)
-        launch_seg_final_f32((const float*)tptr(o.src0, o.src0_coff), ts.t.channels, o.src0_c, B, ts.H, ts.W,
+      if (i > 0 && e->ops[i - 1].ran == "conv_halo3_kernel+taps") {   // its producer stored the tap products P (B,H,W,16)
+        launch_seg_final_gather((const float*)tensor_ptr(e, o.src0, o.src0_coff), B, ts.H, ts.W, 0.f, x.mask, x.mask_u8, st);
+        k = "seg_final_gather_kernel";
+      } else if (ts.esize == 4) {
+        launch_seg_final_f32((const float*)tensor_ptr(e, o.src0, o.src0_coff), ts.t.channels, o.src0_c, B, ts.H, ts.W,
                              (const float*)s.w_dev, x.mask, x.mask_u8, st);
-      else
-        launch_seg_final((const half_t*)tptr(o.src0, o.src0_coff), ts.t.channels, o.src0_c, B, ts.H, ts.W,
-                         (const float*)s.w_dev, 0.f, x.mask, x.mask_u8, st);
+        k = "seg_final_f32_kernel";
+      } else {
+        k = launch_seg_final((const half_t*)tensor_ptr(e, o.src0, o.src0_coff), ts.t.channels, o.src0_c, B, ts.H, ts.W,
+                             (const float*)s.w_dev, 0.f, x.mask, x.mask_u8, st);
+      }
       break;
     }
     case CTD_OP_DB_UP: {
       const TensorState& ts = e->tensors[o.src0];
       if (!x.lines) break;
-      launch_db_up(tptr(o.src0, o.src0_coff), ts.esize == 4, ts.t.channels, o.aux[1], o.aux[2] > 0 ? o.aux[2] : 2, B, ts.H, ts.W,
-                   (const float*)s.w_dev, x.lines, x.bitmap, o.faux[0], st);
+      k = launch_db_up(tensor_ptr(e, o.src0, o.src0_coff), ts.esize == 4, ts.t.channels, o.aux[1], o.aux[2] > 0 ? o.aux[2] : 2, B,
+                       ts.H, ts.W, (const float*)s.w_dev, x.lines, x.bitmap, o.faux[0], st);
       break;
     }
   }
-  return CTD_OK;
+  s.ran = k;
 }
 
 int prepare(ctd_engine* e, int B, int H, int W, hipStream_t st = nullptr) {
   HIP_TRY(hipSetDevice(e->device));
-  if (B != e->pB || H != e->pH || W != e->pW || e->p_fuse != g_fuse + 64 * g_fuse_epoch) return plan(e, B, H, W, st);
+  if (B != e->pB || H != e->pH || W != e->pW || e->p_epoch != g_plan_epoch) return plan(e, B, H, W, st);
   return CTD_OK;
 }
 
@@ -1175,8 +1211,7 @@ int ctd_engine_forward(ctd_engine* e, const void* input_dev, int32_t input_fmt, 
   if (int rc = prepare(e, B, H, W, (hipStream_t)stream)) return rc;
   Outs x{input_dev, input_fmt, blks_dev, mask_dev, lines_dev, mask_u8_dev, bitmap_dev,
          e->det_rows_per_unit * (H / 64) * (W / 64)};
-  for (int i = 0; i < (int)e->ops.size(); ++i)
-    if (int rc = launch_op(e, i, x, (hipStream_t)stream)) return rc;
+  for (int i = 0; i < (int)e->ops.size(); ++i) launch_op(e, i, x, (hipStream_t)stream);
   HIP_TRY(hipGetLastError());
   return CTD_OK;
 }
@@ -1197,44 +1232,7 @@ int ctd_engine_op_kernel(const ctd_engine* e, int32_t i, char* name, int32_t cap
   if (!e || !name || cap < 2) return fail(CTD_ERR_INVALID, "null argument");
   if (i < 0 || i >= (int)e->ops.size()) return fail(CTD_ERR_INVALID, "op index out of range");
   if (!e->pB) return fail(CTD_ERR_INVALID, "no plan yet: run a forward of the shape first");
-  const OpState& s = e->ops[i];
-  const ctd_op& o = s.op;
-  const bool f16 = e->prec == CTD_PREC_F16;
-  const char* k = "?";
-  auto conv_kernel = [&]() -> const char* {   // mirrors launch_op / launch_conv_igemm / launch_conv_split
-    if (s.skip) return "(fused)";
-    if (s.c3_head) return "c3_fused_kernel";
-    if (s.c3b_head) return "c3b_kernel";
-    if (s.post_head && conv_halo3_post_supported(s.post_args)) return "conv_halo3_kernel+1x1";
-    if (s.segp_head && conv_halo3_segp_supported(s.post_args)) return "conv_halo3_kernel+taps";
-    if (s.stemsp_head) return "stem_split_kernel";
-    const bool mfma = s.impl == IMPL_IGEMM || s.impl == IMPL_IGEMM_T;
-    if (mfma && s.split) return conv_split_halo_supported(s.args) ? "conv_split_halo_kernel" : "conv_split_kernel";
-    if (mfma && !f16) return "conv_f32_mfma_kernel";
-    if (mfma) {
-      ConvArgs a = s.args;
-      if (!a.bk) a.bk = igemm_pick_bk(a.s0.c, a.s1.c, a.K, a.N, 0);
-      const bool d32 = o.kind == CTD_OP_CONV && e->tensors[o.dst].esize == 4;
-      if (conv_halo3_supported(a, d32)) return "conv_halo3_kernel";
-      if (conv_halo2_supported(a, d32)) return "conv_halo2_kernel";
-      if (conv_halo_supported(a, d32)) return "conv_halo_kernel";
-      return "conv_igemm_kernel";
-    }
-    return o.kind == CTD_OP_CONV ? "conv_direct_kernel" : "convt_direct_kernel";
-  };
-  switch (o.kind) {
-    case CTD_OP_INPUT: k = s.skip ? "(fused)" : "input_kernel"; break;
-    case CTD_OP_STEM: k = s.stem2_head ? "stem_conv2_kernel" : "stem_mfma_kernel"; break;
-    case CTD_OP_CONV:
-    case CTD_OP_CONVT: k = conv_kernel(); break;
-    case CTD_OP_MAXPOOL: k = s.skip ? "(fused)" : s.sppf_head ? "sppf_pool3_kernel" : "maxpool_kernel"; break;
-    case CTD_OP_AVGPOOL2: k = "avgpool2_kernel"; break;
-    case CTD_OP_DETECT: k = "detect_decode_kernel"; break;
-    case CTD_OP_EXPORT: k = "export_plane_kernel"; break;
-    case CTD_OP_SEG_FINAL: k = (i > 0 && e->ops[i - 1].segp_head && conv_halo3_segp_supported(e->ops[i - 1].post_args)) ? "seg_final_gather_kernel" : e->tensors[o.src0].esize == 4 ? "seg_final_f32_kernel" : (g_seg_final_mfma ? "seg_final_mfma_kernel" : "seg_final_kernel"); break;
-    case CTD_OP_DB_UP: k = (e->tensors[o.src0].esize == 2 && g_db_up_mfma) ? "db_up_mfma_kernel" : "db_up_kernel"; break;
-  }
-  std::snprintf(name, (size_t)cap, "%s", k);
+  std::snprintf(name, (size_t)cap, "%s", e->ops[i].ran.c_str());
   return CTD_OK;
 }
 
@@ -1251,7 +1249,7 @@ int ctd_engine_profile(ctd_engine* e, const void* input_dev, int32_t input_fmt, 
          e->det_rows_per_unit * (H / 64) * (W / 64)};
   HIP_TRY(hipEventRecord(ev[0], st));
   for (int i = 0; i < n; ++i) {
-    if (int rc = launch_op(e, i, x, st)) return rc;
+    launch_op(e, i, x, st);
     HIP_TRY(hipEventRecord(ev[i + 1], st));
   }
   HIP_TRY(hipStreamSynchronize(st));
@@ -1288,48 +1286,51 @@ int64_t ctd_engine_workspace_bytes(const ctd_engine* e) { return e ? (int64_t)e-
 int32_t ctd_engine_arena_generation(const ctd_engine* e) { return e ? e->arena_gen : -1; }
 
 int ctd_tuning_set(const char* key, int64_t value) {
-  if (key && std::string(key) == "fuse") { g_fuse = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "tail_max_blocks") { g_tail_max_blocks = (int)std::max<int64_t>(1, value); return CTD_OK; }
-  if (key && std::string(key) == "tail_chain") { g_tail_chain = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "tail_fused_rounds") { g_tail_fused_rounds = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "tail_fused_max_pix") { g_tail_fused_max_pix = value; return CTD_OK; }
-  if (key && std::string(key) == "tail_lds") { g_tail_lds = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "tail_lds_rcap") { g_tail_lds_rcap = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "tail_lds_max_bytes") { g_tail_lds_max_bytes = value; return CTD_OK; }
-  if (key && std::string(key) == "tail_lds_runs_x10") { g_tw_lds_runs_x10 = (int)std::max<int64_t>(1, value); return CTD_OK; }
-  if (key && std::string(key) == "tail_lds_threads") { g_tw_lds_threads = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "tail_lds_cls0") { g_tail_lds_cls0 = value; return CTD_OK; }
-  if (key && std::string(key) == "tail_lds_cls1") { g_tail_lds_cls1 = value; return CTD_OK; }
-  if (key && std::string(key) == "tail_dma_min") { g_tail_dma_min = value; return CTD_OK; }
+  const std::string k = key ? key : "";
+  if (k == "fuse") g_fuse = (int)value;
+  else if (k == "tail_max_blocks") g_tail_max_blocks = (int)std::max<int64_t>(1, value);
+  else if (k == "tail_chain") g_tail_chain = (int)value;
+  else if (k == "tail_fused_rounds") g_tail_fused_rounds = (int)value;
+  else if (k == "tail_fused_max_pix") g_tail_fused_max_pix = value;
+  else if (k == "tail_lds") g_tail_lds = (int)value;
+  else if (k == "tail_lds_rcap") g_tail_lds_rcap = (int)value;
+  else if (k == "tail_lds_max_bytes") g_tail_lds_max_bytes = value;
+  else if (k == "tail_lds_runs_x10") g_tw_lds_runs_x10 = (int)std::max<int64_t>(1, value);
+  else if (k == "tail_lds_threads") g_tw_lds_threads = (int)value;
+  else if (k == "tail_lds_cls0") g_tail_lds_cls0 = value;
+  else if (k == "tail_lds_cls1") g_tail_lds_cls1 = value;
+  else if (k == "tail_dma_min") g_tail_dma_min = value;
 #ifdef CTD_MEASURE_KNOBS   // not in the shipped library: these return incomplete results
-  if (key && std::string(key) == "tail_skip_page_download") { g_tail_skip_pages = value != 0; return CTD_OK; }
-  if (key && std::string(key) == "tail_ablate") { g_tail_ablate = (int)value; return CTD_OK; }
+  else if (k == "tail_skip_page_download") g_tail_skip_pages = value != 0;
+  else if (k == "tail_ablate") g_tail_ablate = (int)value;
 #endif
-  if (key && std::string(key) == "tail_priority") { g_tail_priority = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "tail_cus") { g_tail_cus = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "tail_cu_first") { g_tail_cu_first = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "no_reuse") { g_no_reuse = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "f32_mfma") { g_f32_mfma = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "split_halo") { g_split_halo = (int)value; return CTD_OK; }
+  else if (k == "tail_priority") g_tail_priority = (int)value;
+  else if (k == "tail_cus") g_tail_cus = (int)value;
+  else if (k == "tail_cu_first") g_tail_cu_first = (int)value;
+  else if (k == "no_reuse") g_no_reuse = (int)value;
+  else if (k == "f32_mfma") g_f32_mfma = (int)value;
+  else if (k == "split_halo") g_split_halo = (int)value;
 #ifdef CTD_AB_VARIANTS
-  if (key && std::string(key) == "split_halo_small") { g_split_halo_small = (int)value; return CTD_OK; }
+  else if (k == "split_halo_small") g_split_halo_small = (int)value;
 #endif
-  if (key && std::string(key) == "split_halo_min_patches") { g_split_halo_min_patches = value; return CTD_OK; }
-  if (key && std::string(key) == "fwd_prio") { g_fwd_prio = (int)value; ++g_fuse_epoch; return CTD_OK; }
-  if (key && std::string(key) == "split_stem") { g_split_stem = (int)value; ++g_fuse_epoch; return CTD_OK; }
-  if (key && std::string(key) == "split_planes") { g_split_planes = (int)value; ++g_fuse_epoch; return CTD_OK; }
+  else if (k == "split_halo_min_patches") g_split_halo_min_patches = value;
+  else if (k == "fwd_prio") g_fwd_prio = (int)value;
+  else if (k == "split_stem") g_split_stem = (int)value;
+  else if (k == "split_planes") g_split_planes = (int)value;
 #ifdef CTD_AB_VARIANTS
-  if (key && std::string(key) == "split_wdma") { g_split_wdma = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "split_bm256") { g_split_bm256 = (int)value; return CTD_OK; }
+  else if (k == "split_wdma") g_split_wdma = (int)value;
+  else if (k == "split_bm256") g_split_bm256 = (int)value;
 #endif
-  if (key && std::string(key) == "db_up_mfma") { g_db_up_mfma = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "seg_final_mfma") { g_seg_final_mfma = (int)value; return CTD_OK; }
-  if (key && std::string(key) == "c3_min_patches") { g_c3_min_patches = value; g_fuse_epoch++; return CTD_OK; }
-  if (key && std::string(key) == "c3b_min_patches") { g_c3b_min_patches = value; g_fuse_epoch++; return CTD_OK; }
-  if (key && std::string(key) == "c3b_max_ch") { g_c3b_max_ch = (int)value; g_fuse_epoch++; return CTD_OK; }
-  if (key && std::string(key) == "c3b_cfg64") { g_c3b_cfg64 = (int)value; g_fuse_epoch++; return CTD_OK; }
-  if (key && std::string(key) == "c3b_cfg128") { g_c3b_cfg128 = (int)value; g_fuse_epoch++; return CTD_OK; }
-  if (conv_tuning_set(key, (long long)value) != 0) return fail(CTD_ERR_INVALID, "unknown tuning key");
+  else if (k == "db_up_mfma") g_db_up_mfma = (int)value;
+  else if (k == "seg_final_mfma") g_seg_final_mfma = (int)value;
+  else if (k == "c3_min_patches") g_c3_min_patches = value;
+  else if (k == "c3b_min_patches") g_c3b_min_patches = value;
+  else if (k == "c3b_max_ch") g_c3b_max_ch = (int)value;
+  else if (k == "c3b_cfg64") g_c3b_cfg64 = (int)value;
+  else if (k == "c3b_cfg128") g_c3b_cfg128 = (int)value;
+  else if (conv_tuning_set(key, (long long)value) != 0) return fail(CTD_ERR_INVALID, "unknown tuning key");
+  // every key but the tail's is read by plan() or by a launcher whose choice a plan builds on: cached plans are re-made
+  if (k.compare(0, 5, "tail_") != 0) ++g_plan_epoch;
   return CTD_OK;
 }
 

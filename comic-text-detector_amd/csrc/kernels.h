@@ -42,7 +42,8 @@ void igemm_pack_weights(const float* logical, int nphase, int N, int K, int bn, 
                         std::vector<half_t>& out);
 bool igemm_supported(const ConvArgs& a);
 int igemm_ntile(int N);  // N tile the dispatcher will use (weights must be padded to it)
-void launch_conv_igemm(const ConvArgs& a, bool dst_f32, hipStream_t st);   // dispatches to the halo kernel when it applies
+// dispatches to a halo kernel when one applies; returns the name of the kernel it launched
+const char* launch_conv_igemm(const ConvArgs& a, bool dst_f32, hipStream_t st);
 
 // ---- kernels_f32.hip : f32-operand MFMA implicit-GEMM conv (the exact-fp32 engine) ----
 // weights: f32 [nphase][Npad][K], K index = (ty*KW+tx)*(c0+c1) + c; bias f32 padded to Npad
@@ -56,7 +57,8 @@ extern int g_split_wdma;   // selftest build: 0 = weight tiles through registers
 extern int g_split_bm256;  // selftest build: 1 = 256-pixel blocks for 64-channel N tiles (ctd_tuning_set("split_bm256"))
 #endif
 bool conv_split_supported(const ConvArgs& a);
-void launch_conv_split(const ConvArgs& a, hipStream_t st);   // dispatches to the halo kernel below when it applies
+// dispatches to the halo kernel below when it applies; returns the name of the kernel it launched
+const char* launch_conv_split(const ConvArgs& a, hipStream_t st);
 // ---- kernels_split_stem.hip : the fp32s engine's first layer straight from the network input (no INPUT launch) ----
 bool stem_split_supported(const ConvArgs& a);
 void launch_stem_split(const ConvArgs& a, const void* input, int in_fmt, hipStream_t st);
@@ -157,9 +159,9 @@ void launch_stem_conv2(const Stem2Args& a, hipStream_t st);
 void launch_stem(const void* in, int in_fmt, half_t* dst, int pitchD, int B, int H, int W, int N,
                  const half_t* wfrag, const float* bias, int act, hipStream_t st);
 void stem_pack_weights(const float* W /* (32, 3, 6, 6) */, std::vector<half_t>& out);
-// seg final: ConvT 4x4 s2 p1 (C -> 1) + sigmoid; src (B,H,W,C) half; weights f32 [16][C] (ky*4+kx)
-void launch_seg_final(const half_t* src, int pitch, int C, int B, int H, int W, const float* w, float bias,
-                      float* mask, uint8_t* mask_u8, hipStream_t st);
+// seg final: ConvT 4x4 s2 p1 (C -> 1) + sigmoid; src (B,H,W,C) half; weights f32 [16][C] (ky*4+kx); returns the kernel's name
+const char* launch_seg_final(const half_t* src, int pitch, int C, int B, int H, int W, const float* w, float bias,
+                             float* mask, uint8_t* mask_u8, hipStream_t st);
 // db tail: src (B,H,W, 2q) half [binarize q | thresh q] (already conv3x3+BN+ReLU)
 // params f32 per branch: W1[q][q][2][2] (cin,cout,ky,kx) b1[q] W2[q][1][2][2] b2[1]
 void launch_seg_final_f32(const float* src, int pitch, int C, int B, int H, int W, const float* w, float* mask,
@@ -168,8 +170,9 @@ void launch_seg_final_f32(const float* src, int pitch, int C, int B, int H, int 
 void launch_seg_final_gather(const float* P, int B, int H, int W, float bias, float* mask, uint8_t* mask_u8, hipStream_t st);
 extern int g_seg_final_mfma;   // fp16 engine: seg-final's channel reduction on the MFMA (CTD_SEGFINAL_MFMA / "seg_final_mfma")
 extern int g_db_up_mfma;   // fp16 engine: DB tail's first stage on the MFMA (CTD_DBUP_MFMA / ctd_tuning_set("db_up_mfma"))
-void launch_db_up(const void* src, bool f32in, int pitch, int q, int nbr, int B, int H, int W, const float* params, float* lines,
-                  uint8_t* bitmap, float thresh, hipStream_t st);
+// returns the name of the kernel it launched
+const char* launch_db_up(const void* src, bool f32in, int pitch, int q, int nbr, int B, int H, int W, const float* params,
+                         float* lines, uint8_t* bitmap, float thresh, hipStream_t st);
 
 // ---- kernels_post.hip -------------------------------------------------------
 size_t nms_workspace_bytes(int B, int rows);

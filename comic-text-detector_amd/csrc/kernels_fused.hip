@@ -699,14 +699,15 @@ void stem_pack_weights(const float* W /* (32, 3, 6, 6) */, std::vector<half_t>& 
         }
 }
 
-void launch_seg_final(const half_t* src, int pitch, int C, int B, int H, int W, const float* w, float bias,
-                      float* mask, uint8_t* mask_u8, hipStream_t st) {
+const char* launch_seg_final(const half_t* src, int pitch, int C, int B, int H, int W, const float* w, float bias,
+                             float* mask, uint8_t* mask_u8, hipStream_t st) {
   const int g = ((W + SF_T - 1) / SF_T) * ((H + SF_T - 1) / SF_T) * B;
-  if (g_seg_final_mfma && C == 64 && pitch % 8 == 0 && (((uintptr_t)src | (uintptr_t)w) & 15) == 0)
+  if (g_seg_final_mfma && C == 64 && pitch % 8 == 0 && (((uintptr_t)src | (uintptr_t)w) & 15) == 0) {
     hipLaunchKernelGGL(seg_final_mfma_kernel, dim3(g), dim3(256), 0, st, src, pitch, B, H, W, (const half_t*)w, bias, mask, mask_u8);
-  else
-    hipLaunchKernelGGL((seg_final_kernel<64>), dim3(g), dim3(256), 0, st, src, pitch, B, H, W, w, bias, mask, mask_u8);
-  (void)C;
+    return "seg_final_mfma_kernel";
+  }
+  hipLaunchKernelGGL((seg_final_kernel<64>), dim3(g), dim3(256), 0, st, src, pitch, B, H, W, w, bias, mask, mask_u8);
+  return "seg_final_kernel";
 }
 
 void launch_seg_final_f32(const float* src, int pitch, int C, int B, int H, int W, const float* w, float* mask,
@@ -719,8 +720,8 @@ void launch_seg_final_f32(const float* src, int pitch, int C, int B, int H, int 
 int g_seg_final_mfma = 1;   // ctd_tuning_set("seg_final_mfma", 0): the VALU kernel (the fallback for odd pitches; A/B reference)
 int g_db_up_mfma = 1;   // ctd_tuning_set("db_up_mfma", 0): the VALU kernel (the fallback for odd pitches; A/B reference)
 
-void launch_db_up(const void* src, bool f32in, int pitch, int q, int nbr, int B, int H, int W, const float* params, float* lines,
-                  uint8_t* bitmap, float thresh, hipStream_t st) {
+const char* launch_db_up(const void* src, bool f32in, int pitch, int q, int nbr, int B, int H, int W, const float* params,
+                         float* lines, uint8_t* bitmap, float thresh, hipStream_t st) {
   const long long total = (long long)B * H * W;
   const int g = (int)((total + 255) / 256);
   if (f32in)
@@ -731,8 +732,10 @@ void launch_db_up(const void* src, bool f32in, int pitch, int q, int nbr, int B,
     const int blocks = (int)std::min<long long>((ngroups + 3) / 4, 256 * 16);
     hipLaunchKernelGGL(db_up_mfma_kernel, dim3(blocks), dim3(256), 0, st, (const half_t*)src, pitch, nbr, B, H, W, params, lines,
                        bitmap, thresh, ngroups);
+    return "db_up_mfma_kernel";
   } else
     hipLaunchKernelGGL((db_up_kernel<16, half_t>), dim3(g), dim3(256), 0, st, (const half_t*)src, pitch, nbr, B, H, W, params,
                        lines, bitmap, thresh);
   (void)q;
+  return "db_up_kernel";
 }

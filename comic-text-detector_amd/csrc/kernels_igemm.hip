@@ -591,23 +591,14 @@ static void magic_div(int d, unsigned& mul, unsigned& sh) {
   mul = (unsigned)(((1ull << sh) / (unsigned)d) + 1);
 }
 
-void launch_conv_igemm(const ConvArgs& a_in, bool dst_f32, hipStream_t st) {
+const char* launch_conv_igemm(const ConvArgs& a_in, bool dst_f32, hipStream_t st) {
   ConvArgs a = a_in;
   magic_div(a.Mw, a.mw_mul, a.mw_sh);
   magic_div(a.Mh, a.mh_mul, a.mh_sh);
   a.bk = pick_bk(a);
-  if (conv_halo3_supported(a, dst_f32)) {
-    launch_conv_halo3(a, st);
-    return;
-  }
-  if (conv_halo2_supported(a, dst_f32)) {
-    launch_conv_halo2(a, st);
-    return;
-  }
-  if (conv_halo_supported(a, dst_f32)) {
-    launch_conv_halo(a, st);
-    return;
-  }
+  if (conv_halo3_supported(a, dst_f32)) { launch_conv_halo3(a, st); return "conv_halo3_kernel"; }
+  if (conv_halo2_supported(a, dst_f32)) { launch_conv_halo2(a, st); return "conv_halo2_kernel"; }
+  if (conv_halo_supported(a, dst_f32)) { launch_conv_halo(a, st); return "conv_halo_kernel"; }
   const int bn = igemm_ntile(a.N);
   if (pick_bk(a) == 64) {
     if (bn == 128) launch_cfg<128, 128, 2, 2, 64>(a, dst_f32, st);
@@ -618,6 +609,7 @@ void launch_conv_igemm(const ConvArgs& a_in, bool dst_f32, hipStream_t st) {
     else if (bn == 64) launch_cfg<64, 128, 2, 2, 32>(a, dst_f32, st);
     else launch_cfg<32, 128, 1, 4, 32>(a, dst_f32, st);
   }
+  return "conv_igemm_kernel";
 }
 
 void launch_mfma_probe(const half_t* a, const half_t* b, float* out, hipStream_t st) {

@@ -397,8 +397,8 @@ bool conv_split_supported(const ConvArgs& a) {
   return a.nphase == 1 || a.nphase == 4;
 }
 
-void launch_conv_split(const ConvArgs& a, hipStream_t st) {
-  if (conv_split_halo_supported(a)) return launch_conv_split_halo(a, st);
+const char* launch_conv_split(const ConvArgs& a, hipStream_t st) {
+  if (conv_split_halo_supported(a)) { launch_conv_split_halo(a, st); return "conv_split_halo_kernel"; }
   int bn = a.Npad % 128 == 0 ? 128 : (a.Npad % 64 == 0 ? 64 : 32);
   // small maps: narrower N tiles give 2-4x the blocks (the packing is in 32-row blocks, any multiple of 32 reads it)
   const long long ntm = (a.M + 127) / 128;
@@ -409,6 +409,7 @@ void launch_conv_split(const ConvArgs& a, hipStream_t st) {
 #endif
   else if (bn == 64) launch_split_cfg<64, 128, 1, 4>(a, st);
   else launch_split_cfg<32, 128, 1, 4>(a, st);
+  return "conv_split_kernel";
 }
 
 // logical weights float [nphase][N][K] (K index = tap * Ctot + c) -> hi plane, lo plane ([nphase][npad/32][K/32][32][32]

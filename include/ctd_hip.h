@@ -155,10 +155,11 @@ int ctd_engine_op_work(const ctd_engine* e, double* flops, double* bytes, int32_
 /* kernel_class: 0 = pointwise/pool/export, 1 = MFMA implicit-GEMM conv, 2 = MFMA convT,
  *               3 = direct (VALU) conv, 4 = fused stem / seg-final / db-up */
 
-/* ABI v5.  Name of the kernel op `op_index` launches under the CURRENT plan and tuning ("conv_halo3_kernel",
- * "conv_igemm_kernel", "c3b_kernel", ...; "(fused)" for an op whose work another op's launch does): lets a test assert
- * WHICH dispatch a parity comparison ran through (grid thresholds pick different kernels at B = 1 and B = 32).  `name` gets
- * at most cap - 1 characters and a terminator.  Valid after a forward / profile of the shape in question. */
+/* ABI v5.  Name of the kernel op `op_index` launched in the last forward / profile ("conv_halo3_kernel",
+ * "conv_igemm_kernel", "c3b_kernel", ...; "(fused)" for an op whose work another op's launch did; "(none)" for an op that
+ * launched nothing because the caller passed no buffer for any of its outputs): lets a test assert WHICH dispatch a parity
+ * comparison ran through (grid thresholds pick different kernels at B = 1 and B = 32).  `name` gets at most cap - 1
+ * characters and a terminator.  Valid after a forward / profile. */
 int ctd_engine_op_kernel(const ctd_engine* e, int32_t op_index, char* name, int32_t cap);
 
 /* Runs one forward with a hipEvent pair around every op on `stream` and
@@ -184,11 +185,12 @@ int32_t ctd_engine_arena_generation(const ctd_engine* e);
 /* Kernel-dispatch knobs (process-wide; no reference counterpart).  Keys: "halo_min_patches" (default 1024:
  * maps with fewer 16x16 patches take the implicit-GEMM kernel), "halo" (0: never the halo kernel), "halo_pair",
  * "halo_1x1"; "fuse" = bit mask of the fp16 engine's multi-layer kernels (1: C3 block with 32 hidden channels,
- * 2: SPPF's three pools, 4: stem + layer 1; default 7; 0 = one launch per layer; results are bit-identical either
- * way), "c3_min_patches" (default 1024: smaller grids take the per-layer kernels); "db_up_mfma" / "seg_final_mfma"
- * (default 1: the DB tail / the seg-final layer with their channel reductions on the MFMA, 0: the VALU kernels; same
+ * 2: SPPF's three pools, 4: stem + layer 1, 8: C3 bottlenecks with 64 / 128 hidden channels, 16: ConvTranspose + its 1x1
+ * consumer, 32: the last ConvTranspose + seg-final's tap products; default 63; 0 = one launch per layer; results are
+ * bit-identical either way), "c3_min_patches" (default 1024: smaller grids take the per-layer kernels);
+ * "db_up_mfma" / "seg_final_mfma" (default 1: the DB tail / the seg-final layer with their channel reductions on the MFMA, 0: the VALU kernels; same
  * results within 2e-4 / 1e-6).  The environment variables CTD_HALO_* / CTD_FUSE / CTD_DBUP_MFMA / CTD_SEGFINAL_MFMA give
- * the initial values.  Engines re-plan on their next forward.  For tests and A/B
+ * the initial values.  Engines re-plan on their next forward after any key but the tail_* keys.  For tests and A/B
  * measurements. */
 int ctd_tuning_set(const char* key, int64_t value);
 
