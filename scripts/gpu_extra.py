@@ -41,7 +41,7 @@ for B in (1, 4):
     out[f"fwd_ms_b{B}_graph"] = round(timeit(replay), 3)
 
 from test_post_host import fake_outputs          # noqa: E402
-from test_gpu_e2e import blks_tensor             # noqa: E402
+from sweep_cases import blks_tensor              # noqa: E402
 det = pkg.detector.TextDetector(ck, input_size=1024, device="cuda", half=True)
 NP = int(os.environ.get("EXTRA_PAGES", "32"))
 pages, args = [], []

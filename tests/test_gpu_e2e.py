@@ -10,6 +10,7 @@ import torch
 
 from conftest import checkpoint, pkg
 from oracle import postproc_ref as R
+from sweep_cases import blks_tensor, letterbox_tail_case, tail_case   # noqa: F401 (blks_tensor: imported from here by other tests)
 from test_post_host import blocks_equal, fake_outputs
 
 pytestmark = pytest.mark.gpu
@@ -42,17 +43,6 @@ def full_outputs(det, x):
     assert torch.equal(b2, blks) and torch.equal(l2[:, 0], lines_map[:, 0])
     assert torch.equal(trim.mask_u8, side[0]) and torch.equal(trim.bitmap, side[1])
     return blks, mask, lines_map
-
-
-def blks_tensor(blks, rows=4096):
-    """(blines, cls, confs) -> a fake Detect tensor (1,rows,7) whose NMS gives those blocks back."""
-    blines, cls, confs = blks
-    t = np.zeros((1, rows, 7), np.float32)
-    for i, (bb, c, s) in enumerate(zip(blines, cls, confs)):
-        x1, y1, x2, y2 = bb
-        t[0, i] = [(x1 + x2) / 2, (y1 + y2) / 2, x2 - x1, y2 - y1, 0.99, 0.0, 0.0]
-        t[0, i, 5 + c] = s / 0.99
-    return t
 
 
 @pytest.mark.parametrize("seed,keep", [(0, False), (1, True), (2, True)])
@@ -91,85 +81,83 @@ def _equal_up_to_tied_lines(got, ref):
     return True
 
 
-def test_tail_seed_sweep_by_hand():
-    """CTD_TAIL_SWEEP="first:last[:size]" -- the whole-tail parity of the test above over a range of seeds, alternating the two
-    configurations (by hand; the suite skips it).  A page whose ONLY difference is the order of lines with tied distances is
-    counted apart (see `_equal_up_to_tied_lines`); anything else fails.  Round 6: the first sweep (120 pages) found four
-    mismatching pages -- numpy's default argsort (x86-simd-sort on this host) on blocks of more than 16 tied lines, numpy's SVML
-    arccos against glibc's acos ordering lines of one text row (the product now calls numpy's own functions for both,
-    csrc/np_dispatch.h), and two hull edges bounding rectangles of equal area told apart by rounding noise (both `min_area_box` use
-    a relative margin).  545 pages at seven sizes since: 0 mismatches, 0 tie-order differences."""
+def _tail_sweep(name, cases, strict):
+    """Runs (seed, keep, got, ref) of `cases` through the three assertions of the test above.  A page whose ONLY difference is the
+    order of lines with tied distances is counted apart (see `_equal_up_to_tied_lines`); anything else fails -- and with `strict`
+    (the default range, run by the suite) a page of the first kind fails too."""
+    bad, tied = [], []
+    for what, keep, got, ref in cases:
+        try:
+            np.testing.assert_array_equal(got[0], ref[0])
+            blocks_equal(got[2], ref[2])
+            np.testing.assert_array_equal(got[1], ref[1])
+        except AssertionError as e:
+            if np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and _equal_up_to_tied_lines(got[2], ref[2]):
+                tied.append(what)
+            else:
+                bad.append((what, keep, str(e)[:200]))
+    print(f"\n{name}: {len(bad)} mismatching pages {bad[:5]}; {len(tied)} pages equal up to the order of tied lines {tied}")
+    assert not bad, bad
+    if strict:
+        assert not tied, f"equal up to the order of tied lines only (the numeric fallback of csrc/np_dispatch.h?): {tied}"
+
+
+TAIL_SWEEP_DEFAULT = (1000, 1023, 1024)
+LETTERBOX_SWEEP_DEFAULT = (2000, 2023)
+
+
+def test_tail_seed_sweep():
+    """The whole-tail parity of the test above over a range of seeds, alternating the two configurations: seeds 1000 .. 1023 at
+    1024, or CTD_TAIL_SWEEP="first:last[:size]" by hand.  A page whose ONLY difference is the order of lines with tied distances
+    is counted apart (see `_equal_up_to_tied_lines`) and fails the default range only; anything else fails.  Round 6: the first
+    sweep (120 pages) found four mismatching pages -- numpy's default argsort (x86-simd-sort on this host) on blocks of more than
+    16 tied lines, numpy's SVML arccos against glibc's acos ordering lines of one text row (the product now calls numpy's own
+    functions for both, csrc/np_dispatch.h), and two hull edges bounding rectangles of equal area told apart by rounding noise
+    (both `min_area_box` use a relative margin).  545 pages at seven sizes since: 0 mismatches, 0 tie-order differences."""
     spec = os.environ.get("CTD_TAIL_SWEEP", "")
-    if not spec:
-        pytest.skip("set CTD_TAIL_SWEEP=first:last[:size]")
-    parts = [int(v) for v in spec.split(":")]
+    parts = [int(v) for v in spec.split(":")] if spec else list(TAIL_SWEEP_DEFAULT)
     first, last, size = parts[0], parts[1], (parts[2] if len(parts) > 2 else 1024)
     det = detector(size)
-    bad, tied = [], []
-    for seed in range(first, last + 1):
-        keep = bool(seed & 1)
-        page, mask_u8, prob, blks = fake_outputs(seed, size)
-        bt = blks_tensor(blks)
-        bitmap = (prob > 0.3).astype(np.uint8)
-        got = det.tail_batch([page], torch.from_numpy(bt).cuda(), torch.from_numpy(mask_u8)[None].cuda(),
-                             torch.from_numpy(prob)[None].cuda(), torch.from_numpy(bitmap)[None].cuda(),
-                             refine_mode=1 if keep else 0, keep_undetected_mask=keep)[0]
-        mask_f = (mask_u8.astype(np.float32) + 0.5) / 255
-        lines_map = np.stack([prob, np.zeros_like(prob)])[None]
-        ref = R.detector_tail(page, bt, mask_f[None, None], lines_map, input_size=(size, size),
-                              refine_mode=1 if keep else 0, keep_undetected_mask=keep)
-        try:
-            np.testing.assert_array_equal(got[0], ref[0])
-            blocks_equal(got[2], ref[2])
-            np.testing.assert_array_equal(got[1], ref[1])
-        except AssertionError as e:
-            if np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and _equal_up_to_tied_lines(got[2], ref[2]):
-                tied.append(seed)
-            else:
-                bad.append((seed, keep, str(e)[:200]))
-    print(f"\ntail sweep: seeds {first}..{last} at {size}: {len(bad)} mismatching pages {bad[:5]}; "
-          f"{len(tied)} pages equal up to the order of tied lines {tied}")
-    assert not bad, bad
+
+    def cases():
+        for seed in range(first, last + 1):
+            keep = bool(seed & 1)
+            page, bt, mask_u8, prob, mask_f, lines_map, what = tail_case(seed, size)
+            bitmap = (prob > 0.3).astype(np.uint8)
+            got = det.tail_batch([page], torch.from_numpy(bt).cuda(), torch.from_numpy(mask_u8)[None].cuda(),
+                                 torch.from_numpy(prob)[None].cuda(), torch.from_numpy(bitmap)[None].cuda(),
+                                 refine_mode=1 if keep else 0, keep_undetected_mask=keep)[0]
+            ref = R.detector_tail(page, bt, mask_f, lines_map, input_size=(size, size),
+                                  refine_mode=1 if keep else 0, keep_undetected_mask=keep)
+            yield seed, keep, got, ref
+    _tail_sweep(f"tail sweep: seeds {first}..{last} at {size}", cases(), strict=not spec)
 
 
-def test_letterboxed_tail_sweep_by_hand():
-    """CTD_LETTERBOX_SWEEP="first:last" -- pages of RANDOM sizes and aspect ratios (200 .. 1500 pixels a side) with network
-    outputs consistent with their letterbox at 512 (tests/test_reference_pin.py `letterboxed_case`): the native tail's inverse
-    mapping (mask crop + resize to the page, box / line rescale with the reference's truncations) and everything after it against
-    `R.detector_tail`, both configurations (by hand; the suite skips it)."""
+def test_letterboxed_tail_sweep():
+    """Pages of RANDOM sizes and aspect ratios (200 .. 1500 pixels a side) with network outputs consistent with their letterbox
+    at 512 (tests/sweep_cases.py `letterbox_tail_case`): the native tail's inverse mapping (mask crop + resize to the page, box /
+    line rescale with the reference's truncations) and everything after it against `R.detector_tail`, both configurations.
+    Seeds 2000 .. 2023, or CTD_LETTERBOX_SWEEP="first:last" by hand (tied-line order fails the default range only)."""
     spec = os.environ.get("CTD_LETTERBOX_SWEEP", "")
-    if not spec:
-        pytest.skip("set CTD_LETTERBOX_SWEEP=first:last")
-    from test_reference_pin import letterboxed_case
-    first, last = [int(v) for v in spec.split(":")[:2]]
+    first, last = [int(v) for v in spec.split(":")[:2]] if spec else LETTERBOX_SWEEP_DEFAULT
     size = 512
     det = detector(size)
-    bad, tied = [], []
-    for seed in range(first, last + 1):
-        rng = np.random.RandomState(7000 + seed)
-        im_hw = (int(rng.randint(200, 1500)), int(rng.randint(200, 1500)))
-        keep = bool(seed & 1)
-        page, bt, mask, lines_map, (dw, dh) = letterboxed_case(seed, im_hw, size)
-        prob = np.ascontiguousarray(lines_map[0, 0])
-        mask_u8 = (mask[0, 0] * 255).astype(np.uint8)                 # postprocess_mask's truncation
-        bitmap = (prob > 0.3).astype(np.uint8)
-        got = det.tail_batch([page], torch.from_numpy(bt).cuda(), torch.from_numpy(mask_u8)[None].cuda(),
-                             torch.from_numpy(prob)[None].cuda(), torch.from_numpy(bitmap)[None].cuda(),
-                             refine_mode=1 if keep else 0, keep_undetected_mask=keep,
-                             metas=[(im_hw[0], im_hw[1], dw, dh)])[0]
-        ref = R.detector_tail(page, bt, mask, lines_map, input_size=(size, size), dw=dw, dh=dh,
-                              refine_mode=1 if keep else 0, keep_undetected_mask=keep)
-        try:
-            np.testing.assert_array_equal(got[0], ref[0])
-            blocks_equal(got[2], ref[2])
-            np.testing.assert_array_equal(got[1], ref[1])
-        except AssertionError as e:
-            if np.array_equal(got[0], ref[0]) and np.array_equal(got[1], ref[1]) and _equal_up_to_tied_lines(got[2], ref[2]):
-                tied.append(seed)
-            else:
-                bad.append((seed, im_hw, keep, str(e)[:160]))
-    print(f"\nletterbox sweep: seeds {first}..{last}: {len(bad)} mismatching pages {bad[:4]}; tied-line order only: {tied}")
-    assert not bad, bad
+
+    def cases():
+        for seed in range(first, last + 1):
+            keep = bool(seed & 1)
+            page, bt, mask, lines_map, (dw, dh), what = letterbox_tail_case(seed, size)
+            prob = np.ascontiguousarray(lines_map[0, 0])
+            mask_u8 = (mask[0, 0] * 255).astype(np.uint8)                 # postprocess_mask's truncation
+            bitmap = (prob > 0.3).astype(np.uint8)
+            got = det.tail_batch([page], torch.from_numpy(bt).cuda(), torch.from_numpy(mask_u8)[None].cuda(),
+                                 torch.from_numpy(prob)[None].cuda(), torch.from_numpy(bitmap)[None].cuda(),
+                                 refine_mode=1 if keep else 0, keep_undetected_mask=keep,
+                                 metas=[(page.shape[0], page.shape[1], dw, dh)])[0]
+            ref = R.detector_tail(page, bt, mask, lines_map, input_size=(size, size), dw=dw, dh=dh,
+                                  refine_mode=1 if keep else 0, keep_undetected_mask=keep)
+            yield (seed, page.shape[:2]), keep, got, ref
+    _tail_sweep(f"letterbox sweep: seeds {first}..{last}", cases(), strict=not spec)
 
 
 def test_full_detector_on_network_outputs_matches_oracle():

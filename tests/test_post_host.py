@@ -69,7 +69,7 @@ def test_db_boxes_group_output_match_oracle(seed):
 ])
 def test_native_host_stages_on_the_findings_of_the_round6_seed_sweep(seed, size, what):
     """The five pages (of 120) on which the first seed sweep of the whole-tail parity test (tests/test_gpu_e2e.py
-    `test_tail_seed_sweep_by_hand`) found the product's native host code and the oracle apart -- every one a TIE that the
+    `test_tail_seed_sweep`) found the product's native host code and the oracle apart -- every one a TIE that the
     reference breaks by an implementation detail of numpy.  DB boxes (product geometry on scipy labels) and grouping against
     the oracle, as in the test above; DESIGN 5."""
     p = pkg()

@@ -97,7 +97,7 @@ def test_speckle_bitmaps_equal_reference_code():
 def letterboxed_case(seed, im_hw=(420, 300), size=512):
     """A page of another aspect ratio + network outputs that are consistent with its letterbox."""
     from oracle import cv_ref as cv
-    from test_gpu_e2e import blks_tensor
+    from sweep_cases import blks_tensor
     page512, mask_u8, prob, blks = fake_outputs(seed, size)
     im_h, im_w = im_hw
     r = min(size / im_h, size / im_w)
