@@ -46,10 +46,20 @@ SEG_FINAL: the ConvT bound + sigmoid + f32 storage.
 Exact ops stay exact: MAXPOOL is bit-identical to the max of the engine's own input; EXPORT copies; on the engine's own
 outputs bitmap == (lines[:, 0] > thresh) and mask_u8 == (mask * float32(255)).astype(uint8) (reference inference.py).
 
-Sampling.  Maps larger than 128 x 128 per page are checked on 16 x 16 output windows, all channels, on pages 0 and
-B - 1: the four corners, the middle of each edge, windows straddling the seams at 16, 32, 64, 128 and 256 (patch and
-tile edges of the halo, halo3 and split-halo kernels) and four seeded random windows.  The reference of a window is
-computed from a zero-padded crop of the input.  Smaller maps are checked in full on every page.
+Sampling.  Maps larger than 128 x 128 per page are checked on 16 x 16 output windows, all channels.  The windows follow the
+kernels' geometry (`EDGES`, one row per patch / tile shape with the kernel it comes from): for every row of the table the
+windows straddle the first, one interior (nearest the middle) and the LAST interior multiple of the edge, in both axes and
+crossed with each other -- corners of four patches, 3 x 3 per row of the table.  `LINEAR_BLOCKS` adds, in a late row, the two
+ends of a row wrap and the block edge nearest to it for the kernels that walk the map in linear blocks of pixels.  On top of
+that the earlier set stays as it was: the four corners, the middle of each edge, the seams at 16, 32, 64, 128 and 256 on
+the diagonal and on two crosses, and four seeded random windows.  The reference of a window is computed from a zero-padded
+crop of the input.  Smaller maps are checked in full.
+
+Pages.  Without `pages`: the sampled maps on pages 0 and B - 1, the smaller maps on every page.  With `pages`: every op on
+exactly those pages; the checker then keeps only those pages of every tensor it reads (`read_tensor` hands out all B), and
+`check_all` drops a tensor once no later op's check reads it.  What a sampled check leaves out is stated as a condition (every
+row of `EDGES`, every requested page, for every op); the share of elements it looked at is reported (`n` of `total`), no
+number is asserted for it.
 """
 from __future__ import annotations
 
@@ -70,6 +80,23 @@ ENGINES = ("fp32", "fp32s", "fp16")
 WIN = 16
 FULL_MAX = 128
 SEAMS = (16, 32, 64, 128, 256)
+# (rows, columns) of a patch / tile in OUTPUT pixels, and the kernels that cut the map that way (their own constants, as
+# tests/c3_emul.py, tests/stem2_emul.py, tests/test_halo3_emul.py and tests/test_split_halo_emul.py restate them)
+EDGES = (
+    (16, 16, "conv_halo_kernel, conv_halo3_kernel (kernels_halo*.hip TWP x THP = 16 x 16), conv_split_halo_kernel THP = 16, "
+             "stem_split_kernel (kernels_split_stem.hip ST = 16), kernels_fused.hip SF_T = 16"),
+    (8, 16, "c3_fused_kernel (C3_TW x C3_TH = 16 x 8), c3b_kernel (BW = 16, BH = 8), stem_conv2_kernel (S2_TW x S2_TH = 16 x 8), "
+            "conv_split_halo_kernel THP = 8"),
+    (8, 32, "the first layer of kernels_fused.hip (SM_TW x SM_TH = 32 x 8 outputs)"),
+    (32, 32, "a ConvTranspose 4x4 / stride 2 through conv_halo_kernel / conv_halo3_kernel / conv_split_halo_kernel (a 16 x 16 "
+             "input patch writes 32 x 32) and seg_final_mfma_kernel / seg_final_gather_kernel (SF_T = 16 input pixels, 2 x 2 each)"),
+    (4, 128, "db_up_mfma_kernel: a group of 32 quarter-resolution pixels writes 4 rows of 128 outputs"),
+    (64, 64, "a 16 x 16 patch two stride-2 ConvTransposes below the map (the heads' last two layers)"),
+    (128, 128, "conv_f32_kernel (FBM = 128), conv_igemm_kernel / conv_split_kernel BM = 128: block edges of a map whose width "
+               "is a multiple of 128, and a block of whole rows"),
+    (256, 256, "conv_igemm_kernel / conv_split_kernel BM = 256 (SBM): likewise"),
+)
+LINEAR_BLOCKS = (128, 256)          # pixels per block of kernels_f32.hip / kernels_igemm.hip / kernels_split.hip
 INF = float("inf")
 
 
@@ -185,6 +212,53 @@ def _ratio(got, ref, bound) -> float:
     return float((np.where(bound > 0, d, 0.0) / b).max()) if d.size else 0.0
 
 
+def _ratio_pages(got, ref, bound):
+    """-> (worst ratio, index along axis 0 where it is)."""
+    r = [_ratio(got[b], ref[b], bound[b]) for b in range(len(ref))]
+    j = int(np.argmax(r)) if r else 0
+    return (r[j] if r else 0.0), j
+
+
+def seam_positions(e: int, n: int):
+    """The first, the interior (nearest n / 2) and the last multiple of e inside (0, n)."""
+    if e >= n:
+        return []
+    last = (n - 1) // e * e
+    mid = min(max(int(round(n / 2 / e)) * e, e), last)
+    return sorted({e, mid, last})
+
+
+def legacy_positions(Ho: int, Wo: int, seed: int, salt: int):
+    """Window origins of the earlier sampling (before clamping): corners, edge middles, SEAMS on the diagonal and two crosses,
+    four seeded random windows."""
+    pos = [(0, 0), (0, Wo), (Ho, 0), (Ho, Wo), (0, Wo // 2 - 8), (Ho, Wo // 2 - 8), (Ho // 2 - 8, 0), (Ho // 2 - 8, Wo)]
+    for m in SEAMS:
+        if m < Ho or m < Wo:
+            pos.append((m - 8, m - 8))
+            pos.append((m - 8, Wo // 2 + 3))
+            pos.append((Ho // 2 + 5, m - 8))
+    r = np.random.RandomState(seed * 7919 + salt)
+    pos += [(int(r.randint(0, Ho - WIN + 1)), int(r.randint(0, Wo - WIN + 1))) for _ in range(4)]
+    return pos
+
+
+def geometry_positions(Ho: int, Wo: int):
+    """Window origins (before clamping) that straddle, crossed in both axes, the first / interior / last seam of every row of
+    EDGES, and the row wraps and late block edges of LINEAR_BLOCKS."""
+    h = WIN // 2
+    pos = []
+    for eh, ew, _ in EDGES:
+        ys, xs = seam_positions(eh, Ho), seam_positions(ew, Wo)
+        pos += [(y - h, x - h) for y in ys for x in xs]
+    late = max(Ho - WIN - h, 0)                           # rows [late, late + WIN): the ends of 16 rows and the starts of the next
+    pos += [(late, Wo), (late, 0)]
+    for lb in LINEAR_BLOCKS:
+        if Ho * Wo > lb:
+            p = ((late + h) * Wo + Wo // 2) // lb * lb   # a block edge in a late row (on a column seam when lb divides Wo)
+            pos.append((p // Wo - h, p % Wo - h))
+    return pos
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the checker
 # ---------------------------------------------------------------------------------------------------------------------
@@ -193,31 +267,45 @@ class LayerCheck:
     """prog: the lowered program (NOT the snapshot one); snaps: `snapshot_program`'s third result (or {} when nothing is
     overwritten); engine: "fp32" / "fp32s" / "fp16"; get(tid) -> engine tensor (B,H,W,C) f32 (`read_tensor` layout);
     outs: dict(blks, mask, lines, mask_u8, bitmap) numpy; page: (B,3,H,W) what the network sees (u8 / 255 or the float
-    input); u8: the page came in as uint8; kernels: per original op the kernel name (None: every op wrote its tensor)."""
+    input); u8: the page came in as uint8; kernels: per original op the kernel name (None: every op wrote its tensor);
+    pages: the pages to check (None: see the module docstring) -- everything the checker keeps is cut down to them, and
+    results name the page of the batch, not its position in `pages`; legacy_windows: the earlier window set only (kept so
+    that a test can show what that set misses)."""
 
     def __init__(self, prog, snaps: Dict[int, int], engine: str, get: Callable, outs: dict, page, u8: bool = False,
-                 kernels: Optional[List[str]] = None, seed: int = 0):
+                 kernels: Optional[List[str]] = None, seed: int = 0, pages=None, legacy_windows: bool = False):
         assert engine in ENGINES
-        self.p, self.snaps, self.engine, self._get, self.outs = prog, snaps, engine, get, outs
-        self.page = np.asarray(page, np.float64)
-        self.u8, self.kernels, self.seed = u8, kernels, seed
+        self.p, self.snaps, self.engine, self._get = prog, snaps, engine, get
+        self.B_all = len(page)
+        self.pages = None if pages is None else sorted({int(b) for b in pages})
+        assert self.pages is None or (self.pages and 0 <= self.pages[0] and self.pages[-1] < self.B_all), pages
+        self.real = list(range(self.B_all)) if self.pages is None else self.pages      # kept position -> page of the batch
+        self.page = np.asarray(page if self.pages is None else page[self.pages], np.float64)   # (anything with len and [list])
+        self.outs = outs if self.pages is None else {k: np.asarray(v)[self.pages] for k, v in outs.items()}
+        self.u8, self.kernels, self.seed, self.legacy = u8, kernels, seed, legacy_windows
         self.blob = prog.blob().astype(np.float64)
         self.B, _, self.H, self.W = self.page.shape
         self.rng = [_write_range(prog, o) for o in prog.ops]
         self._cache: Dict[int, np.ndarray] = {}
+        self.peak_cached_bytes = 0
 
     # -- engine values ------------------------------------------------------------------------------------------------
     def get(self, tid: int) -> np.ndarray:
         if tid not in self._cache:
-            self._cache[tid] = np.asarray(self._get(tid), np.float32)
+            a = self._get(tid)
+            assert len(a) == self.B_all, (tid, a.shape)
+            self._cache[tid] = np.asarray(a, np.float32) if self.pages is None else np.ascontiguousarray(a[self.pages], np.float32)
+            del a
+            self.peak_cached_bytes = max(self.peak_cached_bytes, sum(v.nbytes for v in self._cache.values()))
         return self._cache[tid]
 
     def _fused(self, i: int) -> bool:
         return self.kernels is not None and self.kernels[i] == "(fused)"
 
-    def value(self, tid: int, coff: int, c: int, t: int) -> np.ndarray:
-        """Channels [coff, coff + c) of tensor `tid` as they were right before op t (B,H,W,c) f64."""
-        parts = []
+    def _segments(self, tid: int, coff: int, c: int, t: int):
+        """Where channels [coff, coff + c) of tensor `tid`, as they were right before op t, are to be read: a list of
+        ("page", writer op, ch, end) / ("tensor", tensor id, first channel there, ch, end)."""
+        segs = []
         ch = coff
         while ch < coff + c:
             w = max((j for j in range(t) if self.rng[j] is not None and self.rng[j][0] == tid
@@ -227,16 +315,48 @@ class LayerCheck:
             end = min(coff + c, self.rng[w][2])
             final = not any(q is not None and q[0] == tid and q[1] <= ch < q[2] for q in self.rng[w + 1:])
             if self.p.ops[w]["kind"] == L.OP_INPUT and self._fused(w):
+                segs.append(("page", w, ch, end))
+            elif final:
+                segs.append(("tensor", tid, ch, ch, end))
+            else:
+                segs.append(("tensor", self.snaps[w], ch - self.rng[w][1], ch, end))
+            ch = end
+        return segs
+
+    def value(self, tid: int, coff: int, c: int, t: int, f64: bool = True) -> np.ndarray:
+        """Channels [coff, coff + c) of tensor `tid` as they were right before op t (B,H,W,c) f64 -- or, with f64 = False, as
+        stored (f32, a view where one tensor holds them all): for callers that cut windows out before they compute."""
+        parts = []
+        for seg in self._segments(tid, coff, c, t):
+            if seg[0] == "page":
+                _, w, ch, end = seg
                 x = self.page.transpose(0, 2, 3, 1)
                 x = np.concatenate([x, np.zeros(x.shape[:3] + (self.rng[w][2] - 3,))], 3)
                 parts.append(x[..., ch: end])
-            elif final:
-                parts.append(self.get(tid)[..., ch: end].astype(np.float64))
             else:
-                lo = self.rng[w][1]
-                parts.append(self.get(self.snaps[w])[..., ch - lo: end - lo].astype(np.float64))
-            ch = end
+                _, src, first, ch, end = seg
+                a = self.get(src)[..., first: first + end - ch]
+                parts.append(a.astype(np.float64) if f64 else a)
         return np.concatenate(parts, 3) if len(parts) > 1 else parts[0]
+
+    def reads(self, i: int) -> set:
+        """Ids of the engine tensors that check(i) fetches."""
+        o = self.p.ops[i]
+        want = []
+        if self.rng[i] is not None and not (o["kind"] == L.OP_INPUT and self._fused(i)):
+            tid, lo, hi = self.rng[i]
+            want.append((tid, lo, hi - lo, i + 1))
+        if o["kind"] not in (L.OP_INPUT, L.OP_STEM):
+            if o["src0"] >= 0:
+                want.append((o["src0"], o["src0_coff"], o["src0_c"], i))
+            if o["src1"] >= 0:
+                want.append((o["src1"], o["src1_coff"], o["src1_c"], i))
+            if o["kind"] in (L.OP_CONV, L.OP_CONVT) and o["res"] >= 0:
+                want.append((o["res"], o["res_coff"], o["cout"], i))
+        ids = set()
+        for tid, coff, c, t in want:           # (more channels than the check reads does no harm: a tensor stays longer)
+            ids |= {seg[1] for seg in self._segments(tid, coff, max(c, 1), t) if seg[0] == "tensor"}
+        return ids
 
     def from_page(self, tid: int, t: int) -> bool:
         w = max((j for j in range(t) if self.rng[j] is not None and self.rng[j][0] == tid), default=None)
@@ -244,27 +364,25 @@ class LayerCheck:
 
     def sources(self, o, t: int):
         """[(array (B,h,w,c), up)] of the op's (concatenated) sources."""
-        s = [(self.value(o["src0"], o["src0_coff"], o["src0_c"], t), o["src0_up"])]
+        s = [(self.value(o["src0"], o["src0_coff"], o["src0_c"], t, f64=False), o["src0_up"])]
         if o["src1"] >= 0:
-            s.append((self.value(o["src1"], o["src1_coff"], o["src1_c"], t), o["src1_up"]))
+            s.append((self.value(o["src1"], o["src1_coff"], o["src1_c"], t, f64=False), o["src1_up"]))
         return s
 
     # -- windows ------------------------------------------------------------------------------------------------------
-    def windows(self, Ho: int, Wo: int, B: int, salt: int = 0):
+    def windows(self, Ho: int, Wo: int, B: int, salt: int = 0, legacy: Optional[bool] = None):
+        """(kept page position, y0, x0, h, w) of the output windows of a (B, Ho, Wo) map."""
+        legacy = self.legacy if legacy is None else legacy
         if Ho <= FULL_MAX and Wo <= FULL_MAX:
             return [(b, 0, 0, Ho, Wo) for b in range(B)]
         ys = lambda v: min(max(v, 0), Ho - WIN)      # noqa: E731
         xs = lambda v: min(max(v, 0), Wo - WIN)      # noqa: E731
-        pos = [(0, 0), (0, Wo), (Ho, 0), (Ho, Wo), (0, Wo // 2 - 8), (Ho, Wo // 2 - 8), (Ho // 2 - 8, 0), (Ho // 2 - 8, Wo)]
-        for m in SEAMS:
-            if m < Ho or m < Wo:
-                pos.append((m - 8, m - 8))
-                pos.append((m - 8, Wo // 2 + 3))
-                pos.append((Ho // 2 + 5, m - 8))
-        r = np.random.RandomState(self.seed * 7919 + salt)
-        pos += [(int(r.randint(0, Ho - WIN + 1)), int(r.randint(0, Wo - WIN + 1))) for _ in range(4)]
+        pos = legacy_positions(Ho, Wo, self.seed, salt)
+        if not legacy:
+            pos = pos + geometry_positions(Ho, Wo)
         pos = sorted({(ys(y), xs(x)) for y, x in pos})
-        return [(b, y, x, WIN, WIN) for b in sorted({0, B - 1}) for y, x in pos]
+        on = sorted({0, B - 1}) if (self.pages is None or legacy) else range(B)
+        return [(b, y, x, WIN, WIN) for b in on for y, x in pos]
 
     @staticmethod
     def crop(a: np.ndarray, b: int, r0: int, r1: int, c0: int, c1: int, up: int = 0) -> np.ndarray:
@@ -275,7 +393,7 @@ class LayerCheck:
         vr, vc = (rr >= 0) & (rr < Hl), (cc >= 0) & (cc < Wl)
         x = a[b][np.clip(rr, 0, Hl - 1) >> up][:, np.clip(cc, 0, Wl - 1) >> up]
         x = x * (vr[:, None, None] & vc[None, :, None])
-        return np.ascontiguousarray(x.transpose(2, 0, 1))
+        return np.ascontiguousarray(x.transpose(2, 0, 1), np.float64)
 
     def _par(self, off: int, n: int) -> np.ndarray:
         return self.blob[off: off + n]
@@ -316,24 +434,34 @@ class LayerCheck:
               L.OP_EXPORT: self._export, L.OP_SEG_FINAL: self._seg_final, L.OP_DB_UP: self._db_up}[k]
         r = fn(i, o)
         r.setdefault("name", o["name"])
+        r["page"] = self.real[r["page"]] if r.get("page") is not None else None     # where the worst ratio is
+        r.setdefault("win", None)
+        r["total"] = r.pop("per_page", 0) * self.B_all                              # elements the op wrote, all pages
         return r
 
-    def out_value(self, i: int) -> np.ndarray:
+    def out_value(self, i: int, f64: bool = True) -> np.ndarray:
         tid, lo, hi = self.rng[i]
-        return self.value(tid, lo, hi - lo, i + 1)
+        return self.value(tid, lo, hi - lo, i + 1, f64)
 
     def _input(self, i, o):
         if self._fused(i):
             return dict(ratio=0.0, n=0, skipped=True)
         got = self.out_value(i)
         ref = np.concatenate([self.page.transpose(0, 2, 3, 1), np.zeros(got.shape[:3] + (got.shape[3] - 3,))], 3)
-        return dict(ratio=_ratio(got, ref, U * np.abs(ref)), n=got.size)
+        ratio, pg = _ratio_pages(got, ref, U * np.abs(ref))
+        return dict(ratio=ratio, page=pg, n=got.size, per_page=got[0].size)
 
-    def _conv(self, i, o):
+    def conv_bounds(self, i: int, wins):
+        """[(window, f64 reference (C,h,w), bound (C,h,w))] of conv op i on the given windows (kept page positions)."""
+        out = []
+        self._conv(i, self.p.ops[i], wins=wins, collect=out)
+        return out
+
+    def _conv(self, i, o, wins=None, collect=None):
         k, s, p = o["k"], o["stride"], o["pad"]
         kind = o["kind"]
         transposed = kind == L.OP_CONVT
-        got_all = self.out_value(i)
+        got_all = self.out_value(i, f64=False)
         Ho, Wo = got_all.shape[1:3]
         cout = o["cout"]
         if kind == L.OP_STEM:
@@ -350,10 +478,10 @@ class LayerCheck:
             w = self._par(o["w_off"], cout * cin * k * k).reshape(cout, cin, k, k)
             K = cin * k * k
         b = self._par(o["b_off"], cout) if o["b_off"] >= 0 else None
-        res = self.value(o["res"], o["res_coff"], cout, i) if o["res"] >= 0 else None
+        res = self.value(o["res"], o["res_coff"], cout, i, f64=False) if o["res"] >= 0 else None
         f32 = self.p.tensors[o["dst"]][2] == 1
-        worst, n = 0.0, 0
-        wins = self.windows(Ho, Wo, self.B, salt=i)
+        worst, n, at = 0.0, 0, None
+        wins = self.windows(Ho, Wo, self.B, salt=i) if wins is None else wins
         for (h, ww), group in _by_size(wins).items():
             crops, offs = [], []
             for bb, y0, x0, _, _ in group:
@@ -374,20 +502,25 @@ class LayerCheck:
                 y = _act(vj, o["act"])
                 D = _act_err(vj, Aj, o["act"], y)
                 if res is not None:
-                    r = res[bb, y0: y0 + h, x0: x0 + ww].transpose(2, 0, 1)
+                    r = res[bb, y0: y0 + h, x0: x0 + ww].transpose(2, 0, 1).astype(np.float64)
                     y = y + r
                     D = D + U * np.abs(y) + (_split_err(r) if self.engine == "fp32s" else 0.0)
                 D = D + storage_err(self.engine, np.abs(y) + D, f32)   # rounds the value the engine had
                 got = got_all[bb, y0: y0 + h, x0: x0 + ww].transpose(2, 0, 1)
-                worst = max(worst, _ratio(got, y, D))
+                if collect is not None:
+                    collect.append(((bb, y0, x0, h, ww), y, D))
+                r = _ratio(got, y, D)
+                if at is None or r > worst:
+                    worst, at = r, (bb, y0, x0)
                 n += got.size
-        return dict(ratio=worst, n=n)
+        return dict(ratio=worst, n=n, page=at[0], win=at[1:], per_page=got_all[0].size)
 
     def _maxpool(self, i, o):
         a = self.value(o["src0"], o["src0_coff"], o["src0_c"], i).astype(np.float32)
         ref = F.max_pool2d(torch.from_numpy(a.transpose(0, 3, 1, 2).copy()), o["k"], 1, o["k"] // 2).numpy()
-        got = self.out_value(i).transpose(0, 3, 1, 2)
-        return dict(ratio=0.0 if np.array_equal(got.astype(np.float32), ref) else INF, n=got.size, exact=True)
+        got = self.out_value(i).transpose(0, 3, 1, 2).astype(np.float32)
+        bad = [b for b in range(len(ref)) if not np.array_equal(got[b], ref[b])]
+        return dict(ratio=INF if bad else 0.0, page=bad[0] if bad else 0, n=got.size, exact=True, per_page=got[0].size)
 
     def _avgpool(self, i, o):
         a = self.value(o["src0"], o["src0_coff"], o["src0_c"], i)
@@ -396,7 +529,8 @@ class LayerCheck:
         ref = q.mean(axis=(2, 4))
         D = 0.5 * U * np.abs(q).sum(axis=(2, 4))
         D = D + storage_err(self.engine, np.abs(ref) + D, self.p.tensors[o["dst"]][2] == 1)
-        return dict(ratio=_ratio(self.out_value(i), ref, D), n=ref.size)
+        ratio, pg = _ratio_pages(self.out_value(i), ref, D)
+        return dict(ratio=ratio, page=pg, n=ref.size, per_page=ref[0].size)
 
     def _detect(self, i, o):
         stride, row_unit, na, no = o["aux"][:4]
@@ -419,7 +553,8 @@ class LayerCheck:
         unit = (self.H // 64) * (self.W // 64)
         r0 = row_unit * unit
         got = self.outs["blks"][:, r0: r0 + na * ny * nx]
-        return dict(ratio=_ratio(got, ref.reshape(B, -1, no), D.reshape(B, -1, no)), n=got.size)
+        ratio, pg = _ratio_pages(got, ref.reshape(B, -1, no), D.reshape(B, -1, no))
+        return dict(ratio=ratio, page=pg, n=got.size, per_page=got[0].size)
 
     def _export(self, i, o):
         a = self.value(o["src0"], o["src0_coff"], 1, i)[..., 0].astype(np.float32)
@@ -428,7 +563,7 @@ class LayerCheck:
             ok = np.array_equal(self.outs["mask"][:, 0], a) and self._mask_u8_ok()
         else:
             ok = np.array_equal(self.outs["lines"][:, plane], a) and (plane != 0 or self._bitmap_ok(o))
-        return dict(ratio=0.0 if ok else INF, n=a.size, exact=True)
+        return dict(ratio=0.0 if ok else INF, page=0, n=a.size, exact=True, per_page=a[0].size)
 
     def _mask_u8_ok(self) -> bool:
         m = np.asarray(self.outs["mask"][:, 0], np.float32)
@@ -438,11 +573,11 @@ class LayerCheck:
         return np.array_equal(self.outs["bitmap"].astype(bool), self.outs["lines"][:, 0] > np.float32(o["faux"][0]))
 
     def _seg_final(self, i, o):
-        a = self.value(o["src0"], o["src0_coff"], o["src0_c"], i)
+        a = self.value(o["src0"], o["src0_coff"], o["src0_c"], i, f64=False)
         cin = a.shape[3]
         w = self._par(o["w_off"], cin * 16).reshape(cin, 1, 4, 4)
         got_all = self.outs["mask"]
-        worst, n = 0.0, 0
+        worst, n, at = 0.0, 0, None
         for (h, ww), group in _by_size(self.windows(self.H, self.W, self.B, salt=i)).items():
             crops, offs = [], []
             for bb, y0, x0, _, _ in group:
@@ -456,16 +591,18 @@ class LayerCheck:
                 vj, Aj = v[j, 0, oy: oy + h, ox: ox + ww], A[j, 0, oy: oy + h, ox: ox + ww]
                 y = _sig(vj)
                 D = _act_err(vj, Aj, L.ACT["sigmoid"], y) + U * y
-                worst = max(worst, _ratio(got_all[bb, 0, y0: y0 + h, x0: x0 + ww], y, D))
+                r = _ratio(got_all[bb, 0, y0: y0 + h, x0: x0 + ww], y, D)
+                if at is None or r > worst:
+                    worst, at = r, (bb, y0, x0)
                 n += h * ww
-        return dict(ratio=worst if self._mask_u8_ok() else INF, n=n)
+        return dict(ratio=worst if self._mask_u8_ok() else INF, n=n, page=at[0], win=at[1:], per_page=self.H * self.W)
 
     def _db_up(self, i, o):
-        a = self.value(o["src0"], o["src0_coff"], o["src0_c"], i)
+        a = self.value(o["src0"], o["src0_coff"], o["src0_c"], i, f64=False)
         q = o["aux"][1]
         nbr = o["aux"][2] or 2
         pb = q * q * 4 + q + q * 4 + 1
-        worst, n = 0.0, 0
+        worst, n, at = 0.0, 0, None
         wins = _by_size(self.windows(self.H, self.W, self.B, salt=i))
         for br in range(nbr):
             prm = self._par(o["w_off"] + br * pb, pb)
@@ -488,12 +625,25 @@ class LayerCheck:
                     vj, Aj = v[j, 0, oy: oy + h, ox: ox + ww], A[j, 0, oy: oy + h, ox: ox + ww]
                     y = _sig(vj)
                     D = _act_err(vj, Aj, L.ACT["sigmoid"], y) + U * y
-                    worst = max(worst, _ratio(got_all[bb, y0: y0 + h, x0: x0 + ww], y, D))
+                    r = _ratio(got_all[bb, y0: y0 + h, x0: x0 + ww], y, D)
+                    if at is None or r > worst:
+                        worst, at = r, (bb, y0, x0)
                     n += h * ww
-        return dict(ratio=worst if self._bitmap_ok(o) else INF, n=n)
+        return dict(ratio=worst if self._bitmap_ok(o) else INF, n=n, page=at[0], win=at[1:], per_page=nbr * self.H * self.W)
 
     def check_all(self, ops=None) -> Dict[int, dict]:
-        return {i: self.check(i) for i in (range(len(self.p.ops)) if ops is None else ops)}
+        """Checks the ops in program order; a tensor is dropped from the cache once no later op of `ops` reads it."""
+        ops = sorted(range(len(self.p.ops)) if ops is None else ops)
+        last = {}
+        for i in ops:
+            for tid in self.reads(i):
+                last[tid] = i
+        res = {}
+        for i in ops:
+            res[i] = self.check(i)
+            for tid in [t for t in self._cache if last.get(t, -1) <= i]:
+                del self._cache[tid]
+        return res
 
 
 def _by_size(wins):

@@ -2,12 +2,13 @@
 thresholds; at that shape the engine launches kernels that a B = 1 forward never selects (`conv_halo3_kernel`: at least
 1024 blocks; `c3_fused_kernel`, `c3b_kernel`: at least 1024 patches).  Every other oracle comparison of the suite runs small
 shapes, where those kernels are either off or forced on by a tuning key and checked against OTHER HIP kernels.  Here the
-benchmark's own batch (its checkpoint, its first 32 pages) goes through the fp16 and the fp32s engine ONCE, as benchmarked,
+benchmark's own batch (its checkpoint, its first 32 pages) goes through the fp16, the fp32s and the fp32 engine (the detector's
+default precision) ONCE, as benchmarked,
 and all 32 pages' outputs are compared with the oracle network (the reference's torch modules on the CPU, fp32) --
 reference seam `inference.py:129,146`:
 
   * the kernels that ran are asserted by name (`ctd_engine_op_kernel`);
-  * fp32s: the fp32 tolerances of tests/test_gpu_net.py (maps 2e-5 abs, Detect rows 1e-4 rel, u8 mask at most one level
+  * fp32s, fp32: the fp32 tolerances of tests/test_gpu_net.py (maps 2e-5 abs, Detect rows 1e-4 rel, u8 mask at most one level
     on < 0.1 % of the pixels) on every page;
   * fp16: the golden tolerances (2e-2 max / 2e-3 mean) on every page and the threshold-band assertions of
     tests/test_gpu_accept.py on pages 0, 10, 21 and 31;
@@ -87,7 +88,7 @@ def run_batch(prec):
     return _S[key]
 
 
-@pytest.mark.parametrize("prec", ["fp16", "fp32s"])
+@pytest.mark.parametrize("prec", ["fp16", "fp32s", "fp32"])
 def test_the_timed_dispatch_ran(prec):
     k = run_batch(prec)["kernels"]
     names = {kern for _, kern in k}
@@ -102,12 +103,29 @@ def test_the_timed_dispatch_ran(prec):
         # model.4 (x2), model.6 (x3), model.13 / 17 / 20, seg.upconv4 / 5.conv.0, db.upconv4.conv.0
         assert len(c3b) == 11 and "upconv5.conv.0.m.0.cv1.conv" in c3b, c3b
         assert {"stem_conv2_kernel", "conv_halo_kernel", "conv_igemm_kernel", "sppf_pool3_kernel", "db_up_mfma_kernel"} <= names, names
-    else:
+    elif prec == "fp32s":
         assert {"conv_split_halo_kernel", "conv_split_kernel", "stem_split_kernel"} <= names, names
+    else:
+        # f32 operands all the way: the page through input_kernel, every conv layer on the f32 MFMA kernel, the two heads'
+        # tails on their f32 kernels -- and nothing of the fp16 or the split engine
+        assert {"input_kernel", "conv_f32_mfma_kernel", "seg_final_f32_kernel", "db_up_kernel"} <= names, names
+        assert not [n for n in names if any(w in n for w in ("split", "igemm", "halo", "c3", "stem"))], names
+        conv = [kern for _, kern in k if kern.startswith("conv")]
+        assert set(conv) <= {"conv_f32_mfma_kernel", "conv_direct_kernel", "convt_direct_kernel"}, set(conv)
+        assert conv.count("conv_f32_mfma_kernel") * 2 > len(conv) >= 60, conv
 
 
 def test_fp32s_batch_of_32_matches_oracle_on_every_page():
-    r = run_batch("fp32s")
+    _fp32_bars_on_every_page("fp32s")
+
+
+def test_fp32_batch_of_32_matches_oracle_on_every_page():
+    """The detector's DEFAULT precision at the timed shape: exactly the bars of the fp32s test above."""
+    _fp32_bars_on_every_page("fp32")
+
+
+def _fp32_bars_on_every_page(prec):
+    r = run_batch(prec)
     mask_u8, bitmap = r["mask_u8"].cpu().numpy(), r["bitmap"].cpu().numpy()
     for b, (ob, om, ol) in enumerate(oracle()):
         np.testing.assert_allclose(r["mask"][b: b + 1], om, rtol=0, atol=2e-5, err_msg=f"page {b}")
@@ -143,7 +161,7 @@ def test_fp16_batch_of_32_stays_inside_the_band_on_every_page():
     print(f"\nfp16 B=32: worst |map - oracle| over 32 pages {worst:.3g}")
 
 
-@pytest.mark.parametrize("prec", ["fp32s", "fp16"])
+@pytest.mark.parametrize("prec", ["fp32s", "fp16", "fp32"])
 def test_detect_batch_of_32_matches_oracle_end_to_end(prec):
     p = pkg()
     r = run_batch(prec)
@@ -154,7 +172,7 @@ def test_detect_batch_of_32_matches_oracle_end_to_end(prec):
         rep = accept.compare(got, ref)
         print(f"\nB=32 dispatch, engine {prec}, page {b}: {rep}")
         assert rep["lines"]["ref"] >= 5
-        if prec == "fp32s":
+        if prec in ("fp32s", "fp32"):
             assert rep["mask_u8_max_level_diff"] <= 1 and rep["mask_u8_equal_frac"] > 0.999
             assert rep["lines"]["identical"] == rep["lines"]["ref"] == rep["lines"]["ours"]
             assert rep["blocks"]["identical"] == rep["blocks"]["ref"] == rep["blocks"]["ours"]

@@ -131,7 +131,7 @@ def _tune(key, value):
 
 
 @pytest.mark.parametrize("shape,u8", [((1, 64, 64), False), ((3, 128, 64), True), ((2, 320, 448), False),
-                                      ((2, 1024, 1024), True), ((1, 1536, 1536), True)])
+                                      ((2, 1024, 1024), True), ((1, 1536, 1536), True), ((32, 1024, 1024), True)])
 def test_fused_blocks_equal_the_layer_per_launch_program_bit_for_bit(shape, u8):
     """The multi-layer kernels of the fp16 engine (stem + layer 1, the 32-channel C3 block, SPPF's three pools, bit 8:
     bottleneck + cv3 of the 64 / 128-channel C3 blocks of backbone, neck and heads -- kernels_c3b.hip; bit 16: a 128-channel
@@ -141,7 +141,8 @@ def test_fused_blocks_equal_the_layer_per_launch_program_bit_for_bit(shape, u8):
     of the network must be IDENTICAL with and without them -- interior and border patches, float and uint8 input,
     maps smaller than one patch (the C3 kernels are forced onto them with c3_min_patches = c3b_min_patches = 1), and
     for bit 8 both K walks of the 3x3 it absorbs (the halo kernel's, forced onto every map by halo_min_patches = 1,
-    and the implicit GEMM's).  (This test is what found that the compiler rounded SiLU outputs once or twice depending
+    and the implicit GEMM's).  32 x 1024 x 1024 is the shape bench.py times: the grids, page counts and tensor sizes of the
+    published number.  (This test is what found that the compiler rounded SiLU outputs once or twice depending
     on the kernel: ctd_common.h ctd_act_fast.)"""
     be = pkg().backend.HipTextDetBackend(checkpoint(0), device="cuda", precision="fp16")
     if u8:
@@ -191,7 +192,44 @@ def test_fused_blocks_equal_the_layer_per_launch_program_bit_for_bit(shape, u8):
                                       f"(max |d| {float((g.float() - r.float()).abs().max()):.3g})"
 
 
-@pytest.mark.parametrize("shape", [(2, 512, 512), (1, 1024, 768), (3, 256, 512)])
+@pytest.mark.parametrize("prec", ["fp16", "fp32s", "fp32"])
+def test_timed_dispatch_fused_equals_unfused_on_all_32_pages(prec):
+    """bench.py's batch (its checkpoint, its first 32 pages of 1024 x 1024, uint8) at the DEFAULT thresholds -- no tuning key
+    but `fuse` is touched: the program with every multi-layer kernel (fuse = 63, what is timed) against the one launch per
+    layer program (fuse = 0, what tests/test_gpu_layers.py checks op by op at this shape).  Every output equal on every page.
+    The fp16 engine is the one that is timed and has all seven multi-layer kernels; on the fp32 / fp32s engines the only
+    fusion is SPPF's three max pools (exact in any precision)."""
+    from test_gpu_dispatch import workload
+    ck, pages = workload()
+    x = torch.from_numpy(np.stack(pages)).cuda()
+    assert tuple(x.shape) == (32, 1024, 1024, 3)
+    be = pkg().backend.HipTextDetBackend(ck, device="cuda", precision=prec)
+    names = ("blks", "mask", "lines", "mask_u8", "bitmap")
+    run = lambda: [t.clone() for t in be.forward_u8(x)] + [be.mask_u8.clone(), be.bitmap.clone()]       # noqa: E731
+    try:
+        got = run()
+        kernels = be.op_kernels()
+        _tune(b"fuse", 0)
+        ref = run()
+        plain = be.op_kernels()
+        torch.cuda.synchronize()
+    finally:
+        _tune(b"fuse", 63)
+    fused = {k for _, k in kernels} - {k for _, k in plain}
+    want = {"c3_fused_kernel", "c3b_kernel", "conv_halo3_kernel+1x1", "conv_halo3_kernel+taps", "seg_final_gather_kernel",
+            "stem_conv2_kernel", "sppf_pool3_kernel"} if prec == "fp16" else {"sppf_pool3_kernel"}
+    assert want <= fused, fused
+    for name, g, r in zip(names, got, ref):
+        assert g.shape == r.shape and g.shape[0] == 32
+        if not torch.equal(g, r):
+            page = int((g != r).reshape(32, -1).any(1).nonzero()[0])
+            at = [int(v) for v in (g[page] != r[page]).nonzero()[0]]
+            raise AssertionError(f"{name}: first difference on page {page} at {at}: fused {g[page][tuple(at)].item()!r}, "
+                                 f"per layer {r[page][tuple(at)].item()!r}; {int((g != r).sum())} elements differ on pages "
+                                 f"{(g != r).reshape(32, -1).any(1).nonzero().flatten().tolist()}")
+
+
+@pytest.mark.parametrize("shape", [(2, 512, 512), (1, 1024, 768), (3, 256, 512), (32, 1024, 1024)])
 def test_big_tile_convt_kernels_reproduce_the_256x128_kernel_bit_for_bit(shape):
     """The ConvTranspose layers on kernels_halo3.hip (256 x 128 tiles, four waves, two blocks per CU) and on
     kernels_halo2.hip (selftest build only) walk K and issue their MFMAs per accumulator in the order of kernels_halo.hip:

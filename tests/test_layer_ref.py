@@ -283,3 +283,195 @@ def test_wide_checkpoint_fp32s_emulation_passes_its_bound():
     blob, hook = fp32s_emulation(prog)
     res = run_and_check("fp32s", prog, x=_x((1, 128, 128), 6), blob=blob, hook=hook)
     assert all(r["ratio"] <= 1 for r in res.values()), {prog.ops[i]["name"]: r for i, r in res.items() if not r["ratio"] <= 1}
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# sampling that follows the kernels' geometry, and the pages
+# ---------------------------------------------------------------------------------------------------------------------
+
+TIMED_PAGES = (0, 1, 15, 16, 30, 31, 7, 22)
+
+
+def _windows_as_before(Ho, Wo, B, seed, salt):
+    """The window set of the sampling before EDGES, restated (not imported): pages 0 and B - 1."""
+    ys = lambda v: min(max(v, 0), Ho - 16)      # noqa: E731
+    xs = lambda v: min(max(v, 0), Wo - 16)      # noqa: E731
+    pos = [(0, 0), (0, Wo), (Ho, 0), (Ho, Wo), (0, Wo // 2 - 8), (Ho, Wo // 2 - 8), (Ho // 2 - 8, 0), (Ho // 2 - 8, Wo)]
+    for m in (16, 32, 64, 128, 256):
+        if m < Ho or m < Wo:
+            pos += [(m - 8, m - 8), (m - 8, Wo // 2 + 3), (Ho // 2 + 5, m - 8)]
+    r = np.random.RandomState(seed * 7919 + salt)
+    pos += [(int(r.randint(0, Ho - 16 + 1)), int(r.randint(0, Wo - 16 + 1))) for _ in range(4)]
+    pos = sorted({(ys(y), xs(x)) for y, x in pos})
+    return [(b, y, x, 16, 16) for b in sorted({0, B - 1}) for y, x in pos]
+
+
+def _planner(B, pages=None, seed=0):
+    return LayerCheck(_prog("fp32"), {}, "fp32", None, {}, np.zeros((B, 3, 64, 64)), pages=pages, seed=seed)
+
+
+def _straddled(wins, b, axis):
+    """Positions p of the axis (0: rows, 1: columns) with p - 1 and p both inside one window of page position b."""
+    out = set()
+    for w in wins:
+        if w[0] == b:
+            out |= set(range(w[1 + axis] + 1, w[1 + axis] + w[3 + axis]))
+    return out
+
+
+@pytest.mark.parametrize("shape", [(256, 256), (512, 512), (1024, 1024), (1536, 1536), (640, 1024), (320, 448)])
+def test_window_plan_visits_every_seam_class_on_every_requested_page(shape):
+    import layer_ref as LR
+    Ho, Wo = shape
+    chk = _planner(32, TIMED_PAGES, seed=3)
+    wins = chk.windows(Ho, Wo, len(TIMED_PAGES), salt=5)
+    assert {w[0] for w in wins} == set(range(len(TIMED_PAGES))) and chk.real == sorted(TIMED_PAGES)
+    assert all(0 <= y and y + h <= Ho and 0 <= x and x + w <= Wo for _, y, x, h, w in wins)
+    per_page = [{w[1:] for w in wins if w[0] == b} for b in range(len(TIMED_PAGES))]
+    assert all(s == per_page[0] for s in per_page)                       # the same windows on every requested page
+    have = per_page[0]
+    classes = 0
+    for eh, ew, kernel in LR.EDGES:
+        ys, xs = LR.seam_positions(eh, Ho), LR.seam_positions(ew, Wo)
+        for e, n, got in ((eh, Ho, ys), (ew, Wo, xs)):
+            if e < n:                                                    # first, last, and an interior one where there is one
+                last = (n - 1) // e * e
+                assert got[0] == e and got[-1] == last and all(p % e == 0 and 0 < p < n for p in got), (kernel, n, got)
+                assert last - e < 2 * e or any(e < p < last for p in got), (kernel, n, got)
+        for y in ys:                                                     # crossed: a corner of four patches of THIS kernel
+            for x in xs:
+                assert any(y0 < y < y0 + h and x0 < x < x0 + w for y0, x0, h, w in have), (kernel, shape, y, x)
+                classes += 1
+    assert classes >= 9 * 4
+    if shape == (1024, 1024):
+        for axis in (0, 1):
+            assert {512, 768, 1008} <= _straddled(wins, 0, axis)
+    # a row wrap of the linear-block kernels in a late row: the right end of rows and the left start of the same rows
+    late = [y for y, x, _, _ in have if x == 0 and (y, Wo - 16, 16, 16) in have and Ho // 2 < y < Ho - 16]
+    assert late, shape
+    inside = lambda q: any(y <= q // Wo < y + h and x <= q % Wo < x + w for y, x, h, w in have)      # noqa: E731
+    for lb in LR.LINEAR_BLOCKS:              # a block edge past the middle of the map: its first pixel and the one before it
+        assert any(inside(q) and inside(q - 1) for q in range((Ho // 2 * Wo) // lb * lb + lb, Ho * Wo, lb)), (shape, lb)
+    # what the earlier sampling looked at is all still there: on the pages it used, with and without `pages`
+    old = _windows_as_before(Ho, Wo, len(TIMED_PAGES), 3, 5)
+    assert set(old) <= set(wins) and set(old) == set(chk.windows(Ho, Wo, len(TIMED_PAGES), salt=5, legacy=True))
+    plain = _planner(32, None, seed=3)
+    assert set(_windows_as_before(Ho, Wo, 32, 3, 5)) <= set(plain.windows(Ho, Wo, 32, salt=5))
+    assert {w[0] for w in plain.windows(Ho, Wo, 32, salt=5)} == {0, 31}
+    print(f"\n{shape}: {len(have)} windows per page ({len(old) // 2} before), "
+          f"{len(have) * 256 / (Ho * Wo):.2%} of a page's positions at the most")
+
+
+def test_small_maps_are_checked_in_full_on_the_requested_pages():
+    chk = _planner(32, TIMED_PAGES)
+    assert chk.windows(128, 128, 8) == [(b, 0, 0, 128, 128) for b in range(8)] and chk.B == 8 and chk.B_all == 32
+    assert _planner(4).windows(64, 128, 4) == [(b, 0, 0, 64, 128) for b in range(4)]
+
+
+BIG = (3, 512, 512)
+_BIG = {}
+
+
+def _big():
+    """The fp32 program on three 512 x 512 pages (the first conv's map is 256 x 256: sampled), run once."""
+    if not _BIG:
+        L = _L()
+        prog = _prog("fp32")
+        snap, index, snaps = snapshot_program(prog)
+        x = _x(BIG, 8)
+        out = run_program(snap, x, return_tensors=True)
+        i = next(j for j, o in enumerate(prog.ops) if o["kind"] == L.OP_CONV and prog.tensors[o["dst"]][1] == 1)
+        assert i not in snaps and prog.ops[i]["dst_coff"] == 0
+        _BIG.update(prog=prog, snaps=snaps, x=x, T=out["tensors"], i=i,
+                    outs={k: out[k].numpy() for k in ("blks", "mask", "lines", "mask_u8", "bitmap")})
+    return _BIG
+
+
+def _check_big(T, **kw):
+    g = _big()
+    chk = LayerCheck(g["prog"], g["snaps"], "fp32", lambda t: T[t].permute(0, 2, 3, 1).numpy(), g["outs"], g["x"].numpy(), **kw)
+    return chk, chk.check_all([g["i"]])[g["i"]]
+
+
+def _with_error(page, y0, x0, factor=4.0):
+    """The engine's tensors with `factor` times the bound added to the 16 x 16 patch at (y0, x0) of one page of the op."""
+    g = _big()
+    i = g["i"]
+    chk = LayerCheck(g["prog"], g["snaps"], "fp32", lambda t: g["T"][t].permute(0, 2, 3, 1).numpy(), g["outs"], g["x"].numpy())
+    (_, ref, D), = chk.conv_bounds(i, [(page, y0, x0, 16, 16)])
+    assert float(D.min()) > 0
+    T = dict(g["T"])
+    t = T[g["prog"].ops[i]["dst"]].clone()
+    t[page, :, y0: y0 + 16, x0: x0 + 16] = torch.from_numpy(ref + factor * D).float()
+    T[g["prog"].ops[i]["dst"]] = t
+    return T
+
+
+def test_unmutated_large_map_passes_with_the_new_windows_on_every_page():
+    chk, r = _check_big(_big()["T"], pages=(0, 1, 2))
+    assert r["ratio"] <= 1 and r["total"] == 3 * 256 * 256 * _big()["prog"].ops[_big()["i"]]["cout"] and 0 < r["n"] < r["total"]
+    _, r2 = _check_big(_big()["T"])
+    assert r2["ratio"] <= r["ratio"] and r2["n"] < r["n"]                     # pages 0 and 2 only
+
+
+def test_mutation_in_one_interior_patch_is_missed_by_the_earlier_windows_and_rejected_now():
+    import layer_ref as LR
+    g = _big()
+    Ho = Wo = BIG[1] // 2
+    old = LayerCheck(g["prog"], g["snaps"], "fp32", None, g["outs"], g["x"].numpy(), legacy_windows=True)
+    before = old.windows(Ho, Wo, BIG[0], salt=g["i"])
+    assert set(before) == set(_windows_as_before(Ho, Wo, BIG[0], 0, g["i"]))
+    s = LR.seam_positions(16, Ho)
+    # a 16 x 16 patch up and left of a corner of four patches (last seam x interior seam first) that no earlier window touches
+    cand = [(y - 16, x - 16) for y in reversed(s) for x in s[1:]]
+    free = [(y, x) for y, x in cand if not any(y0 < y + 16 and y < y0 + 16 and x0 < x + 16 and x < x0 + 16
+                                                for _, y0, x0, _, _ in before)]
+    assert free, cand
+    y0, x0 = free[0]
+    assert 16 <= y0 and y0 + 32 <= Ho and 16 <= x0 and x0 + 32 <= Wo        # interior
+    T = _with_error(0, y0, x0)
+    _, missed = _check_big(T, legacy_windows=True)
+    _, caught = _check_big(T)
+    print(f"\npatch ({y0}, {x0}) of page 0 off by 4 bounds: earlier windows {missed['ratio']:.3g}, now {caught['ratio']:.3g} "
+          f"at page {caught['page']} window {caught['win']}")
+    assert missed["ratio"] <= 1, missed
+    assert caught["ratio"] > 1 and caught["page"] == 0, caught
+    assert caught["ratio"] > 2.9                                              # 4 bounds, less the engine's own error (< 1)
+
+
+def test_mutation_on_a_middle_page_is_missed_by_the_earlier_pages_and_rejected_now():
+    T = _with_error(1, 0, 0)                                                  # the corner window: every plan has it
+    _, missed = _check_big(T, legacy_windows=True)
+    _, missed_too = _check_big(T)                                             # without `pages`: 0 and B - 1, as before
+    _, caught = _check_big(T, pages=(0, 1, 2))
+    assert missed["ratio"] <= 1 and missed_too["ratio"] <= 1, (missed, missed_too)
+    assert caught["ratio"] > 2.9 and caught["page"] == 1 and caught["win"] == (0, 0), caught
+    _, named = _check_big(T, pages=(1,))                                      # results name the page of the batch
+    assert named["ratio"] > 2.9 and named["page"] == 1
+
+
+def test_only_the_requested_pages_are_kept_and_tensors_are_dropped_after_their_last_reader():
+    L = _L()
+    prog = _prog("fp32")
+    snap, index, snaps = snapshot_program(prog)
+    x = _x((4, 64, 64), 9)
+    out = run_program(snap, x, return_tensors=True)
+    T = out["tensors"]
+    outs = {k: out[k].numpy() for k in ("blks", "mask", "lines", "mask_u8", "bitmap")}
+    reads = []
+
+    def get(t):
+        reads.append(t)
+        return T[t].permute(0, 2, 3, 1).numpy()
+    full = LayerCheck(prog, snaps, "fp32", get, outs, x.numpy()).check_all()
+    assert len(reads) == len(set(reads))                                      # eviction never made the checker read twice
+    chk = LayerCheck(prog, snaps, "fp32", get, outs, x.numpy(), pages=(1, 2))
+    part = chk.check_all()
+    assert not chk._cache and chk.peak_cached_bytes > 0
+    everything = sum(T[t].numel() * 4 for t in set(reads)) // 2               # two of four pages of every tensor read
+    assert chk.peak_cached_bytes < everything / 2, (chk.peak_cached_bytes, everything)
+    only = LayerCheck(prog, snaps, "fp32", lambda t: T[t][1:3].permute(0, 2, 3, 1).numpy(), {k: v[1:3] for k, v in outs.items()},
+                      x[1:3].numpy()).check_all()
+    for i in full:
+        assert part[i]["ratio"] == only[i]["ratio"] <= full[i]["ratio"] <= 1 and part[i]["n"] == only[i]["n"], (i, part[i], only[i])
+        assert part[i]["page"] in (None, 1, 2) and part[i]["total"] == full[i]["total"]
