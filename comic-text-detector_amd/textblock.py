@@ -272,14 +272,16 @@ def blocks_from_records(recs, lines: np.ndarray, dist: np.ndarray, n: Optional[i
     tail, new = _TAIL_DICT, TextBlock.__new__
     out = []
     # one row per block: plain Python values from .tolist() (C loops), np.float64 / (2,) float64 arrays where the
-    # reference holds numpy values (`norm`, `weight`, `vec`); `distance` is a view into this page's distance array
+    # reference holds numpy values (`norm`, `weight`, `vec`); `distance` and `vec` are arrays the block OWNS, as
+    # csrc/pyblocks.c builds them: a copy of the slice / of the row, so that holding one block does not keep the page's
+    # arrays alive and an in-place edit of one block's arrays never reaches another's (the ranges of split blocks overlap)
     for xyxy, lang, vert, ang, mg, lo, nl, do, nd, fs, isf, vec, norm, weight in zip(
             a["xyxy"].tolist(), a["language"].tolist(), a["vertical"].tolist(), a["angle"].tolist(), a["merged"].tolist(),
             a["line_off"].tolist(), a["n_lines"].tolist(), a["dist_off"].tolist(), a["n_dist"].tolist(),
-            a["font_size"].tolist(), a["font_is_float"].tolist(), a["vec"].copy(), a["norm"], a["weight"]):
+            a["font_size"].tolist(), a["font_is_float"].tolist(), a["vec"], a["norm"], a["weight"]):
         d = {"xyxy": xyxy, "lines": all_lines[lo: lo + nl], "vertical": vert != 0, "language": LANG_LIST[lang],
-             "font_size": fs if isf else int(fs), "distance": dval[do: do + nd], "angle": ang,
-             "vec": vec, "norm": norm, "merged": mg != 0, "weight": weight}
+             "font_size": fs if isf else int(fs), "distance": dval[do: do + nd].copy(), "angle": ang,
+             "vec": vec.copy(), "norm": norm, "merged": mg != 0, "weight": weight}
         d.update(tail)                               # the record's non-detection fields, in the reference's order
         d["text"] = []
         t = new(TextBlock)

@@ -235,6 +235,24 @@ def letterbox_tail_case(seed, size=LETTERBOX_SIZE):
     return page, bt, mask, lines_map, (dw, dh), f"letterbox seed {seed} page {im_hw[0]}x{im_hw[1]} at {size}"
 
 
+# ------------------------------------------------------------------------------------------ block lists up to tied lines
+
+def equal_up_to_tied_lines(got, ref):
+    """Same blocks, and every block's lines equal as a set and in order except among lines whose distances agree to 1e-6:
+    `TextBlock.sort_lines` orders lines of one text row -- a mathematical tie -- by the last bit of `|sin(acos(c))| * len`,
+    which numpy's SIMD libm and glibc compute differently now and then ("ties")."""
+    if len(got) != len(ref):
+        return False
+    for a, b in zip(got, ref):
+        if [int(v) for v in a.xyxy] != [int(v) for v in b.xyxy] or len(a.lines) != len(b.lines):
+            return False
+        key = lambda blk: sorted((round(float(d), 6), tuple(np.asarray(l).reshape(-1).tolist()))               # noqa: E731
+                                 for d, l in zip(np.asarray(blk.distance).reshape(-1), blk.lines))
+        if key(a) != key(b):
+            return False
+    return True
+
+
 # ------------------------------------------------------------------------------------- histograms that tie (mask refinement)
 
 TIED_KINDS = ("one value", "two or three values with equal counts", "equal peaks closer than color_var",

@@ -11,6 +11,7 @@ import torch
 from conftest import checkpoint, pkg
 from oracle import postproc_ref as R
 from sweep_cases import blks_tensor, letterbox_tail_case, tail_case   # noqa: F401 (blks_tensor: imported from here by other tests)
+from sweep_cases import equal_up_to_tied_lines as _equal_up_to_tied_lines
 from test_post_host import blocks_equal, fake_outputs
 
 pytestmark = pytest.mark.gpu
@@ -63,22 +64,6 @@ def test_tail_on_text_like_outputs_matches_oracle(seed, keep):
     blocks_equal(got[2], ref[2])
     np.testing.assert_array_equal(got[1], ref[1])                # refined mask, bit exact
     assert len(got[2]) > 3 and (got[1] > 0).mean() > 0.005
-
-
-def _equal_up_to_tied_lines(got, ref):
-    """Same blocks, and every block's lines equal as a set and in order except among lines whose distances agree to 1e-6:
-    `TextBlock.sort_lines` orders lines of one text row -- a mathematical tie -- by the last bit of `|sin(acos(c))| * len`,
-    which numpy's SIMD libm and glibc compute differently now and then ("ties")."""
-    if len(got) != len(ref):
-        return False
-    for a, b in zip(got, ref):
-        if [int(v) for v in a.xyxy] != [int(v) for v in b.xyxy] or len(a.lines) != len(b.lines):
-            return False
-        key = lambda blk: sorted((round(float(d), 6), tuple(np.asarray(l).reshape(-1).tolist()))               # noqa: E731
-                                 for d, l in zip(np.asarray(blk.distance).reshape(-1), blk.lines))
-        if key(a) != key(b):
-            return False
-    return True
 
 
 def _tail_sweep(name, cases, strict):

@@ -105,12 +105,11 @@ def test_db_boxes_short_side_of_exactly_two_pixels(key):
     np.testing.assert_allclose(scores, rscores, rtol=0, atol=1e-6)
 
 
-@pytest.mark.parametrize("case", ["noise", "holes", "thin", "empty", "full", "cap"])
-def test_db_boxes_native_host_geometry_edge_cases(case):
-    """`ctd_db_boxes` (csrc/host_db.cpp, host-only: runs without a GPU) against the oracle's
-    contour walk + polygon fill on bitmaps that stress it: speckle, nested holes/islands,
-    1-px lines (min-side rejection), no foreground, all foreground, more contours than the cap."""
-    p = pkg()
+EDGE_CASES = ["noise", "holes", "thin", "empty", "full", "cap"]
+
+
+def edge_case_map(case):
+    """(prob (96,160) f32, max_candidates) of one geometry edge case (tests/host_replay.py replays the same maps)."""
     rng = np.random.RandomState(7)
     H, W = 96, 160
     prob = np.full((H, W), 0.05, np.float32)
@@ -138,6 +137,17 @@ def test_db_boxes_native_host_geometry_edge_cases(case):
         prob[::3, ::3] = 0.9                # > 1000 single-pixel contours
         prob[40:60, 40:100] = 0.9
         cap = 50
+    return prob, cap
+
+
+@pytest.mark.parametrize("case", EDGE_CASES)
+def test_db_boxes_native_host_geometry_edge_cases(case):
+    """`ctd_db_boxes` (csrc/host_db.cpp, host-only: runs without a GPU) against the oracle's
+    contour walk + polygon fill on bitmaps that stress it: speckle, nested holes/islands,
+    1-px lines (min-side rejection), no foreground, all foreground, more contours than the cap."""
+    p = pkg()
+    prob, cap = edge_case_map(case)
+    H, W = prob.shape
     bitmap = prob > 0.3
     nf, lab_f, st_f = R.connected_components_with_stats(bitmap.astype(np.uint8), 8)
     nb, lab_b, st_b = R.connected_components_with_stats((~bitmap).astype(np.uint8), 4)
@@ -152,18 +162,24 @@ def test_db_boxes_native_host_geometry_edge_cases(case):
         assert (scores > 0).sum() == 6      # 3 outer borders + 2 hole borders + the separate bar
 
 
+def speckle_map(seed):
+    """Map `seed` (0 .. 11) of the speckle sweep below."""
+    from scipy import ndimage
+    rng = np.random.RandomState(100 + seed)
+    H, W = 64 + 3 * seed, 100 + 5 * seed
+    prob = ndimage.uniform_filter(rng.rand(H, W), 1 + seed % 4).astype(np.float32)
+    return (prob - prob.min()) / (prob.max() - prob.min()) * (0.55 + 0.01 * (seed % 10))
+
+
 def test_db_boxes_native_host_geometry_speckle_sweep():
     """Random speckle at several correlation lengths: many nested holes, peninsulas and diagonal
     links -- the cases where 'pixels of the filled contour polygon' is subtle (a hole border's
     polygon excludes foreground that its ring merely surrounds)."""
-    from scipy import ndimage
     p = pkg()
     rep = p.postproc.SegRepresenter()
     for seed in range(12):
-        rng = np.random.RandomState(100 + seed)
-        H, W = 64 + 3 * seed, 100 + 5 * seed
-        prob = ndimage.uniform_filter(rng.rand(H, W), 1 + seed % 4).astype(np.float32)
-        prob = (prob - prob.min()) / (prob.max() - prob.min()) * (0.55 + 0.01 * (seed % 10))
+        prob = speckle_map(seed)
+        H, W = prob.shape
         bitmap = prob > 0.3
         nf, lab_f, st_f = R.connected_components_with_stats(bitmap.astype(np.uint8), 8)
         nb, lab_b, st_b = R.connected_components_with_stats((~bitmap).astype(np.uint8), 4)
@@ -173,8 +189,8 @@ def test_db_boxes_native_host_geometry_speckle_sweep():
         np.testing.assert_allclose(scores, rscores, rtol=0, atol=1e-6)
 
 
-def test_group_output_hand_built_scenes():
-    p = pkg()
+def hand_built_scene():
+    """(blks, lines, W, H, mask) of the hand-built page below."""
     W = H = 600
     mask = np.full((H, W), 255, np.uint8)
 
@@ -188,6 +204,12 @@ def test_group_output_hand_built_scenes():
     mask[5:25, 5:50] = 0
     blks = (np.array([[110, 40, 330, 260], [40, 390, 260, 460]], np.int32), np.array([1, 0], np.int32),
             np.array([0.9, 0.8]))
+    return blks, lines, W, H, mask
+
+
+def test_group_output_hand_built_scenes():
+    p = pkg()
+    blks, lines, W, H, mask = hand_built_scene()
     got = p.textblock.group_output(copy.deepcopy(blks), lines.copy(), W, H, mask)
     ref = R.group_output(copy.deepcopy(blks), lines.copy(), W, H, mask)
     blocks_equal(got, ref)
@@ -197,12 +219,11 @@ def test_group_output_hand_built_scenes():
     assert p.textblock.group_output((np.zeros((0, 4), np.int32), np.zeros(0, np.int32), np.zeros(0)), [], W, H, mask) == []
 
 
-def test_refine_host_decisions_match_oracle():
-    """csrc/host_refine.cpp: the colour pick (np.histogram(bins=255) + get_topk_color), the Otsu threshold
-    and the cv2.inRange bounds against the oracle's restatements, on random and degenerate histograms."""
-    import ctypes as C
-    lib = pkg()._lib.lib()
+def refine_decision_inputs():
+    """(pixels of 300 random and degenerate histograms, bound pairs for cv2.inRange) of the test below, from one stream
+    (tests/host_replay.py replays the same inputs)."""
     rng = np.random.RandomState(3)
+    pixels = []
     for it in range(300):
         kind = it % 6
         if kind == 0:
@@ -218,6 +239,20 @@ def test_refine_host_decisions_match_oracle():
         else:
             lo = rng.randint(0, 200)
             px = rng.randint(lo, lo + rng.randint(2, 56), rng.randint(1, 3000)).astype(np.uint8)
+        pixels.append(px)
+    bounds = [(7.4, 67.4), (7.5, 67.5), (8.5, 68.5), (-12.3, 47.7), (195.0, 255), (-70.2, -10.2), (254.6, 255),
+              (300.0, 360.0), (100.5, 100.4), (0.5, 0.5), (-0.5, 0.49)] + [tuple(rng.uniform(-80, 300, 2)) for _ in range(50)]
+    return pixels, bounds
+
+
+def test_refine_host_decisions_match_oracle():
+    """csrc/host_refine.cpp: the colour pick (np.histogram(bins=255) + get_topk_color), the Otsu threshold
+    and the cv2.inRange bounds against the oracle's restatements, on random and degenerate histograms."""
+    import ctypes as C
+    lib = pkg()._lib.lib()
+    pixels, bounds = refine_decision_inputs()
+    assert len(pixels) == 300 and len(bounds) == 61
+    for px in pixels:
         hist = np.bincount(px, minlength=256).astype(np.int64)
         out = np.zeros(3, np.float64)
         n = lib.ctd_topk_colors(hist.ctypes.data, out.ctypes.data)
@@ -227,8 +262,7 @@ def test_refine_host_decisions_match_oracle():
         np.testing.assert_array_equal(out[:n], np.asarray(ref, np.float64))
         if len(px):
             assert lib.ctd_otsu_from_hist(hist.ctypes.data) == cv.otsu_threshold_value(px)
-    for lo, hi in [(7.4, 67.4), (7.5, 67.5), (8.5, 68.5), (-12.3, 47.7), (195.0, 255), (-70.2, -10.2), (254.6, 255),
-                   (300.0, 360.0), (100.5, 100.4), (0.5, 0.5), (-0.5, 0.49)] + [tuple(rng.uniform(-80, 300, 2)) for _ in range(50)]:
+    for lo, hi in bounds:
         lb, ub = C.c_int32(), C.c_int32()
         lib.ctd_inrange_bounds(lo, hi, C.byref(lb), C.byref(ub))
         rl, ru = cv.in_range_bounds(lo, hi)

@@ -177,3 +177,48 @@ def test_textblocks_built_in_c_equal_the_python_loop():
             assert isinstance(batch[b], list)
         for blk in (x for pg in batch for x in pg):                  # the objects are ordinary TextBlocks
             assert isinstance(blk, TB.TextBlock) and isinstance(blk.to_dict(), dict)
+
+
+@pytest.mark.parametrize("path", ["records, C loop", "records, Python loop", "batch, C loop", "batch, Python loop"])
+def test_every_block_owns_its_distance_and_vec_arrays(path, monkeypatch):
+    """csrc/pyblocks.c hands every block arrays it OWNS (a copy of its slice of the page's distances, a copy of its `vec` row),
+    and the Python loop is documented as building the same objects: no array is a view (`base is None`), so one block does not
+    keep the page's arrays alive, and an in-place edit of one block's arrays leaves every other block of the page unchanged --
+    also where the distance ranges of two blocks OVERLAP, as they do after `split_textblk` (every part gets the whole array)."""
+    TB = pkg().textblock
+    if TB._PYB is None:
+        pkg()._lib.build()
+        TB = importlib.reload(TB)
+    assert TB._PYB is not None, "csrc/pyblocks.c was not built (make -C comic-text-detector_amd/csrc)"
+    if path.endswith("Python loop"):
+        monkeypatch.setattr(TB, "_PYB", None)
+    rng = np.random.RandomState(5)
+    recs, lines, dist, counts = _random_records(rng, 4, 12)
+    ob = np.concatenate(([0], np.cumsum(counts[:, 0])))
+    for b in range(len(counts)):                                     # split parts: block 1 of a page shares block 0's range
+        if counts[b, 0] >= 2:
+            recs["dist_off"][ob[b] + 1], recs["n_dist"][ob[b] + 1] = recs["dist_off"][ob[b]], recs["n_dist"][ob[b]]
+    assert any(counts[b, 0] >= 2 and recs["n_dist"][ob[b]] > 0 for b in range(len(counts)))
+
+    def build():
+        if path.startswith("batch"):
+            return TB.blocks_from_batch(recs, lines, dist, counts)
+        ol = np.concatenate(([0], np.cumsum(counts[:, 1])))
+        od = np.concatenate(([0], np.cumsum(counts[:, 2])))
+        return [TB.blocks_from_records(recs[ob[b]: ob[b + 1]], lines[ol[b]: ol[b + 1]], dist[od[b]: od[b + 1]],
+                                       native=path.endswith("C loop")) for b in range(len(counts))]
+    pages, fresh = build(), build()
+    assert sum(len(p) for p in pages) == int(counts[:, 0].sum()) > 8
+    for page in pages:
+        for blk in page:
+            assert isinstance(blk.distance, np.ndarray) and blk.distance.base is None and blk.distance.flags.owndata
+            assert isinstance(blk.vec, np.ndarray) and blk.vec.base is None and blk.vec.flags.owndata
+    for page, same in zip(pages, fresh):
+        for i, blk in enumerate(page):
+            blk.distance += 1000.0
+            blk.vec *= -3.0
+            blk.distance[...] = np.nan
+            for j, (other, want) in enumerate(zip(page, same)):
+                if j > i:                                            # not edited yet
+                    assert np.array_equal(other.distance, want.distance, equal_nan=True), (i, j)
+                    assert np.array_equal(other.vec, want.vec), (i, j)
