@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libctd_hip.so")
 SELFTEST_PATH = os.path.join(_HERE, "ctd_selftest")
 
 # ---- constants mirrored from include/ctd_hip.h -------------------------------
-ABI_VERSION = 6
+ABI_VERSION = 7
 OK = 0
 PREC_F32, PREC_F16, PREC_F32S = 0, 1, 2
 ACT = {"none": 0, "silu": 1, "leaky": 2, "relu": 3, "sigmoid": 4}
@@ -22,6 +22,7 @@ IN_NCHW_F32, IN_NHWC_U8 = 0, 1
 (OP_INPUT, OP_CONV, OP_CONVT, OP_MAXPOOL, OP_AVGPOOL2, OP_DETECT, OP_EXPORT, OP_STEM, OP_SEG_FINAL,
  OP_DB_UP) = range(1, 11)
 OUT_MASK, OUT_LINES = 0, 1
+REGION_OK, REGION_DEGENERATE, REGION_MAX_SIDE, REGION_TILE = 0, 1, 32766, 1024
 
 
 class CtdTensor(C.Structure):
@@ -61,6 +62,12 @@ class CtdBlk(C.Structure):
                 ("dist_off", C.c_int32), ("n_dist", C.c_int32), ("pad_", C.c_int32)]
 
 
+class CtdRegionJob(C.Structure):
+    _fields_ = [("page_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("C", C.c_int32), ("pitch", C.c_int32),
+                ("Minv", C.c_double * 9), ("w", C.c_int32), ("h", C.c_int32), ("rotate", C.c_int32), ("pad_", C.c_int32),
+                ("out_off", C.c_int64)]
+
+
 # every symbol include/ctd_hip.h declares: (restype, argtypes)
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -85,6 +92,8 @@ SYMBOLS = {
     "ctd_ccl": (_i32, [_vp, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, C.c_size_t, _vp]),
     "ctd_ccl_dual": (_i32, [_vp, _i32, _i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp, C.c_size_t, _vp]),
     "ctd_resize_linear_u8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ctd_region_transforms": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp]),
+    "ctd_warp_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),
     "ctd_tail_destroy": (None, [_vp]),

@@ -1398,4 +1398,14 @@ int ctd_resize_linear_u8(const uint8_t* src_dev, int32_t sH, int32_t sW, int32_t
   return CTD_OK;
 }
 
+int ctd_warp_regions(const ctd_region_job* jobs_dev, int32_t n, const int32_t* tile_first_dev, int32_t n_tiles, uint8_t* out_dev,
+                     void* stream) {
+  if (n < 0 || n_tiles < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (n == 0 || n_tiles == 0) return CTD_OK;
+  if (!jobs_dev || !tile_first_dev || !out_dev) return fail(CTD_ERR_INVALID, "null pointer");
+  launch_region_warp(jobs_dev, n, tile_first_dev, n_tiles, out_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CTD_OK;
+}
+
 }  // extern "C"

@@ -194,5 +194,9 @@ void launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* l
 void launch_resize_linear_u8(const uint8_t* src, int sH, int sW, int C, uint8_t* dst, int dH, int dW, int canvasH,
                              int canvasW, hipStream_t st);
 
+// ---- kernels_region.hip ---------------------------------------------------------
+// cv2.warpPerspective (INTER_LINEAR, BORDER_CONSTANT 0) [+ rotate 90 ccw] of n crops in one launch; n >= 1, n_tiles >= 1
+void launch_region_warp(const ctd_region_job* jobs, int n, const int* tile_first, int n_tiles, uint8_t* out, hipStream_t st);
+
 // ---- mfma layout probe (selftest) -------------------------------------------
 void launch_mfma_probe(const half_t* a, const half_t* b, float* out, hipStream_t st);

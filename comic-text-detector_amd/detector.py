@@ -454,5 +454,20 @@ class TextDetector:
         return thread_tail(dev).run(gpu, metas, blks, mask_u8, prob, bitmap, self.conf_thresh, self.nms_thresh, 0.6, True,
                                     refine_mode, keep_undetected_mask, None, want_extras)
 
+    def line_regions(self, pages: Sequence[Page], results, textheight: int = 48):
+        """The OCR stage's input for a detected batch: the `TextBlock.get_transformed_region` crop of every text line of
+        every page, in one kernel launch on the detector's device (`regions.line_regions`; returns its `LineRegions`).
+        `results`: what `detect_batch` / `detect_stream` returned for `pages` -- (mask, mask_refined, blk_list) triples -- or
+        just the blk_lists (lists of `TextBlock`s or `BlockList`s).  Host pages are uploaded through the pinned staging
+        ring (`_stage`); pages already on the device are read where they are."""
+        from . import regions
+        blk_lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in results]
+        dev = self.net.device
+        if not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
+                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
+            pages, ev = self._stage(pages)
+            torch.cuda.current_stream(dev).wait_event(ev)
+        return regions.line_regions(pages, blk_lists, textheight, device=dev)
+
     def __call__(self, img: np.ndarray, refine_mode=REFINEMASK_INPAINT, keep_undetected_mask=False):
         return self.detect_batch([img], refine_mode, keep_undetected_mask)[0]

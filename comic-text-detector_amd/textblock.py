@@ -61,7 +61,8 @@ class TextBlock:
     returned `blk_list` (`min_rect`, `bounding_rect`, `aspect_ratio`, `alignment`, `get_text`, the font-colour
     accessors, `stroke_width`, `target_lang` :110-265) are here as well, checked against the reference's own class in
     tests/test_textblock_helpers.py; they cost nothing on the hot path (`blocks_from_records` fills `__dict__`
-    directly).  Only `get_transformed_region` (:162-196, cv2 homography of the OCR stage) is left out."""
+    directly).  `get_transformed_region` (:162-194, the OCR stage's line crop: cv2 homography + warp) runs on the GPU
+    (regions.py; all lines of a batch at once: `regions.line_regions` / `TextDetector.line_regions`)."""
 
     def __init__(self, xyxy: Sequence, lines: Optional[list] = None, language: str = "unknown",
                  vertical: bool = False, font_size: float = -1, distance=None, angle: int = 0, vec=None,
@@ -162,6 +163,15 @@ class TextBlock:
 
     def target_lang(self):
         return self._target_lang
+
+    def get_transformed_region(self, img, idx: int, textheight):
+        """Line `idx` of the block cut out of `img` and rectified to `textheight` rows, vertical lines turned by 90 degrees
+        counter-clockwise (textblock.py:162-194): `img` uint8 (H,W,3) or (H,W), a numpy array (numpy out, like the
+        reference) or a CUDA tensor (CUDA tensor out, no host round trip).  The warp is a HIP kernel (csrc/kernels_region.hip)
+        and there is no CPU fallback: `CtdError` without a GPU.  `ValueError` for a degenerate line (the reference raises from
+        inside cv2).  All lines of a batch in one launch: `regions.line_regions`."""
+        from . import regions
+        return regions.transformed_region(self, img, idx, textheight)
 
     def get_text(self) -> str:
         """The recognised text: a string as it is, a list of line strings joined by blanks (textblock.py:198-201)."""

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CTD_ABI_VERSION 6
+#define CTD_ABI_VERSION 7
 
 /* ---- error codes ------------------------------------------------------ */
 #define CTD_OK 0
@@ -251,6 +251,55 @@ int ctd_db_step(const float* lines_dev, int32_t B, int32_t H, int32_t W, float k
  * inference.py:165. */
 int ctd_resize_linear_u8(const uint8_t* src_dev, int32_t sH, int32_t sW, int32_t C, uint8_t* dst_dev,
                          int32_t dH, int32_t dW, int32_t canvasH, int32_t canvasW, void* stream);
+
+/* ---- OCR line crops: `TextBlock.get_transformed_region`, batched (ABI v7) ------------------------ */
+
+/* Steps of the reference's `TextBlock.get_transformed_region` (utils/textblock.py:162-194) that need no pixels, for n
+ * text lines in one call.  HOST memory only, no device work, plain float64 without contraction.  Per line i:
+ *   quads (n,8) i32      the line's four points in the order the detector emits them
+ *   language (n) i32     0 eng, 1 ja, 2 unknown; vertical (n) i32; font_size (n) f64: fields of the line's block
+ *   im_w / im_h (n) i32  size of the page the line lies on (lines of several pages may share a call)
+ * the margin of English / unknown-horizontal lines (font_size / 3, clipped to [0, im_w] x [0, im_h], :167-172), the
+ * edge-midpoint ratio (:174-177), the crop size (:180-181 / :186-187; round-half-even), and the homography of
+ * cv2.findHomography on four points = the unique one through the four correspondences with h22 = 1, solved as
+ * cv2.getPerspectiveTransform does (8x8 system, LU with partial pivoting).  Outputs:
+ *   wh (n,2) i32 = (w, h) of the warp (BEFORE the rotation of vertical lines); M (n,9) f64 source -> crop;
+ *   Minv (n,9) f64 = inverse of M by the adjugate formula (what cv2.warpPerspective maps output pixels with);
+ *   status (n) i32: CTD_REGION_OK, or CTD_REGION_DEGENERATE (w < 1, h < 1, a side beyond CTD_REGION_MAX_SIDE, a
+ *   non-finite ratio, a singular system = one whose solution does not map the four points onto the crop's corners
+ *   within 1e-4 px: the reference raises from inside cv2 / int(round(nan))) with wh = 0. */
+#define CTD_REGION_OK 0
+#define CTD_REGION_DEGENERATE 1
+#define CTD_REGION_MAX_SIDE 32766
+int ctd_region_transforms(const int32_t* quads, const int32_t* language, const int32_t* vertical, const double* font_size,
+                          const int32_t* im_w, const int32_t* im_h, int32_t n, double textheight, int32_t* wh, double* M,
+                          double* Minv, int32_t* status);
+
+/* One crop of a ctd_warp_regions launch (a row of the device job table). */
+typedef struct ctd_region_job {
+  const uint8_t* page_dev; /* the page: u8, C interleaved channels, rows `pitch` bytes apart                        */
+  int32_t H, W, C;         /* page size; C = 1 or 3                                                                 */
+  int32_t pitch;           /* >= W * C                                                                              */
+  double Minv[9];          /* crop pixel (x, y) -> page coordinates                                                 */
+  int32_t w, h;            /* size of the warp                                                                      */
+  int32_t rotate;          /* 1: the crop is stored turned by 90 degrees counter-clockwise, (w, h, C) instead of
+                              (h, w, C) (cv2.rotate(.., ROTATE_90_COUNTERCLOCKWISE), textblock.py:191)              */
+  int32_t pad_;
+  int64_t out_off;         /* byte offset of the crop in out_dev                                                    */
+} ctd_region_job;
+
+#define CTD_REGION_TILE 1024 /* output pixels of a crop per block */
+
+/* cv2.warpPerspective(page, M, (w, h)) with the defaults INTER_LINEAR / BORDER_CONSTANT 0 (+ the rotation) for n crops
+ * in ONE launch: OpenCV's fixed-point path (imgproc/imgwarp.cpp of 4.1.2 - 4.10): per output pixel in double, without
+ * contraction, W = (Minv[6] x + Minv[7] y) + Minv[8], W = W ? 32 / W : 0, X = rint(clamp(((Minv[0] x + Minv[1] y) +
+ * Minv[2]) W)), Y likewise; taps (X >> 5, Y >> 5) + {0,1}^2 with weights 32 (32 - ax)(32 - ay) ... of ax = X & 31,
+ * ay = Y & 31, taps outside the page read 0, dst = (sum + 16384) >> 15.  jobs_dev: n jobs; tile_first_dev (n + 1) i32:
+ * tile_first[i] = number of CTD_REGION_TILE-pixel tiles of the crops before crop i (a crop of w * h pixels has
+ * ceil(w h / CTD_REGION_TILE) of them, a crop with w = 0 none), n_tiles = tile_first[n]; each crop is written at
+ * out_dev + out_off as (h, w, C), or (w, h, C) when rotated, contiguous.  n = 0 / n_tiles = 0 launch nothing. */
+int ctd_warp_regions(const ctd_region_job* jobs_dev, int32_t n, const int32_t* tile_first_dev, int32_t n_tiles,
+                     uint8_t* out_dev, void* stream);
 
 /* ---- the detector tail ------------------------------------------------------ */
 
