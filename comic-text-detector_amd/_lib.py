@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libctd_hip.so")
 SELFTEST_PATH = os.path.join(_HERE, "ctd_selftest")
 
 # ---- constants mirrored from include/ctd_hip.h -------------------------------
-ABI_VERSION = 7
+ABI_VERSION = 8
 OK = 0
 PREC_F32, PREC_F16, PREC_F32S = 0, 1, 2
 ACT = {"none": 0, "silu": 1, "leaky": 2, "relu": 3, "sigmoid": 4}
@@ -23,6 +23,8 @@ IN_NCHW_F32, IN_NHWC_U8 = 0, 1
  OP_DB_UP) = range(1, 11)
 OUT_MASK, OUT_LINES = 0, 1
 REGION_OK, REGION_DEGENERATE, REGION_MAX_SIDE, REGION_TILE = 0, 1, 32766, 1024
+REGION_U8, REGION_F16, REGION_F32 = 0, 1, 2
+LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 
 
 class CtdTensor(C.Structure):
@@ -68,6 +70,10 @@ class CtdRegionJob(C.Structure):
                 ("out_off", C.c_int64)]
 
 
+class CtdRegionBatchJob(C.Structure):
+    _fields_ = [("warp", CtdRegionJob), ("slot", C.c_int32), ("rows", C.c_int32), ("Wk", C.c_int32), ("cut", C.c_int32)]
+
+
 # every symbol include/ctd_hip.h declares: (restype, argtypes)
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -94,6 +100,7 @@ SYMBOLS = {
     "ctd_resize_linear_u8": (_i32, [_vp, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ctd_region_transforms": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp]),
     "ctd_warp_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
+    "ctd_warp_region_batches": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),
     "ctd_tail_destroy": (None, [_vp]),

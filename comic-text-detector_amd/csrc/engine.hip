@@ -1408,4 +1408,20 @@ int ctd_warp_regions(const ctd_region_job* jobs_dev, int32_t n, const int32_t* t
   return CTD_OK;
 }
 
+int ctd_warp_region_batches(const ctd_region_batch_job* jobs_dev, int32_t n, const int32_t* tile_first_dev, int32_t n_tiles,
+                            const void* tables_dev, void* out_dev, int32_t dtype, int32_t layout, int32_t reverse, int32_t pad,
+                            void* stream) {
+  if (n < 0 || n_tiles < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (dtype != CTD_REGION_U8 && dtype != CTD_REGION_F16 && dtype != CTD_REGION_F32) return fail(CTD_ERR_INVALID, "bad dtype");
+  if (layout != CTD_LAYOUT_NCHW && layout != CTD_LAYOUT_NHWC) return fail(CTD_ERR_INVALID, "bad layout");
+  if (pad < 0 || pad > 255) return fail(CTD_ERR_INVALID, "pad is a u8 page value");
+  if (n == 0 || n_tiles == 0) return CTD_OK;
+  if (!jobs_dev || !tile_first_dev || !out_dev || (dtype != CTD_REGION_U8 && !tables_dev))
+    return fail(CTD_ERR_INVALID, "null pointer");
+  launch_region_batches(jobs_dev, n, tile_first_dev, n_tiles, tables_dev, out_dev, dtype, layout, reverse, pad,
+                        (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CTD_OK;
+}
+
 }  // extern "C"

@@ -197,6 +197,9 @@ void launch_resize_linear_u8(const uint8_t* src, int sH, int sW, int C, uint8_t*
 // ---- kernels_region.hip ---------------------------------------------------------
 // cv2.warpPerspective (INTER_LINEAR, BORDER_CONSTANT 0) [+ rotate 90 ccw] of n crops in one launch; n >= 1, n_tiles >= 1
 void launch_region_warp(const ctd_region_job* jobs, int n, const int* tile_first, int n_tiles, uint8_t* out, hipStream_t st);
+// the same warp + value table + layout + padding into batch tensors (ctd_warp_region_batches); n >= 1, n_tiles >= 1
+void launch_region_batches(const ctd_region_batch_job* jobs, int n, const int* tile_first, int n_tiles, const void* tables,
+                           void* out, int dtype, int layout, int reverse, int pad, hipStream_t st);
 
 // ---- mfma layout probe (selftest) -------------------------------------------
 void launch_mfma_probe(const half_t* a, const half_t* b, float* out, hipStream_t st);

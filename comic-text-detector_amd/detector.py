@@ -20,7 +20,7 @@ from __future__ import annotations
 
 from collections import deque
 from concurrent.futures import ThreadPoolExecutor
-from typing import Iterable, Iterator, List, Sequence, Tuple, Union
+from typing import Iterable, Iterator, List, Optional, Sequence, Tuple, Union
 
 import ctypes as C
 import gc
@@ -318,6 +318,18 @@ class TextDetector:
                                                 0.6, True, refine_mode, keep_undetected_mask, job["ev"], records=records,
                                                 lazy=lazy)
 
+    def _tail_batches(self, job, refine_mode, keep_undetected_mask, lo, hi, records, lazy, kw):
+        """`_tail`, then the OCR input batches of the same pages (`regions.line_batches`) from the batch's staged device
+        pages, on the calling worker's tail stream: (results, LineBatches)."""
+        from . import regions
+        res = self._tail(job, refine_mode, keep_undetected_mask, lo, hi, records, lazy)
+        dev = self.net.device
+        lb = regions.line_batches(job["gpu"][slice(lo, hi)], [r[2] for r in res], stream=thread_tail(dev).stream(), device=dev,
+                                  **kw)
+        lb.page0 = int(lo or 0)
+        lb.index[:, 0] += lb.page0                            # pages count within the yielded batch
+        return res, lb
+
     @staticmethod
     def _split(n: int, parts: int):
         """Page ranges of a batch's tail work items: `parts` near-equal contiguous pieces (pages are independent after
@@ -334,7 +346,7 @@ class TextDetector:
     def detect_stream(self, batches: Iterable[Sequence[Page]], refine_mode=REFINEMASK_INPAINT,
                       keep_undetected_mask=False, workers: int = 0, depth: int = 4, engines: int = 1,
                       loaders: int = 2, tail_split: int = 0, lazy: bool = False, records=None,
-                      tune: bool = True) -> Iterator[list]:
+                      tune: bool = True, line_batches: Optional[dict] = None) -> Iterator[list]:
         """Yields `detect_batch(batch)` for every batch, in order, with up to `depth` batches in flight:
         the forward of the next batches is launched while `workers` threads run the tails of earlier ones.
         Host (numpy) pages are staged to the GPU by `loaders` threads up to `depth` batches ahead (`_stage`).
@@ -351,6 +363,11 @@ class TextDetector:
         the native per-page geometry threads of every worker from the same budget unless `tail.set_host_threads` was called.
         `tune=True`: `serve_tuning()` once per process, after the pools are warm.  `records=(cap_blk, cap_line)`: every page
         comes back as a `PageResult` carrying its multi-GPU gather record (`dist.gather_results`).
+        `line_batches=dict` of `regions.line_batches` keywords ({} = its defaults): every item is (results, batches) instead,
+        `batches` a list of `LineBatches`, one per tail work item in page order -- the OCR network's input tensors of that
+        item's pages, made by the worker that ran its tail, on that tail's own stream, from the staged device pages (host
+        pages are not uploaded again).  Their `index[:, 0]` counts pages within the yielded batch, `.page0` is the item's
+        first page; call `.wait()` before using one on another stream.
         This generator IS what `bench.py`'s headline times (its `Pipeline` only feeds it batches and counts the results).
         The pools stay alive between calls (`close()` stops them): each worker thread keeps a native tail object with a
         HIP stream and ~250 MB of device tables at 32 pages per batch."""
@@ -375,6 +392,12 @@ class TextDetector:
         tail_split = int(tail_split) if int(tail_split) > 0 else max(1, workers)
         main = torch.cuda.current_stream(self.net.device)
 
+        def collect(futs):
+            if line_batches is None:
+                return [r for f in futs for r in f.result()]
+            done = [f.result() for f in futs]
+            return [r for res, _ in done for r in res], [lb for _, lb in done]
+
         def staged():
             ahead, it = deque(), iter(batches)
             for batch in it:
@@ -395,12 +418,17 @@ class TextDetector:
                     st.wait_stream(main)                  # pages the caller produced on its stream
                     with torch.cuda.stream(st):
                         job = self._forward(batch, net)
-                pending.append([pool.submit(self._tail, job, refine_mode, keep_undetected_mask, lo, hi, records, lazy)
-                                for lo, hi in self._split(len(job["metas"]), tail_split)])
+                if line_batches is None:
+                    pending.append([pool.submit(self._tail, job, refine_mode, keep_undetected_mask, lo, hi, records, lazy)
+                                    for lo, hi in self._split(len(job["metas"]), tail_split)])
+                else:
+                    pending.append([pool.submit(self._tail_batches, job, refine_mode, keep_undetected_mask, lo, hi, records,
+                                                lazy, dict(line_batches))
+                                    for lo, hi in self._split(len(job["metas"]), tail_split)])
                 while len(pending) >= depth:
-                    yield [r for f in pending.popleft() for r in f.result()]
+                    yield collect(pending.popleft())
             while pending:
-                yield [r for f in pending.popleft() for r in f.result()]
+                yield collect(pending.popleft())
         finally:
             for futs in pending:                          # the consumer stopped early: let the queued tails finish
                 for f in futs:
@@ -468,6 +496,19 @@ class TextDetector:
             pages, ev = self._stage(pages)
             torch.cuda.current_stream(dev).wait_event(ev)
         return regions.line_regions(pages, blk_lists, textheight, device=dev)
+
+    def line_batches(self, pages: Sequence[Page], results, **kw):
+        """`line_regions`' lines as the input tensors of an OCR network -- width-bucketed, normalised, padded per bucket -- in
+        one kernel launch on the detector's device (`regions.line_batches` and its keywords; returns its `LineBatches`).
+        `pages` / `results` as for `line_regions`."""
+        from . import regions
+        blk_lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in results]
+        dev = self.net.device
+        if not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
+                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
+            pages, ev = self._stage(pages)
+            torch.cuda.current_stream(dev).wait_event(ev)
+        return regions.line_batches(pages, blk_lists, device=dev, **kw)
 
     def __call__(self, img: np.ndarray, refine_mode=REFINEMASK_INPAINT, keep_undetected_mask=False):
         return self.detect_batch([img], refine_mode, keep_undetected_mask)[0]

@@ -13,11 +13,17 @@ Packed, not padded: one 2000-px line would otherwise size every crop of the batc
 (N, textheight, width, C) tensor an OCR network wants when asked.  There is no per-line Python in this path and no CPU
 fallback: without a GPU it raises `CtdError` like the rest of the package.
 
+An OCR network reads float tensors (N, C, textheight, W), normalised, the lines sorted by width and cut into chunks, each
+chunk padded to its own widest line.  `line_batches` writes exactly those tensors in the same single launch
+(`ctd_warp_region_batches`): warp, value table, layout and padding fused, no packed intermediate; `batch_plan` is the
+bucketing (host, numpy).
+
 What is restated from cv2 here (four-point homography, the fixed-point linear warp) is listed in DESIGN.md section 5.
 """
 from __future__ import annotations
 
 import ctypes as C
+from collections import namedtuple
 from typing import List, Optional, Sequence, Union
 
 import numpy as np
@@ -26,12 +32,16 @@ import torch
 from . import _lib as L
 from .textblock import LANGCLS2IDX, BlockList, TextBlock
 
-__all__ = ["line_regions", "LineRegions", "transforms", "warp", "JOB_DTYPE"]
+__all__ = ["line_regions", "LineRegions", "transforms", "warp", "JOB_DTYPE", "line_batches", "LineBatches", "batch_plan",
+           "BatchPlan", "value_tables", "warp_batches", "BATCH_JOB_DTYPE"]
 
 # numpy view of `ctd_region_job` (include/ctd_hip.h; _lib.CtdRegionJob)
 JOB_DTYPE = np.dtype([("page_dev", "<u8"), ("H", "<i4"), ("W", "<i4"), ("C", "<i4"), ("pitch", "<i4"), ("Minv", "<f8", (9,)),
                       ("w", "<i4"), ("h", "<i4"), ("rotate", "<i4"), ("pad_", "<i4"), ("out_off", "<i8")])
 assert JOB_DTYPE.itemsize == C.sizeof(L.CtdRegionJob)
+# numpy view of `ctd_region_batch_job` (_lib.CtdRegionBatchJob)
+BATCH_JOB_DTYPE = np.dtype([("warp", JOB_DTYPE), ("slot", "<i4"), ("rows", "<i4"), ("Wk", "<i4"), ("cut", "<i4")])
+assert BATCH_JOB_DTYPE.itemsize == C.sizeof(L.CtdRegionBatchJob) == 136
 
 Page = Union[np.ndarray, torch.Tensor]
 
@@ -218,6 +228,18 @@ def _page_lines(blk_list):
     return (quads, np.asarray(lang, np.int32)[blk], np.asarray(vert, bool)[blk], np.asarray(fs, np.float64)[blk], blk, within)
 
 
+def _batch_lines(blk_lists):
+    """The lines of every page of a batch as columns: index (n,3) i32 = (page, block, line), quads, language, vertical,
+    font_size."""
+    cols = [_page_lines(b) for b in blk_lists]
+    counts = [len(c[0]) for c in cols]
+    cat = lambda k, dt: (np.concatenate([c[k] for c in cols]).astype(dt) if cols else np.zeros((0,), dt))   # noqa: E731
+    index = np.stack([np.repeat(np.arange(len(cols)), counts), cat(4, np.int64), cat(5, np.int64)], axis=1).astype(np.int32) \
+        if cols else np.zeros((0, 3), np.int32)
+    quads = np.concatenate([c[0] for c in cols]) if cols else np.zeros((0, 8), np.int32)
+    return index, quads, cat(1, np.int32), cat(2, np.int32), cat(3, np.float64)
+
+
 def _regions(pages, ch, index, quads, lang, vert, fs, textheight, stream) -> LineRegions:
     H = np.array([p.shape[0] for p in pages], np.int32)
     W = np.array([p.shape[1] for p in pages], np.int32)
@@ -240,13 +262,8 @@ def line_regions(pages: Sequence[Page], blk_lists: Sequence, textheight: int = 4
     if textheight < 1 or int(textheight) > L.REGION_MAX_SIDE:
         raise ValueError("textheight out of range")
     pages, ch, device = _device_pages(pages, device)
-    cols = [_page_lines(b) for b in blk_lists]
-    counts = [len(c[0]) for c in cols]
-    cat = lambda k, dt: (np.concatenate([c[k] for c in cols]).astype(dt) if cols else np.zeros((0,), dt))   # noqa: E731
-    index = np.stack([np.repeat(np.arange(len(cols)), counts), cat(4, np.int64), cat(5, np.int64)], axis=1).astype(np.int32) \
-        if cols else np.zeros((0, 3), np.int32)
-    quads = np.concatenate([c[0] for c in cols]) if cols else np.zeros((0, 8), np.int32)
-    return _regions(pages, ch, index, quads, cat(1, np.int32), cat(2, np.int32), cat(3, np.float64), textheight, stream)
+    index, quads, lang, vert, fs = _batch_lines(blk_lists)
+    return _regions(pages, ch, index, quads, lang, vert, fs, textheight, stream)
 
 
 def transformed_region(blk: TextBlock, img: Page, idx: int, textheight):
@@ -266,3 +283,244 @@ def transformed_region(blk: TextBlock, img: Page, idx: int, textheight):
                          "aspect ratio or singular homography)")
     out = regs[0] if pages[0].dim() == 3 else regs[0][:, :, 0]
     return out.cpu().numpy() if host else out
+
+
+# ---- OCR input batches ------------------------------------------------------------------------------------------------------
+
+BatchPlan = namedtuple("BatchPlan", "order bounds batch_width cut")
+BatchPlan.__doc__ = """`batch_plan`'s record: `order` (M,) i64 the lines in batch order; batch k holds
+order[bounds[k]: bounds[k + 1]] and is `batch_width[k]` columns wide; `cut[j]` = the columns kept of line order[j]."""
+
+_NP_DTYPE = {torch.uint8: np.uint8, torch.float16: np.float16, torch.float32: np.float32}
+_ABI_DTYPE = {torch.uint8: L.REGION_U8, torch.float16: L.REGION_F16, torch.float32: L.REGION_F32}
+_LAYOUT = {"nchw": L.LAYOUT_NCHW, "nhwc": L.LAYOUT_NHWC}
+
+
+def batch_plan(widths, valid, max_batch: Optional[int] = 16, width_multiple: int = 8, max_width: Optional[int] = None) -> BatchPlan:
+    """Width buckets of the lines of a batch (host, numpy, needs no GPU).  The valid lines of width >= 1, sorted by width
+    with a STABLE sort (ties keep line order; the sort is on the uncut widths), cut into consecutive runs of at most
+    `max_batch` lines (None: one run).  Run k is `batch_width[k]` columns wide: its largest min(width, max_width), rounded up
+    to a multiple of `width_multiple`; `cut` = min(width, max_width) per line of `order` (the right end of a longer line is
+    lost, as in `LineRegions.padded(width)`).  No valid line: no batch."""
+    widths = np.asarray(widths, np.int64).reshape(-1)
+    valid = np.asarray(valid).astype(bool).reshape(-1)
+    if len(widths) != len(valid):
+        raise ValueError("one width and one valid flag per line")
+    width_multiple = int(width_multiple)
+    if width_multiple < 1 or (max_batch is not None and int(max_batch) < 1) or (max_width is not None and int(max_width) < 1):
+        raise ValueError("max_batch, width_multiple and max_width must be >= 1")
+    if max_width is not None and int(max_width) % width_multiple:
+        raise ValueError("max_width must be a multiple of width_multiple")
+    lines = np.nonzero(valid & (widths >= 1))[0].astype(np.int64)
+    order = lines[np.argsort(widths[lines], kind="stable")]
+    m = len(order)
+    cut = widths[order] if max_width is None else np.minimum(widths[order], int(max_width))
+    if m == 0:
+        return BatchPlan(order, np.zeros((1,), np.int64), np.zeros((0,), np.int64), cut)
+    step = m if max_batch is None else int(max_batch)
+    bounds = np.append(np.arange(0, m, step, dtype=np.int64), m)
+    widest = cut[bounds[1:] - 1]                          # `cut` is non-decreasing along `order`
+    return BatchPlan(order, bounds, (widest + width_multiple - 1) // width_multiple * width_multiple, cut)
+
+
+def value_tables(dtype, channels: int, mean=127.5, std=127.5) -> np.ndarray:
+    """(channels, 256) array of `dtype`: table[c][v] = ((v - mean[c]) / std[c]) in float32, converted to `dtype` --
+    `((np.arange(256, dtype=np.float32) - mean[c]) / std[c]).astype(dtype)`.  mean / std: a scalar or one value per output
+    channel, taken as float32.  uint8: the identity (any other mean / std is a ValueError)."""
+    if isinstance(dtype, torch.dtype) and dtype not in _NP_DTYPE:
+        raise ValueError("dtype must be uint8, float16 or float32")
+    npdt = np.dtype(_NP_DTYPE.get(dtype, dtype))
+    if npdt not in (np.dtype(np.uint8), np.dtype(np.float16), np.dtype(np.float32)):
+        raise ValueError("dtype must be uint8, float16 or float32")
+    mean = np.asarray(mean, np.float32).reshape(-1)
+    std = np.asarray(std, np.float32).reshape(-1)
+    if len(mean) not in (1, channels) or len(std) not in (1, channels):
+        raise ValueError("mean / std: a scalar or one value per output channel")
+    if npdt == np.uint8:
+        if (mean != np.float32(127.5)).any() or (std != np.float32(127.5)).any():
+            raise ValueError("uint8 batches are not normalised: leave mean / std at their defaults")
+        return np.tile(np.arange(256, dtype=np.uint8), (channels, 1))
+    mean, std = np.broadcast_to(mean, (channels,)), np.broadcast_to(std, (channels,))
+    return np.stack([((np.arange(256, dtype=np.float32) - mean[c]) / std[c]).astype(npdt) for c in range(channels)])
+
+
+def warp_batches(pages: Sequence[torch.Tensor], page_of, wh, Minv, rotate, channels: int, batch_of, slot, cut, batch_n,
+                 batch_width, textheight, dtype=torch.float16, layout: str = "nchw", tables: Optional[np.ndarray] = None,
+                 rgb: bool = False, pad: int = 0, stream: Optional[torch.cuda.Stream] = None):
+    """`ctd_warp_region_batches`: the crops of `warp` (same arguments up to `channels`) written straight into K batch tensors
+    in ONE launch.  Job i fills slot `slot[i]` of batch `batch_of[i]` (-1: the job is in no batch) with the first `cut[i]`
+    columns of its stored crop; batch k holds `batch_n[k]` slots of `textheight` (one value, or one per batch) rows and
+    `batch_width[k]` columns, laid out `layout` with `dtype` elements = tables[c][u8 value] (`value_tables`; channel order
+    reversed where `rgb`), `tables[c][pad]` outside the crop.  Returns (storage, offsets): ONE device tensor of `dtype` and
+    the element offset of every batch in it, each on a 16-byte boundary.  One upload (jobs, tile prefix, tables)."""
+    if not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages):
+        raise L.CtdError("the kernel reads its pages in device memory: CPU tensors cannot be warped (no CPU fallback)")
+    n = len(wh)
+    wh = np.asarray(wh, np.int64).reshape(n, 2)
+    rotate = np.asarray(rotate).astype(bool).reshape(n)
+    batch_of = np.asarray(batch_of, np.int64).reshape(n)
+    slot = np.asarray(slot, np.int64).reshape(n)
+    cut = np.asarray(cut, np.int64).reshape(n)
+    batch_n = np.asarray(batch_n, np.int64).reshape(-1)
+    batch_width = np.asarray(batch_width, np.int64).reshape(-1)
+    K = len(batch_n)
+    th = np.broadcast_to(np.asarray(textheight, np.int64), (K,))
+    if dtype not in _ABI_DTYPE or layout not in _LAYOUT:
+        raise ValueError("dtype: torch.uint8 / float16 / float32; layout: 'nchw' / 'nhwc'")
+    if not 0 <= int(pad) <= 255:
+        raise ValueError("pad is a uint8 page value")
+    if n and (wh.min() < 0 or wh.max() > L.REGION_MAX_SIDE or ((wh[:, 0] == 0) != (wh[:, 1] == 0)).any()):
+        raise ValueError("crop sizes must be (0, 0) or 1 ... REGION_MAX_SIDE a side")
+    if len(batch_width) != K or (K and (batch_n.min() < 1 or batch_width.min() < 1 or th.min() < 1 or
+                                        (th * batch_width).max() >= 2 ** 31)):
+        raise ValueError("every batch needs >= 1 slot, >= 1 row and >= 1 column (rows * columns within int32)")
+    used = batch_of >= 0
+    sizes = np.where(rotate[:, None], wh, wh[:, ::-1])   # (rows, cols) of the stored crops
+    bk = batch_of[used]
+    if len(bk) and (bk.max() >= K or (slot[used] < 0).any() or (slot[used] >= batch_n[bk]).any() or (cut[used] < 0).any() or
+                    (cut[used] > np.minimum(sizes[used, 1], batch_width[bk])).any() or (sizes[used, 0] > th[bk]).any()):
+        raise ValueError("a slot outside its batch, or a crop larger than its slot")
+    item = torch.empty((), dtype=dtype).element_size()
+    elems = batch_n * channels * th * batch_width
+    align = 16 // item
+    offsets = np.zeros((K,), np.int64)
+    total = 0
+    for k in range(K):                                   # per BATCH: every batch starts on a 16-byte boundary
+        offsets[k] = (total + align - 1) // align * align
+        total = int(offsets[k] + elems[k])
+    dev = pages[0].device if pages else torch.device("cuda", 0)
+    tiles = np.zeros((n,), np.int64)
+    tiles[used] = (th[bk] * batch_width[bk] + L.REGION_TILE - 1) // L.REGION_TILE
+    n_tiles = int(tiles.sum())
+    if n_tiles >= 2 ** 31:
+        raise ValueError("too many pixels for one launch")
+    with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev):
+        st = torch.cuda.current_stream(dev)
+        storage = torch.empty((total,), dtype=dtype, device=dev)
+        if n_tiles == 0:
+            return storage, offsets
+        page_of = np.asarray(page_of, np.int64).reshape(n)
+        ptr = np.array([p.data_ptr() for p in pages], np.uint64)
+        H = np.array([p.shape[0] for p in pages], np.int32)
+        W = np.array([p.shape[1] for p in pages], np.int32)
+        pitch = np.array([p.stride(0) for p in pages], np.int64)
+        if pitch.max() >= 2 ** 31:
+            raise ValueError("row pitch beyond int32")
+        tab_bytes = b""
+        if dtype != torch.uint8:
+            if tables is None:
+                tables = value_tables(dtype, channels)
+            tables = np.ascontiguousarray(tables, _NP_DTYPE[dtype])
+            if tables.shape != (channels, 256):
+                raise ValueError("tables: (channels, 256)")
+            tab_bytes = tables.tobytes()
+        o_pre = n * BATCH_JOB_DTYPE.itemsize             # jobs, the tile prefix, the value tables: one upload
+        o_tab = o_pre + (n + 1) * 4
+        table = np.zeros((o_tab + len(tab_bytes),), np.uint8)
+        rows = table[:o_pre].view(BATCH_JOB_DTYPE)
+        jobs = rows["warp"]
+        jobs["page_dev"], jobs["H"], jobs["W"], jobs["C"], jobs["pitch"] = ptr[page_of], H[page_of], W[page_of], channels, pitch[page_of]
+        jobs["Minv"] = np.asarray(Minv, np.float64).reshape(n, 9)
+        jobs["w"], jobs["h"], jobs["rotate"] = wh[:, 0], wh[:, 1], rotate
+        safe = np.where(used, batch_of, 0)
+        jobs["out_off"] = np.where(used, offsets[safe] if K else 0, 0)
+        rows["slot"] = np.where(used, slot, 0)
+        rows["rows"] = np.where(used, th[safe] if K else 0, 0)
+        rows["Wk"] = np.where(used, batch_width[safe] if K else 0, 0)
+        rows["cut"] = np.where(used, cut, 0)
+        table[o_pre:o_tab].view(np.int32)[:] = np.concatenate(([0], np.cumsum(tiles)))
+        table[o_tab:] = np.frombuffer(tab_bytes, np.uint8)
+        tab = torch.from_numpy(table).to(dev)
+        L.check(L.lib().ctd_warp_region_batches(tab.data_ptr(), n, tab.data_ptr() + o_pre, n_tiles,
+                                                (tab.data_ptr() + o_tab) if tab_bytes else None, storage.data_ptr(),
+                                                _ABI_DTYPE[dtype], _LAYOUT[layout], int(bool(rgb)), int(pad), st.cuda_stream),
+                "ctd_warp_region_batches")
+    return storage, offsets
+
+
+class LineBatches:
+    """The OCR input of `line_batches`: K width buckets in ONE device tensor `storage`.  `lb[k]` = (x, lines): x the
+    (n_k, C, textheight, W_k) view ('nhwc': (n_k, textheight, W_k, C)) of batch k, `lines` the rows of `index` its slots hold,
+    in order.  `index` (N,3) = (page, block, line), `valid`, `widths`: `LineRegions`' arrays of the same call (all N lines;
+    a degenerate line is in no batch); `order`, `bounds`, `batch_width`, `cut`: the `batch_plan`; `offsets`: the element
+    offset of every batch in `storage` (16-byte aligned).  `ready` is recorded behind the launch: `wait()` before use on
+    another stream.  `page0`: the first page of the work item inside its batch (`detect_stream`)."""
+
+    def __init__(self, storage: torch.Tensor, offsets: np.ndarray, index: np.ndarray, valid: np.ndarray, widths: np.ndarray,
+                 plan: BatchPlan, textheight: int, channels: int, layout: str, ready: Optional[torch.cuda.Event], keep=None):
+        self.storage, self.offsets, self.index, self.valid, self.widths = storage, offsets, index, valid, widths
+        self.order, self.bounds, self.batch_width, self.cut = plan
+        self.textheight, self.channels, self.dtype, self.layout = int(textheight), int(channels), storage.dtype, layout
+        self.ready = ready
+        self.page0 = 0
+        self._keep = keep                                # the pages the launch reads, alive until the batches are dropped
+
+    def __len__(self) -> int:
+        return len(self.batch_width)
+
+    def __getitem__(self, k):
+        k = range(len(self))[k]
+        lines = self.order[self.bounds[k]: self.bounds[k + 1]]
+        n, th, ch, wk, o = len(lines), self.textheight, self.channels, int(self.batch_width[k]), int(self.offsets[k])
+        shape = (n, ch, th, wk) if self.layout == "nchw" else (n, th, wk, ch)
+        return self.storage[o: o + n * ch * th * wk].view(shape), lines
+
+    def __iter__(self):
+        return (self[k] for k in range(len(self)))
+
+    def wait(self, stream: Optional[torch.cuda.Stream] = None) -> "LineBatches":
+        """Orders `stream` (default: the current stream of the batches' device) behind the launch and tells the allocator
+        that the storage is in use there."""
+        st = stream if stream is not None else torch.cuda.current_stream(self.storage.device)
+        if self.ready is not None:
+            st.wait_event(self.ready)
+        if self.storage.numel():
+            self.storage.record_stream(st)
+        return self
+
+    def __repr__(self) -> str:
+        return (f"LineBatches({len(self)} batches of {len(self.order)} lines, widths {self.batch_width.tolist()}, textheight "
+                f"{self.textheight}, {self.layout} {self.dtype}, {self.storage.numel()} elements)")
+
+
+def line_batches(pages: Sequence[Page], blk_lists: Sequence, textheight: int = 48, max_batch: Optional[int] = 16,
+                 width_multiple: int = 8, max_width: Optional[int] = None, dtype=torch.float16, layout: str = "nchw",
+                 mean=127.5, std=127.5, rgb: bool = False, pad: int = 0, stream: Optional[torch.cuda.Stream] = None,
+                 device=None) -> LineBatches:
+    """The lines of `line_regions(pages, blk_lists, textheight)` as the input tensors of an OCR network: sorted by width, cut
+    into batches of at most `max_batch` lines (`batch_plan`), every batch padded to its own widest line, normalised
+    ((v - mean[c]) / std[c] through a 256-entry table per output channel, `value_tables`), channel order reversed where `rgb`
+    (BGR pages to RGB planes), padding = normalise(`pad`), laid out `layout` in `dtype` (torch.uint8: values unchanged).  One
+    native host call for the transforms, one upload, ONE kernel launch writing one allocation; no packed intermediate and
+    no torch kernel.  Asynchronous on `stream` (default: the current stream of the pages' device); see `LineBatches`."""
+    if len(pages) != len(blk_lists):
+        raise ValueError("one blk_list per page")
+    if textheight < 1 or int(textheight) > L.REGION_MAX_SIDE:
+        raise ValueError("textheight out of range")
+    if dtype not in _ABI_DTYPE or layout not in _LAYOUT:
+        raise ValueError("dtype: torch.uint8 / float16 / float32; layout: 'nchw' / 'nhwc'")
+    if any(isinstance(p, torch.Tensor) and not p.is_cuda for p in pages):
+        raise L.CtdError("line_batches takes numpy pages or CUDA tensors (there is no CPU path for CPU tensors)")
+    pages, ch, device = _device_pages(pages, device)
+    tables = value_tables(dtype, ch, mean, std)
+    index, quads, lang, vert, fs = _batch_lines(blk_lists)
+    H = np.array([p.shape[0] for p in pages], np.int32)
+    W = np.array([p.shape[1] for p in pages], np.int32)
+    pg = index[:, 0]
+    wh, _, Minv, status = transforms(quads, lang, vert, fs, W[pg] if len(pg) else 0, H[pg] if len(pg) else 0, textheight)
+    vert = np.asarray(vert).astype(bool)
+    valid = status == L.REGION_OK
+    widths = np.where(vert, wh[:, 1], wh[:, 0]).astype(np.int64)          # columns of the stored crops
+    plan = batch_plan(widths, valid, max_batch, width_multiple, max_width)
+    n, m = len(widths), len(plan.order)
+    batch_of, slot, cut = np.full((n,), -1, np.int64), np.zeros((n,), np.int64), np.zeros((n,), np.int64)
+    counts = np.diff(plan.bounds)
+    batch_of[plan.order] = np.repeat(np.arange(len(counts)), counts)
+    slot[plan.order] = np.arange(m) - np.repeat(plan.bounds[:-1], counts)
+    cut[plan.order] = plan.cut
+    with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(device):
+        storage, offsets = warp_batches(pages, pg, wh, Minv, vert, ch, batch_of, slot, cut, counts, plan.batch_width,
+                                        int(textheight), dtype, layout, tables, rgb, pad, None)
+        ready = torch.cuda.Event()
+        ready.record(torch.cuda.current_stream(device))
+    return LineBatches(storage, offsets, index, valid, widths, plan, int(textheight), ch, layout, ready, keep=pages)

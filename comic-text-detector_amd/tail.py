@@ -69,6 +69,14 @@ class Tail:
                 pass
             self._h = None
 
+    def stream(self) -> torch.cuda.Stream:
+        """The tail's own HIP stream (`ctd_tail_stream`) as a torch stream: work a worker thread adds behind its tail runs
+        there, so the process's stream count does not grow."""
+        st = getattr(self, "_torch_stream", None)
+        if st is None:
+            st = self._torch_stream = torch.cuda.ExternalStream(self._lib.ctd_tail_stream(self._h), device=self.device)
+        return st
+
     # -- helpers --------------------------------------------------------------------------------
     @staticmethod
     def _page_table(pages_gpu: Sequence[Optional[torch.Tensor]], metas):

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CTD_ABI_VERSION 7
+#define CTD_ABI_VERSION 8
 
 /* ---- error codes ------------------------------------------------------ */
 #define CTD_OK 0
@@ -300,6 +300,40 @@ typedef struct ctd_region_job {
  * out_dev + out_off as (h, w, C), or (w, h, C) when rotated, contiguous.  n = 0 / n_tiles = 0 launch nothing. */
 int ctd_warp_regions(const ctd_region_job* jobs_dev, int32_t n, const int32_t* tile_first_dev, int32_t n_tiles,
                      uint8_t* out_dev, void* stream);
+
+/* ---- OCR input batches: the same crops as the tensors a recogniser reads (ABI v8) ------------------ */
+
+#define CTD_REGION_U8 0  /* element types of the batch tensors */
+#define CTD_REGION_F16 1
+#define CTD_REGION_F32 2
+#define CTD_LAYOUT_NCHW 0
+#define CTD_LAYOUT_NHWC 1
+
+/* One SLOT of a ctd_warp_region_batches launch: the rows x Wk pixels that one line takes inside its batch tensor, padding
+ * included.  `warp` is the line's crop exactly as in ctd_warp_regions, except that warp.out_off is the ELEMENT offset of
+ * the slot's batch tensor in out_dev.  A job with rows = 0 or Wk = 0 has no slot and no tiles. */
+typedef struct ctd_region_batch_job {
+  ctd_region_job warp;
+  int32_t slot; /* position of the line in its batch                                                             */
+  int32_t rows; /* rows of the slot (the textheight of the batch): crop rows beyond it are lost, slot rows below
+                   the crop are padding                                                                            */
+  int32_t Wk;   /* columns of the slot: the width of the batch tensor                                             */
+  int32_t cut;  /* columns of the stored crop that are kept (<= Wk); the crop's right end beyond it is lost       */
+} ctd_region_batch_job;
+
+/* ctd_warp_regions fused with what an OCR network's input needs, for n slots in ONE launch.  Per slot pixel (y, x) and
+ * page channel s: u = the ctd_warp_regions value of stored-crop pixel (y, x) (same doubles, same taps, (sum + 16384) >> 15;
+ * rotated crops read region[x][w - 1 - y]) where x < cut and y < the crop's rows, else u = pad (no map, no loads).  Output
+ * channel c reads page channel s = c, or C - 1 - c when `reverse` (a BGR page into RGB planes).  The element is
+ * tables[c][u]: tables_dev holds C tables of 256 entries IN THE OUTPUT TYPE (the caller builds them, e.g.
+ * ((0..255) - mean[c]) / std[c]); the kernel copies bit patterns and does no floating-point arithmetic on values, so the
+ * result is the table's to the bit.  dtype CTD_REGION_U8: no table (tables_dev may be NULL), the element is u.  It is
+ * stored at element out_off + ((slot C + c) rows + y) Wk + x (CTD_LAYOUT_NCHW) or out_off + ((slot rows + y) Wk + x) C + c
+ * (CTD_LAYOUT_NHWC) of out_dev, all in 64 bits.  tile_first_dev (n + 1) i32 as in ctd_warp_regions with rows * Wk pixels
+ * per slot; n_tiles = tile_first[n].  pad in 0 .. 255.  n = 0 / n_tiles = 0 launch nothing. */
+int ctd_warp_region_batches(const ctd_region_batch_job* jobs_dev, int32_t n, const int32_t* tile_first_dev, int32_t n_tiles,
+                            const void* tables_dev, void* out_dev, int32_t dtype, int32_t layout, int32_t reverse,
+                            int32_t pad, void* stream);
 
 /* ---- the detector tail ------------------------------------------------------ */
 
