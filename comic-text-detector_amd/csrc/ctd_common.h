@@ -49,12 +49,10 @@ struct ConvArgs {
   int nphase;              // 1, or 4 for convT 4x4 s2 (blockIdx.z)
   int bk;                  // igemm K step the weights were packed for (32 / 64)
   int w_tiled;             // igemm weights are tile-major [phase][n_tile][k_step][BN][bk]
-  const void* zeros;       // CTD_ZEROS_BYTES of zeros in HBM: source of padding rows for LDS-DMA loads (kernels_halo2.hip walks
+  const void* zeros;       // CTD_ZEROS_BYTES of zeros in HBM: source of padding rows for LDS-DMA loads (kernels_halo3.hip walks
                            // a padding piece through it in step with the channel chunks: 2 B per input channel)
-  long long* dbg;          // selftest only (k_rot & 16): per-block cycle stamps [nblk][8]; null in the product
   unsigned mw_mul, mw_sh;  // igemm: n / Mw == (uint64(n) * mw_mul) >> mw_sh for n < 2^31 (filled by the launcher)
   unsigned mh_mul, mh_sh;  //        same for Mh
-  int k_rot;               // igemm: selftest ablation bits (0 in the product): 1 no K-loop loads, 2 no MFMAs, 4 no stores
   const void* w2;          // split kernel (kernels_split.hip): the lo plane of the weights (`w` is the hi plane)
   const float* oscale;     // split kernel: per output channel 1 / (power of two its weights were scaled by), padded to Npad
   int prio;                // 1: the kernel raises its waves' issue priority (s_setprio): the forward's kernels against a co-running tail

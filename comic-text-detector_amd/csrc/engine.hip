@@ -1310,17 +1310,10 @@ int ctd_tuning_set(const char* key, int64_t value) {
   else if (k == "no_reuse") g_no_reuse = (int)value;
   else if (k == "f32_mfma") g_f32_mfma = (int)value;
   else if (k == "split_halo") g_split_halo = (int)value;
-#ifdef CTD_AB_VARIANTS
-  else if (k == "split_halo_small") g_split_halo_small = (int)value;
-#endif
   else if (k == "split_halo_min_patches") g_split_halo_min_patches = value;
   else if (k == "fwd_prio") g_fwd_prio = (int)value;
   else if (k == "split_stem") g_split_stem = (int)value;
   else if (k == "split_planes") g_split_planes = (int)value;
-#ifdef CTD_AB_VARIANTS
-  else if (k == "split_wdma") g_split_wdma = (int)value;
-  else if (k == "split_bm256") g_split_bm256 = (int)value;
-#endif
   else if (k == "db_up_mfma") g_db_up_mfma = (int)value;
   else if (k == "seg_final_mfma") g_seg_final_mfma = (int)value;
   else if (k == "c3_min_patches") g_c3_min_patches = value;

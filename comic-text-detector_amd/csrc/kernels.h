@@ -35,7 +35,6 @@ void launch_db_step(const float* lines, float k, float* out, uint8_t* bitmap, fl
 // ---- kernels_igemm.hip : MFMA implicit-GEMM conv (fp16 in, fp32 acc) ------
 // weights: half [nphase][Npad][K], K index = (ty*KW+tx)*(c0+c1) + c
 extern int g_tail_max_blocks;   // kernels_post.hip: grid cap of the tail's big-grid kernels ("tail_max_blocks")
-extern int g_igemm_occ_lo;
 extern int g_igemm_force_bk;  // tuning knob: 0 = heuristic, 32 / 64 = forced K step
 int igemm_pick_bk(int c0, int c1, int K, int N, int log2_down);
 void igemm_pack_weights(const float* logical, int nphase, int N, int K, int bn, int bk, bool tiled,
@@ -52,10 +51,6 @@ bool conv_f32_mfma_supported(const ConvArgs& a);
 void launch_conv_f32_mfma(const ConvArgs& a, hipStream_t st);
 
 // ---- kernels_split.hip : split-operand (fp16 hi + lo, 3 MFMAs per product) conv on f32 tensors: the "fp32s" engine ----
-#ifdef CTD_AB_VARIANTS
-extern int g_split_wdma;   // selftest build: 0 = weight tiles through registers instead of LDS-DMA (ctd_tuning_set("split_wdma"))
-extern int g_split_bm256;  // selftest build: 1 = 256-pixel blocks for 64-channel N tiles (ctd_tuning_set("split_bm256"))
-#endif
 bool conv_split_supported(const ConvArgs& a);
 // dispatches to the halo kernel below when it applies; returns the name of the kernel it launched
 const char* launch_conv_split(const ConvArgs& a, hipStream_t st);
@@ -64,9 +59,6 @@ bool stem_split_supported(const ConvArgs& a);
 void launch_stem_split(const ConvArgs& a, const void* input, int in_fmt, hipStream_t st);
 // ---- kernels_split_halo.hip : the same arithmetic on a 256-pixel haloed patch staged once per channel chunk (3x3 / ConvT) ----
 extern int g_split_halo;                    // 0 disables ("split_halo")
-#ifdef CTD_AB_VARIANTS
-extern int g_split_halo_small;              // selftest build: 64-channel layers on 16x8 patches ("split_halo_small")
-#endif
 extern long long g_split_halo_min_patches;  // "split_halo_min_patches"
 bool conv_split_halo_supported(const ConvArgs& a);
 void launch_conv_split_halo(const ConvArgs& a, hipStream_t st);
@@ -80,14 +72,7 @@ bool conv_halo_supported(const ConvArgs& a, bool dst_f32);
 int conv_tuning_set(const char* key, long long value);   // dispatch knobs of the MFMA conv kernels (kernels_halo.hip)
 void launch_conv_halo(const ConvArgs& a, hipStream_t st);
 
-// ---- kernels_halo2.hip : 256-pixel x 256-column (phase, channel) tiles for the ConvTranspose layers, one block per CU ----
-extern long long g_halo2;              // 0 disables ("halo2")
-extern long long g_halo2_min_blocks;   // "halo2_min_blocks"
-bool conv_halo2_supported(const ConvArgs& a, bool dst_f32);
-void launch_conv_halo2(const ConvArgs& a, hipStream_t st);
-int halo2_tuning_set(const char* key, long long value);
-
-// ---- kernels_halo3.hip : the same K loop on 256-pixel x 128-column tiles, four waves per block, two blocks per CU ----
+// ---- kernels_halo3.hip : ConvTranspose phases on 256-pixel x 128-column tiles, four waves per block, two blocks per CU ----
 extern long long g_halo3;              // 0 disables ("halo3")
 extern long long g_halo3_min_blocks;   // "halo3_min_blocks"
 bool conv_halo3_supported(const ConvArgs& a, bool dst_f32);

@@ -2,8 +2,8 @@
 // sub-pixel phases of ConvTranspose 4x4/s2/p1 (reference: Conv / C3 bottlenecks of
 // models/yolov5/common.py and the ConvTranspose2d of basemodel.py double_conv_up_c3).
 //
-// Why a second kernel next to kernels_igemm.hip: ablations of the implicit-GEMM kernel (selftest
-// ST_ABL=1) show its K loop is bound by bytes through the vector-memory -> LDS path, not by MFMA
+// Why a second kernel next to kernels_igemm.hip: ablations of the implicit-GEMM kernel (DESIGN.md
+// 4.1) showed its K loop is bound by bytes through the vector-memory -> LDS path, not by MFMA
 // issue or by bytes in flight: dropping the (always L1/L2-hit) weight loads alone buys 15-20 %,
 // dropping the activation loads ~30 %.  Per K step that kernel moves a 128-pixel activation tile
 // for EVERY tap plus a 128-row weight tile, 16 KB per 1 MFLOP.  Here
@@ -23,14 +23,6 @@
 #include "kernels.h"
 
 int g_conv_halo = 1;   // selftest / tuning: 0 sends everything to the implicit-GEMM kernel
-// A/B variants that lost their measurements (two taps per barrier, 1x1 layers through this kernel, the
-// cycle-stamped instantiation) exist in the selftest build only (-DCTD_AB_VARIANTS, csrc/Makefile); the product library
-// holds the kernels the engine launches, and no environment reads.
-#ifdef CTD_AB_VARIANTS
-int g_halo_tps = 1;     // taps per barrier of the halo kernel: 1 or 2 (conv_tuning_set("halo_tps"))
-#else
-constexpr int g_halo_tps = 1;
-#endif
 
 namespace {
 
@@ -41,22 +33,20 @@ constexpr int AROWS_PAD = 336;        // 18x18 = 324 haloed rows, rounded up to 
                                       // (LDS decides the blocks per CU: 336 rows let the 64-channel variant keep 3)
 constexpr int NTHR = 512;
 
-// TPS = taps per barrier: the weight tiles of TPS consecutive taps are staged together, so a chunk of a
-// ConvTranspose phase (4 taps) takes 2 barriers instead of 4 and a 3x3 chunk 5 instead of 9.
+// One tap per barrier (two taps per barrier, with their weight tiles staged together, measured slower: DESIGN.md 4.1).
 // PAIR (ConvT 4x4/s2 with 64 output channels, BN = 128): a block computes the two sub-pixel phases (py, px = 0)
 // and (py, px = 1) of its patch -- N columns 0-63 are phase px = 0, 64-127 phase px = 1.  The two phases read the
 // same input rows and overlapping columns (dx in {-1,0} and {0,+1}), so ONE 17x18 patch serves both: half the
 // patch DMA per MFMA, and the wave tile is the 2x4-fragment tile of the 128-channel layers (6 LDS reads per 8
 // MFMAs) instead of 1x2 (3 reads per 2 MFMAs).
-template <int BN, int WGN, int WGM, bool PROF, int TPS = 1, bool PAIR = false>
+template <int BN, int WGN, int WGM, bool PAIR = false>
 __global__ __launch_bounds__(NTHR, 4) void conv_halo_kernel(ConvArgs a) {   // 4 waves / SIMD = 2 blocks / CU
   if (a.prio) __builtin_amdgcn_s_setprio(3);   // ahead of a co-running tail's waves in the issue arbiter
   constexpr int TN = BN / (32 * WGN);
   constexpr int TM = BMH / (32 * WGM);
   static_assert(WGN * WGM == 8, "8 waves");
   constexpr int A_BUF = AROWS_PAD * BKH;          // halves
-  constexpr int W_TILE = BN * BKH;                // one tap's weight tile
-  constexpr int W_BUF = TPS * W_TILE;
+  constexpr int W_BUF = BN * BKH;                 // one tap's weight tile
   constexpr int LDS_STAGE = 2 * A_BUF + 2 * W_BUF;
   constexpr int OP = BN + 8;
   constexpr int LDS_OUT = BMH * OP;
@@ -67,10 +57,6 @@ __global__ __launch_bounds__(NTHR, 4) void conv_halo_kernel(ConvArgs a) {   // 4
   half_t* As = lds;               // [2][AROWS_PAD][32]
   half_t* Ws = lds + 2 * A_BUF;   // [2][BN][32]
 
-  constexpr bool prof = PROF;   // selftest instantiation: cycle stamps of wave 0 (compiled out otherwise)
-  auto stamp = [&]() -> long long { return PROF ? (long long)__builtin_readcyclecounter() : 0ll; };
-  const long long T0 = stamp();
-  long long t_issue = 0, t_comp = 0, t_wait = 0;
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wave_u = __builtin_amdgcn_readfirstlane(t >> 6);
@@ -164,10 +150,10 @@ __global__ __launch_bounds__(NTHR, 4) void conv_halo_kernel(ConvArgs a) {   // 4
     if ((i * NTHR + wave_u * 64) / 4 < AROWS_PAD)   // pass 2: waves 0..4 cover rows 256..335
       __builtin_amdgcn_global_load_lds((gptr_t)g, (lptr_t)dst, 16, 0, 0);
   };
-  auto dma_w = [&](int chunk, int tap, int buf, int slot = 0) {
+  auto dma_w = [&](int chunk, int tap, int buf) {
     if (WCHUNKS >= NTHR || t < WCHUNKS) {
       const char* wk = wtile + (size_t)(tap * nkc + chunk) * (WPACK * BKH * 2);
-      half_t* dst = Ws + (size_t)buf * W_BUF + (size_t)slot * W_TILE + (size_t)(wave_u * 64) * 8;
+      half_t* dst = Ws + (size_t)buf * W_BUF + (size_t)(wave_u * 64) * 8;
       __builtin_amdgcn_global_load_lds((gptr_t)(wk + (PAIR ? woff_p : woff)), (lptr_t)dst, 16, 0, 0);
     }
   };
@@ -196,79 +182,59 @@ __global__ __launch_bounds__(NTHR, 4) void conv_halo_kernel(ConvArgs a) {   // 4
   const int flw = swz(l31);   // weight rows of one fragment differ by multiples of 32
 
   // prologue: patch of chunk 0 + weights of step 0
-  const long long T1 = stamp();
   dma_a(0, 0);
   dma_a(0, 1);
   if (HH * HW > 256) dma_a(0, 2);
   dma_w(0, 0, 0);
-  if (TPS > 1)
-    for (int j = 1; j < TPS && j < taps; ++j) dma_w(0, j, 0, j);
   __syncthreads();
-  const long long T2 = stamp();
 
   // One step of prefetch.  (Weight tiles two steps ahead in a 3-deep ring with a counted
   // s_waitcnt vmcnt measured slower: the extra 4-8 KB of LDS costs the 32/64-channel variants
   // their third resident block, and the 128-channel variant gains nothing -- like the
   // implicit-GEMM kernel, the loop is not short of bytes in flight.)
   int step = 0;
-  const int nst = (taps + TPS - 1) / TPS;     // barriers per channel chunk
   for (int c = 0; c < nchunk; ++c) {
     const half_t* Ac = As + (size_t)(c & 1) * A_BUF;
-    for (int sidx = 0; sidx < nst; ++sidx, ++step) {
-      const int tap0 = sidx * TPS;
-      // next step's weight tiles, and the next chunk's patch spread over this chunk's first steps
-      const long long s0 = stamp();
-      const bool last_st = sidx + 1 == nst;
+    for (int tap = 0; tap < taps; ++tap, ++step) {
+      // next step's weight tile, and the next chunk's patch spread over this chunk's first steps
+      const bool last_st = tap + 1 == taps;
       if (!(last_st && c + 1 == nchunk)) {
-        const int nc = last_st ? c + 1 : c, nt0 = last_st ? 0 : tap0 + TPS;
-#pragma unroll
-        for (int j = 0; j < TPS; ++j)
-          if (nt0 + j < taps) dma_w(nc, nt0 + j, (step + 1) & 1, j);
+        const int nc = last_st ? c + 1 : c, nt = last_st ? 0 : tap + 1;
+        // A one-trip loop and a dead `taps == 1` arm below, on purpose: in this shape the compiler emits the instructions it
+        // emitted while the loop still had a taps-per-barrier parameter.  The plain `if` is equivalent but compiles to
+        // other scalar control code in the K loop, which would have to be timed before it replaces this.
+        for (int j = 0; j < 1; ++j)
+          if (nt + j < taps) dma_w(nc, nt + j, (step + 1) & 1);
       }
       if (c + 1 < nchunk) {   // static pass indices: the row tables stay in registers
-        if (TPS == 1) {
-          if (sidx == 0) {
-            dma_a(c + 1, 0);
-            if (nst == 1) dma_a(c + 1, 1);      // 1x1: one step per chunk, the 256-row patch is two passes
-          } else if (sidx == 1) dma_a(c + 1, 1);
-          else if (sidx == 2) dma_a(c + 1, 2);
-        } else {
-          if (sidx == 0) { dma_a(c + 1, 0); dma_a(c + 1, 1); }
-          else if (sidx == 1) dma_a(c + 1, 2);
-        }
+        if (tap == 0) {
+          dma_a(c + 1, 0);
+          if (taps == 1) dma_a(c + 1, 1);      // never taken: conv_halo_supported admits 4 or 9 taps (see above)
+        } else if (tap == 1) dma_a(c + 1, 1);
+        else if (tap == 2) dma_a(c + 1, 2);
       }
-      const long long s1 = stamp();
+      const int ty = tap / a.KW, tx = tap - ty * a.KW;
+      const half_t* Wb = Ws + (size_t)(step & 1) * W_BUF + (size_t)(wn * TN * 32 + l31) * BKH;
+      const int tapoff = ty * HW + tx + (PAIR ? wn : 0);   // PAIR: phase px = 1 (wn = 1) reads one column further right
 #pragma unroll
-      for (int j = 0; j < TPS; ++j) {
-        const int tap = tap0 + j;
-        if (TPS > 1 && tap >= taps) break;
-        const int ty = tap / a.KW, tx = tap - ty * a.KW;
-        const half_t* Wb = Ws + (size_t)(step & 1) * W_BUF + (size_t)j * W_TILE + (size_t)(wn * TN * 32 + l31) * BKH;
-        const int tapoff = ty * HW + tx + (PAIR ? wn : 0);   // PAIR: phase px = 1 (wn = 1) reads one column further right
+      for (int kk = 0; kk < BKH / 16; ++kk) {
+        half8_t fw[TN], fx[TM];
 #pragma unroll
-        for (int kk = 0; kk < BKH / 16; ++kk) {
-          half8_t fw[TN], fx[TM];
+        for (int i = 0; i < TN; ++i) fw[i] = *(const half8_t*)(Wb + i * 32 * BKH + (((kk * 2 + khalf) ^ flw) * 8));
 #pragma unroll
-          for (int i = 0; i < TN; ++i) fw[i] = *(const half8_t*)(Wb + i * 32 * BKH + (((kk * 2 + khalf) ^ flw) * 8));
-#pragma unroll
-          for (int jj = 0; jj < TM; ++jj) {
-            const int row = row0[jj] + tapoff;
-            fx[jj] = *(const half8_t*)(Ac + row * BKH + (((kk * 2 + khalf) ^ swz(row)) * 8));
-          }
-#pragma unroll
-          for (int i = 0; i < TN; ++i)
-#pragma unroll
-            for (int jj = 0; jj < TM; ++jj)
-              acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[i], fx[jj], acc[i][jj], 0, 0, 0);
+        for (int jj = 0; jj < TM; ++jj) {
+          const int row = row0[jj] + tapoff;
+          fx[jj] = *(const half8_t*)(Ac + row * BKH + (((kk * 2 + khalf) ^ swz(row)) * 8));
         }
+#pragma unroll
+        for (int i = 0; i < TN; ++i)
+#pragma unroll
+          for (int jj = 0; jj < TM; ++jj)
+            acc[i][jj] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[i], fx[jj], acc[i][jj], 0, 0, 0);
       }
-      const long long s2 = stamp();
       __syncthreads();   // waits the DMAs (vmcnt 0) and fences the LDS buffers for reuse
-      const long long s3 = stamp();
-      t_issue += s1 - s0; t_comp += s2 - s1; t_wait += s3 - s2;
     }
   }
-  const long long T3 = stamp();
 
   // ---- epilogue: bias + activation (+ residual), transposed through LDS for 16-B row stores ----
   const int hi = lane >> 5;
@@ -300,7 +266,6 @@ __global__ __launch_bounds__(NTHR, 4) void conv_halo_kernel(ConvArgs a) {   // 4
     case CTD_ACT_SIGMOID: epilogue(std::integral_constant<int, CTD_ACT_SIGMOID>{}); break;
     default: epilogue(std::integral_constant<int, CTD_ACT_NONE>{}); break;
   }
-  const long long T4 = stamp();
   __syncthreads();
   constexpr int CPP = BN / 8;          // 16-B chunks per pixel row of the tile
   constexpr int PPI = NTHR / CPP;      // pixels covered by one pass of the block
@@ -341,19 +306,12 @@ __global__ __launch_bounds__(NTHR, 4) void conv_halo_kernel(ConvArgs a) {   // 4
       if (okp[it]) *(half8_t*)((half_t*)a.dst + opix[it] * a.pitchD + n) = *(const half8_t*)(Os + (size_t)pl * OP + cch * 8);
     }
   }
-  if (prof) {
-    const long long T5 = stamp();
-    if (t == 0) {
-      long long* d = a.dbg + (size_t)blockIdx.x * 8;
-      d[0] = T1 - T0; d[1] = T2 - T1; d[2] = t_issue; d[3] = t_comp; d[4] = t_wait; d[5] = T4 - T3; d[6] = T5 - T4; d[7] = T5 - T0;
-    }
-  }
 }
 
 void launch_halo_pair(const ConvArgs& a, hipStream_t st) {
   const int tilesX = (a.Mw + TWP - 1) / TWP, tilesY = (a.Mh + THP - 1) / THP;
   dim3 grid((unsigned)(2 * tilesX * tilesY * a.B), 1, 1);
-  hipLaunchKernelGGL((conv_halo_kernel<128, 2, 4, false, 1, true>), grid, dim3(NTHR), 0, st, a);
+  hipLaunchKernelGGL((conv_halo_kernel<128, 2, 4, true>), grid, dim3(NTHR), 0, st, a);
 }
 
 template <int BN, int WGN, int WGM>
@@ -361,17 +319,7 @@ void launch_halo_cfg(const ConvArgs& a, hipStream_t st) {
   const int ntn = a.Npad / BN;
   const int tilesX = (a.Mw + TWP - 1) / TWP, tilesY = (a.Mh + THP - 1) / THP;
   dim3 grid((unsigned)(ntn * a.nphase * tilesX * tilesY * a.B), 1, 1);
-#ifdef CTD_AB_VARIANTS
-  if ((a.k_rot & 16) && a.dbg) {
-    hipLaunchKernelGGL((conv_halo_kernel<BN, WGN, WGM, true>), grid, dim3(NTHR), 0, st, a);
-    return;
-  }
-  if (g_halo_tps == 2) {
-    hipLaunchKernelGGL((conv_halo_kernel<BN, WGN, WGM, false, 2>), grid, dim3(NTHR), 0, st, a);
-    return;
-  }
-#endif
-  hipLaunchKernelGGL((conv_halo_kernel<BN, WGN, WGM, false>), grid, dim3(NTHR), 0, st, a);
+  hipLaunchKernelGGL((conv_halo_kernel<BN, WGN, WGM>), grid, dim3(NTHR), 0, st, a);
 }
 
 }  // namespace
@@ -380,22 +328,13 @@ void launch_halo_cfg(const ConvArgs& a, hipStream_t st) {
 // small maps that way; the host side applies CTD_TUNING="key=value,..." once after loading the library).
 long long g_halo_min_patches = 1024;   // fewer 256-pixel patches: implicit GEMM
 int g_halo_pair = 1;                   // 64-channel ConvT: both px phases per block
-#ifdef CTD_AB_VARIANTS
-int g_halo_1x1 = 0;                    // 1x1 layers through the halo kernel (measured slower: selftest only)
-#else
-constexpr int g_halo_1x1 = 0;
-#endif
 
 int conv_tuning_set(const char* key, long long value) {
   const std::string k(key ? key : "");
   if (k == "halo_min_patches") g_halo_min_patches = value;
   else if (k == "halo_pair") g_halo_pair = (int)value;
   else if (k == "halo") g_conv_halo = (int)value;
-#ifdef CTD_AB_VARIANTS
-  else if (k == "halo_1x1") g_halo_1x1 = (int)value;
-  else if (k == "halo_tps") g_halo_tps = (int)value;
-#endif
-  else return halo2_tuning_set(key, value);
+  else return halo3_tuning_set(key, value);
   return 0;
 }
 
@@ -404,8 +343,7 @@ int conv_tuning_set(const char* key, long long value) {
 bool conv_halo_supported(const ConvArgs& a, bool dst_f32) {
   if (!g_conv_halo || dst_f32) return false;
   if (a.stride != 1 || a.s0.up || (a.s1.c && a.s1.up)) return false;
-  if (!((a.KH == 3 && a.KW == 3) || (a.KH == 2 && a.KW == 2) || (g_halo_1x1 && a.KH == 1 && a.KW == 1 && a.nphase == 1)))
-    return false;
+  if (!((a.KH == 3 && a.KW == 3) || (a.KH == 2 && a.KW == 2))) return false;
   if (a.Mh != a.Hin || a.Mw != a.Win) return false;
   if (a.s0.c % BKH || a.s1.c % BKH || a.bk != BKH || !a.w_tiled) return false;
   if (a.pitchD % 8 || a.N % 8) return false;
@@ -418,7 +356,7 @@ bool conv_halo_supported(const ConvArgs& a, bool dst_f32) {
 
 void launch_conv_halo(const ConvArgs& a, hipStream_t st) {
   const int bn = igemm_ntile(a.N);
-  if (g_halo_pair && a.nphase == 4 && a.N == 64 && a.Npad == 64 && !a.res && !((a.k_rot & 16) && a.dbg) && g_halo_tps == 1)
+  if (g_halo_pair && a.nphase == 4 && a.N == 64 && a.Npad == 64 && !a.res)
     return launch_halo_pair(a, st);
   if (bn == 128) launch_halo_cfg<128, 2, 4>(a, st);
   else if (bn == 64) launch_halo_cfg<64, 2, 4>(a, st);

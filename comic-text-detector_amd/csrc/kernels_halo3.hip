@@ -1,12 +1,12 @@
 // ConvTranspose 4x4/s2 phases on 256-pixel x 128-column tiles with FOUR waves per block and two blocks per CU (gfx950) --
-// kernels_halo2.hip's K loop (128-register wave tiles of 128 pixels x 64 columns, fragment addresses computed under the
+// a K loop of big wave tiles (128-register wave tiles of 128 pixels x 64 columns, fragment addresses computed under the
 // MFMAs, 3-slot weight ring, counted s_waitcnt vmcnt, one LDS-DMA pointer add per piece) in a shape whose prologue and
 // epilogue do not stop the CU.
 //
-// Why.  kernels_halo2.hip runs its K loop at the matrix-pipe occupancy of the guide's 256x256 GEMM template (0.58 busy), but
-// with ONE block per CU nothing overlaps a block's prologue (first DMA round trip) and epilogue (a 128-KB tile leaves at
+// Why.  Its predecessor (256-pixel x 256-column tiles, eight waves, removed: DESIGN 4.10) ran this K loop at the matrix-pipe
+// occupancy of the guide's 256x256 GEMM template (0.58 busy), but with ONE block per CU nothing overlapped a block's prologue (first DMA round trip) and epilogue (a 128-KB tile leaves at
 // ~10 B per clock and CU): 13 % of a block's life at 512 -> 256, 27 % at 256 -> 128, 45 % at 128 -> 64 channels
-// (ST_H2_ABL ablations).  Here a block has one wave per SIMD and 72 KB of LDS, so a CU holds two blocks with the
+// (ablations).  Here a block has one wave per SIMD and 72 KB of LDS, so a CU holds two blocks with the
 // same 2 waves per SIMD and 256 registers per wave: while one block stores its tile the other one computes, and the two
 // waves of a SIMD (one from each block) alternate between LOAD and MFMA segments without being told to.
 //
@@ -18,13 +18,13 @@
 // share of the next chunk's patch, s_waitcnt vmcnt(issued now) lgkmcnt(0)] | s_barrier | MFMA(k) [16 MFMAs + the address
 // arithmetic of step k + 1].  One barrier per step is enough: a ring slot is rewritten two LOAD segments after its last
 // read, and every wave's reads are complete (lgkmcnt 0) before it passes the barrier in between.
-// Arithmetic: K walk and MFMA order per accumulator as in kernels_halo.hip / kernels_halo2.hip -- bit-identical results.
+// Arithmetic: K walk and MFMA order per accumulator as in kernels_halo.hip -- bit-identical results.
 #include <string>
 #include <type_traits>
 
 #include "kernels.h"
 
-long long g_halo3 = 1;                 // "halo3": 0 leaves the ConvT layers to kernels_halo2.hip / kernels_halo.hip
+long long g_halo3 = 1;                 // "halo3": 0 leaves the ConvT layers to kernels_halo.hip
 long long g_halo3_min_blocks = 1024;   // "halo3_min_blocks"
 
 namespace {
@@ -111,7 +111,7 @@ __global__ __launch_bounds__(NTHR, 2) void conv_halo3_kernel(ConvArgs a) {   // 
   using lptr_t = __attribute__((address_space(3))) void*;
   auto swz = [](int row) { return (row >> 2) & 3; };
 
-  // ---- six haloed-patch pieces per thread and chunk, as running pointers (kernels_halo2.hip)
+  // ---- six haloed-patch pieces per thread and chunk, as running pointers
   const char* ap[6];
   auto patch_ptrs = [&](const SrcView& sv) {
 #pragma unroll
@@ -487,7 +487,6 @@ bool conv_halo3_supported(const ConvArgs& a, bool dst_f32) {
   if (a.s0.c % BKH || a.s1.c % BKH || a.bk != BKH || !a.w_tiled) return false;
   if (a.pitchD % 8) return false;
   if (a.s0.H != a.Hin || a.s0.W != a.Win || (a.s1.c && (a.s1.H != a.Hin || a.s1.W != a.Win))) return false;
-  if (a.k_rot) return false;
   if ((a.s0.c + a.s1.c) * 2 + 16 > CTD_ZEROS_BYTES) return false;
   const long long blocks = (long long)a.B * (a.Mh / THP) * (a.Mw / TWP) * (a.N == 64 ? 2 : (a.N == 128 ? 4 : 8));
   return blocks >= g_halo3_min_blocks;

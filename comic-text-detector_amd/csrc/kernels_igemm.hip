@@ -27,14 +27,11 @@
 
 #include "kernels.h"
 
-int g_igemm_occ_lo = 0;  // selftest build (-DCTD_AB_VARIANTS) only: 1 = register-staged loads instead of LDS-DMA
-
 namespace {
 
 // K step BK = 32 or 64 halves per LDS row (64 / 128 B), XOR-swizzled 16-B chunks.
-// ABL: selftest-only instantiation that honours the ablation bits of a.k_rot; in the product
-// instantiations (ABL = false) every hook below is a compile-time zero.
-template <int BN, int BM, int WGN, int WGM, int BK, bool DST_F32, int MINW, int PF, bool PROF = false, bool ABL = false>
+// PF = 2: global -> LDS by LDS-DMA (the fp16 destinations); PF = 1: register-staged loads (the fp32 destinations).
+template <int BN, int BM, int WGN, int WGM, int BK, bool DST_F32, int MINW, int PF>
 __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
   if (a.prio) __builtin_amdgcn_s_setprio(3);   // ahead of a co-running tail's waves in the issue arbiter
   constexpr int LP = BK;                            // LDS row pitch in halves (XOR swizzled, no pad)
@@ -55,11 +52,9 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
   // every K step (a block no longer overlapped its own DMAs with its MFMAs).
   __shared__ __attribute__((aligned(16))) half_t lds[LDS_MAIN + 2 * BN];
   float* bias_s = (float*)(lds + LDS_MAIN);
-  const int krot = ABL ? a.k_rot : 0;
   half_t* As = lds;                 // [2][BM][LP]  pixels
   half_t* Ws = lds + 2 * BM * LP;   // [2][BN][LP]  weights
 
-  const long long T0 = PROF ? (long long)__builtin_readcyclecounter() : 0ll;
   const int t = threadIdx.x;
   const int lane = t & 63;
   const int wave = t >> 6;
@@ -81,12 +76,8 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
   }
   const int tile_n = bid % ntn;
   const int bq = bid / ntn;
-  int phase = a.nphase == 4 ? (bq & 3) : 0;
-  int tile_m = a.nphase == 4 ? (bq >> 2) : bq;
-  if ((krot & 8) && a.nphase == 4) {   // selftest A/B: phase-major order
-    phase = bq / ntm;
-    tile_m = bq % ntm;
-  }
+  const int phase = a.nphase == 4 ? (bq & 3) : 0;
+  const int tile_m = a.nphase == 4 ? (bq >> 2) : bq;
   const int n0 = tile_n * BN;
   const int m0 = tile_m * BM;
   if (t < BN) bias_s[t] = a.bias[n0 + t];   // visible after the first barrier of the K loop
@@ -163,7 +154,7 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
     bool ok = true;
 #pragma unroll
     for (int i = 0; i < AROWS; ++i) ok = ok && vmask[i] == full;
-    interior = __builtin_amdgcn_ballot_w64(ok) == ~0ull && !(krot & 32);
+    interior = __builtin_amdgcn_ballot_w64(ok) == ~0ull;
   }
   // weights: tile-major [n_tile][k_step][BN][BK]; per-thread constant part of the address
   int woff[WROWS];
@@ -204,9 +195,7 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
     const int ch = first ? cc : cc - a.s0.c;
     const int tap = ty * a.KW + tx;
     rok = 0;
-    if ((krot & 128) && kp > 0) {
-      // selftest ablation: no activation loads after the first K step
-    } else if (GLDS && interior && !s.up) {
+    if (GLDS && interior && !s.up) {
       // interior pixel tile: every tap of every row is inside the image.  One scalar base per
       // K step + this thread's constant 32-bit row offset -> no per-row VALU work at all
       // (the K loop spends its issue slots on address arithmetic, not on MFMAs, otherwise).
@@ -248,7 +237,7 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
     const char* wk = wtile + (size_t)kp * (BN * BK * 2);
 #pragma unroll
     for (int i = 0; i < WROWS; ++i)
-      if ((WCHUNKS >= 256 || t + 256 * i < WCHUNKS) && !((krot & 64) && kp > 0)) {
+      if (WCHUNKS >= 256 || t + 256 * i < WCHUNKS) {
         if (GLDS) dma(wk + woff[i], Wd, i);
         else rw[i] = *(const half8_t*)(wk + woff[i]);
       }
@@ -297,16 +286,10 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
 
-  // selftest instrumentation (k_rot & 16): cycle stamps of wave 0 -> where a block's time goes
-  constexpr bool prof = PROF;   // selftest instantiation only; compiled out of the product kernels
-  auto stamp = [&]() -> long long { return PROF ? (long long)__builtin_readcyclecounter() : 0ll; };
-  long long t_issue = 0, t_comp = 0, t_wait = 0;
-  const long long T1 = stamp();
   Stage sA;
   load_tile(sA, 0);
   if (!GLDS) store_tile(sA, 0);
   __syncthreads();     // with LDS-DMA pending the compiler's barrier sequence waits vmcnt(0) first
-  const long long T2 = stamp();
 
   const int l31 = lane & 31, khalf = lane >> 5;
   const int fl = swz(l31);   // rows of one fragment differ by multiples of 32 -> same swizzle
@@ -328,23 +311,16 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
           acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fw[i], fx[j], acc[i][j], 0, 0, 0);
     }
   };
-  const int abl = krot;   // selftest ablation bits: 1 = no loads in the K loop, 2 = no MFMAs, 4 = no stores
   // One K step in flight: the LDS-DMAs (or loads) of step k+1 are issued before the MFMAs of step k.
   // (A 3-deep ring with two steps in flight and a counted vmcnt measured 3-6 % SLOWER on every
   // layer shape: the K loop is not short of bytes in flight, see DESIGN.md.)
   for (int ks = 0; ks < nk; ++ks) {
     const int buf = ks & 1;
-    const long long s0 = stamp();
-    if (ks + 1 < nk && !(abl & 1)) load_tile(sA, buf ^ 1);
-    const long long s1 = stamp();
-    if (!(abl & 2)) compute(buf);
+    if (ks + 1 < nk) load_tile(sA, buf ^ 1);
+    compute(buf);
     if (!GLDS && ks + 1 < nk) store_tile(sA, buf ^ 1);
-    const long long s2 = stamp();
     __syncthreads();
-    const long long s3 = stamp();
-    t_issue += s1 - s0; t_comp += s2 - s1; t_wait += s3 - s2;
   }
-  const long long T3 = stamp();
 
   // ---- epilogue: bias + activation (+ residual) -> NHWC store -----------------
   const int hi = lane >> 5;
@@ -435,7 +411,6 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
     case CTD_ACT_SIGMOID: epilogue(std::integral_constant<int, CTD_ACT_SIGMOID>{}); break;
     default: epilogue(std::integral_constant<int, CTD_ACT_NONE>{}); break;
   }
-  const long long T4 = stamp();
   if (staged) {
     // The MFMA C layout gives each lane 4 channels of one pixel: storing that directly makes
     // 16-B write requests scattered over 32 cache lines per instruction (PMC: TCP_TCC_WRITE_REQ
@@ -454,7 +429,7 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
 #pragma unroll
     for (int it = 0; it < NIT; ++it) {
       const int m = m0 + it * PPI + t / CPP;
-      okp[it] = m < a.M && n < a.N && !(abl & 4);
+      okp[it] = m < a.M && n < a.N;
       opx[it] = okp[it] ? out_pixel(m) : 0;
     }
     if (a.res) {
@@ -477,13 +452,6 @@ __global__ __launch_bounds__(256, MINW) void conv_igemm_kernel(ConvArgs a) {
           *(half8_t*)((half_t*)a.dst + opx[it] * a.pitchD + n) = *(const half8_t*)(Os + (size_t)(it * PPI + t / CPP) * OP + c * 8);
     }
   }
-  if (prof) {
-    const long long T5 = stamp();
-    if (t == 0) {
-      long long* d = a.dbg + (size_t)blockIdx.x * 8;
-      d[0] = T1 - T0; d[1] = T2 - T1; d[2] = t_issue; d[3] = t_comp; d[4] = t_wait; d[5] = T4 - T3; d[6] = T5 - T4; d[7] = T5 - T0;
-    }
-  }
 }
 
 // MINW = minimum waves per SIMD the register allocator must allow (launch bound).  The
@@ -495,18 +463,8 @@ void launch_cfg(const ConvArgs& a, bool dst_f32, hipStream_t st) {
   const int ntm = (a.M + BM - 1) / BM;
   dim3 grid(ntn * ntm * a.nphase, 1, 1);
   constexpr int HI = BK == 32 ? 4 : 2;
-  constexpr int LO = BK == 32 ? 3 : 2;
-  (void)LO;
   if (dst_f32) {
-    hipLaunchKernelGGL((conv_igemm_kernel<BN, BM, WGN, WGM, BK, true, HI, 1>), grid, dim3(256), 0, st, a);
-#ifdef CTD_AB_VARIANTS                // selftest build only: the A/B variants that lost, and the instrumented instantiations
-  } else if (g_igemm_occ_lo == 1) {   // register-staged loads (global -> VGPR -> ds_write)
-    hipLaunchKernelGGL((conv_igemm_kernel<BN, BM, WGN, WGM, BK, false, HI, 1>), grid, dim3(256), 0, st, a);
-  } else if ((a.k_rot & 16) && a.dbg) {   // cycle-stamped instantiation
-    hipLaunchKernelGGL((conv_igemm_kernel<BN, BM, WGN, WGM, BK, false, HI, 2, true, true>), grid, dim3(256), 0, st, a);
-  } else if (a.k_rot) {                   // ablation instantiation
-    hipLaunchKernelGGL((conv_igemm_kernel<BN, BM, WGN, WGM, BK, false, HI, 2, false, true>), grid, dim3(256), 0, st, a);
-#endif
+    hipLaunchKernelGGL((conv_igemm_kernel<BN, BM, WGN, WGM, BK, true, HI, 1>), grid, dim3(256), 0, st, a);   // register-staged loads
   } else {                            // LDS-DMA (global_load_lds, 16 B per lane), +5..10 % measured
     hipLaunchKernelGGL((conv_igemm_kernel<BN, BM, WGN, WGM, BK, false, HI, 2>), grid, dim3(256), 0, st, a);
   }
@@ -597,7 +555,6 @@ const char* launch_conv_igemm(const ConvArgs& a_in, bool dst_f32, hipStream_t st
   magic_div(a.Mh, a.mh_mul, a.mh_sh);
   a.bk = pick_bk(a);
   if (conv_halo3_supported(a, dst_f32)) { launch_conv_halo3(a, st); return "conv_halo3_kernel"; }
-  if (conv_halo2_supported(a, dst_f32)) { launch_conv_halo2(a, st); return "conv_halo2_kernel"; }
   if (conv_halo_supported(a, dst_f32)) { launch_conv_halo(a, st); return "conv_halo_kernel"; }
   const int bn = igemm_ntile(a.N);
   if (pick_bk(a) == 64) {

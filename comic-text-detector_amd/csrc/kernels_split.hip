@@ -55,6 +55,8 @@
 namespace {
 
 constexpr int SBK = 32;    // channels per K step
+constexpr int SBM = 128;   // pixels per block (256-pixel blocks for the 64-channel outputs measured 3-20 % slower:
+                           // profiles/r03_split_selftest.txt -- the 80-KB block leaves no LDS for a third block per CU)
 
 __device__ __forceinline__ void split8(const float4_t& a, const float4_t& b, half8_t& hi, half8_t& lo) {
 #pragma unroll
@@ -67,12 +69,10 @@ __device__ __forceinline__ void split8(const float4_t& a, const float4_t& b, hal
   }
 }
 
-// WDMA: weight tiles by LDS-DMA (global_load_lds, swizzle on the source chunk) instead of through registers
-// SBM = pixels per block: 128, or 256 for the 64-channel outputs (the weight tile of a K step then feeds twice the MFMAs
-// and every wave holds a 2x2-fragment tile like the 128 x 128 configuration)
+// Weight tiles go to LDS by LDS-DMA (global_load_lds, swizzle on the source chunk; through registers measured 7 % slower).
 // XSP: the sources are stored SPLIT (see "Split-plane activations" above): their 16-B chunks go to LDS by LDS-DMA like the
 // weights, and nothing is converted in the K loop
-template <int BN, int SBM, int WGN, int WGM, bool WDMA, bool XSP>
+template <int BN, int WGN, int WGM, bool XSP>
 __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a) {
   if (a.prio) __builtin_amdgcn_s_setprio(3);   // ahead of a co-running tail's waves in the issue arbiter
   constexpr int TN = BN / (32 * WGN);
@@ -146,14 +146,13 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a) {
     pb[i] = q / a.Mh;
   }
   // this thread's weight chunks: chunk q = t + 256 i of the tile = row q/4, LDS chunk position q%4
-  int woff[WROWS], wlds[WROWS];
+  int woff[WROWS];
 #pragma unroll
   for (int i = 0; i < WROWS; ++i) {
     const int q = t + 256 * i;
     const int r = (q >> 2) % BN, pos = q & 3;
-    const int srcc = WDMA ? (pos ^ swz(r)) : pos;                    // DMA writes lane-linear: swizzle the source
+    const int srcc = pos ^ swz(r);                                   // DMA writes lane-linear: swizzle the source
     woff[i] = (((n0 + r) >> 5) * nk * 32 + (r & 31)) * SBK + srcc * 8;   // + ks * 1024 per K step
-    wlds[i] = r * SBK + (WDMA ? pos : (pos ^ swz(r))) * 8;
   }
 
   using gptr_t = const __attribute__((address_space(1))) void*;
@@ -163,7 +162,6 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a) {
   };
 
   float4_t ra[AR][2];
-  half8_t rwh[WROWS], rwl[WROWS];
   int nx_cc = 0, nx_ty = 0, nx_tx = 0;   // (channel offset, tap) of the NEXT tile to load
   auto load_tile = [&](int ks, int dbuf) {
     if (XSP) {
@@ -231,13 +229,8 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a) {
 #pragma unroll
     for (int i = 0; i < WROWS; ++i)
       if (WCH >= 256 * (i + 1) || t + 256 * i < WCH) {
-        if (WDMA) {
-          dma(wh + woff[i] + kofs, Ws + (dbuf * 2 + 0) * WT, i);
-          dma(wl + woff[i] + kofs, Ws + (dbuf * 2 + 1) * WT, i);
-        } else {
-          rwh[i] = *(const half8_t*)(wh + woff[i] + kofs);
-          rwl[i] = *(const half8_t*)(wl + woff[i] + kofs);
-        }
+        dma(wh + woff[i] + kofs, Ws + (dbuf * 2 + 0) * WT, i);
+        dma(wl + woff[i] + kofs, Ws + (dbuf * 2 + 1) * WT, i);
       }
   };
   auto store_tile = [&](int buf) {
@@ -249,14 +242,6 @@ __global__ __launch_bounds__(256, 2) void conv_split_kernel(ConvArgs a) {
       const int o = r * SBK + ((seg ^ swz(r)) * 8);
       *(half8_t*)(Xs + (buf * 2 + 0) * XT + o) = hi;
       *(half8_t*)(Xs + (buf * 2 + 1) * XT + o) = lo;
-    }
-    if (!WDMA) {
-#pragma unroll
-      for (int i = 0; i < WROWS; ++i)
-        if (WCH >= 256 * (i + 1) || t + 256 * i < WCH) {
-          *(half8_t*)(Ws + (buf * 2 + 0) * WT + wlds[i]) = rwh[i];
-          *(half8_t*)(Ws + (buf * 2 + 1) * WT + wlds[i]) = rwl[i];
-        }
     }
   };
 
@@ -359,7 +344,7 @@ void split_magic_div(int d, unsigned& mul, unsigned& sh) {
   mul = (unsigned)(((1ull << sh) / (unsigned)d) + 1);
 }
 
-template <int BN, int SBM, int WGN, int WGM>
+template <int BN, int WGN, int WGM>
 void launch_split_cfg(const ConvArgs& a_in, hipStream_t st) {
   ConvArgs a = a_in;
   split_magic_div(a.Mw, a.mw_mul, a.mw_sh);
@@ -367,20 +352,11 @@ void launch_split_cfg(const ConvArgs& a_in, hipStream_t st) {
   const int ntn = a.Npad / BN;
   const int ntm = (a.M + SBM - 1) / SBM;
   const dim3 grid((unsigned)(ntn * ntm * a.nphase));
-  if (a.x_sp) { hipLaunchKernelGGL((conv_split_kernel<BN, SBM, WGN, WGM, true, true>), grid, dim3(256), 0, st, a); return; }
-#ifdef CTD_AB_VARIANTS
-  if (!g_split_wdma) { hipLaunchKernelGGL((conv_split_kernel<BN, SBM, WGN, WGM, false, false>), grid, dim3(256), 0, st, a); return; }
-#endif
-  hipLaunchKernelGGL((conv_split_kernel<BN, SBM, WGN, WGM, true, false>), grid, dim3(256), 0, st, a);
+  if (a.x_sp) { hipLaunchKernelGGL((conv_split_kernel<BN, WGN, WGM, true>), grid, dim3(256), 0, st, a); return; }
+  hipLaunchKernelGGL((conv_split_kernel<BN, WGN, WGM, false>), grid, dim3(256), 0, st, a);
 }
 
 }  // namespace
-
-#ifdef CTD_AB_VARIANTS    // selftest build only: weight tiles through registers instead of LDS-DMA (7 % slower)
-int g_split_wdma = 1;
-// ... and 256-pixel blocks for 64-channel N tiles -- measured 3-20 % SLOWER than 128
-int g_split_bm256 = 0;    // (profiles/r03_split_selftest.txt): the 80-KB block leaves no LDS for a third block per CU
-#endif
 
 // f32 sources / destination with 16-B aligned channel rows, source channel counts multiples of 32
 bool conv_split_supported(const ConvArgs& a) {
@@ -401,14 +377,11 @@ const char* launch_conv_split(const ConvArgs& a, hipStream_t st) {
   if (conv_split_halo_supported(a)) { launch_conv_split_halo(a, st); return "conv_split_halo_kernel"; }
   int bn = a.Npad % 128 == 0 ? 128 : (a.Npad % 64 == 0 ? 64 : 32);
   // small maps: narrower N tiles give 2-4x the blocks (the packing is in 32-row blocks, any multiple of 32 reads it)
-  const long long ntm = (a.M + 127) / 128;
+  const long long ntm = (a.M + SBM - 1) / SBM;
   while (bn > 32 && (a.Npad / bn) * ntm * a.nphase < 512) bn >>= 1;
-  if (bn == 128) launch_split_cfg<128, 128, 2, 2>(a, st);
-#ifdef CTD_AB_VARIANTS
-  else if (bn == 64 && g_split_bm256 && (a.Npad / 64) * ((a.M + 255) / 256) * a.nphase >= 1024) launch_split_cfg<64, 256, 1, 4>(a, st);
-#endif
-  else if (bn == 64) launch_split_cfg<64, 128, 1, 4>(a, st);
-  else launch_split_cfg<32, 128, 1, 4>(a, st);
+  if (bn == 128) launch_split_cfg<128, 2, 2>(a, st);
+  else if (bn == 64) launch_split_cfg<64, 1, 4>(a, st);
+  else launch_split_cfg<32, 1, 4>(a, st);
   return "conv_split_kernel";
 }
 

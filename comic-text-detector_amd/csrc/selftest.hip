@@ -178,37 +178,26 @@ static void run_case(const Case& cs, int B, bool timing) {
   const double flops = cs.kind ? 2.0 * B * Hin * Win * 16.0 * cin * cs.N : 2.0 * (double)ig.M * cs.N * ig.K;
   const double bytes = 2.0 * ((double)n0 + n1 + (double)B * Ho * Wo * cs.N * (cs.res ? 2 : 1) + (double)cs.N * cin * k * k);
   std::printf("[case] %-32s B=%d out %dx%dx%d |", cs.name, B, Ho, Wo, cs.N);
-  struct Var { const char* name; int bk, tiled, rot, abl, h1 = 0; };   // h1: 1 = only kernels_halo.hip, 2 = kernels_halo2.hip, 0 = product dispatch
-  // ST_ABL=1 appends ablations of the default kernel (wrong results by construction, timing only)
-  // rot: 0 = default dispatch (halo kernel where it applies), 2 = implicit-GEMM kernel only, 1 = register staged
-  const Var vars[] = {{"default", 32, 1, 0, 0}, {"halo2", 32, 1, 0, 0, 2}, {"halo1", 32, 1, 0, 0, 1}, {"igemm", 32, 1, 2, 0}, {"bk32/reg", 32, 1, 1, 0}, {"bk64/glds", 64, 1, 2, 0},
-                      // ablations of the implicit-GEMM kernel (rot 2 keeps the halo kernel out of the way)
-                      {"noload", 32, 1, 2, 1}, {"nomfma", 32, 1, 2, 2}, {"nostore", 32, 1, 2, 4},
-                      {"loadonly", 32, 1, 2, 6}, {"mfmaonly", 32, 1, 2, 5}, {"phasemajor", 32, 1, 2, 8},
-                      {"nofastpath", 32, 1, 2, 32}, {"noWloads", 32, 1, 2, 64}, {"noAloads", 32, 1, 2, 128}};
+  struct Var { const char* name; int bk, rot, h1 = 0; };   // h1: 1 = only kernels_halo.hip, 0 = product dispatch
+  // rot: 0 = default dispatch (halo kernels where they apply), 2 = implicit-GEMM kernel only
+  const Var vars[] = {{"default", 32, 0}, {"igemm", 32, 2}, {"bk64/glds", 64, 2}, {"halo1", 32, 0, 1}};
 
   const char* vsel = std::getenv("ST_VAR");   // ST_VAR=1: only variant index 1
   for (const Var& v : vars) {
     if (vsel && std::atoi(vsel) != (int)(&v - vars)) continue;
-    if (v.abl && !std::getenv("ST_ABL")) continue;
     const int bk = v.bk;
     if (bk == 64 && (cs.c0 % 64 || cs.c1 % 64)) continue;
     g_igemm_force_bk = bk;
-    ig.bk = bk; ig.w_tiled = v.tiled; ig.k_rot = v.abl;
-    g_igemm_occ_lo = v.rot == 1;   // staging mode: 0 = LDS-DMA, 1 = register staged
+    ig.bk = bk; ig.w_tiled = 1;
     g_conv_halo = v.rot == 0;
-    if (v.h1) {                                       // only where the default variant ran one of the big-tile kernels
-      ConvArgs q = ig;
-      q.bk = 32, q.w_tiled = 1, q.k_rot = 0;
-      g_halo2 = 1, g_halo3 = 1, g_conv_halo = 1;
-      if (!conv_halo3_supported(q, false) || !conv_halo2_supported(q, false) || !conv_halo_supported(q, false)) continue;
+    if (v.h1) {                                       // only where the default variant ran the big-tile kernel
+      g_halo3 = 1;
+      if (!conv_halo3_supported(ig, false) || !conv_halo_supported(ig, false)) continue;
     }
     g_halo3 = (v.rot == 0 && !v.h1 && !std::getenv("ST_NO_H3")) ? 1 : 0;
-    g_halo2 = (v.rot == 0 && v.h1 != 1) ? (std::getenv("ST_H2_NOPRIO") ? 2 : 1) : 0;
-    if (g_halo2 && std::getenv("ST_H2_ABL")) g_halo2 = 1 + 16 * std::atoi(std::getenv("ST_H2_ABL"));   // timing-only ablation of the big-tile kernel
     {
       std::vector<half_t> wig;
-      igemm_pack_weights(lg.data(), nphase, cs.N, Kig, bn, bk, v.tiled, wig);
+      igemm_pack_weights(lg.data(), nphase, cs.N, Kig, bn, bk, true, wig);
       CK(hipMemcpy(dWig, wig.data(), wig.size() * 2, hipMemcpyHostToDevice));
     }
     CK(hipMemset(dOut, 0xff, nout * 2));
@@ -223,10 +212,10 @@ static void run_case(const Case& cs, int B, bool timing) {
       maxerr = std::fmax(maxerr, e);
       if (!(e <= 4e-3 * (1.0 + std::fabs((double)r[i])))) ++bad;
     }
-    if (bad && !v.abl) ++g_fail;
+    if (bad) ++g_fail;
     static std::vector<half_t> o_default;             // the big-tile kernel must reproduce the 256 x 128 kernel bit for bit
     if (&v == vars) o_default = o;
-    if (&v == vars && ((g_halo2 == 1 && conv_halo2_supported(ig, false)) || conv_halo3_supported(ig, false))) {
+    if (&v == vars && conv_halo3_supported(ig, false)) {
       // its LDS hand-offs are ordered by counted waits and barriers only: repeat the launch and demand identical bits
       // (a race shows as a run-to-run difference long before it shows as an error beyond the tolerance)
       size_t racy = 0;
@@ -241,7 +230,7 @@ static void run_case(const Case& cs, int B, bool timing) {
       std::printf("  [x6 repeat: %s]", racy ? "DIFFERS RUN TO RUN" : "stable");
       if (racy) ++g_fail;
     }
-    if (v.h1) {
+    if (v.h1 && o_default.size() == nout) {           // ST_VAR=3 alone skipped the default variant: nothing to compare with
       size_t diff = 0;
       for (size_t i = 0; i < nout; ++i)
         if ((int)(i % pitchD) < cs.N && std::memcmp(&o[i], &o_default[i], 2) != 0) ++diff;
@@ -262,68 +251,8 @@ static void run_case(const Case& cs, int B, bool timing) {
       CK(hipEventElapsedTime(&t, e0, e1));
       ms = t / it;
     }
-    std::printf("  %s: %s %.3f ms %.0f TF %.0f GB/s |", v.name, v.abl ? "--" : bad ? "FAIL" : "ok", ms,
+    std::printf("  %s: %s %.3f ms %.0f TF %.0f GB/s |", v.name, bad ? "FAIL" : "ok", ms,
                 flops / (ms * 1e-3) / 1e12, bytes / (ms * 1e-3) / 1e9);
-    if (std::getenv("ST_PROF") && &v == vars && conv_halo2_supported(ig, false)) {
-      const size_t nblk = (size_t)B * ((Hin + 15) / 16) * ((Win + 15) / 16) * 4;
-      long long* dd = nullptr;
-      CK(hipMalloc(&dd, (nblk * 16 + 256) * sizeof(long long)));
-      CK(hipMemset(dd, 0, (nblk * 16 + 256) * sizeof(long long)));
-      ig.dbg = dd;
-      launch_conv_igemm(ig, false, 0);
-      CK(hipDeviceSynchronize());
-      ig.dbg = nullptr;
-      std::vector<long long> hd(nblk * 16 + 256);
-      CK(hipMemcpy(hd.data(), dd, hd.size() * sizeof(long long), hipMemcpyDeviceToHost));
-      double m[2][8] = {{0}};
-      size_t used = 0, same_simd = 0;
-      for (size_t bq = 0; bq < nblk; ++bq) {
-        if (!hd[bq * 16 + 7]) continue;
-        ++used;
-        same_simd += ((hd[bq * 16 + 6] >> 4) & 3) == ((hd[bq * 16 + 8 + 6] >> 4) & 3);     // HW_ID[5:4] of waves 0 and 4
-        for (int h = 0; h < 2; ++h) {
-          hd[(bq * 2 + h) * 8 + 6] >>= 8;
-          for (int q = 0; q < 8; ++q) m[h][q] += (double)hd[(bq * 2 + h) * 8 + q];
-        }
-      }
-      std::printf("\n      [halo2 prof] waves 0 and 4 on the same SIMD in %zu of %zu blocks", same_simd, used);
-      {   // block 0: when each wave starts LOAD, reaches / leaves the barrier after it, ends its MFMAs, leaves the second barrier
-        const size_t nb_launched = (size_t)B * ((Hin + 15) / 16) * ((Win + 15) / 16) * (4 / (cs.N == 256 ? 1 : (cs.N == 128 ? 2 : 4)));
-        const long long* tl = hd.data() + nb_launched * 16;
-        const long long t0 = tl[0];
-        for (int st_ = 0; st_ < 8; ++st_)
-          for (int h = 0; h < 2; ++h) {
-            const long long* q = tl + ((size_t)h * 12 + st_) * 6;
-            std::printf("\n        step %d wave %d: LOAD starts %6lld  at barrier %6lld  released %6lld  MFMAs issued %6lld  released %6lld", st_,
-                        h * 4, q[0] - t0, q[1] - t0, q[2] - t0, q[3] - t0, q[4] - t0);
-          }
-      }
-      const int nst = ig.K / 32;
-      for (int h = 0; h < 2; ++h)
-        std::printf("\n      [halo2 prof, wave %d, cycles per K step (%d steps, %zu blocks)] reads %.0f  dma-issue %.0f  waitcnt %.0f  barrier1 %.0f  mfma %.0f  barrier2 %.0f | epilogue+store %.0f  block total %.0f",
-                    h * 4, nst, used, m[h][0] / used / nst, m[h][1] / used / nst, m[h][2] / used / nst, m[h][3] / used / nst,
-                    m[h][4] / used / nst, m[h][5] / used / nst, m[h][6] / used, m[h][7] / used);
-      std::printf("\n      ");
-      (void)hipFree(dd);
-    } else if (std::getenv("ST_PROF") && !v.abl && (v.rot == 2 || v.rot == 0) && bk == 32) {
-      // cycle stamps of wave 0 of every block (s_memtime): mean over blocks
-      const int bnp = igemm_ntile(cs.N);
-      const size_t nblk = (size_t)((cs.N + bnp - 1) / bnp) * ((ig.M + 127) / 128) * nphase;   // >= halo grid too
-      long long* dd = nullptr;
-      CK(hipMalloc(&dd, nblk * 8 * sizeof(long long)));
-      CK(hipMemset(dd, 0, nblk * 8 * sizeof(long long)));
-      ig.k_rot = 16; ig.dbg = dd;
-      launch_conv_igemm(ig, false, 0);
-      CK(hipDeviceSynchronize());
-      std::vector<long long> hd(nblk * 8);
-      CK(hipMemcpy(hd.data(), dd, hd.size() * sizeof(long long), hipMemcpyDeviceToHost));
-      double m8[8] = {0};
-      for (size_t b = 0; b < nblk; ++b) for (int q = 0; q < 8; ++q) m8[q] += (double)hd[b * 8 + q] / nblk;
-      std::printf("\n      [prof, cycles/block of wave 0, %zu blocks, %d K steps] setup %.0f  first-tile %.0f  K-loop: issue %.0f compute %.0f wait+barrier %.0f  epilogue math %.0f  staged store %.0f  total %.0f\n      ",
-                  nblk, ig.K / 32, m8[0], m8[1], m8[2], m8[3], m8[4], m8[5], m8[6], m8[7]);
-      ig.k_rot = 0; ig.dbg = nullptr;
-      (void)hipFree(dd);
-    }
     (void)maxerr;
   }
   std::printf("\n");
@@ -381,7 +310,6 @@ static void run_c3_case(const C3Case& cs, int B, int Hh, int Ww) {
   const ConvArgs cD = conv(ls[3], SrcView{dY, 64, 64, 0, H, W}, none, dZ, 64, nullptr, 0);
   g_igemm_force_bk = 32;
   g_conv_halo = 1;
-  g_igemm_occ_lo = 0;
   auto unfused = [&]() {
     launch_conv_igemm(cA, false, 0);
     launch_conv_igemm(cB, false, 0);
@@ -538,7 +466,7 @@ static void run_stem2_case(const char* name, int B, int H, int W, int in_fmt, in
   c.B = B; c.Hin = Hs; c.Win = Ws; c.Mh = Ho; c.Mw = Wo; c.KH = c.KW = 3; c.stride = 2; c.dy0 = c.dx0 = -1;
   c.w = dW1; c.bias = dB1; c.dst = dZ; c.pitchD = 64; c.oH = Ho; c.oW = Wo; c.osy = c.osx = 1; c.act = act1; c.N = 64; c.Npad = 64;
   c.K = 288; c.M = B * Ho * Wo; c.nphase = 1; c.bk = 32; c.w_tiled = 1; c.zeros = zeros;
-  g_igemm_force_bk = 32; g_conv_halo = 1; g_igemm_occ_lo = 0;
+  g_igemm_force_bk = 32; g_conv_halo = 1;
   auto unfused = [&]() {
     launch_stem(dIn, in_fmt, dS, 32, B, H, W, 32, dWf, dB0, CTD_ACT_SILU, 0);
     launch_conv_igemm(c, false, 0);
@@ -997,11 +925,7 @@ static void run_split_case(const Case& cs, int B, bool timing) {
   };
   const double ms_f = timing ? time_it([&]() { launch_conv_f32_mfma(af, 0); }) : 0;
   std::printf(" f32-MFMA: err vs f64 rms %.2e max %.2e, %.3f ms %.0f TF |", rms_f, mx_f, ms_f, flops / (ms_f * 1e-3) / 1e12);
-  for (int var = 0; var < 3; ++var) {   // LDS-DMA weights (default) | weights through registers | 256-pixel blocks for 64-channel tiles
-    const int wdma = var != 1;
-    g_split_wdma = wdma;
-    g_split_bm256 = var == 2;
-    if (var == 2 && !(Npad % 64 == 0 && Npad % 128 != 0)) continue;   // only 64-channel N tiles have the 256-pixel variant
+  {
     CK(hipMemset(dOut, 0xff, nout * 4));
     launch_conv_split(as, 0);
     CK(hipDeviceSynchronize());
@@ -1019,12 +943,10 @@ static void run_split_case(const Case& cs, int B, bool timing) {
     const bool fail = bad || !(rms_s <= 3.0 * rms_f + 1e-7);
     if (fail) ++g_fail;
     const double ms_s = timing ? time_it([&]() { launch_conv_split(as, 0); }) : 0;
-    std::printf(" split(%s): %s err vs f64 rms %.2e max %.2e, max|d| vs f32-MFMA %.2e (%zu > 2e-5), %.3f ms %.0f TF %.0f GB/s |",
-                var == 0 ? "dma" : var == 1 ? "reg" : "dma,bm256", fail ? "FAIL" : "ok", rms_s, mx_s, maxd, bad, ms_s, flops / (ms_s * 1e-3) / 1e12,
+    std::printf(" split(dma): %s err vs f64 rms %.2e max %.2e, max|d| vs f32-MFMA %.2e (%zu > 2e-5), %.3f ms %.0f TF %.0f GB/s |",
+                fail ? "FAIL" : "ok", rms_s, mx_s, maxd, bad, ms_s, flops / (ms_s * 1e-3) / 1e12,
                 bytes / (ms_s * 1e-3) / 1e9);
   }
-  g_split_wdma = 1;
-  g_split_bm256 = 0;
   // split-plane tensors: sources, residual and destination stored as 32 hi halves + 32 lo halves per 32-channel group
   if (cs.c0 % 32 == 0 && cs.c1 % 32 == 0 && cs.N % 32 == 0) {
     auto to_sp = [](const std::vector<float>& f) {
@@ -1226,7 +1148,7 @@ int main(int argc, char** argv) {
   int64_t hbm = 0;
   const int arch = ctd_device_info(0, name, &cus, &hbm);
   std::printf("device: %s gfx%d CUs=%d HBM=%.1f GB\n", name, arch, cus, hbm / 1e9);
-  if (const char* tu = std::getenv("CTD_TUNING")) {   // "key=value,key=value" -> ctd_tuning_set (this build has the A/B keys too)
+  if (const char* tu = std::getenv("CTD_TUNING")) {   // "key=value,key=value" -> ctd_tuning_set
     std::string s(tu);
     for (size_t p = 0; p < s.size();) {
       const size_t e = s.find(',', p), q = s.find('=', p);
@@ -1276,7 +1198,7 @@ int main(int argc, char** argv) {
                            {"convT4 64->32 @9", 1, 64, 0, 0, 32, 4, 2, 9, 0},
                            {"3x3 64->16 @24 (db branch)", 0, 64, 0, 0, 16, 3, 1, 24, 0},
                            {"stem 6x6s2 4->32 @44 ragged", 0, 4, 0, 0, 32, 6, 2, 44, 0},
-                           {"3x3 64->64 @21 +res (halo)", 0, 64, 0, 0, 64, 3, 1, 21, 1},
+                           {"3x3 64->64 @21 +res", 0, 64, 0, 0, 64, 3, 1, 21, 1},
                            {"3x3 cat(32,32)->128 @18 (halo)", 0, 32, 32, 0, 128, 3, 1, 18, 0},
                            {"convT4 64->64 @19 (halo)", 1, 64, 0, 0, 64, 4, 2, 19, 0},
                            {"convT4 96->128 @33 (halo)", 1, 96, 0, 0, 128, 4, 2, 33, 0}};

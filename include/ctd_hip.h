@@ -183,14 +183,14 @@ int64_t ctd_engine_workspace_bytes(const ctd_engine* e);
 int32_t ctd_engine_arena_generation(const ctd_engine* e);
 
 /* Kernel-dispatch knobs (process-wide; no reference counterpart).  Keys: "halo_min_patches" (default 1024:
- * maps with fewer 16x16 patches take the implicit-GEMM kernel), "halo" (0: never the halo kernel), "halo_pair",
- * "halo_1x1"; "fuse" = bit mask of the fp16 engine's multi-layer kernels (1: C3 block with 32 hidden channels,
+ * maps with fewer 16x16 patches take the implicit-GEMM kernel), "halo" (0: never the halo kernel), "halo_pair";
+ * "fuse" = bit mask of the fp16 engine's multi-layer kernels (1: C3 block with 32 hidden channels,
  * 2: SPPF's three pools, 4: stem + layer 1, 8: C3 bottlenecks with 64 / 128 hidden channels, 16: ConvTranspose + its 1x1
  * consumer, 32: the last ConvTranspose + seg-final's tap products; default 63; 0 = one launch per layer; results are
  * bit-identical either way), "c3_min_patches" (default 1024: smaller grids take the per-layer kernels);
  * "db_up_mfma" / "seg_final_mfma" (default 1: the DB tail / the seg-final layer with their channel reductions on the MFMA, 0: the VALU kernels; same
- * results within 2e-4 / 1e-6).  The environment variables CTD_HALO_* / CTD_FUSE / CTD_DBUP_MFMA / CTD_SEGFINAL_MFMA give
- * the initial values.  Engines re-plan on their next forward after any key but the tail_* keys.  For tests and A/B
+ * results within 2e-4 / 1e-6).  The library reads no environment variables; an unknown key returns CTD_ERR_INVALID.
+ * Engines re-plan on their next forward after any key but the tail_* keys.  For tests and A/B
  * measurements. */
 int ctd_tuning_set(const char* key, int64_t value);
 

@@ -231,8 +231,8 @@ def test_timed_dispatch_fused_equals_unfused_on_all_32_pages(prec):
 
 @pytest.mark.parametrize("shape", [(2, 512, 512), (1, 1024, 768), (3, 256, 512), (32, 1024, 1024)])
 def test_big_tile_convt_kernels_reproduce_the_256x128_kernel_bit_for_bit(shape):
-    """The ConvTranspose layers on kernels_halo3.hip (256 x 128 tiles, four waves, two blocks per CU) and on
-    kernels_halo2.hip (selftest build only) walk K and issue their MFMAs per accumulator in the order of kernels_halo.hip:
+    """The ConvTranspose layers on kernels_halo3.hip (256 x 128 tiles, four waves, two blocks per CU) walk K and issue
+    their MFMAs per accumulator in the order of kernels_halo.hip:
     with the grid threshold lifted (`halo3_min_blocks` = 1: also maps whose ConvT inputs are 16x16 ... 64x48, i.e. every
     tile at an image border) every output of the network equals the output without it, bit for bit."""
     ck = checkpoint(0)
