@@ -991,7 +991,7 @@ void launch_op(ctd_engine* e, int i, const Outs& x, hipStream_t st) {
     case ROLE_OWN: break;
     case ROLE_FUSED: s.ran = "(fused)"; return;
     case ROLE_C3: launch_c3_fused(s.c3, st); s.ran = "c3_fused_kernel"; return;
-    case ROLE_C3B: launch_c3b(s.c3b, st); s.ran = "c3b_kernel"; return;
+    case ROLE_C3B: s.ran = launch_c3b(s.c3b, st); return;
     case ROLE_SPPF: {
       const TensorState& tp = e->tensors[o.src0];
       launch_sppf_pool3(tensor_ptr(e, o.src0, o.src0_coff), tp.t.channels, o.src0_c, o.src0_c, B, tp.H, tp.W, o.k, st, tp.esize);

@@ -124,7 +124,7 @@ extern long long g_c3b_min_patches;   // "c3b_min_patches"
 extern int g_c3b_max_ch;              // "c3b_max_ch"
 extern int g_c3b_cfg64, g_c3b_cfg128; // tiling variants per hidden width ("c3b_cfg64" 0 / 1 / 2, "c3b_cfg128" 0 / 1)
 bool c3b_supported(const C3bArgs& a);
-void launch_c3b(const C3bArgs& a, hipStream_t st);
+const char* launch_c3b(const C3bArgs& a, hipStream_t st);
 
 // ---- kernels_stem2.hip : stem (6x6/s2, 3 -> 32) + layer 1 (3x3/s2, 32 -> 64) in one kernel -----------
 struct Stem2Args {

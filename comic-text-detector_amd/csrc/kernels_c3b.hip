@@ -501,13 +501,15 @@ bool c3b_supported(const C3bArgs& a) {
   return patches >= g_c3b_min_patches * 8 / bh;   // the threshold counts 128-pixel patches
 }
 
-void launch_c3b(const C3bArgs& a, hipStream_t st) {
+// -> the name recorded for the op: "c3b_kernel" for the default tiling of each width, the tiling spelled out otherwise
+const char* launch_c3b(const C3bArgs& a, hipStream_t st) {
   if (a.ch == 64) {
-    if (g_c3b_cfg64 == 1) launch_cv3<64, 16, 2>(a, st);
-    else if (g_c3b_cfg64 == 2) launch_cv3<64, 8, 2>(a, st);
-    else launch_cv3<64, 8, 1>(a, st);
-  } else {
-    if (g_c3b_cfg128 == 1) launch_cv3<128, 8, 2>(a, st);
-    else launch_cv3<128, 8, 1>(a, st);
+    if (g_c3b_cfg64 == 1) { launch_cv3<64, 16, 2>(a, st); return "c3b_kernel<64,16,2>"; }
+    if (g_c3b_cfg64 == 2) { launch_cv3<64, 8, 2>(a, st); return "c3b_kernel<64,8,2>"; }
+    launch_cv3<64, 8, 1>(a, st);
+    return "c3b_kernel";
   }
+  if (g_c3b_cfg128 == 1) { launch_cv3<128, 8, 2>(a, st); return "c3b_kernel"; }
+  launch_cv3<128, 8, 1>(a, st);
+  return "c3b_kernel<128,8,1>";
 }

@@ -1,9 +1,11 @@
-"""GPU: the bottleneck (+ cv3) kernel of the 64 / 128-channel C3 blocks (csrc/kernels_c3b.hip, fuse bit 8) against the
-launches it replaces -- every activation tensor of the network compared bit for bit (engine without arena reuse, so
-`read_tensor` sees every intermediate), the first differing tensors named; then per-op times of the chains at the
-benchmark shape with the kernel on and off.
+"""GPU: per-op times of the C3 chains at the benchmark shape with the bottleneck (+ cv3) kernel of the 64 / 128-channel C3
+blocks (csrc/kernels_c3b.hip, fuse bit 8) and the other round-5 multi-layer kernels on and off.
 
-    python scripts/gpu_c3b_check.py [check] [time]
+    python scripts/gpu_c3b_check.py [time]
+
+The comparison with the launches they replace (`check`) is in the suite now:
+tests/test_gpu_edge.py::test_c3b_tilings_equal_the_layer_per_launch_program_bit_for_bit (every tiling, both K walks, leaky
+and relu heads) and ::test_fused_blocks_equal_the_per_layer_program_for_silu_and_relu_heads.
 """
 import importlib
 import os
@@ -24,62 +26,10 @@ def tune(key, value):
 
 
 def check():
-    ck = pkg.synth.make_checkpoint(0)
-    tune("no_reuse", 1)
-    be = pkg.backend.HipTextDetBackend(ck, device="cuda", precision="fp16")
-    tune("no_reuse", 0)
-    names = {tid: n for n, tid in be.program.taps.items()}
-    writer = {}
-    for o in be.program.ops:
-        if o["dst"] >= 0:
-            writer.setdefault(o["dst"], o["name"])
-    bad = 0
-    cases = [((2, 256, 256), 1024, 0, 0), ((2, 256, 256), 1, 0, 0), ((1, 320, 448), 1, 0, 0), ((3, 128, 192), 1024, 0, 0)]
-    for c64, c128 in ((1, 1), (2, 1)):                   # the other tilings of the kernel
-        cases += [((2, 256, 256), 1024, c64, c128), ((1, 320, 448), 1, c64, c128), ((3, 128, 192), 1, c64, c128)]
-    for shape, halo_min, c64, c128 in cases:
-        g = torch.Generator().manual_seed(7)
-        x = torch.rand((shape[0], 3, shape[1], shape[2]), generator=g).cuda()
-        tune("c3b_min_patches", 1)
-        tune("halo_min_patches", halo_min)
-        tune("c3b_cfg64", c64)
-        tune("c3b_cfg128", c128)
-        tune("halo3_min_blocks", 1)
-        res = {}
-        for fuse in (7, 63):
-            tune("fuse", fuse)
-            outs = [t.clone() for t in be(x)] + [be.mask_u8.clone(), be.bitmap.clone()]
-            torch.cuda.synchronize()
-            tens = {}
-            for tid in range(len(be.program.tensors)):
-                try:
-                    tens[tid] = be.read_tensor(tid)
-                except Exception:
-                    pass
-            res[fuse] = (outs, tens)
-        tune("fuse", 63)
-        tune("c3b_min_patches", 1024)
-        tune("halo_min_patches", 1024)
-        tune("halo3_min_blocks", 1024)
-        tune("c3b_cfg64", 0)
-        tune("c3b_cfg128", 1)
-        nd = 0
-        for tid in sorted(res[7][1]):
-            a, b = res[7][1][tid], res[63][1][tid]
-            if not np.array_equal(a, b, equal_nan=True):
-                d = np.abs(a.astype(np.float64) - b.astype(np.float64))
-                w = writer.get(tid, "?")
-                # tensors the fused program never writes (t of a fused bottleneck, y1 overwritten in place) differ by design
-                if os.environ.get("C3B_VERBOSE"):
-                    print(f"  shape {shape} halo_min {halo_min}: tensor {tid} ({names.get(tid, '')}, written by {w}) differs: "
-                          f"{int((d > 0).sum())} of {d.size} values, max |d| {np.nanmax(d):.4g}")
-                nd += 1
-        same = all(torch.equal(u, v) for u, v in zip(res[7][0], res[63][0]))
-        print(f"shape {shape} halo_min_patches {halo_min} cfg64 {c64} cfg128 {c128}: network outputs identical: {same}; "
-              f"{nd} intermediate tensors differ (by design: y1 / t of fused bottlenecks)")
-        bad += 0 if same else 1
-    print("C3B CHECK", "PASS" if bad == 0 else "FAIL")
-    return bad
+    print("the check is part of the suite: pytest -m gpu tests/test_gpu_edge.py -k 'c3b_tilings or fused_blocks' compares the\n"
+          "network outputs of every tiling of c3b_kernel (c3b_cfg64 x c3b_cfg128), both K walks of the absorbed 3x3 and the head\n"
+          "activations with the per-layer program, bit for bit, and asserts by op_kernels() which tiling ran")
+    return 0
 
 
 def time_chains():
@@ -129,7 +79,7 @@ def time_chains():
 
 
 if __name__ == "__main__":
-    what = sys.argv[1:] or ["check", "time"]
+    what = sys.argv[1:] or ["time"]
     rc = 0
     if "check" in what:
         rc = check()

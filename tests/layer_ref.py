@@ -60,6 +60,12 @@ exactly those pages; the checker then keeps only those pages of every tensor it 
 `check_all` drops a tensor once no later op's check reads it.  What a sampled check leaves out is stated as a condition (every
 row of `EDGES`, every requested page, for every op); the share of elements it looked at is reported (`n` of `total`), no
 number is asserted for it.
+
+Programs built by hand.  `direct_program` is a small program no lowering of the network produces: channel counts and
+offsets that no vector path can take, so that every engine runs it on its direct (VALU) kernels -- the universal fallback,
+and the yardstick of the native selftest.  It has no Detect / seg-final / DB ops: `outs` may be {} for such a program, and
+the INPUT op is left out through `check_all(ops=...)` where the engine stores the page in fp16 (the network's fp16 program
+has a STEM op instead, so the checker has no fp16 INPUT bound).
 """
 from __future__ import annotations
 
@@ -148,6 +154,45 @@ def snapshot_program(prog):
                     b_off=snap.param(np.zeros(c, np.float32)), name=(o["name"] or f"op{i}") + ".snapshot")
             snaps[i] = t
     return snap, index, snaps
+
+
+def direct_program(prec: int, seed: int = 0):
+    """-> (program, indices of the ops to check).  B x 192 x 320 pages, two average pools, then seven conv ops around a
+    24 x 40 map with cin = 24 / 40 / 48 and cout = 20 / 24 (no multiple of 16 or 32 among the sources, channel offsets 3 and
+    23 in a 44-channel tensor): a 3x3 / s2 conv (padding on the top and left only) twice, a residual add into a channel offset
+    of a wider tensor, a two-source conv with one source through the x2 upsample, ConvTranspose 4x4 / s2 / p1 and 2x2 / s2 /
+    p0, and silu, leaky, relu and none.  Weights ~ N(0, gain^2 / fan_in) with synth's gains: activations stay O(1)."""
+    G = importlib.import_module("comic-text-detector_amd.graph")
+    r = np.random.RandomState(4000 + seed)
+    P = G.Program(prec)
+    P.meta = dict(no=1)                                   # no Detect op: blks is (B, 0, 1)
+
+    def w(shape, fan_in, gain=1.0):
+        return (r.standard_normal(shape) * gain / math.sqrt(fan_in)).astype(np.float32)
+
+    def b(c):
+        return (0.1 * r.standard_normal(c)).astype(np.float32)
+
+    t_in = P.tensor(4, 0, 0, "input")
+    P.op(L.OP_INPUT, dst=t_in, name="input")
+    cur = t_in
+    for d in (1, 2):
+        t = P.tensor(4, d, 0, f"d.pool{d}")
+        P.op(L.OP_AVGPOOL2, src0=cur, src0_coff=0, src0_c=4, dst=t, name=f"d.pool{d}")
+        cur = t
+    first = len(P.ops)
+    w0 = w((24, 4, 3, 3), 27, 1.25)
+    w0[:, 3] = 0                                          # the page's zero 4th channel
+    A = P.conv([G.View(cur, 0, 4, 2)], w0, b(24), 3, 2, 1, "silu", name="d.stem")                  # 24 x 40, 24 channels
+    wide = P.tensor(44, 3, 0, "d.wide")
+    P.conv([A], w((20, 24, 1, 1), 24), b(20), 1, 1, 0, "leaky", dst=G.View(wide, 3, 20, 3), name="d.pw")
+    P.conv([A], w((20, 24, 3, 3), 216), b(20), 3, 1, 1, "relu", dst=G.View(wide, 23, 20, 3), res=G.View(wide, 3, 20, 3),
+           name="d.res")
+    D = P.conv([G.View(wide, 3, 40, 3)], w((24, 40, 3, 3), 360), None, 3, 2, 1, "none", name="d.down")     # 12 x 20
+    E = P.conv([A, G.View(D.tid, 0, 24, 3, up=1)], w((20, 48, 3, 3), 432, 1.25), b(20), 3, 1, 1, "silu", name="d.cat")
+    P.convt(D, w((24, 20, 4, 4), 96), b(20), 4, 2, 1, "leaky", name="d.up4")                       # 12 x 20 -> 24 x 40
+    P.convt(E, w((20, 24, 2, 2), 20), b(24), 2, 2, 0, "relu", name="d.up2")                        # 24 x 40 -> 48 x 80
+    return P, list(range(first, len(P.ops)))
 
 
 # ---------------------------------------------------------------------------------------------------------------------

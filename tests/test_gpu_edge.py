@@ -192,6 +192,141 @@ def test_fused_blocks_equal_the_layer_per_launch_program_bit_for_bit(shape, u8):
                                       f"(max |d| {float((g.float() - r.float()).abs().max()):.3g})"
 
 
+NAMES = ("blks", "mask", "lines", "mask_u8", "bitmap")
+# (c3b_cfg64, c3b_cfg128) -> the names launch_c3b reports for the 64-wide and the 128-wide blocks: "c3b_kernel" for the
+# default tiling of each width, the tiling spelled out for the others
+C3B_TILINGS = {
+    (0, 1): {64: "c3b_kernel", 128: "c3b_kernel"},
+    (0, 0): {64: "c3b_kernel", 128: "c3b_kernel<128,8,1>"},
+    (1, 1): {64: "c3b_kernel<64,16,2>", 128: "c3b_kernel"},
+    (2, 1): {64: "c3b_kernel<64,8,2>", 128: "c3b_kernel"},
+    (1, 0): {64: "c3b_kernel<64,16,2>", 128: "c3b_kernel<128,8,1>"},
+    (2, 0): {64: "c3b_kernel<64,8,2>", 128: "c3b_kernel<128,8,1>"},
+}
+_KEYS = ((b"fuse", 63), (b"halo3_min_blocks", 1024), (b"c3_min_patches", 1024), (b"c3b_min_patches", 1024), (b"c3b_max_ch", 128),
+         (b"halo_min_patches", 1024), (b"c3b_cfg64", 0), (b"c3b_cfg128", 1))
+_BE = {}
+_RUNS = {}
+
+
+def _act_backend(act):
+    """One fp16 engine per head activation, on a checkpoint made for it (the heads' activations see both signs)."""
+    if act not in _BE:
+        p = pkg()
+        ck = checkpoint(0) if act == "leaky" else p.synth.make_checkpoint(0, act=act)
+        _BE[act] = p.backend.HipTextDetBackend(ck, device="cuda", precision="fp16", act=act)
+    return _BE[act]
+
+
+def _runner(be, shape, u8):
+    if u8:
+        x = torch.randint(0, 256, (shape[0], shape[1], shape[2], 3), dtype=torch.uint8,
+                          generator=torch.Generator().manual_seed(5)).cuda()
+        fwd = lambda: be.forward_u8(x)              # noqa: E731
+    else:
+        x = gen_golden.make_input(77, shape).cuda()
+        fwd = lambda: be(x)                         # noqa: E731
+
+    def run():
+        return [t.clone() for t in fwd()] + [be.mask_u8.clone(), be.bitmap.clone()]
+    return run
+
+
+def _differences(got, ref):
+    return [f"{n}: {int((g != r).sum())} elements differ, max |d| {float((g.float() - r.float()).abs().max()):.3g}"
+            for n, g, r in zip(NAMES, got, ref) if not torch.equal(g, r)]
+
+
+def fused_runs(act, shape, u8, masks, cfg=(0, 1), halo_walks=False):
+    """Cached.  The fp16 engine with head activation `act` at `shape`, c3_min_patches = c3b_min_patches = 1 and the c3b
+    tilings `cfg`: every fuse mask of `masks` against fuse = 0 -- at the default thresholds (with `halo_walks`: also with
+    halo_min_patches = 1, the other K walk of the 3x3 that c3b_kernel absorbs), and with halo3_min_blocks = 1 on top.
+    -> {label: (differences from the per-layer program, [(op name, cout, kernel)] of the run)}"""
+    key = (act, shape, u8, tuple(masks), cfg, halo_walks)
+    if key in _RUNS:
+        return _RUNS[key]
+    be = _act_backend(act)
+    run = _runner(be, shape, u8)
+    out = {}
+
+    def compare(label):
+        _tune(b"fuse", 0)
+        ref = run()
+        for mask in masks:
+            _tune(b"fuse", mask)
+            got = run()
+            torch.cuda.synchronize()
+            kern = [(n, be.program.ops[i]["cout"], k) for i, (n, k) in enumerate(be.op_kernels())]
+            out[f"{mask}{label}"] = (_differences(got, ref), kern)
+    try:
+        _tune(b"c3_min_patches", 1)
+        _tune(b"c3b_min_patches", 1)
+        _tune(b"c3b_cfg64", cfg[0])
+        _tune(b"c3b_cfg128", cfg[1])
+        compare("")
+        if halo_walks:
+            _tune(b"halo_min_patches", 1)
+            compare(" + halo")
+        _tune(b"halo3_min_blocks", 1)
+        compare(" + halo3")
+    finally:
+        for k, v in _KEYS:
+            _tune(k, v)
+    _RUNS[key] = out
+    return out
+
+
+def _c3b_names(kern):
+    """{block width: the names the c3b launches of that width reported}"""
+    by = {}
+    for _, cout, k in kern:
+        if k.startswith("c3b_kernel"):
+            by.setdefault(cout, set()).add(k)
+    return by
+
+
+C3B_SHAPES = [pytest.param((3, 128, 64), True, id="u8_3x128x64"), pytest.param((2, 320, 448), False, id="2x320x448")]
+
+
+@pytest.mark.parametrize("act", ["leaky", "relu"])
+@pytest.mark.parametrize("shape,u8", C3B_SHAPES)
+@pytest.mark.parametrize("cfg", [(0, 0), (1, 1), (2, 1), (1, 0), (2, 0)], ids=lambda c: f"cfg64_{c[0]}-cfg128_{c[1]}")
+def test_c3b_tilings_equal_the_layer_per_launch_program_bit_for_bit(cfg, shape, u8, act):
+    """The tilings of c3b_kernel that `c3b_cfg64` / `c3b_cfg128` select besides the default pair (0, 1): <64,16,2>, <64,8,2> and
+    <128,8,1>, with and without cv3, for the head activations leaky and relu.  (3, 128, 64) makes every patch partial (a
+    16 x 8 map at stride 8); (2, 320, 448) has 40 x 56 and 20 x 28 maps: two full 16-row patches plus a half, full plus half
+    16-column patches -- interior, ragged right edge and ragged bottom edge at once for BH = 16.  fuse = 8 against fuse = 0 for
+    both K walks of the absorbed 3x3, and fuse = 63 against fuse = 0 with halo3_min_blocks = 1; by op_kernels() the blocks of
+    each width ran the tiling that was asked for."""
+    runs = fused_runs(act, shape, u8, (8, 63), cfg, halo_walks=True)
+    for label in ("8", "8 + halo", "63 + halo3"):
+        diff, kern = runs[label]
+        assert not diff, (cfg, act, label, diff)
+        assert _c3b_names(kern) == {w: {n} for w, n in C3B_TILINGS[cfg].items()}, (label, _c3b_names(kern))
+
+
+@pytest.mark.parametrize("act", ["silu", "relu"])
+@pytest.mark.parametrize("shape,u8", C3B_SHAPES + [pytest.param((2, 128, 128), True, id="u8_2x128x128")])
+def test_fused_blocks_equal_the_per_layer_program_for_silu_and_relu_heads(shape, u8, act):
+    """test_fused_blocks_equal_the_layer_per_launch_program_bit_for_bit for the other two head activations, each on a
+    checkpoint made for it: c3b_kernel in seg.* / db.*, conv_halo3_kernel+1x1 (epilogue2 with CTD_ACT_SILU / CTD_ACT_RELU as
+    post_act) and conv_halo3_kernel+taps.  The big-tile kernel takes maps that are multiples of 16 only, and the 128-channel
+    ConvTranspose of the +1x1 form reads the maps at stride 8: it can run only where H and W are multiples of 128, which
+    neither (3, 128, 64) nor (2, 320, 448) is -- (2, 128, 128) is the smallest shape that has it."""
+    runs = fused_runs(act, shape, u8, (8, 16, 32, 63))
+    for label, (diff, _) in runs.items():
+        assert not diff, (act, label, diff)
+    names = {k for _, _, k in runs["63 + halo3"][1]}
+    want = {"c3b_kernel", "conv_halo3_kernel+taps"} | ({"conv_halo3_kernel+1x1"} if shape[1] % 128 == 0 and shape[2] % 128 == 0 else set())
+    assert want <= names, (want - names, sorted(names))
+    # ... and c3b_kernel ran inside both heads (their inner layers carry no head prefix: by position in the program)
+    kern = runs["63 + halo3"][1]
+    seg0 = next(i for i, (n, _, _) in enumerate(kern) if n == "seg.down_conv1.down")
+    seg1 = next(i for i, (n, _, _) in enumerate(kern) if n == "seg.upconv6")
+    c3b = [i for i, (_, _, k) in enumerate(kern) if k == "c3b_kernel"]
+    assert any(seg0 < i < seg1 for i in c3b) and any(i > seg1 for i in c3b), [kern[i] for i in c3b]
+
+
 @pytest.mark.parametrize("prec", ["fp16", "fp32s", "fp32"])
 def test_timed_dispatch_fused_equals_unfused_on_all_32_pages(prec):
     """bench.py's batch (its checkpoint, its first 32 pages of 1024 x 1024, uint8) at the DEFAULT thresholds -- no tuning key

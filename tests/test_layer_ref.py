@@ -149,6 +149,39 @@ def test_export_ops_are_checked_exactly():
     assert all(r["ratio"] <= 1 for r in res.values())
 
 
+@pytest.mark.parametrize("engine", ["fp32", "fp16"])
+def test_hand_built_direct_program_passes_and_a_swapped_tap_index_is_rejected(engine):
+    """layer_ref.direct_program (the program tests/test_gpu_layers.py runs on the direct kernels): the checker takes a
+    program without the network's output ops, correct arithmetic passes on every op, and a ConvTranspose that reads its
+    weights with ky and kx swapped is rejected at both ConvTranspose ops and nowhere else."""
+    from layer_ref import direct_program
+    L = _L()
+    prog, ops = direct_program(L.PREC_F16 if engine == "fp16" else L.PREC_F32)
+    x = _x((2, 192, 320), 8)
+    blob = hook = None
+    if engine == "fp16":
+        blob, hook = fp16_emulation(prog)
+    kinds = [prog.ops[i]["kind"] for i in ops]
+    assert kinds.count(L.OP_CONV) == 5 and kinds.count(L.OP_CONVT) == 2
+    assert {prog.ops[i]["act"] for i in ops} == {L.ACT[a] for a in ("silu", "leaky", "relu", "none")}
+
+    def run(hk):
+        out = run_program(prog, x, blob=blob, hook=hk, return_tensors=True)
+        T = out["tensors"]
+        chk = LayerCheck(prog, {}, engine, lambda t: T[t].permute(0, 2, 3, 1).numpy(), {}, x.numpy())
+        return chk.check_all(ops)
+    res = run(hook)
+    assert all(r["n"] > 0 and r["ratio"] <= 1 for r in res.values()), res
+    print(f"\n{engine}: worst ratio {max(r['ratio'] for r in res.values()):.3g}")
+
+    def swapped(i, o, stage, y, ctx):
+        if stage == "pre" and o["kind"] == L.OP_CONVT:
+            y = F.conv_transpose2d(ctx["a"], ctx["w"].transpose(2, 3), ctx["b"], o["stride"], o["pad"])
+        return y if hook is None else hook(i, o, stage, y, ctx)
+    bad = run(swapped)
+    assert {i for i, r in bad.items() if r["ratio"] > 1} == {i for i in ops if prog.ops[i]["kind"] == L.OP_CONVT}, bad
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # mutations: each must be rejected at the op it hits
 # ---------------------------------------------------------------------------------------------------------------------
@@ -248,11 +281,44 @@ def test_snapshot_program_computes_the_same_outputs():
         assert torch.equal(a[k], b[k]), k
 
 
+def tuning_keys_in_the_sources():
+    """The keys ctd_tuning_set accepts: the `k == "..."` comparisons of the three sources that parse them."""
+    import os
+    import re
+    src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "comic-text-detector_amd", "csrc")
+    keys = []
+    for f in ("engine.hip", "kernels_halo.hip", "kernels_halo3.hip"):
+        with open(os.path.join(src, f)) as fh:
+            keys += re.findall(r'\bk == "([a-z0-9_]+)"', fh.read())
+    return keys
+
+
+def test_every_tuning_key_is_in_the_ledger(monkeypatch):
+    """A key of ctd_tuning_set is either a dispatch key with the kernels that prove each value (checked on the GPU by
+    tests/test_gpu_layers.py) or is listed as knowingly not one, with the reason: a new key needs a decision."""
+    import test_gpu_layers as G
+    keys = tuning_keys_in_the_sources()
+    assert len(keys) == len(set(keys)) and len(keys) > 30 and {"fuse", "halo_pair", "halo3", "c3b_cfg64"} <= set(keys)
+    dispatch = {k for k, *_ in G.DISPATCH_KEYS}
+
+    def unlisted():
+        return sorted(set(keys) - dispatch - set(G.NOT_DISPATCH_KEYS))
+    assert not unlisted()
+    assert not dispatch & set(G.NOT_DISPATCH_KEYS)
+    assert not (dispatch | set(G.NOT_DISPATCH_KEYS)) - set(keys), "the ledger names a key the library does not parse"
+    assert all(reason for reason in G.NOT_DISPATCH_KEYS.values())
+    # every key a keyed configuration sets is restored by _DEFAULTS
+    assert {k for c in G.KEYED.values() for k in c[3]} <= {k for k, _ in G._DEFAULTS}
+    # the check bites: a key in neither table is reported
+    monkeypatch.delitem(G.NOT_DISPATCH_KEYS, "fwd_prio")
+    assert unlisted() == ["fwd_prio"]
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # the wide-dynamic-range checkpoint family (tests/wide_ckpt.py)
 # ---------------------------------------------------------------------------------------------------------------------
 
-@pytest.mark.parametrize("act", ["leaky", "silu"])
+@pytest.mark.parametrize("act", ["leaky", "silu", "relu"])
 def test_wide_checkpoint_family_spans_the_range_it_claims(act):
     from wide_ckpt import make_wide_checkpoint
     L = _L()
