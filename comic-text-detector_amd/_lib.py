@@ -14,7 +14,7 @@ LIB_PATH = os.path.join(_HERE, "libctd_hip.so")
 SELFTEST_PATH = os.path.join(_HERE, "ctd_selftest")
 
 # ---- constants mirrored from include/ctd_hip.h -------------------------------
-ABI_VERSION = 8
+ABI_VERSION = 9
 OK = 0
 PREC_F32, PREC_F16, PREC_F32S = 0, 1, 2
 ACT = {"none": 0, "silu": 1, "leaky": 2, "relu": 3, "sigmoid": 4}
@@ -62,6 +62,13 @@ class CtdBlk(C.Structure):
                 ("font_is_float", C.c_int32), ("font_size", C.c_double), ("vec", C.c_double * 2), ("norm", C.c_double),
                 ("weight", C.c_double), ("merged", C.c_int32), ("line_off", C.c_int32), ("n_lines", C.c_int32),
                 ("dist_off", C.c_int32), ("n_dist", C.c_int32), ("pad_", C.c_int32)]
+
+
+class CtdTraceWin(C.Structure):
+    _fields_ = [("page", C.c_int32), ("x1", C.c_int32), ("y1", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("pass_", C.c_int32), ("path", C.c_int32), ("n_cand", C.c_int32), ("hist", C.c_uint32 * 1024),
+                ("rules", C.c_int32 * 18), ("cand_rule", C.c_int32 * 4), ("cand_invert", C.c_int32 * 4),
+                ("sums", C.c_uint64 * 6), ("cand_dist", C.c_uint64 * 4)]
 
 
 class CtdRegionJob(C.Structure):
@@ -118,6 +125,11 @@ SYMBOLS = {
     "ctd_tail_batch_fetch": (_i32, [_vp, _vp, _vp, _vp]),
     "ctd_tail_pack_records": (_i32, [_vp, _i32, _i32, _vp]),
     "ctd_tail_set_threads": (_i32, [_vp, _i32]),
+    "ctd_tail_set_trace": (_i32, [_vp, _i32]),
+    "ctd_tail_trace_counts": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
+    "ctd_tail_trace_windows": (_i32, [_vp, _vp]),
+    "ctd_tail_trace_db_sizes": (_i32, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
+    "ctd_tail_trace_db_fetch": (_i32, [_vp, _i32, _vp, _vp]),
     "ctd_db_boxes_compact": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                     _vp, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_topk_colors": (_i32, [_vp, _vp]),

@@ -281,6 +281,15 @@ inline double now_ms() {
 
 }  // namespace
 
+static_assert(sizeof(ctd_trace_win) == 4312, "ctd_trace_win is read as a packed record (comic-text-detector_amd/tail.py)");
+// One page of the DB stage as `db_collect` hands it to `ctd_db_boxes_compact` (the trace's copy: `h_tab` is reused later in a run)
+struct DbTrace {
+  int32_t hdr[4] = {0, 0, 0, 0};
+  int nf = 0, nb = 0, nr = 0;         // rows of the tables below (0 on an overflowed page: it takes the label-image path)
+  std::vector<int32_t> i32;           // st_f (nf,5) first_f par_f off_f | st_b (nb,5) first_b par_b off_b ring_cnt | row_lo row_hi (nr)
+  std::vector<double> f64;            // sum_f (nf) | sum_b ring_sum (nb)
+};
+
 struct ctd_tail {
   int device = 0;
   hipStream_t st = nullptr;
@@ -309,6 +318,10 @@ struct ctd_tail {
   int n_lds = 0, n_canvas = 0, n_ovf = 0;
   long long lds_per_block = 64 << 10;  // hipDeviceAttributeMaxSharedMemoryPerBlock (160 KB on gfx950)
   double ms_lds_wait = 0;             // waiting for the window-local merge kernel's overflow flags
+  // "trace" (ctd_tail_set_trace): host copies of what the refine and DB stages download anyway, for tests; off: empty
+  bool trace = false;
+  std::vector<ctd_trace_win> tr_wins;
+  std::vector<DbTrace> tr_db;
 };
 
 namespace {
@@ -464,6 +477,31 @@ int refine_canvas(ctd_tail* t, const TWin* hw, const std::vector<TBand>& bands, 
   return CTD_OK;
 }
 
+// "trace": one record per window of a `refine_windows` call from the pinned host tables the call has downloaded anyway (the
+// candidates are `refine_candidates` again on the same rules and sums: nothing is kept for this while the trace is off)
+void trace_windows(ctd_tail* t, const std::vector<WinReq>& reqs, int pass, const uint32_t* hhist, const RRule* hrules,
+                   const uint64_t* hsums, const std::vector<int>& canvas_win, const std::vector<int>& again) {
+  const size_t base = t->tr_wins.size();
+  t->tr_wins.resize(base + reqs.size());
+  for (size_t i = 0; i < reqs.size(); ++i) {
+    ctd_trace_win& r = t->tr_wins[base + i];
+    std::memset(&r, 0, sizeof(r));
+    r.page = reqs[i].page, r.x1 = reqs[i].x1, r.y1 = reqs[i].y1, r.w = reqs[i].x2 - reqs[i].x1, r.h = reqs[i].y2 - reqs[i].y1;
+    r.pass = pass, r.path = 0;
+    std::memcpy(r.hist, hhist + i * 1024, sizeof(r.hist));
+    for (int k = 0; k < 6; ++k) {
+      const RRule& rl = hrules[i * 6 + k];
+      r.rules[3 * k] = rl.kind, r.rules[3 * k + 1] = rl.lo, r.rules[3 * k + 2] = rl.hi;
+      r.sums[k] = hsums[i * 6 + k];
+    }
+    RCand c[4];
+    r.n_cand = refine_candidates(hrules + i * 6, hsums + i * 6, (long long)r.w * r.h, c);
+    for (int k = 0; k < r.n_cand; ++k) r.cand_rule[k] = c[k].rule, r.cand_invert[k] = c[k].invert, r.cand_dist[k] = c[k].dist;
+  }
+  for (int i : canvas_win) t->tr_wins[base + i].path = 1;
+  for (int i : again) t->tr_wins[base + i].path = 2;
+}
+
 // ---------------------------------------------------------------------------------------------------
 // refine_mask for a list of windows over the pages of the batch (reference utils/textmask.py:159-169):
 // ORs the merged window masks into the refined page buffers on the device.
@@ -472,7 +510,7 @@ int refine_canvas(ctd_tail* t, const TWin* hw, const std::vector<TBand>& bands, 
 //   launches by LDS footprint; windows too big for that -> refine_canvas; after the wait for the overflow flags, windows
 //   whose run table overflowed -> refine_canvas too
 // ---------------------------------------------------------------------------------------------------
-int refine_windows(ctd_tail* t, const std::vector<WinReq>& reqs, int refine_mode) {
+int refine_windows(ctd_tail* t, const std::vector<WinReq>& reqs, int refine_mode, int pass) {
   const int n = (int)reqs.size();
   if (n == 0) return CTD_OK;
   hipStream_t st = t->st;
@@ -602,10 +640,10 @@ int refine_windows(ctd_tail* t, const std::vector<WinReq>& reqs, int refine_mode
   if (int rc = refine_canvas(t, hw, bands, canvas_win, refine_mode)) return rc;
   const double tr4 = now_ms();
   double tr5 = tr4;
+  std::vector<int> again;
   if (nl) {
     T_TRY(hipStreamSynchronize(st));                        // the overflow flags (the merge stage has run when they arrive)
     tr5 = now_ms();
-    std::vector<int> again;
     for (int k = 0; k < nl; ++k)
       if (hovf[lds_win[k]]) again.push_back(lds_win[k]);
     std::sort(again.begin(), again.end());
@@ -615,6 +653,7 @@ int refine_windows(ctd_tail* t, const std::vector<WinReq>& reqs, int refine_mode
     t->n_canvas += (int)canvas_win.size();
   }
   T_TRY(hipGetLastError());
+  if (t->trace) trace_windows(t, reqs, pass, hhist, hrules, hsums, canvas_win, again);
   t->ms_stage[4] += tr1 - tr0;
   t->ms_stage[5] += tr3 - tr2;
   t->ms_stage[6] += (now_ms() - tr5) + (tr4 - tr3) + (tr2 - tr1);
@@ -716,7 +755,7 @@ int undetected_pass(ctd_tail* t, const std::vector<std::vector<int32_t>>& blk_xy
       }
     }
   }
-  return refine_windows(t, reqs, refine_mode);
+  return refine_windows(t, reqs, refine_mode, 1);
 }
 
 // device -> host of the page-size outputs, straight into the caller's arrays (page-locked arrays make
@@ -893,6 +932,30 @@ int db_collect(ctd_tail* t, const DbStage& d, const ctd_tail_params* prm) {
   const double td0 = now_ms();
   T_TRY(hipStreamSynchronize(st));
   t->ms_db_wait = now_ms() - td0;
+  if (t->trace) {
+    t->tr_db.assign(B, DbTrace());
+    for (int b = 0; b < B; ++b) {
+      DbTrace& d = t->tr_db[b];
+      std::memcpy(d.hdr, hhdr + 4 * b, 16);
+      if (d.hdr[3]) continue;
+      d.nf = d.hdr[0], d.nb = d.hdr[1], d.nr = std::min(d.hdr[2], rcap);
+      auto put = [](auto& v, const auto* src, size_t n) { v.insert(v.end(), src, src + n); };
+      put(d.i32, h_st_f + (size_t)b * nf * 5, (size_t)d.nf * 5);
+      put(d.i32, h_first_f + (size_t)b * nf, d.nf);
+      put(d.i32, h_par_f + (size_t)b * nf, d.nf);
+      put(d.i32, h_off_f + (size_t)b * nf, d.nf);
+      put(d.i32, h_st_b + (size_t)b * nb * 5, (size_t)d.nb * 5);
+      put(d.i32, h_first_b + (size_t)b * nb, d.nb);
+      put(d.i32, h_par_b + (size_t)b * nb, d.nb);
+      put(d.i32, h_off_b + (size_t)b * nb, d.nb);
+      put(d.i32, h_ring_cnt + (size_t)b * nb, d.nb);
+      put(d.i32, h_row_lo + (size_t)b * nr, d.nr);
+      put(d.i32, h_row_hi + (size_t)b * nr, d.nr);
+      put(d.f64, h_sum_f + (size_t)b * nf, d.nf);
+      put(d.f64, h_sum_b + (size_t)b * nb, d.nb);
+      put(d.f64, h_ring_sum + (size_t)b * nb, d.nb);
+    }
+  }
   const int maxc = std::max(prm->max_candidates, 0);
   std::atomic<int> err{CTD_OK};
   parallel_for(B, t->host_threads, [&](int b) {
@@ -1047,6 +1110,7 @@ static int tail_run_impl(ctd_tail* t, int32_t B, int32_t Hn, int32_t Wn, const f
   const double t0 = now_ms();
   for (double& v : t->ms_stage) v = 0;
   t->n_lds = t->n_canvas = t->n_ovf = 0, t->ms_lds_wait = 0;
+  t->tr_wins.clear(), t->tr_db.clear();
   if (ready_event) T_TRY(hipStreamWaitEvent(st, (hipEvent_t)ready_event, 0));
   if (int rc = layout_pages(t, B, pages)) return rc;
   for (int b = 0; b < B; ++b)
@@ -1192,7 +1256,7 @@ static int tail_run_impl(ctd_tail* t, int32_t B, int32_t Hn, int32_t Wn, const f
   const double t4 = now_ms();
   double t5 = t4;
   if (prm->refine) {
-    if (int rc = refine_windows(t, reqs, prm->refine_mode)) return rc;
+    if (int rc = refine_windows(t, reqs, prm->refine_mode, 0)) return rc;
     t5 = now_ms();
     if (prm->keep_undetected_mask) {
       const double k4 = t->ms_stage[4], k5 = t->ms_stage[5], k6 = t->ms_stage[6];
@@ -1245,6 +1309,7 @@ static int tail_db_boxes_impl(ctd_tail* t, int32_t B, int32_t Hn, int32_t Wn, co
   T_TRY(hipSetDevice(t->device));
   t->B = B;
   t->out.assign(B, PageOut());
+  t->tr_db.clear();
   DbStage db;
   Batch pre(t->st), post(t->st);
   if (int rc = db_enqueue(t, db, B, Hn, Wn, prob_dev, prob_stride, bitmap_dev, pre, post)) return rc;
@@ -1270,6 +1335,7 @@ static int tail_refine_impl(ctd_tail* t, int32_t n_pages, const ctd_tail_page* p
     return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_refine: bad arguments");
   T_TRY(hipSetDevice(t->device));
   t->n_lds = t->n_canvas = t->n_ovf = 0, t->ms_lds_wait = 0;
+  t->tr_wins.clear();
   hipStream_t st = t->st;
   if (int rc = layout_pages(t, n_pages, pages)) return rc;
   GET(t->d_pmask, t->ptotal, uint8_t, pmask);
@@ -1291,7 +1357,7 @@ static int tail_refine_impl(ctd_tail* t, int32_t n_pages, const ctd_tail_page* p
     }
   }
   T_TRY(hipMemcpyAsync(pmask, hpmask, t->ptotal, hipMemcpyHostToDevice, st));
-  if (int rc = refine_windows(t, reqs, refine_mode)) return rc;
+  if (int rc = refine_windows(t, reqs, refine_mode, 0)) return rc;
   if (keep_undetected_mask)
     if (int rc = undetected_pass(t, bxy, refine_mode)) return rc;
   return download_pages(t, keep_undetected_mask != 0, mask_out, refined_out);
@@ -1366,6 +1432,45 @@ int ctd_tail_pack_records(const ctd_tail* t, int32_t cap_blk, int32_t cap_line, 
     }
     r[0] = (double)po.blks.size(), r[1] = (double)nl, r[2] = cap_blk, r[3] = cap_line;
   }
+  return CTD_OK;
+}
+
+int ctd_tail_set_trace(ctd_tail* t, int32_t on) {
+  if (!t) return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_set_trace: null tail");
+  t->trace = on != 0;
+  std::vector<ctd_trace_win>().swap(t->tr_wins);          // (drops the storage too)
+  std::vector<DbTrace>().swap(t->tr_db);
+  return CTD_OK;
+}
+
+int ctd_tail_trace_counts(const ctd_tail* t, int32_t* n_windows, int32_t* n_db_pages) {
+  if (!t) return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_trace_counts: null tail");
+  if (n_windows) *n_windows = (int32_t)t->tr_wins.size();
+  if (n_db_pages) *n_db_pages = (int32_t)t->tr_db.size();
+  return CTD_OK;
+}
+
+int ctd_tail_trace_windows(const ctd_tail* t, ctd_trace_win* out) {
+  if (!t || !out) return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_trace_windows: null argument");
+  if (!t->tr_wins.empty()) std::memcpy(out, t->tr_wins.data(), t->tr_wins.size() * sizeof(ctd_trace_win));
+  return CTD_OK;
+}
+
+int ctd_tail_trace_db_sizes(const ctd_tail* t, int32_t page, int32_t* hdr4, int32_t* sizes3) {
+  if (!t || page < 0 || page >= (int)t->tr_db.size() || !hdr4 || !sizes3)
+    return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_trace_db_sizes: bad arguments (is the trace on?)");
+  const DbTrace& d = t->tr_db[page];
+  std::memcpy(hdr4, d.hdr, 16);
+  sizes3[0] = d.nf, sizes3[1] = d.nb, sizes3[2] = d.nr;
+  return CTD_OK;
+}
+
+int ctd_tail_trace_db_fetch(const ctd_tail* t, int32_t page, int32_t* i32, double* f64) {
+  if (!t || page < 0 || page >= (int)t->tr_db.size() || !i32 || !f64)
+    return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_trace_db_fetch: bad arguments (is the trace on?)");
+  const DbTrace& d = t->tr_db[page];
+  if (!d.i32.empty()) std::memcpy(i32, d.i32.data(), d.i32.size() * 4);
+  if (!d.f64.empty()) std::memcpy(f64, d.f64.data(), d.f64.size() * 8);
   return CTD_OK;
 }
 

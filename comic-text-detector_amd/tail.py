@@ -40,6 +40,15 @@ class PageResult(tuple):
     record = None
 
 
+# `ctd_trace_win` (include/ctd_hip.h) as a numpy record
+TRACE_WIN_DTYPE = np.dtype([("page", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("w", "<i4"), ("h", "<i4"), ("pass_", "<i4"),
+                            ("path", "<i4"), ("n_cand", "<i4"), ("hist", "<u4", (4, 256)), ("rules", "<i4", (6, 3)),
+                            ("cand_rule", "<i4", (4,)), ("cand_invert", "<i4", (4,)), ("sums", "<u8", (6,)),
+                            ("cand_dist", "<u8", (4,))])
+assert TRACE_WIN_DTYPE.itemsize == C.sizeof(L.CtdTraceWin) == 4312
+TRACE_PATHS = ("lds", "canvas", "overflow")        # ctd_trace_win.path
+
+
 _host_threads = None            # native threads per Tail for its per-page / per-window host loops (None: library default)
 
 
@@ -224,6 +233,49 @@ class Tail:
         c = (C.c_int32 * 3)()
         L.check(self._lib.ctd_tail_refine_paths(self._h, c), "ctd_tail_refine_paths")
         return {"lds": int(c[0]), "canvas": int(c[1]), "overflow": int(c[2])}
+
+    # -- trace of the device-made tables (for tests; off by default) -------------------------------------
+    def set_trace(self, on: bool) -> None:
+        """On: this tail keeps host copies of what its refine and DB stages download anyway (`ctd_tail_set_trace`): the
+        per-window histograms, rules, xor sums and candidates, and the per-page contour tables.  No extra device work."""
+        L.check(self._lib.ctd_tail_set_trace(self._h, int(bool(on))), "ctd_tail_set_trace")
+
+    def trace_windows(self) -> np.ndarray:
+        """The refine windows of the last `run` / `refine` in the order the refine stage saw them, as records of
+        `TRACE_WIN_DTYPE` (`pass_` 0: the blocks' windows, 1: those of refine_undetected_mask; `path`: `TRACE_PATHS`)."""
+        n = C.c_int32()
+        L.check(self._lib.ctd_tail_trace_counts(self._h, C.byref(n), None), "ctd_tail_trace_counts")
+        out = np.zeros((n.value,), TRACE_WIN_DTYPE)
+        if n.value:
+            L.check(self._lib.ctd_tail_trace_windows(self._h, out.ctypes.data), "ctd_tail_trace_windows")
+        return out
+
+    def trace_db(self) -> List[dict]:
+        """Per page of the last DB stage (`run`, `db_boxes`): the contour tables as `ctd_db_boxes_compact` received them,
+        under the names of `DbcTables` (csrc/tail.h), plus `hdr` = [n_f, n_b, rows used, overflow]; an overflowed page
+        (it takes the label-image path) has empty tables."""
+        n = C.c_int32()
+        L.check(self._lib.ctd_tail_trace_counts(self._h, None, C.byref(n)), "ctd_tail_trace_counts")
+        pages = []
+        for b in range(n.value):
+            hdr, sz = np.zeros(4, np.int32), (C.c_int32 * 3)()
+            L.check(self._lib.ctd_tail_trace_db_sizes(self._h, b, hdr.ctypes.data_as(C.POINTER(C.c_int32)), sz), "ctd_tail_trace_db_sizes")
+            nf, nb, nr = sz[0], sz[1], sz[2]
+            i32 = np.zeros(8 * nf + 9 * nb + 2 * nr + 1, np.int32)
+            f64 = np.zeros(nf + 2 * nb + 1, np.float64)
+            L.check(self._lib.ctd_tail_trace_db_fetch(self._h, b, i32.ctypes.data, f64.ctypes.data), "ctd_tail_trace_db_fetch")
+            d, pi, pf = {"hdr": hdr}, 0, 0
+            for name, rows, cols in (("st_f", nf, 5), ("first_f", nf, 1), ("par_f", nf, 1), ("off_f", nf, 1), ("st_b", nb, 5),
+                                     ("first_b", nb, 1), ("par_b", nb, 1), ("off_b", nb, 1), ("ring_cnt", nb, 1),
+                                     ("row_lo", nr, 1), ("row_hi", nr, 1)):
+                a = i32[pi: pi + rows * cols].copy()
+                d[name] = a.reshape(rows, 5) if cols == 5 else a
+                pi += rows * cols
+            for name, rows in (("sum_f", nf), ("sum_b", nb), ("ring_sum", nb)):
+                d[name] = f64[pf: pf + rows].copy()
+                pf += rows
+            pages.append(d)
+        return pages
 
     # -- SegDetectorRepresenter alone -----------------------------------------------------------------
     def db_boxes(self, prob: torch.Tensor, bitmap: torch.Tensor, max_candidates=1000, unclip_ratio=1.5):

@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CTD_ABI_VERSION 8
+#define CTD_ABI_VERSION 9
 
 /* ---- error codes ------------------------------------------------------ */
 #define CTD_OK 0
@@ -446,6 +446,41 @@ int ctd_tail_pack_records(const ctd_tail* t, int32_t cap_blk, int32_t cap_line, 
 /* Host threads the per-page / per-window host loops of this tail object may use (default 8; >= 1).  A node running one
  * process per GPU divides its cores between the ranks' tail workers. */
 int ctd_tail_set_threads(ctd_tail* t, int32_t n);
+
+/* ---- trace of the tail's device-made tables (ABI v9; for tests, off by default) ---------------------------------------
+ * With the trace on, a tail object keeps host copies of what its refine and DB stages download from the device anyway:
+ * no extra kernel, no extra device work; with it off (the default) each stage takes one untaken branch.  Per object.
+ * ctd_tail_set_trace also drops what was recorded. */
+int ctd_tail_set_trace(ctd_tail* t, int32_t on);
+
+/* One refine window (reference utils/textmask.py:159-169), in the order the refine stage saw them: the windows of the
+ * blocks first (pass 0), then those of `refine_undetected_mask` (pass 1).  Cleared at the start of every ctd_tail_run /
+ * ctd_tail_refine. */
+typedef struct ctd_trace_win {
+  int32_t page, x1, y1, w, h; /* page index of the call, window in the page                                           */
+  int32_t pass;               /* 0: a block's window, 1: a window of refine_undetected_mask                           */
+  int32_t path;               /* merge stage: 0 window-local kernel, 1 canvases, 2 canvases after a run-table overflow */
+  int32_t n_cand;             /* candidates `merge_mask_list` walks, 1..4                                             */
+  uint32_t hist[4 * 256];     /* as downloaded: grey of pixels whose 3x3-eroded mask > 127 | B | G | R of the window  */
+  int32_t rules[6 * 3];       /* (kind, lo, hi): kind -1 unused, 0 grey range [lo, hi], 1..3 channel B/G/R > lo       */
+  int32_t cand_rule[4];       /* the candidates in merge order: rule index 0..5,                                      */
+  int32_t cand_invert[4];     /*   1 = the rule's negative was closer,                                                */
+  uint64_t sums[6];           /* as downloaded: sum of xor(rule's mask, predicted mask) per rule, 0 for an unused one */
+  uint64_t cand_dist[4];      /*   and their xor distances                                                            */
+} ctd_trace_win;
+
+/* Windows recorded since the last run / refine; pages of the last DB stage (ctd_tail_run, ctd_tail_db_boxes) recorded. */
+int ctd_tail_trace_counts(const ctd_tail* t, int32_t* n_windows, int32_t* n_db_pages);
+int ctd_tail_trace_windows(const ctd_tail* t, ctd_trace_win* out); /* n_windows records */
+
+/* The device-made contour tables of one page exactly as the host geometry (ctd_db_boxes_compact, below) received them.
+ * hdr4 = [n_f, n_b, row-table entries used, overflow flag]; sizes3 = [nf, nb, nr] rows of the tables kept (all 0 on an
+ * overflowed page, which takes the label-image path).  ctd_tail_trace_db_fetch fills
+ *   i32: st_f (nf,5) | first_f | par_f | off_f (nf each) | st_b (nb,5) | first_b | par_b | off_b | ring_cnt (nb each) |
+ *        row_lo | row_hi (nr each)                                   = 8 nf + 9 nb + 2 nr values
+ *   f64: sum_f (nf) | sum_b | ring_sum (nb each)                     = nf + 2 nb values */
+int ctd_tail_trace_db_sizes(const ctd_tail* t, int32_t page, int32_t* hdr4, int32_t* sizes3);
+int ctd_tail_trace_db_fetch(const ctd_tail* t, int32_t page, int32_t* i32, double* f64);
 
 /* ---- host-side input staging ---------------------------------------------------------------- */
 

@@ -1,6 +1,7 @@
 """TEST INFRASTRUCTURE: numpy emulation of the tables `launch_dbc` (csrc/kernels_tail.hip) compacts on
-the device, so that the host consumer `ctd_db_boxes_compact` can be checked without a GPU (and the
-device kernels against this emulation with one)."""
+the device, so that the host consumer `ctd_db_boxes_compact` can be checked without a GPU (tests/test_db_compact.py), and the device kernels
+`dbc_prep / scan / init / accum_kernel` against this emulation table for table with one (tests/test_gpu_tail_trace.py through
+the tail's trace; the bounds on the f64 sums are derived in tests/tail_trace_cases.py `db_reference`)."""
 import ctypes as C
 
 import numpy as np

@@ -365,15 +365,16 @@ def refine_windows(n=120):
         yield f"window {i} ({kinds[kind]}) {h}x{w}", img, np.ascontiguousarray(msk)
 
 
-def refine_window_expected(img, msk):
+def refine_window_expected(img, msk, libm_side=True):
     """(hist4, rules, sums, npix, expected candidates) of one window from the ORACLE's restatement of reference
-    utils/textmask.py, with numpy on the libm side as in the harness: the colour candidates of `get_topk_masklist` and the
+    utils/textmask.py, with numpy on the libm side as in the harness (`libm_side=False`: numpy as it is, which is what the
+    product inside a Python process calls, csrc/np_dispatch.h -- tests/tail_trace_cases.py): the colour candidates of `get_topk_masklist` and the
     Otsu candidate of `get_otsuthresh_masklist` -- each through `minxor_thresh` -- in the order `merge_mask_list` sorts them.
     The lists are rebuilt here from the same oracle calls only to know WHICH rule each candidate is; the distances are
     checked against the oracle's own functions."""
     from oracle import cv_ref as cv
     from oracle import postproc_ref as R
-    with numpy_on_the_libm_side():
+    with numpy_on_the_libm_side() if libm_side else contextlib.nullcontext():
         grey = cv.cvt_bgr2gray(img)
         sel = grey[np.where(cv.erode(msk, cv.RECT3, 1) > 127)]
         hist4 = np.stack([np.bincount(sel, minlength=256)] + [np.bincount(img[..., c].ravel(), minlength=256) for c in range(3)])

@@ -28,8 +28,11 @@ def test_text_like(seed):
     assert (check(prob) > 0.6).sum() > 3
 
 
-@pytest.mark.parametrize("case", ["holes", "thin", "empty", "full", "cap", "frame"])
-def test_edge_cases(case):
+EDGE_CASES = ["holes", "thin", "empty", "full", "cap", "frame"]
+
+
+def edge_map(case):
+    """(prob (96,160) f32, max_candidates) of one edge case (tests/tail_trace_cases.py runs the same maps on the device)."""
     H, W = 96, 160
     prob = np.full((H, W), 0.05, np.float32)
     cap = 1000
@@ -58,16 +61,26 @@ def test_edge_cases(case):
         prob[60:96, 100:160] = 0.9
         prob[70:96, 120:150] = 0.1
         prob[50:58, 0:160] = 0.8
+    return prob, cap
+
+
+@pytest.mark.parametrize("case", EDGE_CASES)
+def test_edge_cases(case):
+    prob, cap = edge_map(case)
     s = check(prob, cap)
     if case == "holes":
         assert (s > 0).sum() == 6
 
 
-def test_speckle_sweep():
+def speckle(seed):
+    """Map `seed` (0 .. 11) of the sweep below."""
     from scipy import ndimage
+    rng = np.random.RandomState(100 + seed)
+    H, W = 64 + 3 * seed, 100 + 5 * seed
+    prob = ndimage.uniform_filter(rng.rand(H, W), 1 + seed % 4).astype(np.float32)
+    return (prob - prob.min()) / (prob.max() - prob.min()) * 0.62
+
+
+def test_speckle_sweep():
     for seed in range(12):
-        rng = np.random.RandomState(100 + seed)
-        H, W = 64 + 3 * seed, 100 + 5 * seed
-        prob = ndimage.uniform_filter(rng.rand(H, W), 1 + seed % 4).astype(np.float32)
-        prob = (prob - prob.min()) / (prob.max() - prob.min()) * 0.62
-        check(prob)
+        check(speckle(seed))
