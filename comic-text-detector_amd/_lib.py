@@ -5,6 +5,7 @@ be loaded, importing a symbol from here raises.  `build()` compiles it in-tree.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import subprocess
@@ -14,7 +15,7 @@ LIB_PATH = os.path.join(_HERE, "libctd_hip.so")
 SELFTEST_PATH = os.path.join(_HERE, "ctd_selftest")
 
 # ---- constants mirrored from include/ctd_hip.h -------------------------------
-ABI_VERSION = 9
+ABI_VERSION = 10
 OK = 0
 PREC_F32, PREC_F16, PREC_F32S = 0, 1, 2
 ACT = {"none": 0, "silu": 1, "leaky": 2, "relu": 3, "sigmoid": 4}
@@ -98,6 +99,7 @@ SYMBOLS = {
     "ctd_engine_workspace_bytes": (_i64, [_vp]),
     "ctd_engine_arena_generation": (_i32, [_vp]),
     "ctd_tuning_set": (_i32, [C.c_char_p, C.c_int64]),
+    "ctd_tuning_get": (_i32, [C.c_char_p, C.POINTER(C.c_int64)]),
     "ctd_nms_workspace_bytes": (C.c_size_t, [_i32, _i32]),
     "ctd_nms": (_i32, [_vp, _i32, _i32, _i32, _f, _f, _i32, _i32, _f, _vp, _vp, _vp, C.c_size_t, _vp]),
     "ctd_db_step": (_i32, [_vp, _i32, _i32, _i32, _f, _vp, _vp, _f, _vp]),
@@ -212,3 +214,29 @@ def check(rc: int, what: str = "") -> None:
     if rc != OK:
         msg = lib().ctd_last_error().decode("utf8", "replace")
         raise CtdError(f"{what} failed (rc={rc}): {msg}")
+
+
+def tuning_get(key: str) -> int:
+    """The value the library holds for a tuning key (the rows of csrc/tuning.def)."""
+    v = C.c_int64()
+    check(lib().ctd_tuning_get(key.encode(), C.byref(v)), f"ctd_tuning_get({key!r})")
+    return v.value
+
+
+@contextlib.contextmanager
+def tuning(keys=None, **more):
+    """`with tuning(halo_min_patches=1, fuse=0):` (or a dict) -- sets the keys in the order given and, on the way out, puts
+    back what each one held on the way in, last set first, also when the body raises.  What was there is read from the
+    library, so a value that CTD_TUNING set at load time survives.  Every key is read before any is set: an unknown one
+    raises CtdError with nothing changed."""
+    keys = {**(keys or {}), **more}
+    held = [(k, tuning_get(k)) for k in keys]
+    done = []
+    try:
+        for (k, old), v in zip(held, keys.values()):
+            check(lib().ctd_tuning_set(k.encode(), int(v)), f"ctd_tuning_set({k!r})")
+            done.append((k, old))
+        yield
+    finally:
+        for k, old in reversed(done):
+            check(lib().ctd_tuning_set(k.encode(), old), f"ctd_tuning_set({k!r})")

@@ -34,13 +34,7 @@ int fail(int code, const std::string& msg) {
       return fail(CTD_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));                 \
   } while (0)
 
-int g_plan_epoch = 0;   // bumped by every tuning key but the tail's: cached plans are re-made
-int g_no_reuse = 0;     // engines created from now on: no arena reuse (debug: `read_tensor` of any activation); "no_reuse"
-int g_fwd_prio = 1;      // the network's big kernels raise their waves' issue priority (s_setprio 3): a co-running tail stretched the
-                         // VALU-bound stem kernel from 0.42 to 2.1 ms (rocprofv3 timeline); "fwd_prio"
-int g_split_stem = 1;    // fp32s engine: the first conv reads the network input itself (kernels_split_stem.hip); "split_stem"
-int g_split_planes = 1;  // fp32s engine: keep conv-to-conv tensors split in HBM (0: fp32 everywhere, split in the K loop); "split_planes"
-int g_f32_mfma = 1;     // engines created from now on: fp32 convs on the f32 MFMA kernel (0: exact-order direct kernels); "f32_mfma"
+int g_plan_epoch = 0;   // bumped by every tuning key whose row says REPLAN (tuning.def): cached plans are re-made
 
 enum Impl { IMPL_POINT = 0, IMPL_IGEMM = 1, IMPL_IGEMM_T = 2, IMPL_DIRECT = 3, IMPL_FUSED = 4 };
 
@@ -1113,19 +1107,6 @@ int prepare(ctd_engine* e, int B, int H, int W, hipStream_t st = nullptr) {
 }  // namespace
 
 int ctd_fail_msg(int code, const std::string& msg) { return fail(code, msg); }
-extern int g_tail_priority;   // tail.hip
-extern int g_tail_cus, g_tail_cu_first;
-extern long long g_tail_dma_min;
-#ifdef CTD_MEASURE_KNOBS
-extern int g_tail_skip_pages;
-extern int g_tail_ablate;
-#endif
-extern int g_tail_chain;
-extern int g_tail_fused_rounds;
-extern long long g_tail_fused_max_pix;
-extern int g_tail_lds, g_tail_lds_rcap, g_tw_lds_runs_x10, g_tw_lds_threads;
-extern long long g_tail_lds_cls0, g_tail_lds_cls1;
-extern long long g_tail_lds_max_bytes;
 
 extern "C" {
 
@@ -1285,45 +1266,20 @@ int ctd_engine_read_tensor(ctd_engine* e, int32_t tensor_id, float* host_out, in
 int64_t ctd_engine_workspace_bytes(const ctd_engine* e) { return e ? (int64_t)e->arena_bytes : 0; }
 int32_t ctd_engine_arena_generation(const ctd_engine* e) { return e ? e->arena_gen : -1; }
 
+// the keys, their variables, defaults and clamps: tuning.def
 int ctd_tuning_set(const char* key, int64_t value) {
-  const std::string k = key ? key : "";
-  if (k == "fuse") g_fuse = (int)value;
-  else if (k == "tail_max_blocks") g_tail_max_blocks = (int)std::max<int64_t>(1, value);
-  else if (k == "tail_chain") g_tail_chain = (int)value;
-  else if (k == "tail_fused_rounds") g_tail_fused_rounds = (int)value;
-  else if (k == "tail_fused_max_pix") g_tail_fused_max_pix = value;
-  else if (k == "tail_lds") g_tail_lds = (int)value;
-  else if (k == "tail_lds_rcap") g_tail_lds_rcap = (int)value;
-  else if (k == "tail_lds_max_bytes") g_tail_lds_max_bytes = value;
-  else if (k == "tail_lds_runs_x10") g_tw_lds_runs_x10 = (int)std::max<int64_t>(1, value);
-  else if (k == "tail_lds_threads") g_tw_lds_threads = (int)value;
-  else if (k == "tail_lds_cls0") g_tail_lds_cls0 = value;
-  else if (k == "tail_lds_cls1") g_tail_lds_cls1 = value;
-  else if (k == "tail_dma_min") g_tail_dma_min = value;
-#ifdef CTD_MEASURE_KNOBS   // not in the shipped library: these return incomplete results
-  else if (k == "tail_skip_page_download") g_tail_skip_pages = value != 0;
-  else if (k == "tail_ablate") g_tail_ablate = (int)value;
-#endif
-  else if (k == "tail_priority") g_tail_priority = (int)value;
-  else if (k == "tail_cus") g_tail_cus = (int)value;
-  else if (k == "tail_cu_first") g_tail_cu_first = (int)value;
-  else if (k == "no_reuse") g_no_reuse = (int)value;
-  else if (k == "f32_mfma") g_f32_mfma = (int)value;
-  else if (k == "split_halo") g_split_halo = (int)value;
-  else if (k == "split_halo_min_patches") g_split_halo_min_patches = value;
-  else if (k == "fwd_prio") g_fwd_prio = (int)value;
-  else if (k == "split_stem") g_split_stem = (int)value;
-  else if (k == "split_planes") g_split_planes = (int)value;
-  else if (k == "db_up_mfma") g_db_up_mfma = (int)value;
-  else if (k == "seg_final_mfma") g_seg_final_mfma = (int)value;
-  else if (k == "c3_min_patches") g_c3_min_patches = value;
-  else if (k == "c3b_min_patches") g_c3b_min_patches = value;
-  else if (k == "c3b_max_ch") g_c3b_max_ch = (int)value;
-  else if (k == "c3b_cfg64") g_c3b_cfg64 = (int)value;
-  else if (k == "c3b_cfg128") g_c3b_cfg128 = (int)value;
-  else if (conv_tuning_set(key, (long long)value) != 0) return fail(CTD_ERR_INVALID, "unknown tuning key");
-  // every key but the tail's is read by plan() or by a launcher whose choice a plan builds on: cached plans are re-made
-  if (k.compare(0, 5, "tail_") != 0) ++g_plan_epoch;
+  bool replan = false;
+  if (tuning_set(key, (long long)value, &replan) != 0) return fail(CTD_ERR_INVALID, "unknown tuning key");
+  // a key that plan() reads, or a launcher whose choice a plan builds on: cached plans are re-made
+  if (replan) ++g_plan_epoch;
+  return CTD_OK;
+}
+
+int ctd_tuning_get(const char* key, int64_t* value) {
+  long long v = 0;
+  if (!value) return fail(CTD_ERR_INVALID, "null pointer");
+  if (tuning_get(key, &v) != 0) return fail(CTD_ERR_INVALID, "unknown tuning key");
+  *value = (int64_t)v;
   return CTD_OK;
 }
 

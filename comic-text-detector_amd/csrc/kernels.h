@@ -3,6 +3,7 @@
 #include <vector>
 
 #include "ctd_common.h"
+#include "tuning.h"   // the g_* dispatch knobs of ctd_tuning_set
 
 // ---- kernels_basic.hip : direct (VALU) kernels, T = float | half_t -------
 // weights for the direct conv: f32 [KH*KW][cin_total][N]
@@ -34,7 +35,6 @@ void launch_db_step(const float* lines, float k, float* out, uint8_t* bitmap, fl
 
 // ---- kernels_igemm.hip : MFMA implicit-GEMM conv (fp16 in, fp32 acc) ------
 // weights: half [nphase][Npad][K], K index = (ty*KW+tx)*(c0+c1) + c
-extern int g_tail_max_blocks;   // kernels_post.hip: grid cap of the tail's big-grid kernels ("tail_max_blocks")
 extern int g_igemm_force_bk;  // tuning knob: 0 = heuristic, 32 / 64 = forced K step
 int igemm_pick_bk(int c0, int c1, int K, int N, int log2_down);
 void igemm_pack_weights(const float* logical, int nphase, int N, int K, int bn, int bk, bool tiled,
@@ -58,8 +58,6 @@ const char* launch_conv_split(const ConvArgs& a, hipStream_t st);
 bool stem_split_supported(const ConvArgs& a);
 void launch_stem_split(const ConvArgs& a, const void* input, int in_fmt, hipStream_t st);
 // ---- kernels_split_halo.hip : the same arithmetic on a 256-pixel haloed patch staged once per channel chunk (3x3 / ConvT) ----
-extern int g_split_halo;                    // 0 disables ("split_halo")
-extern long long g_split_halo_min_patches;  // "split_halo_min_patches"
 bool conv_split_halo_supported(const ConvArgs& a);
 void launch_conv_split_halo(const ConvArgs& a, hipStream_t st);
 // logical f32 [nphase][N][K] -> hi plane + lo plane (halves, [nphase][npad/32][K/32][32][32] each) + oscale[npad]
@@ -67,19 +65,14 @@ void split_pack_weights(const float* logical, int nphase, int N, int K, int npad
                         std::vector<float>& oscale);
 
 // ---- kernels_halo.hip : halo-tile MFMA conv (stride-1 3x3, ConvTranspose phases) ----
-extern int g_conv_halo;   // 0 disables (selftest A/B)
 bool conv_halo_supported(const ConvArgs& a, bool dst_f32);
-int conv_tuning_set(const char* key, long long value);   // dispatch knobs of the MFMA conv kernels (kernels_halo.hip)
 void launch_conv_halo(const ConvArgs& a, hipStream_t st);
 
 // ---- kernels_halo3.hip : ConvTranspose phases on 256-pixel x 128-column tiles, four waves per block, two blocks per CU ----
-extern long long g_halo3;              // 0 disables ("halo3")
-extern long long g_halo3_min_blocks;   // "halo3_min_blocks"
 bool conv_halo3_supported(const ConvArgs& a, bool dst_f32);
 bool conv_halo3_post_supported(const ConvArgs& a);
 bool conv_halo3_segp_supported(const ConvArgs& a);   // `a` carries post_w = seg-final taps, post_dst = P, post_n = -16   // `a` carries post_*: the layer + its single 1x1 consumer in one launch
 void launch_conv_halo3(const ConvArgs& a, hipStream_t st);
-int halo3_tuning_set(const char* key, long long value);
 
 // ---- kernels_c3.hip : one-kernel C3 block (32 hidden channels, one bottleneck) -------------
 // Weights / biases are the packed arrays of the four unfused ops (tile-major, 32-channel K step):
@@ -96,8 +89,6 @@ struct C3Args {
   int prio;                // as ConvArgs::prio
   half_t* dbg;             // selftest only: three (B,H,W,32) planes receiving y2, t, b of every patch pixel; null in the product
 };
-extern int g_fuse;         // fusion bit mask (CTD_FUSE / ctd_tuning_set("fuse")): 1 C3 block, 2 SPPF pools, 4 stem + model.1, 8 C3 bottleneck + cv3 (kernels_c3b.hip)
-extern long long g_c3_min_patches;
 bool c3_fused_supported(const C3Args& a);
 void launch_c3_fused(const C3Args& a, hipStream_t st);
 
@@ -120,9 +111,6 @@ struct C3bArgs {
   const void* zeros;       // >= 16 B of zeros in HBM (source of out-of-image rows)
   int prio;                // as ConvArgs::prio
 };
-extern long long g_c3b_min_patches;   // "c3b_min_patches"
-extern int g_c3b_max_ch;              // "c3b_max_ch"
-extern int g_c3b_cfg64, g_c3b_cfg128; // tiling variants per hidden width ("c3b_cfg64" 0 / 1 / 2, "c3b_cfg128" 0 / 1)
 bool c3b_supported(const C3bArgs& a);
 const char* launch_c3b(const C3bArgs& a, hipStream_t st);
 
@@ -153,8 +141,6 @@ void launch_seg_final_f32(const float* src, int pitch, int C, int B, int H, int 
                           uint8_t* mask_u8, hipStream_t st);
 // the same layer from the per-tap products P (B,H,W,16) f32 its producer left (kernels_halo3.hip SEGP): col2im + sigmoid + u8
 void launch_seg_final_gather(const float* P, int B, int H, int W, float bias, float* mask, uint8_t* mask_u8, hipStream_t st);
-extern int g_seg_final_mfma;   // fp16 engine: seg-final's channel reduction on the MFMA (CTD_SEGFINAL_MFMA / "seg_final_mfma")
-extern int g_db_up_mfma;   // fp16 engine: DB tail's first stage on the MFMA (CTD_DBUP_MFMA / ctd_tuning_set("db_up_mfma"))
 // returns the name of the kernel it launched
 const char* launch_db_up(const void* src, bool f32in, int pitch, int q, int nbr, int B, int H, int W, const float* params,
                          float* lines, uint8_t* bitmap, float thresh, hipStream_t st);

@@ -328,13 +328,7 @@ __global__ __launch_bounds__(256, 2) void c3_fused_kernel(C3Args a) {
 
 }  // namespace
 
-// Multi-layer fusions of the fp16 engine, one bit each: 1 = C3 block (this file), 2 = SPPF's three pools
-// (kernels_basic.hip), 4 = stem + model.1 (kernels_fused.hip), 8 = bottleneck + cv3 of the wider C3 blocks (kernels_c3b.hip), 16 = a 128-channel ConvTranspose + its single 1x1 consumer, 32 = the last 64-channel ConvTranspose + the tap products of the 64 -> 1 one behind it (kernels_halo3.hip).  ctd_tuning_set("fuse", 0) runs the layer-per-launch
-// program (the bit-identity tests and A/B runs use it).
-int g_fuse = 63;
-
-long long g_c3_min_patches = 1024;   // fewer 128-pixel patches: the per-layer kernels (ctd_tuning_set("c3_min_patches"))
-
+// bit 1 of "fuse"; maps with fewer 128-pixel patches than "c3_min_patches" keep the per-layer kernels (tuning.def)
 bool c3_fused_supported(const C3Args& a) {
   if (!(g_fuse & 1)) return false;
   if (a.s0.c < 32 || a.s0.c % 32 || a.s1.c % 32 || a.s0.up || (a.s1.c && a.s1.up)) return false;

@@ -36,13 +36,6 @@
 
 #include "kernels.h"
 
-long long g_c3b_min_patches = 1024;   // fewer patches (blocks) than this: the per-layer kernels ("c3b_min_patches")
-int g_c3b_max_ch = 128;               // widest hidden width the kernel takes ("c3b_max_ch": 0 / 64 / 128)
-// Tiling per hidden width (A/B knobs, "c3b_cfg64" / "c3b_cfg128"): 0 = 16x8 patch, wave tile 64 channels x 32 pixels (16
-// waves per CU); 1 = wave tile 64 channels x 64 pixels on a 16x16 patch (64 channels) / on the 16x8 patch with four waves
-// (128 channels): 8 waves per CU, a third fewer LDS reads per MFMA; 2 (64 channels only) = 16x8 patch, two waves of 64 x 64
-int g_c3b_cfg64 = 0, g_c3b_cfg128 = 1;
-
 namespace {
 
 constexpr int BW = 16;                             // patch width; the patch height BH is a template parameter

@@ -717,9 +717,6 @@ void launch_seg_final_f32(const float* src, int pitch, int C, int B, int H, int 
   (void)C;
 }
 
-int g_seg_final_mfma = 1;   // ctd_tuning_set("seg_final_mfma", 0): the VALU kernel (the fallback for odd pitches; A/B reference)
-int g_db_up_mfma = 1;   // ctd_tuning_set("db_up_mfma", 0): the VALU kernel (the fallback for odd pitches; A/B reference)
-
 const char* launch_db_up(const void* src, bool f32in, int pitch, int q, int nbr, int B, int H, int W, const float* params,
                          float* lines, uint8_t* bitmap, float thresh, hipStream_t st) {
   const long long total = (long long)B * H * W;

@@ -22,8 +22,6 @@
 
 #include "kernels.h"
 
-int g_conv_halo = 1;   // selftest / tuning: 0 sends everything to the implicit-GEMM kernel
-
 namespace {
 
 constexpr int TWP = 16, THP = 16;     // pixel patch
@@ -323,20 +321,6 @@ void launch_halo_cfg(const ConvArgs& a, hipStream_t st) {
 }
 
 }  // namespace
-
-// Dispatch knobs of the halo kernel, changeable at run time through ctd_tuning_set (tests force the halo kernel onto
-// small maps that way; the host side applies CTD_TUNING="key=value,..." once after loading the library).
-long long g_halo_min_patches = 1024;   // fewer 256-pixel patches: implicit GEMM
-int g_halo_pair = 1;                   // 64-channel ConvT: both px phases per block
-
-int conv_tuning_set(const char* key, long long value) {
-  const std::string k(key ? key : "");
-  if (k == "halo_min_patches") g_halo_min_patches = value;
-  else if (k == "halo_pair") g_halo_pair = (int)value;
-  else if (k == "halo") g_conv_halo = (int)value;
-  else return halo3_tuning_set(key, value);
-  return 0;
-}
 
 // Stride-1 KxK (K = 2 or 3) windows over non-upsampled fp16 sources whose M grid equals the input
 // grid; fp16 destination with 16-B aligned channel rows; weights packed for the 32-channel K step.

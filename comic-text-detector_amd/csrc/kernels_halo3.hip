@@ -24,9 +24,6 @@
 
 #include "kernels.h"
 
-long long g_halo3 = 1;                 // "halo3": 0 leaves the ConvT layers to kernels_halo.hip
-long long g_halo3_min_blocks = 1024;   // "halo3_min_blocks"
-
 namespace {
 
 constexpr int TWP = 16, THP = 16;
@@ -519,12 +516,4 @@ void launch_conv_halo3(const ConvArgs& a, hipStream_t st) {
   if (a.N == 64) launch_cfg<2, 1>(a, st);
   else if (a.N == 128) launch_cfg<1, 1>(a, st);
   else launch_cfg<1, 2>(a, st);
-}
-
-int halo3_tuning_set(const char* key, long long value) {
-  const std::string k(key ? key : "");
-  if (k == "halo3") g_halo3 = value;
-  else if (k == "halo3_min_blocks") g_halo3_min_blocks = value;
-  else return -1;
-  return 0;
 }

@@ -4,11 +4,7 @@
 
 #include "kernels.h"
 
-// The labelling kernels of the tail run NEXT TO the network's forward of the following batch.  A neighbour that fills every
-// wave slot (8 waves per SIMD of short blocks) stretches the forward's VALU-bound kernels 2.5-4x; at <= 4 waves per SIMD
-// they keep their speed (selftest ST_CORUN).  So the big-grid tail kernels are launched with at most this many blocks of
-// 256 threads (measured: no effect on the end-to-end rate between 768 and no cap, 7 % lower at 384, 30 % at 192 where the tail becomes the bottleneck) and walk their tiles; "tail_max_blocks".
-int g_tail_max_blocks = 1024;
+// the big-grid kernels of the tail are launched with at most "tail_max_blocks" blocks and walk their tiles (tuning.def: why)
 
 namespace {
 

@@ -271,9 +271,6 @@ void launch_split_halo_cfg(const ConvArgs& a, hipStream_t st) {
 
 }  // namespace
 
-int g_split_halo = 1;                       // 0: everything through the 128-pixel kernel ("split_halo")
-long long g_split_halo_min_patches = 512;   // fewer 256-pixel patches (x phases x N tiles): the 128-pixel kernel ("split_halo_min_patches")
-
 static bool split_halo_pair(const ConvArgs& a) { return a.nphase == 4 && a.N == 64 && a.Npad == 64; }
 
 // Stride-1 3x3 / 2x2 windows over split-plane sources whose M grid equals the input grid, not upsampled

@@ -476,10 +476,8 @@ size_t tw_lds_bytes(int max_words, int rcap) {
   return ((size_t)3 * max_words + (max_words + 1) / 2 + (size_t)2 * rlay + 20) * 4;
 }
 
-// the run capacity a launch gets for its largest window: `g_tw_lds_runs_x10` / 10 runs per word (default 2.5: text strokes on
-// the reference's real page reach 1.7), at least 1024, at most what a u16 prefix holds
-int g_tw_lds_runs_x10 = 25;     // "tail_lds_runs_x10"
-int g_tw_lds_threads = 512;     // "tail_lds_threads": 256 / 512 / 1024 threads per window (512: a third off the merge wait of a serial tail; end to end the three are equal, profiles/r06_twlds_knobs.txt)
+// the run capacity a launch gets for its largest window: "tail_lds_runs_x10" / 10 runs per word, at least 1024, at most what
+// a u16 prefix holds
 int tw_lds_rcap(int max_words) { return std::min(65000, std::max(1024, (int)((long long)max_words * g_tw_lds_runs_x10 / 10))); }
 
 bool launch_tw_lds(const TWin* wins, const TBand* bands, const int* order, int n, int max_words, int rcap, int dilate, int* ovf,

@@ -2,8 +2,7 @@
 // implements them): everything after the network of reference inference.py:148-178 that is O(pixels).
 #pragma once
 #include "ctd_common.h"
-
-extern int g_tail_max_blocks;   // kernels_post.hip: grid cap of the tail's big-grid kernels ("tail_max_blocks")
+#include "tuning.h"   // "tail_max_blocks": grid cap of the tail's big-grid kernels
 
 // ---- DB text-line stage: per-contour tables compacted on the device ---------------------------------
 // Inputs: the dual labelling of a page batch (8-connected foreground of the bitmap, 4-connected

@@ -30,16 +30,7 @@
 #include "tail.h"
 
 int ctd_fail_msg(int code, const std::string& msg);   // engine.hip: sets the thread-local error text
-// Stream priority of tails created from now on ("tail_priority"): 1 = the device's default priority (the default since
-// round 4), 0 = highest, 2 = lowest.  Rounds 2-3 created the tails' streams at the HIGHEST priority; the runtime has fewer
-// hardware queues for that class than a pipeline with a 4th worker, a loader stream or a second pool needs, and a stream
-// beyond them shares a queue: 4 workers 1994 pages/s at priority 0 against 2554 at priority 1 (3 workers: 2545 either way),
-// pages from host memory 2025-2380 against 2500, the dense-block pages 1828 against 1926-1993.
-int g_tail_priority = 1;
-// > 0: the tails' streams may only use this many CUs, mask bits [g_tail_cu_first, + g_tail_cus) (hipExtStreamCreateWithCUMask; the
-// driver deals mask bits round-robin over the XCDs, so a contiguous run is the same share of every XCD); the caller gives the
-// network's stream the complementary mask ("tail_cus", "tail_cu_first"; bench.py --cu-split)
-int g_tail_cus = 0, g_tail_cu_first = 0;
+// the tail's knobs ("tail_*": stream priority, CU mask, event chain, fused rounds, the LDS path's limits): tuning.def
 
 #define T_TRY(expr)                                                                                  \
   do {                                                                                               \
@@ -143,25 +134,6 @@ void parallel_for(int n, int max_threads, F f) {
   for (auto& x : th) x.join();
 }
 
-}  // namespace
-// Three work items' labellings at a time stretch the network's first kernel 3.5x, one at a time 1.4x (selftest ST_CORUN).
-// "tail_chain": 1 = the stage-1 kernels (NMS, labelling, contour tables) of concurrent work items of this process run one
-// after the other on the GPU (an event chain across their streams) instead of next to each other; 2 = the refine stage's
-// big enqueue (render, labelling, accept rounds, dilate, labelling, holes) too; 0 = side by side.
-int g_tail_chain = 1;
-// "tail_fused_rounds": 1 = a window's merge rounds and its hole-filling passes as one launch each (a block per window);
-// 0 = one count + one apply launch per round and four hole-filling launches over all windows (rounds 2-3)
-int g_tail_fused_rounds = 1;
-// ... for canvas-path window sets whose largest window has fewer pixels than this ("tail_fused_max_pix")
-long long g_tail_fused_max_pix = 100000;
-// "tail_lds": 1 = the merge stage of a window as ONE block on bit planes in LDS (kernels_twlds.hip), 0 = every window through
-// the canvas path; "tail_lds_max_bytes": windows needing more LDS than this take the canvas path; "tail_lds_rcap" > 0: the
-// run-table capacity of every launch (tests force overflows with a tiny one)
-int g_tail_lds = 1, g_tail_lds_rcap = 0;
-long long g_tail_lds_max_bytes = 150 << 10;
-// the window-local kernel runs in up to three launches by LDS footprint ("tail_lds_cls0" / "tail_lds_cls1": the first two limits)
-long long g_tail_lds_cls0 = 40 << 10, g_tail_lds_cls1 = 80 << 10;
-namespace {
 // The chain is PER DEVICE: events belong to the device that was current when they were created, a stream can only record
 // its own device's events (hipErrorInvalidHandle otherwise), and tails on different GPUs have nothing to serialise.
 struct ChainState {
@@ -198,13 +170,6 @@ struct GpuChain {
     return e;
   }
 };
-}  // namespace
-#ifdef CTD_MEASURE_KNOBS               // `make MEASURE=1` only: knobs that return INCOMPLETE results, for ablation timings
-int g_tail_ablate = 0;                 // bit 1 = no refine stage ("tail_ablate")
-int g_tail_skip_pages = 0;             // 1 = the page-size results are not downloaded ("tail_skip_page_download")
-#endif
-long long g_tail_dma_min = 256 << 10;   // device -> host copies of at least this many bytes use the copy engines ("tail_dma_min"; huge = never)
-namespace {
 
 inline void* device_view(const void* host);
 

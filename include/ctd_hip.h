@@ -26,7 +26,7 @@
 extern "C" {
 #endif
 
-#define CTD_ABI_VERSION 9
+#define CTD_ABI_VERSION 10
 
 /* ---- error codes ------------------------------------------------------ */
 #define CTD_OK 0
@@ -182,27 +182,31 @@ int64_t ctd_engine_workspace_bytes(const ctd_engine* e);
  * fails with CTD_ERR_INVALID. */
 int32_t ctd_engine_arena_generation(const ctd_engine* e);
 
-/* Kernel-dispatch knobs (process-wide; no reference counterpart).  Keys: "halo_min_patches" (default 1024:
- * maps with fewer 16x16 patches take the implicit-GEMM kernel), "halo" (0: never the halo kernel), "halo_pair";
+/* Kernel-dispatch knobs (process-wide; no reference counterpart).  Keys: "halo_min_patches" (maps with fewer 16x16
+ * patches take the implicit-GEMM kernel), "halo" (0: never the halo kernel), "halo_pair";
  * "fuse" = bit mask of the fp16 engine's multi-layer kernels (1: C3 block with 32 hidden channels,
  * 2: SPPF's three pools, 4: stem + layer 1, 8: C3 bottlenecks with 64 / 128 hidden channels, 16: ConvTranspose + its 1x1
- * consumer, 32: the last ConvTranspose + seg-final's tap products; default 63; 0 = one launch per layer; results are
- * bit-identical either way), "c3_min_patches" (default 1024: smaller grids take the per-layer kernels);
- * "db_up_mfma" / "seg_final_mfma" (default 1: the DB tail / the seg-final layer with their channel reductions on the MFMA, 0: the VALU kernels; same
- * results within 2e-4 / 1e-6); "halo3" (default 1; 0: the ConvTranspose layers stay with the halo kernel) and
- * "halo3_min_blocks" (default 1024: smaller grids do not take the big-tile ConvTranspose kernel); "c3b_min_patches"
- * (default 1024), "c3b_max_ch" (default 128; 64: only the 64-channel bottlenecks) and "c3b_cfg64" (0 / 1 / 2, default 0) /
- * "c3b_cfg128" (0 / 1, default 1), the tilings of the bit-8 kernel per hidden width (bit-identical results);
- * "f32_mfma" (default 1; 0: engines created afterwards run the fp32 convolutions on the exact-order direct kernels);
- * the fp32s engine: "split_planes" (default 1: conv-to-conv tensors stored as fp16 hi / lo planes; 0: fp32 tensors, split
- * in the K loop), "split_halo" (default 1; 0: never the haloed-patch kernel) with "split_halo_min_patches" (default 512),
- * "split_stem" (default 1: the first layer reads the page itself; 0: an input copy and the generic kernel);
+ * consumer, 32: the last ConvTranspose + seg-final's tap products; 0 = one launch per layer; results are
+ * bit-identical either way), "c3_min_patches" (smaller grids take the per-layer kernels);
+ * "db_up_mfma" / "seg_final_mfma" (1: the DB tail / the seg-final layer with their channel reductions on the MFMA, 0: the
+ * VALU kernels; same results within 2e-4 / 1e-6); "halo3" (0: the ConvTranspose layers stay with the halo kernel) and
+ * "halo3_min_blocks" (smaller grids do not take the big-tile ConvTranspose kernel); "c3b_min_patches",
+ * "c3b_max_ch" (64: only the 64-channel bottlenecks) and "c3b_cfg64" (0 / 1 / 2) / "c3b_cfg128" (0 / 1), the tilings of
+ * the bit-8 kernel per hidden width (bit-identical results);
+ * "f32_mfma" (0: engines created afterwards run the fp32 convolutions on the exact-order direct kernels);
+ * the fp32s engine: "split_planes" (1: conv-to-conv tensors stored as fp16 hi / lo planes; 0: fp32 tensors, split
+ * in the K loop), "split_halo" (0: never the haloed-patch kernel) with "split_halo_min_patches",
+ * "split_stem" (1: the first layer reads the page itself; 0: an input copy and the generic kernel);
  * "fwd_prio" (wave priority of the network's kernels), "no_reuse" (engines created afterwards keep every activation
  * readable) and the tail's "tail_*" keys.
+ * Every key, with its default, its lower bound and the measurements behind it, is one row of csrc/tuning.def.
  * The library reads no environment variables; an unknown key returns CTD_ERR_INVALID.
  * Engines re-plan on their next forward after any key but the tail_* keys.  For tests and A/B
  * measurements. */
 int ctd_tuning_set(const char* key, int64_t value);
+/* The value a key holds now (as stored: after its lower bound and the narrowing to its variable's type), so that a caller
+ * can put back what was there.  An unknown key or a null pointer returns CTD_ERR_INVALID. */
+int ctd_tuning_get(const char* key, int64_t* value);
 
 /* ---- post-processing kernels ------------------------------------------- */
 

@@ -186,7 +186,7 @@ def refine_cases():
     out.append(_case("big, tiny, overlapping and repeated windows in one call", [img], [mask], [bx]))
     # the per-window grid is min(blocks the largest window asks for = 4, tail_max_blocks / windows): 16 / 8 = 2
     out.append(_case("the same call under tail_max_blocks = 16: two blocks per window", [img], [mask], [bx],
-                     tune={"tail_max_blocks": (16, 1024)}))
+                     tune={"tail_max_blocks": 16}))
     pages, masks, boxes = [], [], []
     for k, (im_w, im_h) in enumerate(((203, 90), (64, 131), (131, 77))):
         wins = [(0, 0, 9, 6), (im_w - 1 - 11, 0, 11, 5), (0, im_h - 1 - 7, 6, 7), (im_w - 1 - 15, im_h - 1 - 9, 15, 9),

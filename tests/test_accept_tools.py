@@ -122,3 +122,61 @@ def test_env_tuning_is_applied_by_the_host_side(monkeypatch):
     monkeypatch.setenv("CTD_TUNING", "bogus=1")
     with pytest.raises(L.CtdError):
         L._apply_env_tuning(Fake)
+
+
+def test_tuning_context_puts_back_what_it_found(monkeypatch):
+    """`_lib.tuning` against a fake library that records every call: values go back in reverse order, also when the body
+    raises; nested contexts unwind to what each found; an unknown key raises before anything is set; a value that was not the
+    default on the way in (CTD_TUNING at load, an outer context) is what comes back."""
+    import pytest
+    L = importlib.import_module("comic-text-detector_amd._lib")
+    store = {"fuse": 63, "halo_min_patches": 512, "tail_max_blocks": 1024}   # halo_min_patches: already changed at load time
+    calls = []
+
+    class Fake:
+        @staticmethod
+        def ctd_tuning_get(k, ref):
+            if k.decode() not in store:
+                return -1
+            ref._obj.value = store[k.decode()]
+            return 0
+
+        @staticmethod
+        def ctd_tuning_set(k, v):
+            if k.decode() not in store:
+                return -1
+            calls.append((k.decode(), v))
+            store[k.decode()] = max(v, 1) if k == b"tail_max_blocks" else v
+            return 0
+
+        @staticmethod
+        def ctd_last_error():
+            return b"unknown tuning key"
+    monkeypatch.setattr(L, "_lib", Fake)
+    assert L.tuning_get("halo_min_patches") == 512
+    with L.tuning(fuse=0, halo_min_patches=1):
+        assert store == {"fuse": 0, "halo_min_patches": 1, "tail_max_blocks": 1024}
+    assert calls == [("fuse", 0), ("halo_min_patches", 1), ("halo_min_patches", 512), ("fuse", 63)]
+    # the body raises: restored all the same, the exception passes through
+    del calls[:]
+    with pytest.raises(ZeroDivisionError):
+        with L.tuning({"fuse": 8}, tail_max_blocks=16):
+            1 / 0
+    assert calls == [("fuse", 8), ("tail_max_blocks", 16), ("tail_max_blocks", 1024), ("fuse", 63)]
+    # nested, the same key twice: each level puts back what it found
+    with L.tuning(fuse=0):
+        with L.tuning(fuse=8, tail_max_blocks=0):
+            assert store["fuse"] == 8 and L.tuning_get("tail_max_blocks") == 1         # what the library stored, clamped
+            with L.tuning({}):
+                pass
+        assert store["fuse"] == 0 and store["tail_max_blocks"] == 1024
+    assert store == {"fuse": 63, "halo_min_patches": 512, "tail_max_blocks": 1024}
+    # an unknown key: CtdError before anything is set, whichever position it has
+    del calls[:]
+    for keys in ({"fuse": 0, "bogus": 1}, {"bogus": 1, "fuse": 0}):
+        with pytest.raises(L.CtdError):
+            with L.tuning(keys):
+                raise AssertionError("the body must not run")
+    with pytest.raises(L.CtdError):
+        L.tuning_get("bogus")
+    assert calls == [] and store["fuse"] == 63

@@ -454,18 +454,12 @@ def test_fused_merge_rounds_equal_the_per_round_launches():
         boxes = [[2, 2, W - 2, H - 2], [0, 0, W // 2, H // 2], [W // 3, H // 4, W - 5, H - 9], [5, H // 2, W // 2, H - 1]]
         blks = [p.textblock.TextBlock(b) for b in boxes]
         out = {}
-        try:
-            # round 6: the canvas path for every window (`tail_lds` = 0), and the block-per-window kernels also for these
-            # LARGE windows (by default sets with a window of 100 K pixels or more take the per-round launches)
-            L.check(L.lib().ctd_tuning_set(b"tail_lds", 0), "ctd_tuning_set")
-            L.check(L.lib().ctd_tuning_set(b"tail_fused_max_pix", 1 << 40), "ctd_tuning_set")
+        # round 6: the canvas path for every window (`tail_lds` = 0), and the block-per-window kernels also for these
+        # LARGE windows (by default sets with a window of `tail_fused_max_pix` pixels or more take the per-round launches)
+        with L.tuning(tail_lds=0, tail_fused_max_pix=1 << 40):
             for fused in (1, 0):
-                L.check(L.lib().ctd_tuning_set(b"tail_fused_rounds", fused), "ctd_tuning_set")
-                out[fused] = [p.textmask.refine_mask(page, mask, blks, mode, "cuda") for mode in (0, 1)]
-        finally:
-            L.check(L.lib().ctd_tuning_set(b"tail_fused_rounds", 1), "ctd_tuning_set")
-            L.check(L.lib().ctd_tuning_set(b"tail_fused_max_pix", 100000), "ctd_tuning_set")
-            L.check(L.lib().ctd_tuning_set(b"tail_lds", 1), "ctd_tuning_set")
+                with L.tuning(tail_fused_rounds=fused):
+                    out[fused] = [p.textmask.refine_mask(page, mask, blks, mode, "cuda") for mode in (0, 1)]
         for a, b in zip(out[1], out[0]):
             np.testing.assert_array_equal(a, b)
         assert (out[1][0] > 0).mean() > 0.2
@@ -477,16 +471,9 @@ def test_fused_merge_rounds_equal_the_per_round_launches():
 
 def _refine_under(p, key_values, page, mask, blks, dev="cuda"):
     """refine_mask (both modes) under tuning keys, the keys restored afterwards; returns (masks, paths of the last call)"""
-    L = p._lib
-    defaults = {"tail_lds": 1, "tail_lds_rcap": 0, "tail_lds_max_bytes": 150 << 10}
-    try:
-        for k, v in key_values.items():
-            L.check(L.lib().ctd_tuning_set(k.encode(), v), "ctd_tuning_set")
+    with p._lib.tuning(key_values):
         out = [p.textmask.refine_mask(page, mask, blks, mode, dev) for mode in (0, 1)]
         paths = p.tail.thread_tail(torch.device("cuda", 0)).refine_paths()
-    finally:
-        for k in key_values:
-            L.check(L.lib().ctd_tuning_set(k.encode(), defaults[k]), "ctd_tuning_set")
     return out, paths
 
 

@@ -80,13 +80,9 @@ def test_halo_kernel_forced_onto_small_maps_matches_oracle(shape):
     p = pkg()
     be = p.backend.HipTextDetBackend(ck, device="cuda", precision="fp16")
     ref = [t.clone() for t in be(x.cuda())]
-    L = p._lib
-    L.check(L.lib().ctd_tuning_set(b"halo_min_patches", 1), "ctd_tuning_set")
-    try:
+    with p._lib.tuning(halo_min_patches=1):
         got = [t.clone() for t in be(x.cuda())]
         torch.cuda.synchronize()
-    finally:
-        L.check(L.lib().ctd_tuning_set(b"halo_min_patches", 1024), "ctd_tuning_set")
     assert not all(torch.equal(g, r) for g, r in zip(got, ref)), "the forced dispatch did not change any kernel"
     # the fp16 golden tolerances of tests/test_gpu_net.py (2e-2 max, 2e-3 mean), not a looser bar for the forced dispatch
     for g, o in ((got[1].cpu(), om), (got[2].cpu(), ol)):
@@ -125,11 +121,6 @@ def test_large_batch_is_split_transparently():
     assert torch.equal(one[1][0], mask[B - 1])
 
 
-def _tune(key, value):
-    L = pkg()._lib
-    L.check(L.lib().ctd_tuning_set(key, value), "ctd_tuning_set")
-
-
 @pytest.mark.parametrize("shape,u8", [((1, 64, 64), False), ((3, 128, 64), True), ((2, 320, 448), False),
                                       ((2, 1024, 1024), True), ((1, 1536, 1536), True), ((32, 1024, 1024), True)])
 def test_fused_blocks_equal_the_layer_per_launch_program_bit_for_bit(shape, u8):
@@ -152,39 +143,29 @@ def test_fused_blocks_equal_the_layer_per_launch_program_bit_for_bit(shape, u8):
     else:
         x = gen_golden.make_input(77, shape).cuda()
         run = lambda: [t.clone() for t in be(x)] + [be.mask_u8.clone(), be.bitmap.clone()]              # noqa: E731
-    try:
-        _tune(b"fuse", 0)
+    tuning = pkg()._lib.tuning          # each block puts back what it found: `fuse` is 0 again after every mask
+    outs = {}
+    with tuning(fuse=0):
         ref = run()
-        _tune(b"c3_min_patches", 1)
-        _tune(b"c3b_min_patches", 1)
-        outs = {}
-        for mask in (1, 2, 4, 6, 7, 8, 15, 16, 31, 32, 63):
-            _tune(b"fuse", mask)
-            outs[mask] = run()
-        _tune(b"halo_min_patches", 1)                   # the 3x3s (and ConvT phases) on the halo kernel everywhere
-        _tune(b"fuse", 0)
-        ref_h = run()
-        _tune(b"fuse", 8)
-        outs["8 + halo"] = run()
-        _tune(b"c3b_max_ch", 64)
-        outs["8 + halo, 64 only"] = run()
-        # bit 16 (a 128-channel ConvTranspose + its single 1x1 consumer in one launch of the big-tile kernel) needs that
-        # kernel: lift its grid threshold so that also the small shapes go through it (maps that are multiples of 16)
-        _tune(b"c3b_max_ch", 128)
-        _tune(b"halo3_min_blocks", 1)
-        _tune(b"fuse", 0)
-        ref_3 = run()
-        for mask in (16, 31, 32, 63):
-            _tune(b"fuse", mask)
-            outs[f"{mask} + halo3"] = run()
-        torch.cuda.synchronize()
-    finally:
-        _tune(b"fuse", 63)
-        _tune(b"halo3_min_blocks", 1024)
-        _tune(b"c3_min_patches", 1024)
-        _tune(b"c3b_min_patches", 1024)
-        _tune(b"c3b_max_ch", 128)
-        _tune(b"halo_min_patches", 1024)
+        with tuning(c3_min_patches=1, c3b_min_patches=1):
+            for mask in (1, 2, 4, 6, 7, 8, 15, 16, 31, 32, 63):
+                with tuning(fuse=mask):
+                    outs[mask] = run()
+            with tuning(halo_min_patches=1):            # the 3x3s (and ConvT phases) on the halo kernel everywhere
+                ref_h = run()
+                with tuning(fuse=8):
+                    outs["8 + halo"] = run()
+                    with tuning(c3b_max_ch=64):
+                        outs["8 + halo, 64 only"] = run()
+                # bit 16 (a 128-channel ConvTranspose + its single 1x1 consumer in one launch of the big-tile kernel) needs
+                # that kernel: lift its grid threshold so that also the small shapes go through it (maps that are multiples
+                # of 16)
+                with tuning(halo3_min_blocks=1):
+                    ref_3 = run()
+                    for mask in (16, 31, 32, 63):
+                        with tuning(fuse=mask):
+                            outs[f"{mask} + halo3"] = run()
+                    torch.cuda.synchronize()
     for mask, got in outs.items():
         base = ref if not isinstance(mask, str) else (ref_3 if "halo3" in mask else ref_h)
         for i, (g, r) in enumerate(zip(got, base)):
@@ -203,8 +184,6 @@ C3B_TILINGS = {
     (1, 0): {64: "c3b_kernel<64,16,2>", 128: "c3b_kernel<128,8,1>"},
     (2, 0): {64: "c3b_kernel<64,8,2>", 128: "c3b_kernel<128,8,1>"},
 }
-_KEYS = ((b"fuse", 63), (b"halo3_min_blocks", 1024), (b"c3_min_patches", 1024), (b"c3b_min_patches", 1024), (b"c3b_max_ch", 128),
-         (b"halo_min_patches", 1024), (b"c3b_cfg64", 0), (b"c3b_cfg128", 1))
 _BE = {}
 _RUNS = {}
 
@@ -249,29 +228,24 @@ def fused_runs(act, shape, u8, masks, cfg=(0, 1), halo_walks=False):
     run = _runner(be, shape, u8)
     out = {}
 
+    tuning = pkg()._lib.tuning
+
     def compare(label):
-        _tune(b"fuse", 0)
-        ref = run()
+        with tuning(fuse=0):
+            ref = run()
         for mask in masks:
-            _tune(b"fuse", mask)
-            got = run()
-            torch.cuda.synchronize()
-            kern = [(n, be.program.ops[i]["cout"], k) for i, (n, k) in enumerate(be.op_kernels())]
+            with tuning(fuse=mask):
+                got = run()
+                torch.cuda.synchronize()
+                kern = [(n, be.program.ops[i]["cout"], k) for i, (n, k) in enumerate(be.op_kernels())]
             out[f"{mask}{label}"] = (_differences(got, ref), kern)
-    try:
-        _tune(b"c3_min_patches", 1)
-        _tune(b"c3b_min_patches", 1)
-        _tune(b"c3b_cfg64", cfg[0])
-        _tune(b"c3b_cfg128", cfg[1])
+    with tuning(c3_min_patches=1, c3b_min_patches=1, c3b_cfg64=cfg[0], c3b_cfg128=cfg[1]):
         compare("")
-        if halo_walks:
-            _tune(b"halo_min_patches", 1)
-            compare(" + halo")
-        _tune(b"halo3_min_blocks", 1)
-        compare(" + halo3")
-    finally:
-        for k, v in _KEYS:
-            _tune(k, v)
+        with tuning({"halo_min_patches": 1} if halo_walks else {}):
+            if halo_walks:
+                compare(" + halo")
+            with tuning(halo3_min_blocks=1):
+                compare(" + halo3")
     _RUNS[key] = out
     return out
 
@@ -341,15 +315,12 @@ def test_timed_dispatch_fused_equals_unfused_on_all_32_pages(prec):
     be = pkg().backend.HipTextDetBackend(ck, device="cuda", precision=prec)
     names = ("blks", "mask", "lines", "mask_u8", "bitmap")
     run = lambda: [t.clone() for t in be.forward_u8(x)] + [be.mask_u8.clone(), be.bitmap.clone()]       # noqa: E731
-    try:
-        got = run()
-        kernels = be.op_kernels()
-        _tune(b"fuse", 0)
+    got = run()
+    kernels = be.op_kernels()
+    with pkg()._lib.tuning(fuse=0):
         ref = run()
         plain = be.op_kernels()
         torch.cuda.synchronize()
-    finally:
-        _tune(b"fuse", 63)
     fused = {k for _, k in kernels} - {k for _, k in plain}
     want = {"c3_fused_kernel", "c3b_kernel", "conv_halo3_kernel+1x1", "conv_halo3_kernel+taps", "seg_final_gather_kernel",
             "stem_conv2_kernel", "sppf_pool3_kernel"} if prec == "fp16" else {"sppf_pool3_kernel"}
@@ -375,21 +346,14 @@ def test_big_tile_convt_kernels_reproduce_the_256x128_kernel_bit_for_bit(shape):
     be = pkg().backend.HipTextDetBackend(ck, device="cuda", precision="fp16")
     # both sides run the ConvT layers on their own (fuse bits 16 and 32 off): a tuning key re-plans the engine, and with
     # halo3 on the plan would fold their consumers into them
-    _tune(b"fuse", 15)
-    _tune(b"halo3", 0)
-    _tune(b"halo_min_patches", 1)                       # the reference side: the 256 x 128 halo kernel on every ConvT layer
-    try:
-        ref = [t.clone() for t in be(x)]
-        ref_side = (be.mask_u8.clone(), be.bitmap.clone())
-        _tune(b"halo3", 1)
-        _tune(b"halo3_min_blocks", 1)
-        got = [t.clone() for t in be(x)]
-        got_side = (be.mask_u8.clone(), be.bitmap.clone())
-        torch.cuda.synchronize()
-    finally:
-        _tune(b"fuse", 63)
-        _tune(b"halo3", 1)
-        _tune(b"halo3_min_blocks", 1024)
-        _tune(b"halo_min_patches", 1024)
+    tuning = pkg()._lib.tuning
+    with tuning(fuse=15, halo_min_patches=1):
+        with tuning(halo3=0):                           # the reference side: the 256 x 128 halo kernel on every ConvT layer
+            ref = [t.clone() for t in be(x)]
+            ref_side = (be.mask_u8.clone(), be.bitmap.clone())
+        with tuning(halo3=1, halo3_min_blocks=1):
+            got = [t.clone() for t in be(x)]
+            got_side = (be.mask_u8.clone(), be.bitmap.clone())
+            torch.cuda.synchronize()
     for g, r in zip(got + list(got_side), ref + list(ref_side)):
         assert torch.equal(g, r)

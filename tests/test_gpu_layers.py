@@ -134,19 +134,19 @@ CONFIGS = {
 # the small shape of the wide-range `relu` checkpoint (leaky and silu cover forced_3x320x448)
 SMALL = {"forced_3x128x64": ((3, 128, 64), False, True)}
 # Configurations under tuning keys: name -> (engine, shape, uint8 input, keys).  The keys are set before the engines are
-# created (`f32_mfma` is read at creation) and restored through _DEFAULTS.  (3, 128, 64) is the non-square B > 1 shape of the
+# created (`f32_mfma` is read at creation) and put back by `_lib.tuning`.  (3, 128, 64) is the non-square B > 1 shape of the
 # suite, (1, 64, 64) takes the maps down to 1 x 1; the kernels these keys select have no tile larger than the maps here.
 KEYED = {
-    "f32_direct_1x64x64": ("fp32", (1, 64, 64), False, {b"f32_mfma": 0}),
-    "f32_direct_3x128x64": ("fp32", (3, 128, 64), False, {b"f32_mfma": 0}),
-    "valu_tails_u8_3x128x64": ("fp16", (3, 128, 64), True, {b"db_up_mfma": 0, b"seg_final_mfma": 0}),
-    "halo_unpaired_3x128x64": ("fp16", (3, 128, 64), False, {b"halo_min_patches": 1, b"halo_pair": 0}),
-    "halo_paired_3x128x64": ("fp16", (3, 128, 64), False, {b"halo_min_patches": 1, b"halo_pair": 1}),
-    "halo_off_3x128x64": ("fp16", (3, 128, 64), False, {b"halo_min_patches": 1, b"halo": 0}),
-    "halo3_off_3x128x64": ("fp16", (3, 128, 64), False, {b"halo_min_patches": 1, b"halo3_min_blocks": 1, b"halo3": 0}),
-    "halo3_on_3x128x64": ("fp16", (3, 128, 64), False, {b"halo_min_patches": 1, b"halo3_min_blocks": 1, b"halo3": 1}),
-    "fp32_tensors_3x128x64": ("fp32s", (3, 128, 64), False, {b"split_planes": 0, b"split_halo": 0, b"split_stem": 0}),
-    "planes_off_3x128x64": ("fp32s", (3, 128, 64), False, {b"split_planes": 0}),
+    "f32_direct_1x64x64": ("fp32", (1, 64, 64), False, {"f32_mfma": 0}),
+    "f32_direct_3x128x64": ("fp32", (3, 128, 64), False, {"f32_mfma": 0}),
+    "valu_tails_u8_3x128x64": ("fp16", (3, 128, 64), True, {"db_up_mfma": 0, "seg_final_mfma": 0}),
+    "halo_unpaired_3x128x64": ("fp16", (3, 128, 64), False, {"halo_min_patches": 1, "halo_pair": 0}),
+    "halo_paired_3x128x64": ("fp16", (3, 128, 64), False, {"halo_min_patches": 1, "halo_pair": 1}),
+    "halo_off_3x128x64": ("fp16", (3, 128, 64), False, {"halo_min_patches": 1, "halo": 0}),
+    "halo3_off_3x128x64": ("fp16", (3, 128, 64), False, {"halo_min_patches": 1, "halo3_min_blocks": 1, "halo3": 0}),
+    "halo3_on_3x128x64": ("fp16", (3, 128, 64), False, {"halo_min_patches": 1, "halo3_min_blocks": 1, "halo3": 1}),
+    "fp32_tensors_3x128x64": ("fp32s", (3, 128, 64), False, {"split_planes": 0, "split_halo": 0, "split_stem": 0}),
+    "planes_off_3x128x64": ("fp32s", (3, 128, 64), False, {"split_planes": 0}),
 }
 TIMED = "timed_u8_32x1024x1024"
 # the pages checked at B = 32: both ends with their neighbours, an adjacent middle pair, two seeded random ones
@@ -167,20 +167,12 @@ FUSED = {
     "(fused)": "the op's work is done by the launch of the op next to it (one of the kernels above, or stem_split_kernel "
                "reading the page for the input op)",
 }
-_DEFAULTS = ((b"no_reuse", 0), (b"fuse", 63), (b"halo_min_patches", 1024), (b"halo3_min_blocks", 1024), (b"f32_mfma", 1),
-             (b"db_up_mfma", 1), (b"seg_final_mfma", 1), (b"halo_pair", 1), (b"split_planes", 1), (b"split_halo", 1),
-             (b"split_stem", 1), (b"halo", 1), (b"halo3", 1))
 _S = {}
 OUTS = {}           # keyed config -> the network outputs of its run
 TABLE = {}          # (engine, kernel) -> worst ratio at B <= 3
 TABLEK = {}         # (engine, kernel) -> worst ratio under the tuning keys of KEYED and on the hand-built direct program
 TABLE32 = {}        # (engine, kernel) -> worst ratio at B = 32
 STATS = {}          # engine -> measurements of the B = 32 run
-
-
-def _tune(key, value):
-    L = pkg()._lib
-    L.check(L.lib().ctd_tuning_set(key, value), "ctd_tuning_set")
 
 
 def _engine(ck, prec, prog, act):
@@ -234,31 +226,21 @@ def run_checks(engine, config, ck_key="synth0", act="leaky"):
     snap, index, snaps = snapshot_program(prog)
     xd = x.cuda()
     fwd = (lambda be: be.forward_u8(xd)) if u8 else (lambda be: be(xd))        # noqa: E731
-    try:
-        _tune(b"fuse", 0)
-        if forced:
-            _tune(b"halo_min_patches", 1)
-            _tune(b"halo3_min_blocks", 1)
-        for k, v in keys.items():
-            _tune(k, v)
-        _tune(b"no_reuse", 0)
+    force = {"halo_min_patches": 1, "halo3_min_blocks": 1} if forced else {}
+    with L.tuning({"fuse": 0, **force, **keys, "no_reuse": 0}):
         plain = _engine(ck, engine, prog, act)
         fwd(plain)
         torch.cuda.synchronize()
         plain_kernels = plain.op_kernels()
         del plain
-        _tune(b"no_reuse", 1)
-        be = _engine(ck, engine, snap, act)
-        _tune(b"no_reuse", 0)
+        with L.tuning(no_reuse=1):
+            be = _engine(ck, engine, snap, act)
         blks, mask, lines = fwd(be)
         torch.cuda.synchronize()
         outs = dict(blks=blks.cpu().numpy(), mask=mask.cpu().numpy(), lines=lines.cpu().numpy(),
                     mask_u8=be.mask_u8.cpu().numpy(), bitmap=be.bitmap.cpu().numpy())
         snap_kernels = be.op_kernels()
         workspace = be.workspace_bytes()
-    finally:
-        for k, v in _DEFAULTS:
-            _tune(k, v)
     del xd, blks, mask, lines
     kernels = [snap_kernels[index[i]][1] for i in range(len(prog.ops))]
     # the premise: neither no_reuse nor the snapshot copies change what the program's own ops launch
@@ -472,17 +454,12 @@ def run_direct(engine):
     L = p._lib
     prog, ops = direct_program(L.PREC_F16 if engine == "fp16" else L.PREC_F32)
     x, page = _input((2, 192, 320), False, 13)
-    try:
-        _tune(b"fuse", 0)
-        _tune(b"no_reuse", 1)
-        be = _engine({}, engine, prog, "leaky")
-        _tune(b"no_reuse", 0)
+    with L.tuning(fuse=0):
+        with L.tuning(no_reuse=1):
+            be = _engine({}, engine, prog, "leaky")
         be(x.cuda())
         torch.cuda.synchronize()
         kernels = [k for _, k in be.op_kernels()]
-    finally:
-        for k, v in _DEFAULTS:
-            _tune(k, v)
     res = LayerCheck(prog, {}, engine, be.read_tensor, {}, page, kernels=kernels, seed=5).check_all(ops)
     del be
     for i, r in res.items():
@@ -495,9 +472,8 @@ def run_direct(engine):
 # ---------------------------------------------------------------------------------------------------------------------
 # the ledger of tuning keys
 # ---------------------------------------------------------------------------------------------------------------------
-# Every key of ctd_tuning_set (csrc/engine.hip, with conv_tuning_set of kernels_halo.hip and halo3_tuning_set of
-# kernels_halo3.hip) is in one of the two tables: tests/test_layer_ref.py reads the keys out of the sources and fails on
-# a key that is in neither.  DISPATCH_KEYS: (key, value, what the value selects, where it is proven).  The proof is
+# Every key of ctd_tuning_set (the rows of csrc/tuning.def) is in one of the two tables: tests/test_layer_ref.py reads the
+# rows and fails on a key that is in neither.  DISPATCH_KEYS: (key, value, what the value selects, where it is proven).  The proof is
 #   ("f64", engine, config, kernels)   run_checks(engine, config): each kernel launched by an op with n > 0 checked elements
 #   ("direct", engine, kernels)        the same on the hand-built program
 #   ("bits", act, shape, u8, masks, cfg, label, kernels)
@@ -563,8 +539,8 @@ def test_every_dispatch_key_value_ran_the_kernel_it_selects_and_was_checked():
             _, engine, config, kernels = proof
             res = run_checks(engine, config)
             # the row's value is what that configuration ran under: the key as set there, the library's default otherwise
-            held = KEYED[config][3] if config in KEYED else {b"fuse": 0}
-            assert held.get(key.encode(), dict(_DEFAULTS)[key.encode()]) == value, (key, value, config)
+            held = KEYED[config][3] if config in KEYED else {"fuse": 0}
+            assert held.get(key, pkg()._lib.tuning_get(key)) == value, (key, value, config)
         elif proof[0] == "direct":
             _, engine, kernels = proof
             res = run_direct(engine)

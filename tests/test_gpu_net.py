@@ -292,20 +292,14 @@ def test_split_engine_layouts_and_kernels_agree():
     of a K loop and the 22-bit residual inputs differ -- so the maps agree to a few 1e-7, far inside the tolerance against
     the oracle, and the first-layer switch alone changes nothing at all."""
     p = pkg()
-    L = p._lib.lib()
     pages = torch.from_numpy(np.stack([p.synth.text_like_page((512, 512), s) for s in (3, 4)])).cuda()
 
     def run(**knobs):
-        for k, v in knobs.items():
-            assert L.ctd_tuning_set(k.encode(), v) == p._lib.OK
-        try:
+        with p._lib.tuning(knobs):
             be = p.backend.HipTextDetBackend(checkpoint(0), device="cuda", precision="fp32s")
             blks, mask, lines = [t.clone() for t in be.forward_u8(pages)]
             torch.cuda.synchronize()
             return blks, mask, lines, be.mask_u8.clone(), be.bitmap.clone()
-        finally:
-            for k in knobs:
-                assert L.ctd_tuning_set(k.encode(), 1) == p._lib.OK
 
     ref = run()
     assert all(torch.isfinite(t).all() for t in ref[:3])

@@ -30,22 +30,16 @@ def reference(case):
 
 def traced_refine(case, tune=()):
     """One `Tail.refine` call with the trace on (the calling thread's tail; off again afterwards), under the case's tuning
-    keys and `tune` = {key: (value, value to restore)}.  Returns (records, path counts, refined masks, masks after)."""
+    keys and `tune` = {key: value}, put back afterwards.  Returns (records, path counts, refined masks, masks after)."""
     p = pkg()
-    L = p._lib
     tail = p.tail.thread_tail(torch.device("cuda", torch.cuda.current_device()))
-    keys = dict(case["tune"])
-    keys.update(dict(tune))
     pages = [torch.from_numpy(img).cuda() for img in case["pages"]]
     tail.set_trace(True)
     try:
-        for k, (v, _) in keys.items():
-            L.check(L.lib().ctd_tuning_set(k.encode(), v), "ctd_tuning_set")
-        refined, after = tail.refine(pages, [m.copy() for m in case["masks"]], case["boxes"], case["mode"], case["keep"])
-        recs, paths = tail.trace_windows(), tail.refine_paths()
+        with p._lib.tuning({**case["tune"], **dict(tune)}):
+            refined, after = tail.refine(pages, [m.copy() for m in case["masks"]], case["boxes"], case["mode"], case["keep"])
+            recs, paths = tail.trace_windows(), tail.refine_paths()
     finally:
-        for k, (_, restore) in keys.items():
-            L.check(L.lib().ctd_tuning_set(k.encode(), restore), "ctd_tuning_set")
         tail.set_trace(False)
     return recs, paths, [np.array(r) for r in refined], [np.array(a) for a in after]
 
@@ -72,7 +66,7 @@ def test_refine_tables_of_every_width_class_on_the_three_merge_paths():
     times: default path, every window through the canvases (`tail_lds` = 0), and with a run table of 8 (`tail_lds_rcap`:
     overflows re-done through the canvases).  The records before the merge stage must be the same bytes in all three."""
     case = T.width_class_case()
-    runs = [("", {}), (" [tail_lds = 0]", {"tail_lds": (0, 1)}), (" [tail_lds_rcap = 8]", {"tail_lds_rcap": (8, 0)})]
+    runs = [("", {}), (" [tail_lds = 0]", {"tail_lds": 0}), (" [tail_lds_rcap = 8]", {"tail_lds_rcap": 8})]
     n, bad, before = 0, [], []
     for what, tune in runs:
         got = traced_refine(case, tune)

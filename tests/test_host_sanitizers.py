@@ -1,4 +1,4 @@
-"""The native HOST code (csrc/host_db.cpp, host_group.cpp, host_refine.cpp, host_stage.cpp, np_dispatch.h) under
+"""The native HOST code (csrc/host_db.cpp, host_group.cpp, host_refine.cpp, host_stage.cpp, np_dispatch.h; tuning.cpp) under
 AddressSanitizer + UndefinedBehaviorSanitizer and under ThreadSanitizer.  Every other test of that code compares VALUES; a read
 one element past a label row, a write one record past a pool's capacity, a signed overflow or an unsynchronised static give the
 right values and are still bugs.  Sanitizers are off limits on the device, so the host build is where they go: a host-only
@@ -294,3 +294,50 @@ def test_canary_is_reported(built, flavours, work, flavour, defect, report):
 def test_canary_is_silent_in_the_plain_flavour(built, work, defect):
     r = _run([os.path.join(work, "san_canary_plain"), defect], 120)
     assert r.returncode == 0 and r.stderr == "", (r.returncode, r.stderr[-2000:])
+
+
+# ------------------------------------------------------------------------------------------------------ 4. the tuning table
+
+# The ONE place outside csrc/tuning.def that knows a default: key -> (type, default, lower bound or None, engines re-plan),
+# transcribed from the sources as they were before the table existed.  Retuning a default is an edit of its row there and here.
+TUNING_PIN = {
+    "fuse": ("int", 63, None, True), "c3_min_patches": ("long long", 1024, None, True),
+    "c3b_min_patches": ("long long", 1024, None, True), "c3b_max_ch": ("int", 128, None, True),
+    "c3b_cfg64": ("int", 0, None, True), "c3b_cfg128": ("int", 1, None, True),
+    "seg_final_mfma": ("int", 1, None, True), "db_up_mfma": ("int", 1, None, True),
+    "halo": ("int", 1, None, True), "halo_min_patches": ("long long", 1024, None, True), "halo_pair": ("int", 1, None, True),
+    "halo3": ("long long", 1, None, True), "halo3_min_blocks": ("long long", 1024, None, True),
+    "no_reuse": ("int", 0, None, True), "f32_mfma": ("int", 1, None, True), "fwd_prio": ("int", 1, None, True),
+    "split_stem": ("int", 1, None, True), "split_planes": ("int", 1, None, True), "split_halo": ("int", 1, None, True),
+    "split_halo_min_patches": ("long long", 512, None, True),
+    "tail_max_blocks": ("int", 1024, 1, False), "tail_chain": ("int", 1, None, False),
+    "tail_fused_rounds": ("int", 1, None, False), "tail_fused_max_pix": ("long long", 100000, None, False),
+    "tail_lds": ("int", 1, None, False), "tail_lds_rcap": ("int", 0, None, False),
+    "tail_lds_max_bytes": ("long long", 150 << 10, None, False), "tail_lds_runs_x10": ("int", 25, 1, False),
+    "tail_lds_threads": ("int", 512, None, False), "tail_lds_cls0": ("long long", 40 << 10, None, False),
+    "tail_lds_cls1": ("long long", 80 << 10, None, False), "tail_dma_min": ("long long", 256 << 10, None, False),
+    "tail_priority": ("int", 1, None, False), "tail_cus": ("int", 0, None, False), "tail_cu_first": ("int", 0, None, False),
+}
+
+
+def test_tuning_table_holds_the_pinned_defaults_with_and_without_the_sanitizers(flavours, work):
+    """tests/native/tuning_table.cpp (tuning.cpp alone, its own main): every row's type, default, replan flag, what it stores
+    for a value below any lower bound (-7) and for 1 << 40 (an int key keeps the low 32 bits, a long long key all of it),
+    unknown keys and null pointers refused with nothing written, every key restored.  The -O2 build and the ASan + UBSan build
+    print the same, the sanitized one nothing else, and both print TUNING_PIN."""
+    if flavours["asan"] is not None:
+        pytest.skip(flavours["asan"])
+    r = subprocess.run(["make", "-C", CSRC, "-j2", "san_tuning", "OUT=" + work, "SAN_FLAVOURS=plain asan"], capture_output=True, text=True)
+    assert r.returncode == 0 and "hipcc" not in r.stdout, r.stdout[-3000:] + r.stderr[-3000:]
+    runs = {fl: _run([os.path.join(work, "tuning_table_" + fl)], 120) for fl in ("plain", "asan")}
+    for fl, r in runs.items():
+        assert r.returncode == 0 and r.stderr == "", (fl, r.returncode, r.stdout[-1000:], r.stderr[-3000:])
+    assert runs["plain"].stdout == runs["asan"].stdout
+    assert len(TUNING_PIN) == 35
+    assert all(replan == (not key.startswith("tail_")) for key, (_, _, _, replan) in TUNING_PIN.items())
+    want = sorted(f"{key} {typ} {default} {int(replan)} {-7 if low is None else low} {0 if typ == 'int' else 1 << 40}"
+                  for key, (typ, default, low, replan) in TUNING_PIN.items())
+    *rows, unknown, restored = runs["plain"].stdout.splitlines()
+    assert sorted(rows) == want and len(rows) == len(set(rows))
+    assert unknown == "unknown key: set -1 get -1, null key: set -1 get -1, null value: get -1, untouched 12345 0"
+    assert restored == "restored 35 keys"

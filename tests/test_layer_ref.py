@@ -282,15 +282,12 @@ def test_snapshot_program_computes_the_same_outputs():
 
 
 def tuning_keys_in_the_sources():
-    """The keys ctd_tuning_set accepts: the `k == "..."` comparisons of the three sources that parse them."""
+    """The keys ctd_tuning_set accepts: the rows of csrc/tuning.def (the measurement-only ones included)."""
     import os
     import re
     src = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "comic-text-detector_amd", "csrc")
-    keys = []
-    for f in ("engine.hip", "kernels_halo.hip", "kernels_halo3.hip"):
-        with open(os.path.join(src, f)) as fh:
-            keys += re.findall(r'\bk == "([a-z0-9_]+)"', fh.read())
-    return keys
+    with open(os.path.join(src, "tuning.def")) as fh:
+        return re.findall(r'^TUNE\("([a-z0-9_]+)",', fh.read(), re.M)
 
 
 def test_every_tuning_key_is_in_the_ledger(monkeypatch):
@@ -307,8 +304,9 @@ def test_every_tuning_key_is_in_the_ledger(monkeypatch):
     assert not dispatch & set(G.NOT_DISPATCH_KEYS)
     assert not (dispatch | set(G.NOT_DISPATCH_KEYS)) - set(keys), "the ledger names a key the library does not parse"
     assert all(reason for reason in G.NOT_DISPATCH_KEYS.values())
-    # every key a keyed configuration sets is restored by _DEFAULTS
-    assert {k for c in G.KEYED.values() for k in c[3]} <= {k for k, _ in G._DEFAULTS}
+    # every key a keyed configuration sets is one the library knows (`_lib.tuning` reads it, sets it and puts it back:
+    # tests/test_gpu_tuning.py)
+    assert {k for c in G.KEYED.values() for k in c[3]} <= set(keys)
     # the check bites: a key in neither table is reported
     monkeypatch.delitem(G.NOT_DISPATCH_KEYS, "fwd_prio")
     assert unlisted() == ["fwd_prio"]

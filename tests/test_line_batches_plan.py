@@ -152,4 +152,4 @@ def test_batch_job_mirror_has_the_c_layout():
     assert vals == [120, C.sizeof(J), J.warp.offset, J.slot.offset, J.rows.offset, J.Wk.offset, J.cut.offset, L.ABI_VERSION]
     f = R.BATCH_JOB_DTYPE.fields
     assert vals[1:7] == [R.BATCH_JOB_DTYPE.itemsize] + [f[k][1] for k in ("warp", "slot", "rows", "Wk", "cut")]
-    assert vals[7] == 9
+    assert vals[7] == 10

@@ -105,8 +105,8 @@ def test_big_windows_and_calls():
     overlap = lambda a, b: a != b and a[0] < b[0] + b[2] and b[0] < a[0] + a[2] and a[1] < b[1] + b[3] and b[1] < a[1] + a[3]  # noqa: E731
     assert any(overlap(a, b) for a in mixed for b in mixed)
     capped = by("tail_max_blocks")
-    (low, restore), = capped["tune"].values()
-    assert restore == 1024 and 1 <= low // len(_windows(capped)) < 4             # fewer blocks per window than the largest asks for
+    low, = capped["tune"].values()
+    assert 1 <= low // len(_windows(capped)) < 4                                   # fewer blocks per window than the largest asks for
     three = by("three pages")
     assert len({p.shape[1] for p in three["pages"]}) == 3 and all(len(b) >= 5 for b in three["boxes"])
     keep = by("keep_undetected_mask")
