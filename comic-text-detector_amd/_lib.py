@@ -26,6 +26,8 @@ OUT_MASK, OUT_LINES = 0, 1
 REGION_OK, REGION_DEGENERATE, REGION_MAX_SIDE, REGION_TILE = 0, 1, 32766, 1024
 REGION_U8, REGION_F16, REGION_F32 = 0, 1, 2
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
+COLOR_OK, COLOR_EMPTY, COLOR_NO_MASK, COLOR_NO_CONTRAST, COLOR_TOO_LARGE = range(5)
+COLOR_MAX_PIXELS, COLOR_MAX_COORD = 1 << 24, 1 << 29
 
 
 class CtdTensor(C.Structure):
@@ -82,6 +84,17 @@ class CtdRegionBatchJob(C.Structure):
     _fields_ = [("warp", CtdRegionJob), ("slot", C.c_int32), ("rows", C.c_int32), ("Wk", C.c_int32), ("cut", C.c_int32)]
 
 
+class CtdColorJob(C.Structure):
+    _fields_ = [("page_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32),
+                ("mask_pitch", C.c_int32), ("quad", C.c_int32 * 8)]
+
+
+class CtdLineColor(C.Structure):
+    _fields_ = [("n_fg", C.c_int64), ("s_fg", C.c_int64 * 3), ("n_bg", C.c_int64), ("s_bg", C.c_int64 * 3),
+                ("g_on", C.c_int64), ("g_off", C.c_int64), ("n_on", C.c_int32), ("n_off", C.c_int32), ("status", C.c_int32),
+                ("fg", C.c_uint8 * 3), ("bg", C.c_uint8 * 3), ("pad_", C.c_uint8 * 6)]
+
+
 # every symbol include/ctd_hip.h declares: (restype, argtypes)
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -110,6 +123,7 @@ SYMBOLS = {
     "ctd_region_transforms": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _i32, C.c_double, _vp, _vp, _vp, _vp]),
     "ctd_warp_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
     "ctd_warp_region_batches": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
+    "ctd_line_colors": (_i32, [_vp, _i32, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),
     "ctd_tail_destroy": (None, [_vp]),

@@ -148,8 +148,11 @@ def write_page_annotations(save_dir, imgname, img, mask_refined, blk_list, save_
 
 
 def model2annotations(model_path: Union[str, dict], img_dir_list, save_dir: str, save_json: bool = False,
-                      batch_size: int = 8, device: str = "cuda", detector=None, io_threads: int = 4) -> int:
-    """reference inference.py:19-70, batched.  Returns the number of pages written."""
+                      batch_size: int = 8, device: str = "cuda", detector=None, io_threads: int = 4,
+                      font_colors: bool = False) -> int:
+    """reference inference.py:19-70, batched.  Returns the number of pages written.  `font_colors=True`: the blocks' colour
+    fields in the JSON records are filled (`TextDetector.detect_batch(font_colors=True)`); the default writes the zeros the
+    reference's detector writes."""
     from .detector import TextDetector
     if isinstance(img_dir_list, str):
         img_dir_list = [img_dir_list]
@@ -166,7 +169,8 @@ def model2annotations(model_path: Union[str, dict], img_dir_list, save_dir: str,
         for bi, paths in enumerate(batches):
             imgs = [f.result() for f in nxt]
             nxt = decode(batches[bi + 1]) if bi + 1 < len(batches) else []   # decode k+1 under detection k
-            results = det.detect_batch(imgs, refine_mode=REFINEMASK_ANNOTATION, keep_undetected_mask=True)
+            results = det.detect_batch(imgs, refine_mode=REFINEMASK_ANNOTATION, keep_undetected_mask=True,
+                                       font_colors=font_colors)
             for path, img, (mask, mask_refined, blk_list) in zip(paths, imgs, results):
                 pending_writes.append(pool.submit(write_page_annotations, save_dir, osp.basename(path), img,
                                                   mask_refined, blk_list, save_json))

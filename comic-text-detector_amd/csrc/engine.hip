@@ -1373,4 +1373,13 @@ int ctd_warp_region_batches(const ctd_region_batch_job* jobs_dev, int32_t n, con
   return CTD_OK;
 }
 
+int ctd_line_colors(const ctd_color_job* jobs_dev, int32_t n, ctd_line_color* out_dev, void* stream) {
+  if (n < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (n == 0) return CTD_OK;
+  if (!jobs_dev || !out_dev) return fail(CTD_ERR_INVALID, "null pointer");
+  launch_line_colors(jobs_dev, n, out_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CTD_OK;
+}
+
 }  // extern "C"

@@ -172,5 +172,9 @@ void launch_region_warp(const ctd_region_job* jobs, int n, const int* tile_first
 void launch_region_batches(const ctd_region_batch_job* jobs, int n, const int* tile_first, int n_tiles, const void* tables,
                            void* out, int dtype, int layout, int reverse, int pad, hipStream_t st);
 
+// ---- kernels_color.hip ----------------------------------------------------------
+// fill / surround colour of n text lines in one launch (ctd_line_colors), one block per line; n >= 1
+void launch_line_colors(const ctd_color_job* jobs, int n, ctd_line_color* out, hipStream_t st);
+
 // ---- mfma layout probe (selftest) -------------------------------------------
 void launch_mfma_probe(const half_t* a, const half_t* b, float* out, hipStream_t st);

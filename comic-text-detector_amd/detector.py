@@ -318,11 +318,26 @@ class TextDetector:
                                                 0.6, True, refine_mode, keep_undetected_mask, job["ev"], records=records,
                                                 lazy=lazy)
 
-    def _tail_batches(self, job, refine_mode, keep_undetected_mask, lo, hi, records, lazy, kw):
+    def _tail_colors(self, job, refine_mode, keep_undetected_mask, lo=None, hi=None, records=None):
+        """`_tail`, then the font colours of the same pages (`colors.line_colors`) from the batch's staged device pages and
+        the item's `mask_refined` arrays (page-locked: uploaded non-blocking), on the calling thread's tail stream, applied
+        to the blocks before the item is returned."""
+        from . import colors
+        res = self._tail(job, refine_mode, keep_undetected_mask, lo, hi, records, False)
+        dev = self.net.device
+        st = thread_tail(dev).stream()
+        with torch.cuda.stream(st):
+            masks = [torch.from_numpy(r[1]).to(dev, non_blocking=True) for r in res]
+        lists = [r[2] for r in res]
+        colors.line_colors(job["gpu"][slice(lo, hi)], masks, lists, stream=st, device=dev).apply(lists)
+        return res
+
+    def _tail_batches(self, job, refine_mode, keep_undetected_mask, lo, hi, records, lazy, kw, font_colors=False):
         """`_tail`, then the OCR input batches of the same pages (`regions.line_batches`) from the batch's staged device
         pages, on the calling worker's tail stream: (results, LineBatches)."""
         from . import regions
-        res = self._tail(job, refine_mode, keep_undetected_mask, lo, hi, records, lazy)
+        res = (self._tail_colors(job, refine_mode, keep_undetected_mask, lo, hi, records) if font_colors else
+               self._tail(job, refine_mode, keep_undetected_mask, lo, hi, records, lazy))
         dev = self.net.device
         lb = regions.line_batches(job["gpu"][slice(lo, hi)], [r[2] for r in res], stream=thread_tail(dev).stream(), device=dev,
                                   **kw)
@@ -338,15 +353,20 @@ class TextDetector:
         return [(n * k // parts, n * (k + 1) // parts) for k in range(parts)]
 
     @torch.no_grad()
-    def detect_batch(self, pages: Sequence[Page], refine_mode=REFINEMASK_INPAINT,
-                     keep_undetected_mask=False) -> List[Tuple[np.ndarray, np.ndarray, List[TextBlock]]]:
+    def detect_batch(self, pages: Sequence[Page], refine_mode=REFINEMASK_INPAINT, keep_undetected_mask=False,
+                     font_colors: bool = False) -> List[Tuple[np.ndarray, np.ndarray, List[TextBlock]]]:
+        """`font_colors=True`: every block's colour fields (`fg_*`, `bg_*`: `get_font_colors()`, `stroke_width`) are filled
+        from the page and its `mask_refined` (`colors.line_colors`, one more launch on the tail's stream); the default
+        leaves them 0 and does no work for them."""
+        if font_colors:
+            return self._tail_colors(self._forward(pages), refine_mode, keep_undetected_mask)
         return self._tail(self._forward(pages), refine_mode, keep_undetected_mask)
 
     @torch.no_grad()
     def detect_stream(self, batches: Iterable[Sequence[Page]], refine_mode=REFINEMASK_INPAINT,
                       keep_undetected_mask=False, workers: int = 0, depth: int = 4, engines: int = 1,
                       loaders: int = 2, tail_split: int = 0, lazy: bool = False, records=None,
-                      tune: bool = True, line_batches: Optional[dict] = None) -> Iterator[list]:
+                      tune: bool = True, line_batches: Optional[dict] = None, font_colors: bool = False) -> Iterator[list]:
         """Yields `detect_batch(batch)` for every batch, in order, with up to `depth` batches in flight:
         the forward of the next batches is launched while `workers` threads run the tails of earlier ones.
         Host (numpy) pages are staged to the GPU by `loaders` threads up to `depth` batches ahead (`_stage`).
@@ -368,9 +388,15 @@ class TextDetector:
         item's pages, made by the worker that ran its tail, on that tail's own stream, from the staged device pages (host
         pages are not uploaded again).  Their `index[:, 0]` counts pages within the yielded batch, `.page0` is the item's
         first page; call `.wait()` before using one on another stream.
+        `font_colors=True`: the worker that ran a work item's tail also fills its blocks' colour fields (`colors.line_colors`
+        on that tail's stream, from the staged device pages and the item's `mask_refined`) before the item is returned; not
+        with `lazy=True` (ValueError): a consumer of `BlockList`s calls `font_colors(pages, results, apply=False)` and
+        reads the columns.  Off by default: no device work, no allocation.
         This generator IS what `bench.py`'s headline times (its `Pipeline` only feeds it batches and counts the results).
         The pools stay alive between calls (`close()` stops them): each worker thread keeps a native tail object with a
         HIP stream and ~250 MB of device tables at 32 pages per batch."""
+        if font_colors and lazy:
+            raise ValueError("font_colors=True fills TextBlock objects: not with lazy=True (use font_colors(..., apply=False))")
         if int(workers) <= 0:
             tb = thread_budget()
             workers = tb["tail_workers"]
@@ -418,12 +444,15 @@ class TextDetector:
                     st.wait_stream(main)                  # pages the caller produced on its stream
                     with torch.cuda.stream(st):
                         job = self._forward(batch, net)
-                if line_batches is None:
+                if line_batches is None and not font_colors:
                     pending.append([pool.submit(self._tail, job, refine_mode, keep_undetected_mask, lo, hi, records, lazy)
+                                    for lo, hi in self._split(len(job["metas"]), tail_split)])
+                elif line_batches is None:
+                    pending.append([pool.submit(self._tail_colors, job, refine_mode, keep_undetected_mask, lo, hi, records)
                                     for lo, hi in self._split(len(job["metas"]), tail_split)])
                 else:
                     pending.append([pool.submit(self._tail_batches, job, refine_mode, keep_undetected_mask, lo, hi, records,
-                                                lazy, dict(line_batches))
+                                                lazy, dict(line_batches), font_colors)
                                     for lo, hi in self._split(len(job["metas"]), tail_split)])
                 while len(pending) >= depth:
                     yield collect(pending.popleft())
@@ -509,6 +538,25 @@ class TextDetector:
             pages, ev = self._stage(pages)
             torch.cuda.current_stream(dev).wait_event(ev)
         return regions.line_batches(pages, blk_lists, device=dev, **kw)
+
+    def font_colors(self, pages: Sequence[Page], results, apply: bool = True):
+        """Fill and surround colour of every text line of a detected batch in one kernel launch on the detector's device
+        (`colors.line_colors`; returns its `LineColors`).  `results`: what `detect_batch` / `detect_stream` returned for
+        `pages` -- (mask, mask_refined, blk_list) triples; the masks are their `mask_refined`.  `apply=True` also stores the
+        per-block pooled colours in the blocks (`LineColors.apply`); `apply=False` leaves them alone (and builds no
+        `TextBlock` of a `BlockList`).  Host pages are uploaded through the pinned staging ring (`_stage`)."""
+        from . import colors
+        masks = [r[1] for r in results]
+        blk_lists = [r[2] for r in results]
+        dev = self.net.device
+        if not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
+                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
+            pages, ev = self._stage(pages)
+            torch.cuda.current_stream(dev).wait_event(ev)
+        lc = colors.line_colors(pages, masks, blk_lists, device=dev)
+        if apply:
+            lc.apply(blk_lists)
+        return lc
 
     def __call__(self, img: np.ndarray, refine_mode=REFINEMASK_INPAINT, keep_undetected_mask=False):
         return self.detect_batch([img], refine_mode, keep_undetected_mask)[0]

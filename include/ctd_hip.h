@@ -349,6 +349,73 @@ int ctd_warp_region_batches(const ctd_region_batch_job* jobs_dev, int32_t n, con
                             const void* tables_dev, void* out_dev, int32_t dtype, int32_t layout, int32_t reverse,
                             int32_t pad, void* stream);
 
+/* ---- font colours: fill and surround colour of every text line (added within ABI v10) ------------ */
+
+/* An addition to ABI v10: one new entry point and two new structs, nothing existing changes, so CTD_ABI_VERSION stays (a
+ * caller built against the earlier v10 header keeps working; one that needs the entry point looks the symbol up).
+ * What colour a text line is and what it stands on, from the page, a text mask (normally the page's `mask_refined`, either
+ * refine mode) and the line's quad.  Integers only: a row of the result is a function of (page, mask, quad) to the bit.
+ * The reference has no such code: its OCR models fill `TextBlock.fg_* / bg_*` line by line; this is this library's own
+ * rule.  Per line:
+ *   INSIDE  pixel (x, y) with 0 <= x < W, 0 <= y < H inside the quad's bounding box for which the four cross products
+ *           (p[k+1] - p[k]) x ((x, y) - p[k]), k = 0..3 (p[4] = p[0]), in int64, are all >= 0 or all <= 0: either winding,
+ *           edges included, a degenerate quad selects what the formula selects.
+ *   GREY    g = (B*3735 + G*19235 + R*9798 + 16384) >> 15 (the grey of csrc/kernels_tail.hip).
+ *   PASS 1  over the inside pixels, ON = mask != 0, OFF = mask == 0: n_on, n_off, g_on = sum of g over ON, g_off over OFF.
+ *   PASS 2  a pixel is TEXT-LIKE when its grey is strictly nearer to the ON mean than to the OFF mean, exactly:
+ *           |g n_on - g_on| n_off < |g n_off - g_off| n_on (= one integer threshold per line: 2 g n_on n_off above, or below,
+ *           g_on n_off + g_off n_on).  Fill: n_fg, s_fg[3] over ON and text-like pixels.  Surround: n_bg, s_bg[3] over inside
+ *           pixels that are NOT text-like, ON or OFF.  OFF pixels that are text-like count for neither.
+ *   COLOURS fg[c] = (2 s_fg[c] + n_fg) / (2 n_fg), bg likewise (integer division), c in page channel order.
+ * A dilated mask covers text plus a ring of background: the ON mean then lies between the two greys, text lies beyond it
+ * and is text-like, the ring is not; on a page of two flat colours fg and bg are exactly those colours.  Text whose grey
+ * equals its background's (isoluminant) ends in CTD_COLOR_NO_CONTRAST.  "Surround" is the colour around the glyphs; it is
+ * an outline colour only where the text has an outline.
+ * status:
+ *   CTD_COLOR_OK
+ *   CTD_COLOR_EMPTY        no inside pixel; the whole row is 0
+ *   CTD_COLOR_NO_MASK      n_on == 0: n_on, n_off, g_on, g_off as counted, everything else 0
+ *   CTD_COLOR_NO_CONTRAST  n_off == 0 or g_on n_off == g_off n_on (the means tie): fill = mean of the ON pixels (n_fg = n_on),
+ *                          surround = mean of the OFF pixels (n_bg = n_off), or the fill where there are none
+ *   CTD_COLOR_TOO_LARGE    the bounding box clipped to the page holds more than CTD_COLOR_MAX_PIXELS (2^24) pixels, or a
+ *                          coordinate of the quad lies beyond +-CTD_COLOR_MAX_COORD (2^29); decided from the quad, H and W
+ *                          before any pixel is read; the rest of the row is 0.  The two bounds are what keeps every
+ *                          product above inside int64 (sums <= 255 * 2^24 < 2^32, counts <= 2^24, their products < 2^57;
+ *                          edge vectors < 2^30, point offsets < 2^31) and every per-thread partial sum inside uint32. */
+#define CTD_COLOR_OK 0
+#define CTD_COLOR_EMPTY 1
+#define CTD_COLOR_NO_MASK 2
+#define CTD_COLOR_NO_CONTRAST 3
+#define CTD_COLOR_TOO_LARGE 4
+#define CTD_COLOR_MAX_PIXELS (1 << 24)
+#define CTD_COLOR_MAX_COORD (1 << 29)
+
+/* One line of a ctd_line_colors launch (a row of the device job table). */
+typedef struct ctd_color_job {
+  const uint8_t* page_dev; /* the page: BGR u8, 3 interleaved channels, rows `pitch` bytes apart            */
+  const uint8_t* mask_dev; /* the mask: u8, rows `mask_pitch` bytes apart                                   */
+  int32_t H, W;            /* size of page and mask, >= 1                                                   */
+  int32_t pitch;           /* >= 3 W                                                                        */
+  int32_t mask_pitch;      /* >= W                                                                          */
+  int32_t quad[8];         /* the line's four points (x, y) in the order the detector emits them            */
+} ctd_color_job;
+
+/* One row of the result. */
+typedef struct ctd_line_color {
+  int64_t n_fg, s_fg[3]; /* fill: pixels and per-channel sums (page channel order)                          */
+  int64_t n_bg, s_bg[3]; /* surround                                                                        */
+  int64_t g_on, g_off;   /* grey sums of pass 1                                                             */
+  int32_t n_on, n_off;
+  int32_t status;        /* CTD_COLOR_*                                                                     */
+  uint8_t fg[3], bg[3];  /* the colours, page channel order                                                 */
+  uint8_t pad_[6];
+} ctd_line_color;
+
+/* The rule above for n lines in ONE launch (one block per line, no atomics; integer sums: the result does not depend on
+ * the order of addition); row i of out_dev is line i's.  Pages of any mix of sizes may share a launch.  n = 0 launches
+ * nothing. */
+int ctd_line_colors(const ctd_color_job* jobs_dev, int32_t n, ctd_line_color* out_dev, void* stream);
+
 /* ---- the detector tail ------------------------------------------------------ */
 
 /* Everything `TextDetector.__call__` does after `self.net(img_in)` (reference inference.py:148-178) for a
