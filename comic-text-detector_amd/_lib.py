@@ -28,6 +28,9 @@ REGION_U8, REGION_F16, REGION_F32 = 0, 1, 2
 LAYOUT_NCHW, LAYOUT_NHWC = 0, 1
 COLOR_OK, COLOR_EMPTY, COLOR_NO_MASK, COLOR_NO_CONTRAST, COLOR_TOO_LARGE = range(5)
 COLOR_MAX_PIXELS, COLOR_MAX_COORD = 1 << 24, 1 << 29
+ERASE_PLAIN, ERASE_TEXTURED, ERASE_NO_RING, ERASE_NO_MASK, ERASE_EMPTY, ERASE_TOO_LARGE = range(6)
+ERASE_MAX_PIXELS, ERASE_MAX_COORD, ERASE_MAX_GROW, ERASE_MAX_RING = 1 << 24, 1 << 29, 8, 16
+ERASE_TILE_W, ERASE_TILE_H = 64, 32
 
 
 class CtdTensor(C.Structure):
@@ -95,6 +98,27 @@ class CtdLineColor(C.Structure):
                 ("fg", C.c_uint8 * 3), ("bg", C.c_uint8 * 3), ("pad_", C.c_uint8 * 6)]
 
 
+class CtdEraseJob(C.Structure):
+    _fields_ = [("page", C.c_int32), ("xyxy", C.c_int32 * 4), ("pad_", C.c_int32 * 3)]
+
+
+class CtdErasePage(C.Structure):
+    _fields_ = [("page_dev", C.c_void_p), ("mask_dev", C.c_void_p), ("out_dev", C.c_void_p), ("rest_dev", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32), ("mask_pitch", C.c_int32), ("out_pitch", C.c_int32),
+                ("rest_pitch", C.c_int32), ("block0", C.c_int32), ("n_blocks", C.c_int32), ("tile0", C.c_int32),
+                ("pad_", C.c_int32)]
+
+
+class CtdEraseParams(C.Structure):
+    _fields_ = [("grow", C.c_int32), ("ring", C.c_int32), ("tol", C.c_int32), ("min_ring", C.c_int32), ("n_tiles", C.c_int32),
+                ("pad_", C.c_int32 * 3)]
+
+
+class CtdEraseRow(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_fill", C.c_int32), ("n_ring", C.c_int32), ("cnt", C.c_int32 * 3),
+                ("med", C.c_uint8 * 3), ("pad_", C.c_uint8 * 5)]
+
+
 # every symbol include/ctd_hip.h declares: (restype, argtypes)
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -124,6 +148,7 @@ SYMBOLS = {
     "ctd_warp_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp]),
     "ctd_warp_region_batches": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ctd_line_colors": (_i32, [_vp, _i32, _vp, _vp]),
+    "ctd_erase_text": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(CtdEraseParams), _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),
     "ctd_tail_destroy": (None, [_vp]),

@@ -1382,4 +1382,21 @@ int ctd_line_colors(const ctd_color_job* jobs_dev, int32_t n, ctd_line_color* ou
   return CTD_OK;
 }
 
+int ctd_erase_text(const ctd_erase_job* blocks_dev, int32_t n_blocks, const ctd_erase_page* pages_dev, int32_t n_pages,
+                   const ctd_erase_params* params, ctd_erase_row* rows_dev, void* stream) {
+  if (n_blocks < 0 || n_pages < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
+  const ctd_erase_params prm = *params;
+  if (prm.grow < 0 || prm.grow > CTD_ERASE_MAX_GROW || prm.ring < 1 || prm.ring > CTD_ERASE_MAX_RING || prm.tol < 0 ||
+      prm.tol > 255 || prm.min_ring < 1 || prm.n_tiles < 0)
+    return fail(CTD_ERR_INVALID, "erase: grow 0..8, ring 1..16, tol 0..255, min_ring >= 1, n_tiles >= 0");
+  if (n_blocks > 0 && n_pages == 0) return fail(CTD_ERR_INVALID, "blocks without pages");
+  if (n_pages == 0) return CTD_OK;
+  if (!pages_dev || (n_blocks > 0 && (!blocks_dev || !rows_dev))) return fail(CTD_ERR_INVALID, "null pointer");
+  if (n_blocks > 0) launch_erase_stats(blocks_dev, n_blocks, pages_dev, n_pages, prm, rows_dev, (hipStream_t)stream);
+  if (prm.n_tiles > 0) launch_erase_paint(blocks_dev, n_blocks, pages_dev, n_pages, prm, rows_dev, (hipStream_t)stream);
+  HIP_TRY(hipGetLastError());
+  return CTD_OK;
+}
+
 }  // extern "C"

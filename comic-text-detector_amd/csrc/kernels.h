@@ -176,5 +176,13 @@ void launch_region_batches(const ctd_region_batch_job* jobs, int n, const int* t
 // fill / surround colour of n text lines in one launch (ctd_line_colors), one block per line; n >= 1
 void launch_line_colors(const ctd_color_job* jobs, int n, ctd_line_color* out, hipStream_t st);
 
+// ---- kernels_erase.hip ----------------------------------------------------------
+// ctd_erase_text's two launches: the row of every block (one workgroup per block; n_blocks >= 1), then every byte of every
+// page's `out` and `rest` from the rows (one workgroup per page tile; prm.n_tiles >= 1, n_blocks >= 0)
+void launch_erase_stats(const ctd_erase_job* jobs, int n_blocks, const ctd_erase_page* pages, int n_pages,
+                        const ctd_erase_params& prm, ctd_erase_row* rows, hipStream_t st);
+void launch_erase_paint(const ctd_erase_job* jobs, int n_blocks, const ctd_erase_page* pages, int n_pages,
+                        const ctd_erase_params& prm, const ctd_erase_row* rows, hipStream_t st);
+
 // ---- mfma layout probe (selftest) -------------------------------------------
 void launch_mfma_probe(const half_t* a, const half_t* b, float* out, hipStream_t st);

@@ -558,5 +558,22 @@ class TextDetector:
             lc.apply(blk_lists)
         return lc
 
+    def erase_text(self, pages: Sequence[Page], results, **kw):
+        """The pages of a detected batch with the text on plain backgrounds erased, and the mask an inpainter still needs, on
+        the detector's device (`erase.erase_text` and its keywords `grow`, `ring`, `tol`, `min_ring`; returns its
+        `ErasedPages`).  `results`: what `detect_batch` / `detect_stream` returned for `pages` -- (mask, mask_refined,
+        blk_list) triples; the masks are their `mask_refined`.  Builds no `TextBlock` of a `BlockList`.  Host pages are
+        uploaded through the pinned staging ring (`_stage`)."""
+        from . import erase
+        masks = [r[1] for r in results]
+        blk_lists = [r[2] for r in results]
+        erase.check_params(*(kw.get(k, d) for k, d in (("grow", 2), ("ring", 4), ("tol", 12), ("min_ring", 16))))
+        dev = self.net.device
+        if len(pages) and not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
+                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
+            pages, ev = self._stage(pages)
+            torch.cuda.current_stream(dev).wait_event(ev)
+        return erase.erase_text(pages, masks, blk_lists, device=dev, **kw)
+
     def __call__(self, img: np.ndarray, refine_mode=REFINEMASK_INPAINT, keep_undetected_mask=False):
         return self.detect_batch([img], refine_mode, keep_undetected_mask)[0]

@@ -416,6 +416,107 @@ typedef struct ctd_line_color {
  * nothing. */
 int ctd_line_colors(const ctd_color_job* jobs_dev, int32_t n, ctd_line_color* out_dev, void* stream);
 
+/* ---- erase text on plain backgrounds: cleaned pages and the mask an inpainter still needs (added within ABI v10) ---- */
+
+/* An addition to ABI v10 like the font colours above: one entry point, four structs, nothing existing changes.
+ * Most text of a comic page sits on a flat balloon.  Such text needs no inpainting network: look at the background next to
+ * the glyphs, and where it is one colour, fill the text with that colour; only the other blocks go to the inpainter.  The
+ * reference stops at the mask for that step (`refine_mask(..., REFINEMASK_INPAINT)`); the decision and the fill are this
+ * library's own rule, integers only (counts, comparisons, copies: nothing depends on the order of an addition), restated
+ * in numpy in tests/erase_ref.py.
+ * Per page: the page (BGR u8, H x W x 3, any row pitch), a text mask (u8, H x W, any pitch; a pixel is text where the mask
+ * is not 0; normally `mask_refined`, either refine mode) and the page's blocks in blk_list order, each with its `xyxy`.
+ * Parameters (ctd_erase_params): grow g (0 .. 8, default 2), ring r (1 .. 16, default 4), tol (0 .. 255, default 12),
+ * min_ring (>= 1, default 16).
+ * All sets are clipped to the page:
+ *   M       the text pixels of the page.
+ *   D_k(S)  the pixels of the page within Chebyshev distance <= k of some pixel of S: a (2k+1)^2 square dilation;
+ *           D_0(S) = S.
+ *   X_b     the box x1 <= x < x2, y1 <= y < y2 of block b's xyxy, clipped to the page (the reference's own slicing).
+ *   T_b     = M & X_b, the block's own text.
+ *   F_b     = D_g(T_b), what is filled for block b.
+ *   R_b     = D_{g+r}(T_b) \ D_g(M), the ring: near this block's text and not near anybody's text.
+ * Decision per block: h_c = the 256-bin histogram of page channel c over R_b (c = 0, 1, 2), n_ring = |R_b|,
+ *   med_c   = the smallest v with 2 * sum_{u <= v} h_c[u] >= n_ring (the lower median; 0 where n_ring = 0),
+ *   cnt_c   = sum of h_c[u] over |u - med_c| <= tol,
+ *   PLAIN   iff n_ring >= min_ring and 16 * min_c(cnt_c) >= 15 * n_ring.
+ * status, the first that applies:
+ *   CTD_ERASE_TOO_LARGE  a coordinate of xyxy lies beyond +-CTD_ERASE_MAX_COORD (2^29)
+ *   CTD_ERASE_EMPTY      X_b is empty
+ *   CTD_ERASE_TOO_LARGE  X_b (w x h pixels) grown by g + r, (w + 2 (g + r)) (h + 2 (g + r)), holds more than
+ *                        CTD_ERASE_MAX_PIXELS (2^24) pixels.  EMPTY and TOO_LARGE are decided before any pixel is read,
+ *                        every other field of the row is 0, and the block neither paints nor adds to `rest`.
+ *   CTD_ERASE_NO_MASK    T_b is empty (n_fill = n_ring = 0, cnt = med = 0)
+ *   CTD_ERASE_NO_RING    n_ring < min_ring
+ *   CTD_ERASE_TEXTURED   the histogram test failed
+ *   CTD_ERASE_PLAIN
+ * Row per block: status, n_fill = |F_b|, n_ring, cnt[3], med[3] (page channel order), pad bytes 0.
+ * Outputs per page:
+ *   out  (H x W x 3)  out[p] = med of the PLAIN block with the HIGHEST index on that page among those with p in F_b;
+ *                     page[p] where there is none.
+ *   rest (H x W)      0 where p was painted; otherwise 255 where mask[p] != 0 or p in F_b of a TEXTURED or NO_RING block;
+ *                     otherwise 0.
+ * Limits: a balloon with a gradient is TEXTURED; text that touches the balloon's outline puts outline pixels into the
+ * ring (the 1/16 allowance is for them); a block whose ring is swallowed by its neighbours' text is NO_RING. */
+#define CTD_ERASE_PLAIN 0
+#define CTD_ERASE_TEXTURED 1
+#define CTD_ERASE_NO_RING 2
+#define CTD_ERASE_NO_MASK 3
+#define CTD_ERASE_EMPTY 4
+#define CTD_ERASE_TOO_LARGE 5
+#define CTD_ERASE_MAX_PIXELS (1 << 24)
+#define CTD_ERASE_MAX_COORD (1 << 29)
+#define CTD_ERASE_MAX_GROW 8
+#define CTD_ERASE_MAX_RING 16
+#define CTD_ERASE_TILE_W 64 /* the paint launch's page tiles */
+#define CTD_ERASE_TILE_H 32
+
+/* One block of a ctd_erase_text call (a row of the device job table).  The blocks of one page are consecutive rows, in
+ * blk_list order: "index" in the rule above is the row number. */
+typedef struct ctd_erase_job {
+  int32_t page;    /* row of the page table */
+  int32_t xyxy[4]; /* x1, y1, x2, y2 */
+  int32_t pad_[3];
+} ctd_erase_job;
+
+/* One page of a ctd_erase_text call (a row of the device page table). */
+typedef struct ctd_erase_page {
+  const uint8_t* page_dev; /* BGR u8, rows `pitch` bytes apart                                              */
+  const uint8_t* mask_dev; /* u8, rows `mask_pitch` bytes apart                                             */
+  uint8_t* out_dev;        /* H x W x 3, rows `out_pitch` bytes apart; overlaps no input                    */
+  uint8_t* rest_dev;       /* H x W, rows `rest_pitch` bytes apart; overlaps no input                       */
+  int32_t H, W;            /* >= 1                                                                          */
+  int32_t pitch, mask_pitch, out_pitch, rest_pitch; /* >= 3 W, W, 3 W, W                                    */
+  int32_t block0, n_blocks; /* the page's rows of the job table                                             */
+  int32_t tile0;           /* paint tiles of the pages before this one: each page has ceil(W / CTD_ERASE_TILE_W) *
+                              ceil(H / CTD_ERASE_TILE_H)                                                    */
+  int32_t pad_;
+} ctd_erase_page;
+
+typedef struct ctd_erase_params {
+  int32_t grow, ring, tol, min_ring;
+  int32_t n_tiles; /* paint tiles of all pages (tile0 of a page after the last) */
+  int32_t pad_[3];
+} ctd_erase_params;
+
+/* One row of the result. */
+typedef struct ctd_erase_row {
+  int32_t status; /* CTD_ERASE_* */
+  int32_t n_fill, n_ring;
+  int32_t cnt[3];
+  uint8_t med[3];
+  uint8_t pad_[5];
+} ctd_erase_row;
+
+/* The rule above for all blocks of all pages of a batch in TWO launches on `stream` with no host wait between them,
+ * whatever the number of pages and blocks: the stats launch (one workgroup per block) writes rows_dev[i] for job i, the
+ * paint launch (one workgroup per page tile) reads them and writes every byte of every page's `out` and `rest` exactly
+ * once.  `params` is read on the host during the call.  n_blocks = 0: the pages are copied and rest = 255 (mask != 0) (one
+ * launch); n_pages = 0 launches nothing.  A parameter outside its bounds, a negative count, blocks without pages or a
+ * missing table is an error rc and launches nothing. */
+int ctd_erase_text(const ctd_erase_job* blocks_dev, int32_t n_blocks, const ctd_erase_page* pages_dev, int32_t n_pages,
+                   const ctd_erase_params* params, ctd_erase_row* rows_dev, void* stream);
+
 /* ---- the detector tail ------------------------------------------------------ */
 
 /* Everything `TextDetector.__call__` does after `self.net(img_in)` (reference inference.py:148-178) for a
