@@ -169,6 +169,7 @@ SYMBOLS = {
     "ctd_tail_set_trace": (_i32, [_vp, _i32]),
     "ctd_tail_trace_counts": (_i32, [_vp, C.POINTER(_i32), C.POINTER(_i32)]),
     "ctd_tail_trace_windows": (_i32, [_vp, _vp]),
+    "ctd_tail_trace_lds_launches": (_i32, [_vp, C.POINTER(_i32), _vp]),
     "ctd_tail_trace_db_sizes": (_i32, [_vp, _i32, C.POINTER(_i32), C.POINTER(_i32)]),
     "ctd_tail_trace_db_fetch": (_i32, [_vp, _i32, _vp, _vp]),
     "ctd_db_boxes_compact": (_i32, [_i32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

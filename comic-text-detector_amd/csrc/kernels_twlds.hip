@@ -27,9 +27,24 @@
 // with more runs than `rcap` raises the window's overflow flag and commits nothing: the host sends that window through the
 // canvas path (tail.hip), as it does up front for windows whose planes do not fit.
 //
-// tests/twlds_emul.py is this file word for word in Python, checked against the oracle's pixel-level merge_mask_list
-// (tests/test_twlds_emul.py, CPU); tests/test_gpu_e2e.py compares the kernel itself with the oracle and with the canvas
-// path byte for byte.
+// Tests.  tests/twlds_emul.py is this file word for word in Python, checked against the oracle's pixel-level
+// merge_mask_list (tests/test_twlds_emul.py, CPU).  On the GPU, all byte for byte against the oracle:
+//   tests/test_gpu_e2e.py      the kernel against the canvas path and the forced-overflow path; a seeded stress
+//   tests/test_gpu_tail_trace.py, with the launch log of the tail's trace (ctd_tail_trace_lds_launches: what
+//   launch_tw_lds used per launch -- windows, max_words, rcap, threads, LDS bytes) compared with a plain restatement of
+//   the host's sizing (tests/tail_trace_cases.py `lds_launches`):
+//     test_block_size_case_at_every_block_size   blockDim = 256 / 512 / 1024 on windows of 255 .. 1 026 words on both
+//         sides of each block size (wp = 1, wp = 3, wp = 257 > 256, 1 x 1, 33 x 2, 2 080 words), both refine modes:
+//         18 windows per call, all in LDS, in two launches: (17 windows, 1 026 words, rcap 2 565, 34 964 bytes) and
+//         (1 window, 2 080 words, rcap 5 200, 70 800 bytes)
+//     test_width_classes_and_mixed_windows_at_every_block_size, test_block_size_key_is_clamped_to_256_512_1024
+//     test_launch_classes     cls0 / cls1 moved over 11 windows of 1 .. 4 515 words: 1, 2 or 3 launches per setting
+//         (defaults: 8 windows at 1 197 words / 2 at 2 080 / 1 at 4 515 = 153 588 bytes), a limit at a window's need and
+//         one byte below it
+//     test_run_capacity       0.1 / 2.5 / 16 / 100 runs per word: rcap 1 024 (floor) .. 62 400, windows moving to the
+//         canvases as the need grows (11 / 11 / 7 / 4 of 11 go to LDS), overflows exactly where the emulation's run
+//         count exceeds the launch's rcap (2 or 3 of the 11 at 0.1 per word), the 2 080-word window completing with
+//         rlay = 1 040 > rcap = 1 024, a speckle window of 624 words overflowing at rcap 1 024 and not at 1 560 / 9 984
 #include <algorithm>
 
 #include "kernels.h"
@@ -481,19 +496,21 @@ size_t tw_lds_bytes(int max_words, int rcap) {
 int tw_lds_rcap(int max_words) { return std::min(65000, std::max(1024, (int)((long long)max_words * g_tw_lds_runs_x10 / 10))); }
 
 bool launch_tw_lds(const TWin* wins, const TBand* bands, const int* order, int n, int max_words, int rcap, int dilate, int* ovf,
-                   hipStream_t st) {
+                   hipStream_t st, TwLdsLaunch* used) {
   if (n <= 0) return true;
   TLdsArgs a;
   a.wins = wins, a.bands = bands, a.order = order, a.dilate = dilate, a.max_words = max_words;
   a.rcap = std::min(rcap, 65000), a.rlay = std::max(a.rcap, (max_words + 1) / 2);
   a.ovf = ovf;
   const size_t bytes = tw_lds_bytes(max_words, a.rcap);
+  const int nt = g_tw_lds_threads >= 1024 ? 1024 : (g_tw_lds_threads >= 512 ? 512 : 256);
+  if (used) *used = TwLdsLaunch{n, max_words, a.rcap, nt, (int)bytes, 0};
   if (bytes > 48 * 1024 &&                                     // more dynamic LDS than the default limit: the kernel has to ask
       hipFuncSetAttribute((const void*)tw_lds_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes) != hipSuccess) {
     (void)hipGetLastError();
+    if (used) used->refused = 1;
     return false;                                              // the caller sends these windows through the canvas path
   }
-  const int nt = g_tw_lds_threads >= 1024 ? 1024 : (g_tw_lds_threads >= 512 ? 512 : 256);
   hipLaunchKernelGGL(tw_lds_kernel, dim3(n), dim3(nt), bytes, st, a);
   return true;
 }

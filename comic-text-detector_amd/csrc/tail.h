@@ -85,9 +85,13 @@ void launch_tw_commit(const TWin* wins, int n, int max_pix, const uint8_t* merge
 // labelling; ovf[window] = 1 where a labelling had more runs (nothing committed for that window)
 size_t tw_lds_bytes(int max_words, int rcap);
 int tw_lds_rcap(int max_words);
-// (false: the launch could not get its LDS -- nothing was enqueued)
+// what a launch_tw_lds call used, as clamped by the launcher (the tail's trace keeps these: ctd_tail_trace_lds_launches)
+struct TwLdsLaunch {
+  int n, max_words, rcap, threads, bytes, refused;
+};
+// (false: the launch could not get its LDS -- nothing was enqueued); `used`, if given, receives what the launch ran with
 bool launch_tw_lds(const TWin* wins, const TBand* bands, const int* order, int n, int max_words, int rcap, int dilate, int* ovf,
-                   hipStream_t st);
+                   hipStream_t st, TwLdsLaunch* used = nullptr);
 // mask[p] = 0 where refined[p] > thr (reference utils/textmask.py:136)
 void launch_mask_clear_where(uint8_t* mask, const uint8_t* refined, long long n, int thr, hipStream_t st);
 // dst (rows x cols, pitch dpitch) = src (pitch spitch): the crop of inference.py:164

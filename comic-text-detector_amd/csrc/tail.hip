@@ -287,6 +287,7 @@ struct ctd_tail {
   bool trace = false;
   std::vector<ctd_trace_win> tr_wins;
   std::vector<DbTrace> tr_db;
+  std::vector<TwLdsLaunch> tr_lds;     // one per launch_tw_lds call of the last run / refine, in launch order
 };
 
 namespace {
@@ -583,9 +584,11 @@ int refine_windows(ctd_tail* t, const std::vector<WinReq>& reqs, int refine_mode
       while (k1 < nl && (c == 2 || need(k1) <= cls[c])) ++k1;
       if (k1 > k0) {
         const int mw = words[lds_win[k1 - 1]];
+        TwLdsLaunch used{};
         if (!launch_tw_lds(dw, db, dl + k0, k1 - k0, mw, g_tail_lds_rcap > 0 ? g_tail_lds_rcap : tw_lds_rcap(mw),
-                           refine_mode == 0 ? 1 : 0, dl + n, st))
+                           refine_mode == 0 ? 1 : 0, dl + n, st, t->trace ? &used : nullptr))
           for (int k = k0; k < k1; ++k) refused.push_back(lds_win[k]);
+        if (t->trace) t->tr_lds.push_back(used);
       }
       k0 = k1;
     }
@@ -1075,7 +1078,7 @@ static int tail_run_impl(ctd_tail* t, int32_t B, int32_t Hn, int32_t Wn, const f
   const double t0 = now_ms();
   for (double& v : t->ms_stage) v = 0;
   t->n_lds = t->n_canvas = t->n_ovf = 0, t->ms_lds_wait = 0;
-  t->tr_wins.clear(), t->tr_db.clear();
+  t->tr_wins.clear(), t->tr_db.clear(), t->tr_lds.clear();
   if (ready_event) T_TRY(hipStreamWaitEvent(st, (hipEvent_t)ready_event, 0));
   if (int rc = layout_pages(t, B, pages)) return rc;
   for (int b = 0; b < B; ++b)
@@ -1300,7 +1303,7 @@ static int tail_refine_impl(ctd_tail* t, int32_t n_pages, const ctd_tail_page* p
     return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_refine: bad arguments");
   T_TRY(hipSetDevice(t->device));
   t->n_lds = t->n_canvas = t->n_ovf = 0, t->ms_lds_wait = 0;
-  t->tr_wins.clear();
+  t->tr_wins.clear(), t->tr_lds.clear();
   hipStream_t st = t->st;
   if (int rc = layout_pages(t, n_pages, pages)) return rc;
   GET(t->d_pmask, t->ptotal, uint8_t, pmask);
@@ -1405,6 +1408,7 @@ int ctd_tail_set_trace(ctd_tail* t, int32_t on) {
   t->trace = on != 0;
   std::vector<ctd_trace_win>().swap(t->tr_wins);          // (drops the storage too)
   std::vector<DbTrace>().swap(t->tr_db);
+  std::vector<TwLdsLaunch>().swap(t->tr_lds);
   return CTD_OK;
 }
 
@@ -1418,6 +1422,18 @@ int ctd_tail_trace_counts(const ctd_tail* t, int32_t* n_windows, int32_t* n_db_p
 int ctd_tail_trace_windows(const ctd_tail* t, ctd_trace_win* out) {
   if (!t || !out) return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_trace_windows: null argument");
   if (!t->tr_wins.empty()) std::memcpy(out, t->tr_wins.data(), t->tr_wins.size() * sizeof(ctd_trace_win));
+  return CTD_OK;
+}
+
+int ctd_tail_trace_lds_launches(const ctd_tail* t, int32_t* n_launches, int32_t* out6) {
+  if (!t || !n_launches) return ctd_fail_msg(CTD_ERR_INVALID, "ctd_tail_trace_lds_launches: null argument");
+  *n_launches = (int32_t)t->tr_lds.size();
+  if (out6)
+    for (size_t i = 0; i < t->tr_lds.size(); ++i) {
+      const TwLdsLaunch& l = t->tr_lds[i];
+      const int32_t v[6] = {l.n, l.max_words, l.rcap, l.threads, l.bytes, l.refused};
+      std::memcpy(out6 + 6 * i, v, sizeof(v));
+    }
   return CTD_OK;
 }
 

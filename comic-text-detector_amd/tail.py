@@ -47,6 +47,7 @@ TRACE_WIN_DTYPE = np.dtype([("page", "<i4"), ("x1", "<i4"), ("y1", "<i4"), ("w",
                             ("cand_dist", "<u8", (4,))])
 assert TRACE_WIN_DTYPE.itemsize == C.sizeof(L.CtdTraceWin) == 4312
 TRACE_PATHS = ("lds", "canvas", "overflow")        # ctd_trace_win.path
+TRACE_LDS_FIELDS = ("windows", "max_words", "rcap", "threads", "bytes", "refused")   # ctd_tail_trace_lds_launches
 
 
 _host_threads = None            # native threads per Tail for its per-page / per-window host loops (None: library default)
@@ -249,6 +250,17 @@ class Tail:
         if n.value:
             L.check(self._lib.ctd_tail_trace_windows(self._h, out.ctypes.data), "ctd_tail_trace_windows")
         return out
+
+    def trace_lds_launches(self) -> List[dict]:
+        """The launches of the window-local merge kernel in the last `run` / `refine`, in launch order, as the launcher
+        clamped them (`ctd_tail_trace_lds_launches`): `windows`, `max_words`, `rcap`, `threads`, `bytes` of dynamic LDS,
+        `refused` (the launch did not get its LDS; its windows took the canvases).  Empty while the trace is off."""
+        n = C.c_int32()
+        L.check(self._lib.ctd_tail_trace_lds_launches(self._h, C.byref(n), None), "ctd_tail_trace_lds_launches")
+        out = np.zeros((n.value, 6), np.int32)
+        if n.value:
+            L.check(self._lib.ctd_tail_trace_lds_launches(self._h, C.byref(n), out.ctypes.data), "ctd_tail_trace_lds_launches")
+        return [dict(zip(TRACE_LDS_FIELDS, (int(v) for v in row))) for row in out]
 
     def trace_db(self) -> List[dict]:
         """Per page of the last DB stage (`run`, `db_boxes`): the contour tables as `ctd_db_boxes_compact` received them,

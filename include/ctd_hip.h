@@ -645,6 +645,14 @@ typedef struct ctd_trace_win {
 int ctd_tail_trace_counts(const ctd_tail* t, int32_t* n_windows, int32_t* n_db_pages);
 int ctd_tail_trace_windows(const ctd_tail* t, ctd_trace_win* out); /* n_windows records */
 
+/* An addition within ABI v10 (one new entry point, nothing existing changes, so CTD_ABI_VERSION stays): the launches of the
+ * window-local merge kernel (one block per window on bit planes in LDS) in the refine stage of the last ctd_tail_run /
+ * ctd_tail_refine, in launch order, recorded while the trace is on.  *n_launches = their number; out6 (may be NULL: the
+ * count alone) receives per launch six values as the LAUNCHER used them, after its own clamping, not as the tuning keys
+ * said: [windows (= blocks), max_words (plane words of the LDS layout), rcap (runs a labelling may have), threads per block,
+ * dynamic LDS bytes, 1 if the launch was refused its LDS (nothing enqueued: its windows took the canvases) else 0]. */
+int ctd_tail_trace_lds_launches(const ctd_tail* t, int32_t* n_launches, int32_t* out6);
+
 /* The device-made contour tables of one page exactly as the host geometry (ctd_db_boxes_compact, below) received them.
  * hdr4 = [n_f, n_b, row-table entries used, overflow flag]; sizes3 = [nf, nb, nr] rows of the tables kept (all 0 on an
  * overflowed page, which takes the label-image path).  ctd_tail_trace_db_fetch fills

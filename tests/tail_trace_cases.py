@@ -300,6 +300,250 @@ def before_merge(recs):
     return [recs[k].tobytes() for k in recs.dtype.names if k != "path"]
 
 
+# ============================================================================= refine: the launch-shape keys of the merge stage
+# `tail_lds_threads`, `tail_lds_cls0 / cls1`, `tail_lds_runs_x10` (csrc/tuning.def): cases whose windows have word counts
+# chosen relative to the block sizes, and a plain restatement of how the host sizes and groups the launches of
+# `tw_lds_kernel` (csrc/tail.hip `refine_windows`, csrc/kernels_twlds.hip `tw_lds_rcap / tw_lds_bytes / launch_tw_lds`).
+
+BLOCK_SIZES = (256, 512, 1024)      # what `tail_lds_threads` clamps to
+LDS_KEYS = ("tail_lds", "tail_lds_rcap", "tail_lds_max_bytes", "tail_lds_runs_x10", "tail_lds_threads", "tail_lds_cls0", "tail_lds_cls1")
+
+
+@functools.lru_cache(None)
+def key_defaults():
+    """What the library holds for the keys of the merge stage's launches (csrc/tuning.def), read from the library."""
+    from conftest import pkg
+    L = pkg()._lib
+    return {k: L.tuning_get(k) for k in LDS_KEYS}
+
+
+def clamped_threads(value):
+    """What `launch_tw_lds` makes of `tail_lds_threads`."""
+    return 1024 if value >= 1024 else (512 if value >= 512 else 256)
+
+
+def words_of(w, h):
+    return ((w + 31) >> 5) * h
+
+
+def lds_rcap(words, runs_x10, rcap_key=0):
+    """Runs a labelling may have in a launch whose largest window has `words` plane words: `runs_x10` / 10 per word, at
+    least 1 024, at most 65 000 (a u16 prefix); `rcap_key` > 0 (`tail_lds_rcap`) replaces the rule, still clamped."""
+    return min(65000, rcap_key if rcap_key > 0 else max(1024, words * runs_x10 // 10))
+
+
+def lds_need(words, runs_x10, rcap_key=0):
+    """Bytes of dynamic LDS of a block laid out for `words` plane words: three planes, a u16 prefix per word (rounded up to
+    whole u32), parent + acc of `rlay` = max(rcap, ceil(words / 2)) entries (they double as the scratch plane), 20 words
+    of partials."""
+    rlay = max(lds_rcap(words, runs_x10, rcap_key), (words + 1) // 2)
+    return (3 * words + (words + 1) // 2 + 2 * rlay + 20) * 4
+
+
+def lds_launches(words_list, cls0, cls1, lds_max, runs_x10, rcap_key=0, lds=1):
+    """(indices of the windows that take the canvases up front, launches) for windows of `words_list` plane words: a window
+    goes to LDS if its need is at most `lds_max`; those, in ascending order of words (stable), are cut into up to three
+    launches -- need <= cls0, then need <= cls1, then the rest --, each laid out for its LARGEST window.  A launch is
+    (windows, max_words, rcap, bytes, [window indices])."""
+    need = [lds_need(w, runs_x10, rcap_key) for w in words_list]
+    canvas = [i for i, nd in enumerate(need) if not lds or nd > lds_max]
+    order = sorted((i for i, nd in enumerate(need) if lds and nd <= lds_max), key=lambda i: words_list[i])
+    launches, k0 = [], 0
+    for c, limit in enumerate((cls0, cls1, None)):
+        k1 = k0
+        while k1 < len(order) and (limit is None or need[order[k1]] <= limit):
+            k1 += 1
+        if k1 > k0:
+            mw = words_list[order[k1 - 1]]
+            launches.append((k1 - k0, mw, lds_rcap(mw, runs_x10, rcap_key), lds_need(mw, runs_x10, rcap_key), order[k0:k1]))
+        k0 = k1
+    return canvas, launches
+
+
+def case_words(case):
+    """Plane words of a case's windows in the order the native tail sees them (pass 0 only: no case here keeps undetected)."""
+    assert not case["keep"]
+    return [words_of(w, h) for img, boxes in zip(case["pages"], case["boxes"]) for _, _, w, h in windows_of(img.shape, boxes)]
+
+
+def stroke_page(im_w, im_h, seed, density):
+    """Text-like content: dark horizontal and vertical strokes and a few squares with a light hole on a light ground, light
+    on dark in the left half, mild noise; the mask is the ink grown by one pixel (holes covered) with 3 % of it knocked about.
+    Few runs per word -- the noisy kinds of `page_for_windows` have about 8 and overflow every run table."""
+    from scipy import ndimage
+    rng = np.random.RandomState(seed)
+    ink = np.zeros((im_h, im_w), bool)
+    hole = np.zeros((im_h, im_w), bool)
+    n = max(6, int(density * im_w * im_h / 450))
+    for k in range(n):
+        y, x = rng.randint(0, im_h), rng.randint(0, im_w)
+        if k % 5 in (0, 1):
+            ink[y: y + rng.randint(2, 4), x: x + rng.randint(3, 40)] = True              # horizontal strokes
+        elif k % 5 in (2, 3):
+            ink[y: y + rng.randint(3, 40), x: x + rng.randint(2, 4)] = True              # vertical strokes
+        else:
+            s = rng.randint(9, 14)
+            ink[y: y + s, x: x + s] = True                                               # a square with a hole
+            hole[y + 3: y + s - 3, x + 3: x + s - 3] = True
+    hole &= ndimage.binary_erosion(ink, np.ones((7, 7), bool))                           # holes stay inside their squares
+    page = np.full((im_h, im_w, 3), 215, np.uint8)
+    page[ink & ~hole] = 35
+    page = (page.astype(int) + rng.randint(-6, 7, page.shape)).clip(0, 255).astype(np.uint8)
+    page[:, : im_w // 2] = 255 - page[:, : im_w // 2]
+    mask = (ndimage.maximum_filter(ink.astype(np.uint8), size=3) * 210).astype(np.uint8)
+    knock = rng.rand(im_h, im_w) < 0.03
+    mask[knock] = rng.randint(0, 256, int(knock.sum()))
+    return np.ascontiguousarray(page), np.ascontiguousarray(mask)
+
+
+def _stroke_case(name, sheets, mode=0):
+    """A case from [(im_w, im_h, seed, stroke density, windows or ready-made boxes)]: stroke content everywhere."""
+    pages, masks, boxes = [], [], []
+    for im_w, im_h, seed, density, wins in sheets:
+        img, mask = stroke_page(im_w, im_h, seed, density)
+        pages.append(img), masks.append(mask)
+        boxes.append([w if len(w) == 5 else block_for_window(im_w, im_h, w) for w in wins])
+    for b in boxes:
+        for i, w in enumerate(b):
+            b[i] = list(w[:4])
+    return _case(name, pages, masks, boxes, mode=mode)
+
+
+# word counts of `block_size_case`, in window order (checked against `windows_of` in tests/test_tail_trace_cases.py)
+ONE_WORD_HEIGHTS = (255, 256, 257, 511, 512, 513, 1023, 1024, 1025)
+THREE_WORD_HEIGHTS = (85, 86, 171, 341, 342)                  # 255, 258, 513, 1 023, 1 026 words: blockDim is no multiple of wp = 3
+STRIP = (8193, 3)                                             # wp = 257 > 256: dy_t = 0 at 256 threads
+LARGE = (256, 260)                                            # 2 080 words > 2 048: at `tail_lds_runs_x10` = 1, rlay = 1 040 > rcap = 1 024
+
+
+def block_size_windows():
+    """[page][window] of `block_size_case`: a tall page of one- and three-word columns, the strip's own page, a page with
+    the large window next to a 1 x 1 and a 33 x 2 one.  (A tall window narrower than twice its padding -- about h / 32 --
+    exists only where a page edge cuts it: the 5- and 9-wide ones stand on the left and right edge.)"""
+    im_w, im_h = TALL_PAGE
+    H = ONE_WORD_HEIGHTS
+    tall = [(8, 0, 32, H[0]), (8, 258, 31, H[1]), (8, im_h - 1 - H[2], 17, H[2]), (43, 0, 32, H[3]), (43, im_h - 1 - H[4], 25, H[4]),
+            (78, 0, 30, H[5]), (im_w - 1 - 9, 0, 9, H[6]), (113, 0, 32, H[7]), (0, 0, 5, H[8])]
+    three = ((65, 85), (96, 86), (70, 171), (95, 341), (81, 342))
+    y = 0
+    for w, h in three[:3]:
+        tall.append((148, y, w, h))
+        y += h + 3
+    tall.append((247, 0, *three[3]))
+    tall.append((247, 345, *three[4]))
+    small = [(20, 12, *LARGE), (7, 5, 1, 1), (100, SMALL_PAGE[1] - 1 - 2, 33, 2)]
+    return [tall, [(0, 0, *STRIP)], small]
+
+
+SMALL_DENSITY = 0.4       # the large window's labellings stay under 1 024 runs: it completes at `tail_lds_runs_x10` = 1
+TALL_PAGE, STRIP_PAGE, SMALL_PAGE = (360, 1030), (STRIP[0] + 1, STRIP[1] + 1), (300, 300)
+
+
+@functools.lru_cache(None)
+def block_size_case():
+    """One call whose windows have word counts on both sides of each block size of `tw_lds_kernel` (`tail_lds_threads`)."""
+    tall, strip, small = block_size_windows()
+    # the strip reaches the page's four edges: a block one row high, whose padding (128) overshoots them all
+    strip_box = [10, 1, STRIP[0] - 10, 2, "box"]
+    assert windows_of((STRIP_PAGE[1], STRIP_PAGE[0]), [strip_box[:4]]) == strip
+    return _stroke_case("block sizes: word counts around 256 / 512 / 1 024", [(*TALL_PAGE, 80, 1.0, tall), (*STRIP_PAGE, 81, 1.0, [strip_box]),
+                                                                               (*SMALL_PAGE, 82, SMALL_DENSITY, small)])
+
+
+@functools.lru_cache(None)
+def large_window_case():
+    """`block_size_case`'s large window alone (2 080 words)."""
+    return _stroke_case("the 256 x 260 window alone", [(*SMALL_PAGE, 82, SMALL_DENSITY, [(20, 12, *LARGE)])], mode=1)
+
+
+# (w, h) of `class_case`, in window order: 1 .. 4 515 words (the largest count whose need is within 150 KB, `tail_lds_max_bytes`), two of 600
+CLASS_SIZES = ((480, 301), (1, 1), (96, 200), (256, 260), (20, 40), (160, 120), (200, 171), (64, 50), (224, 186), (100, 100), (33, 2))
+CLASS_PAGE = (520, 640)
+
+
+def class_windows():
+    at = ((3, 0), (7, 5), (10, 20), (2, 310), (400, 8), (150, 40), (262, 310), (340, 200), (270, 450), (330, 60), (100, 640 - 1 - 2))
+    return [(x, y, w, h) for (x, y), (w, h) in zip(at, CLASS_SIZES)]
+
+
+@functools.lru_cache(None)
+def class_case():
+    """About ten windows from 1 x 1 to the largest the default LDS limit admits, unsorted, two of equal word counts."""
+    return _stroke_case("launch classes: 1 to 4 515 words", [(*CLASS_PAGE, 83, 1.0, class_windows())])
+
+
+def need_by_default(words):
+    k = key_defaults()
+    return lds_need(words, k["tail_lds_runs_x10"], k["tail_lds_rcap"])
+
+
+def class_settings():
+    """[(what, {tuning key: value})] for `class_case`: the limits of the first two launch classes moved so that windows
+    change launch, a limit exactly AT a window's need (it stays in the lower class) and one byte below (it moves up)."""
+    k = key_defaults()
+    n400, n600, n1197, n2080 = (need_by_default(w) for w in (400, 600, 1197, 2080))
+    return [("the defaults", {}),
+            ("one class", {"tail_lds_cls0": k["tail_lds_max_bytes"], "tail_lds_cls1": k["tail_lds_max_bytes"]}),
+            ("cls0 = 0", {"tail_lds_cls0": 0}),
+            ("cls1 < cls0", {"tail_lds_cls0": k["tail_lds_cls1"], "tail_lds_cls1": k["tail_lds_cls0"]}),
+            ("cls0 at the need of the 1 197-word window, cls1 at that of the 2 080-word one", {"tail_lds_cls0": n1197, "tail_lds_cls1": n2080}),
+            ("both one byte below", {"tail_lds_cls0": n1197 - 1, "tail_lds_cls1": n2080 - 1}),
+            ("the two 600-word windows a launch of their own", {"tail_lds_cls0": n400, "tail_lds_cls1": n600}),
+            ("the 1 x 1 window alone, then all but the largest", {"tail_lds_cls0": need_by_default(1), "tail_lds_cls1": n2080})]
+
+
+def launches_of_setting(words_list, tune=()):
+    """`lds_launches` under the library's defaults with `tune` = {key: value} on top."""
+    k = {**key_defaults(), **dict(tune)}
+    return lds_launches(words_list, k["tail_lds_cls0"], k["tail_lds_cls1"], k["tail_lds_max_bytes"], k["tail_lds_runs_x10"],
+                        k["tail_lds_rcap"], k["tail_lds"])
+
+
+def compare_launches(got, want):
+    """`Tail.trace_lds_launches()` (plus the threads every launch must show) against (launches of `lds_launches`, threads)."""
+    launches, threads = want
+    mine = [(g["windows"], g["max_words"], g["rcap"], g["bytes"], g["threads"], g["refused"]) for g in got]
+    assert mine == [(n, mw, rc, by, threads, 0) for n, mw, rc, by, _ in launches], f"launches {mine} vs {[l[:4] for l in launches]} at {threads} threads"
+
+
+@functools.lru_cache(None)
+def merge_stats(case_fn):
+    """Per window of a case, from tests/twlds_emul.py on the oracle's own candidates: `words`; `runs` = (most runs of a
+    candidate after the small-component rule, runs of the complement hole filling labels in mode 0, in mode 1);
+    `accepted` = pixels the merge rounds set; `filled` = pixels hole filling added, both modes together."""
+    import twlds_emul as E
+    case = case_fn()
+    out = []
+    for img, mask, boxes in zip(case["pages"], case["masks"], case["boxes"]):
+        for x1, y1, w, h in windows_of(img.shape, boxes):
+            im = np.ascontiguousarray(img[y1: y1 + h, x1: x1 + w])
+            msk = np.ascontiguousarray(mask[y1: y1 + h, x1: x1 + w])
+            ml = R.get_topk_masklist(im, msk) + R.get_otsuthresh_masklist(im, msk)
+            ml.sort(key=lambda c: c[1])
+            win = E.Win(h, w)
+            pred = E.pred_plane(win, msk)
+            merged = [[0] * win.wp for _ in range(h)]
+            runs = [max(E.accept_round(win, E.to_plane(c > 0), pred, merged) for c, _ in ml)]
+            accepted = sum(E.popc(v) for row in merged for v in row)
+            filled = 0
+            for mode in (0, 1):
+                m = E.dilate(win, merged) if mode == 0 else [row[:] for row in merged]
+                before = sum(E.popc(v) for row in m for v in row)
+                runs.append(E.fill_holes(win, pred, m))
+                filled += sum(E.popc(v) for row in m for v in row) - before
+            out.append(dict(words=words_of(w, h), runs=tuple(runs), accepted=accepted, filled=filled))
+    return out
+
+
+def expected_paths(case_fn, mode, tune=()):
+    """`Tail.refine_paths()` of a case in one refine mode from the restatement and the emulation's run counts: a window
+    overflows iff a candidate's labelling, or the complement's, has more runs than its LAUNCH's rcap."""
+    st = merge_stats(case_fn)
+    canvas, launches = launches_of_setting([s["words"] for s in st], tune)
+    over = sum(max(st[i]["runs"][0], st[i]["runs"][1 + mode]) > rcap for _, _, rcap, _, idx in launches for i in idx)
+    return {"lds": len(st) - len(canvas) - over, "canvas": len(canvas) + over, "overflow": over}
+
+
 # ---- what the wrong kernels the issue measured would write (the CPU test: the cases tell them from the right one) -----------
 
 def hist_with(img, msk, mode):

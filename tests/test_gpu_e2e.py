@@ -313,6 +313,52 @@ def test_detect_stream_equals_detect_batch():
                 blocks_equal(bl, bl1)
 
 
+@pytest.mark.parametrize("lds", [1, 0])
+def test_detect_stream_equals_detect_batch_under_every_tail_chain(lds):
+    """`tail_chain` = 0 / 1 / 2 (stage 1 of concurrent work items side by side / one after the other on the GPU / the refine
+    stage's big enqueue too): three workers on four work items per batch return what detect_batch returns.  Once more with
+    every window through the canvases (`tail_lds` = 0), where `refine_canvas`' chained section at 2 is what runs."""
+    size = 256
+    p = pkg()
+    det = detector(size)
+    batches = [[p.synth.text_like_page((size, size), 30 + 3 * k + j, n_blocks=4) for j in range(3)] for k in range(3)]
+    want = [det.detect_batch(b) for b in batches]
+    assert sum(len(bl) for wb in want for _, _, bl in wb) >= 9 and any((r > 0).any() for wb in want for _, r, _ in wb)
+    list(det.detect_stream(batches[:1], workers=3, depth=3, tail_split=4))       # (the pool of three workers and their tails exist)
+    tails = p.tail.live_tails()
+    for chain in (0, 1, 2):
+        with p._lib.tuning(tail_chain=chain, tail_lds=lds):
+            got = list(det.detect_stream(batches, workers=3, depth=3, tail_split=4))
+        assert len(got) == len(want)
+        for gb, wb in zip(got, want):
+            for (m, r, bl), (m1, r1, bl1) in zip(gb, wb):
+                np.testing.assert_array_equal(m, m1, err_msg=f"tail_chain = {chain}")
+                np.testing.assert_array_equal(r, r1, err_msg=f"tail_chain = {chain}")
+                blocks_equal(bl, bl1)
+    assert p.tail.live_tails() == tails
+
+
+@pytest.mark.parametrize("priority", [0, 1, 2])
+def test_tail_created_under_every_stream_priority_refines_exactly(priority):
+    """`tail_priority` = 0 / 1 / 2 (highest / the device's default / lowest, read when a tail is created): a tail object
+    created under the key runs the call of big, tiny, overlapping and repeated windows exactly as the oracle has it."""
+    import tail_trace_cases as T
+    from test_gpu_sweeps import report
+    from test_gpu_tail_trace import check_call, traced_refine
+    p = pkg()
+    start = p.tail.live_tails()
+    with p._lib.tuning(tail_priority=priority):
+        tail = p.tail.Tail(torch.device("cuda", torch.cuda.current_device()))
+    try:
+        case = T.refine_cases()[2]
+        n, bad = check_call(case, traced_refine(case, tail=tail), f" [tail_priority = {priority}]")
+    finally:
+        tail.__del__()
+        del tail
+    assert p.tail.live_tails() == start
+    report(f"refine on a tail of priority {priority}", n, bad)
+
+
 def test_model2annotations_batch_driver_writes_the_reference_files(tmp_path):
     """`model2annotations` (batched detect + threaded decode / write) leaves exactly the files the
     reference's loop writes (inference.py:19-70), with the contents of single-page detector calls."""

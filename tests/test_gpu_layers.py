@@ -520,13 +520,23 @@ NOT_DISPATCH_KEYS = {
     "split_halo_min_patches": "threshold; the default is crossed by u8_2x1024x1024, forced to 1 in the native selftest",
     "fwd_prio": "wave priority of the network's kernels: same kernels, same arithmetic",
     "no_reuse": "arena layout only: every activation stays readable (what the float64 checks run under)",
-    "tail_max_blocks": "tail: grid cap", "tail_chain": "tail: ordering of stage 1 across work items",
+    "tail_max_blocks": "tail: grid cap",
+    "tail_chain": "tests/test_gpu_e2e.py::test_detect_stream_equals_detect_batch_under_every_tail_chain (0, 1, 2; with and without tail_lds)",
     "tail_fused_rounds": "tail: launches per round", "tail_fused_max_pix": "tail: threshold of tail_fused_rounds",
     "tail_lds": "tail: LDS variant of the window kernels (tests/test_gpu_sweeps.py)", "tail_lds_rcap": "tail: LDS run capacity",
-    "tail_lds_max_bytes": "tail: LDS threshold", "tail_lds_runs_x10": "tail: LDS sizing", "tail_lds_threads": "tail: block size",
-    "tail_lds_cls0": "tail: LDS size class", "tail_lds_cls1": "tail: LDS size class", "tail_dma_min": "tail: copy-engine threshold",
+    "tail_lds_max_bytes": "tail: LDS threshold",
+    "tail_lds_runs_x10": "tests/test_gpu_tail_trace.py::test_run_capacity (1, 25, 160, 1000: logged rcap, routing, overflows)",
+    "tail_lds_threads": "tests/test_gpu_tail_trace.py::test_block_size_case_at_every_block_size (256, 512, 1024; the clamp in "
+                        "::test_block_size_key_is_clamped_to_256_512_1024)",
+    "tail_lds_cls0": "tests/test_gpu_tail_trace.py::test_launch_classes (the launch log under every setting of class_settings)",
+    "tail_lds_cls1": "tests/test_gpu_tail_trace.py::test_launch_classes (the launch log under every setting of class_settings)",
+    "tail_dma_min": "tail: copy-engine threshold",
     "tail_skip_page_download": "tail: measurement knob, not in the shipped library", "tail_ablate": "tail: measurement knob, not in the shipped library",
-    "tail_priority": "tail: stream priority", "tail_cus": "tail: CU mask experiment", "tail_cu_first": "tail: CU mask experiment",
+    "tail_priority": "tests/test_gpu_e2e.py::test_tail_created_under_every_stream_priority_refines_exactly (0, 1, 2)",
+    # untested on purpose: CU-masked streams are an experiment of `bench.py --cu-split`; this suite creates none (the GPUs it runs
+    # on are shared)
+    "tail_cus": "tail: CU mask experiment, not exercised (no CU-masked streams in the suite)",
+    "tail_cu_first": "tail: CU mask experiment, not exercised (no CU-masked streams in the suite)",
 }
 
 

@@ -293,6 +293,8 @@ def tuning_keys_in_the_sources():
 def test_every_tuning_key_is_in_the_ledger(monkeypatch):
     """A key of ctd_tuning_set is either a dispatch key with the kernels that prove each value (checked on the GPU by
     tests/test_gpu_layers.py) or is listed as knowingly not one, with the reason: a new key needs a decision."""
+    import os
+    import re
     import test_gpu_layers as G
     keys = tuning_keys_in_the_sources()
     assert len(keys) == len(set(keys)) and len(keys) > 30 and {"fuse", "halo_pair", "halo3", "c3b_cfg64"} <= set(keys)
@@ -304,6 +306,13 @@ def test_every_tuning_key_is_in_the_ledger(monkeypatch):
     assert not dispatch & set(G.NOT_DISPATCH_KEYS)
     assert not (dispatch | set(G.NOT_DISPATCH_KEYS)) - set(keys), "the ledger names a key the library does not parse"
     assert all(reason for reason in G.NOT_DISPATCH_KEYS.values())
+    # a reason that names the test exercising the key's values names one that exists
+    tests = os.path.dirname(os.path.abspath(__file__))
+    named = [m for reason in G.NOT_DISPATCH_KEYS.values() for m in re.findall(r"tests/(test_\w+\.py)::(test_\w+)", reason)]
+    assert len(named) >= 6
+    for mod, fn in named:
+        with open(os.path.join(tests, mod)) as fh:
+            assert re.search(rf"^def {fn}\(", fh.read(), re.M), (mod, fn)
     # every key a keyed configuration sets is one the library knows (`_lib.tuning` reads it, sets it and puts it back:
     # tests/test_gpu_tuning.py)
     assert {k for c in G.KEYED.values() for k in c[3]} <= set(keys)

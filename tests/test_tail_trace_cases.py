@@ -190,6 +190,111 @@ def test_compare_paths_and_before_merge():
     assert T.before_merge(arr) != T.before_merge(other)
 
 
+# ------------------------------------------------------------------------------------- refine: the launch-shape keys' cases
+
+def test_block_size_case_has_word_counts_on_both_sides_of_every_block_size():
+    case = T.block_size_case()
+    wins = [T.windows_of(img.shape, boxes) for img, boxes in zip(case["pages"], case["boxes"])]
+    assert wins == T.block_size_windows()                                          # the blocks give exactly the intended windows
+    tall, (strip,), small = wins
+    assert [p.shape[:2] for p in case["pages"]] == [(1030, 360), (4, 8194), (300, 300)]
+    one = [(w, h) for _, _, w, h in tall[:9]]
+    assert all(w <= 32 for w, _ in one) and [h for _, h in one] == [255, 256, 257, 511, 512, 513, 1023, 1024, 1025]
+    three = [(w, h) for _, _, w, h in tall[9:]]
+    assert all(65 <= w <= 96 for w, _ in three) and [T.words_of(w, h) for w, h in three] == [255, 258, 513, 1023, 1026]
+    assert (strip[2] + 31) >> 5 == 257 and strip[3] == 3                          # wp > 256: no whole row per trip at 256 threads
+    assert [(w, h) for _, _, w, h in small] == [(256, 260), (1, 1), (33, 2)]
+    words = T.case_words(case)
+    assert words == [255, 256, 257, 511, 512, 513, 1023, 1024, 1025, 255, 258, 513, 1023, 1026, 771, 2080, 1, 4]
+    for nt in T.BLOCK_SIZES:                                                       # both sides of, and exactly, each block size
+        assert {nt - 1, nt, nt + 1} <= set(words)
+        assert any(wd % 3 == 0 and wd < nt for wd in words[9:14]) and any(wd % 3 == 0 and wd > nt for wd in words[9:14])
+        assert nt % 3 != 0
+    assert T.words_of(*T.LARGE) > 2048 and (T.words_of(*T.LARGE) + 1) // 2 > T.lds_rcap(T.words_of(*T.LARGE), 1) == 1024   # rlay > rcap at 1
+    assert T.large_window_case()["boxes"][0] == [case["boxes"][2][0]] and np.array_equal(T.large_window_case()["pages"][0], case["pages"][2])
+
+
+@pytest.mark.parametrize("name", ["block_size_case", "class_case"])
+def test_launch_shape_cases_fit_their_run_tables_and_reach_the_late_phases(name):
+    """By the emulation's run counts (tests/twlds_emul.py) no labelling of any window -- a candidate after the small-component
+    rule, or the complement hole filling labels, either refine mode -- has more runs than max(1 024, 2.5 per word): nothing
+    overflows at the default `tail_lds_runs_x10`, whatever launch a window shares.  The merge accepts something in at least
+    half of the windows and hole filling fills a hole, so the late phases are not compared on empty planes."""
+    st = T.merge_stats(getattr(T, name))
+    print("\n(words, runs: candidates / complement mode 0 / mode 1, accepted, filled):", [(s["words"], s["runs"], s["accepted"], s["filled"]) for s in st])
+    for s in st:
+        assert max(s["runs"]) <= max(1024, s["words"] * 25 // 10), s
+    assert sum(s["accepted"] > 0 for s in st) * 2 >= len(st)
+    assert sum(s["filled"] > 0 for s in st) >= 3
+    for mode in (0, 1):
+        assert T.expected_paths(getattr(T, name), mode) == {"lds": len(st), "canvas": 0, "overflow": 0}
+    if name == "block_size_case":                                                  # the large window completes under the floor of 1 024 runs
+        assert max(st[15]["runs"]) <= 1024 and st[15]["words"] == 2080 and st[15]["filled"] > 0
+        assert T.expected_paths(T.large_window_case, 1, {"tail_lds_runs_x10": 1}) == {"lds": 1, "canvas": 0, "overflow": 0}
+        assert T.expected_paths(T.block_size_case, 0, {"tail_lds_runs_x10": 1})["overflow"] >= 1   # ... while taller columns do overflow there
+
+
+def test_lds_restatement_against_hand_computed_rows():
+    """`lds_rcap`, `lds_need`, `lds_launches` against rows worked out by hand from the layout (3 planes + u16 prefix + parent
+    and acc of rlay + 20 words, times 4 bytes) -- not against the library; every key is given, none read from it."""
+    rcap, need = T.lds_rcap, T.lds_need
+    # 2.5 runs per word.  words = 1: rcap 1 024 (floor), rlay 1 024: (3 + 1 + 2 048 + 20) * 4
+    assert (rcap(1, 25), need(1, 25)) == (1024, 8288)
+    # words = 600: rcap 1 500, rlay 1 500: (1 800 + 300 + 3 000 + 20) * 4
+    assert (rcap(600, 25), need(600, 25)) == (1500, 20480)
+    # words = 2 080: rcap 5 200: (6 240 + 1 040 + 10 400 + 20) * 4; at 0.1 runs per word rcap 1 024 < rlay 1 040: (6 240 + 1 040 + 2 080 + 20) * 4
+    assert (rcap(2080, 25), need(2080, 25)) == (5200, 70800) and (rcap(2080, 1), need(2080, 1)) == (1024, 37520)
+    # words = 4 515 (odd: prefix 2 258 words): rcap 11 287: (13 545 + 2 258 + 22 574 + 20) * 4; 4 516 is the first beyond 150 KB
+    assert (rcap(4515, 25), need(4515, 25)) == (11287, 153588) and need(4516, 25) == 153624 > 150 << 10 >= need(4515, 25)
+    # 16 runs per word, 100 words: rcap 1 600: (300 + 50 + 3 200 + 20) * 4; 100 per word, 700 words: clamp 65 000
+    assert (rcap(100, 160), need(100, 160)) == (1600, 14280)
+    assert (rcap(700, 1000), need(700, 1000)) == (65000, (2100 + 350 + 130000 + 20) * 4)
+    # `tail_lds_rcap` = 8, 40 words: rlay = 20 (the scratch plane): (120 + 20 + 40 + 20) * 4; the key is clamped as well
+    assert (rcap(40, 25, 8), need(40, 25, 8)) == (8, 800) and rcap(40, 25, 70000) == 65000
+    # the class loop on class_case's word counts at 40 KB / 80 KB / 150 KB: needs 40 776 <= 40 KB < 44 348 (1 302 words), 70 800 <= 80 KB
+    words = [4515, 1, 600, 2080, 40, 600, 1197, 100, 1302, 400, 4]
+    assert T.case_words(T.class_case()) == words
+    K40, K80, K150 = 40 << 10, 80 << 10, 150 << 10
+    assert T.lds_launches(words, K40, K80, K150, 25) == ([], [(8, 1197, 2992, 40776, [1, 10, 4, 7, 9, 2, 5, 6]), (2, 2080, 5200, 70800, [8, 3]),
+                                                            (1, 4515, 11287, 153588, [0])])
+    # one class: the 1 x 1 window in the layout of the largest
+    assert T.lds_launches(words, K150, K150, K150, 25) == ([], [(11, 4515, 11287, 153588, [1, 10, 4, 7, 9, 2, 5, 6, 8, 3, 0])])
+    # a limit AT a need keeps the window below, one byte less moves it up; cls1 < cls0 leaves the middle launch out
+    assert [l[:2] for l in T.lds_launches(words, 40776, 70800, K150, 25)[1]] == [(8, 1197), (2, 2080), (1, 4515)]
+    assert [l[:2] for l in T.lds_launches(words, 40775, 70799, K150, 25)[1]] == [(7, 600), (2, 1302), (2, 4515)]
+    assert [l[:2] for l in T.lds_launches(words, K80, K40, K150, 25)[1]] == [(10, 2080), (1, 4515)]
+    assert [l[:2] for l in T.lds_launches(words, 0, K80, K150, 25)[1]] == [(10, 2080), (1, 4515)]
+    # 16 runs per word: need 142 w + 80 -> 1 081 words is the last in LDS; the others take the canvases, in window order
+    assert T.lds_launches(words, K40, K80, K150, 160)[0] == [0, 3, 6, 8] and T.lds_launches(words, K40, K80, K150, 25, lds=0) == (list(range(11)), [])
+    # a lower LDS limit sends the largest to the canvases
+    assert T.lds_launches(words, K40, K80, 153587, 25)[0] == [0]
+
+
+def test_class_settings_move_windows_between_launches():
+    words = T.case_words(T.class_case())
+    assert len(words) == 11 and sorted(words)[0] == 1 and sorted(words).count(600) == 2 and max(words) == 4515
+    shapes = {what: [l[:2] for l in T.launches_of_setting(words, tune)[1]] for what, tune in T.class_settings()}
+    assert len({str(v) for v in shapes.values()}) >= 6, shapes                     # the settings differ in what they launch
+    assert shapes["one class"] == [(11, 4515)]
+    assert shapes["the two 600-word windows a launch of their own"] == [(5, 400), (2, 600), (4, 4515)]
+    assert shapes["the 1 x 1 window alone, then all but the largest"] == [(1, 1), (9, 2080), (1, 4515)]
+    assert shapes["both one byte below"] != shapes["cls0 at the need of the 1 197-word window, cls1 at that of the 2 080-word one"] == shapes["the defaults"]
+    assert all(T.launches_of_setting(words, tune)[0] == [] for _, tune in T.class_settings())
+
+
+def test_compare_launches_reports():
+    launches = T.lds_launches([600, 1, 2080], 40 << 10, 80 << 10, 150 << 10, 25)[1]
+    got = [dict(windows=n, max_words=mw, rcap=rc, bytes=by, threads=512, refused=0) for n, mw, rc, by, _ in launches]
+    T.compare_launches(got, (launches, 512))
+    for k in ("windows", "max_words", "rcap", "bytes", "threads", "refused"):
+        bad = [dict(g) for g in got]
+        bad[-1][k] += 1
+        with pytest.raises(AssertionError):
+            T.compare_launches(bad, (launches, 512))
+    with pytest.raises(AssertionError):
+        T.compare_launches(got[:-1], (launches, 512))
+
+
 # ------------------------------------------------------------------------------------------------------------------- DB stage
 
 def test_db_calls_cover_the_listed_maps():
