@@ -31,6 +31,9 @@ COLOR_MAX_PIXELS, COLOR_MAX_COORD = 1 << 24, 1 << 29
 ERASE_PLAIN, ERASE_TEXTURED, ERASE_NO_RING, ERASE_NO_MASK, ERASE_EMPTY, ERASE_TOO_LARGE = range(6)
 ERASE_MAX_PIXELS, ERASE_MAX_COORD, ERASE_MAX_GROW, ERASE_MAX_RING = 1 << 24, 1 << 29, 8, 16
 ERASE_TILE_W, ERASE_TILE_H = 64, 32
+BALLOON_OK, BALLOON_NOT_PLAIN, BALLOON_TOO_LARGE = range(3)
+BALLOON_MAX_WORDS, BALLOON_MAX_REACH, BALLOON_MIN_REACH_MIN, BALLOON_MAX_REACH_MIN = 8192, 32, 8, 1024
+BALLOON_CUT_LEFT, BALLOON_CUT_TOP, BALLOON_CUT_RIGHT, BALLOON_CUT_BOTTOM = 1, 2, 4, 8
 
 
 class CtdTensor(C.Structure):
@@ -119,6 +122,20 @@ class CtdEraseRow(C.Structure):
                 ("med", C.c_uint8 * 3), ("pad_", C.c_uint8 * 5)]
 
 
+class CtdBalloonJob(C.Structure):
+    _fields_ = [("page", C.c_int32), ("xyxy", C.c_int32 * 4), ("erase_row", C.c_int32), ("word0", C.c_int64)]
+
+
+class CtdBalloonParams(C.Structure):
+    _fields_ = [("grow", C.c_int32), ("tol", C.c_int32), ("reach", C.c_int32), ("reach_min", C.c_int32), ("max_words", C.c_int32),
+                ("pad_", C.c_int32 * 3)]
+
+
+class CtdBalloonRow(C.Structure):
+    _fields_ = [("status", C.c_int32), ("area", C.c_int32), ("bbox", C.c_int32 * 4), ("flags", C.c_int32), ("n_seed", C.c_int32),
+                ("sum_x", C.c_int64), ("sum_y", C.c_int64)]
+
+
 # every symbol include/ctd_hip.h declares: (restype, argtypes)
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -149,6 +166,7 @@ SYMBOLS = {
     "ctd_warp_region_batches": (_i32, [_vp, _i32, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, _vp]),
     "ctd_line_colors": (_i32, [_vp, _i32, _vp, _vp]),
     "ctd_erase_text": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(CtdEraseParams), _vp, _vp]),
+    "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),
     "ctd_tail_destroy": (None, [_vp]),

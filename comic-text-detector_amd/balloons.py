@@ -1,0 +1,212 @@
+"""Balloon regions: the free area around every block that stands on a plain background, on the GPU.
+
+After the original text is erased, a comic-translation caller puts the translated text back, and for that it needs the
+extent of the area the old text stood in: the balloon.  Downstream tools flood-fill on the host, page by page and block by
+block, from the text outwards over pixels of the balloon's colour and read the fill's bounding box, area and centre.  The
+detector already holds what decides the region -- the page, the refined text mask, the block boxes and, since `erase_text`,
+per block "this background is one colour" and that colour -- so
+
+    br = balloon_regions(pages, masks, blk_lists)       # or TextDetector.balloons(pages, results[, erased=er])
+    br.ok[j], br.area[j], br.bbox[j], br.center[j], br.flags[j], br.mask(j)
+
+builds the tables with numpy, uploads them once, makes ONE `ctd_balloon_regions` call (csrc/kernels_balloon.hip: one launch,
+one workgroup per block, the window's bit planes in LDS) -- after the erase stats launch on the same stream where no
+`ErasedPages` is passed in -- and downloads one small table; the regions themselves stay on the device as bit planes.  The
+rule is integers only and stated in include/ctd_hip.h (restated in numpy with a queue flood fill in tests/balloon_ref.py;
+DESIGN.md section 4.18 has its limits): in a window around the block's box, the pixels within `tol` of the erase row's median
+in every channel, plus the block's own filled glyphs, are open; the region is what is 4-connected to the glyphs through open
+pixels.  There is no per-block Python and no CPU fallback: without a GPU it raises `CtdError` like the rest of the package.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+from typing import Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from . import erase as E
+from .colors import _shape_of
+from .regions import Page, _device_pages
+
+__all__ = ["balloon_regions", "BalloonRegions", "balloon_tables", "check_params", "JOB_DTYPE", "ROW_DTYPE"]
+
+# numpy views of `ctd_balloon_job` / `ctd_balloon_row` (include/ctd_hip.h; _lib.CtdBalloonJob / CtdBalloonRow); the page table
+# is `erase.PAGE_DTYPE`
+JOB_DTYPE = np.dtype([("page", "<i4"), ("xyxy", "<i4", (4,)), ("erase_row", "<i4"), ("word0", "<i8")])
+ROW_DTYPE = np.dtype([("status", "<i4"), ("area", "<i4"), ("bbox", "<i4", (4,)), ("flags", "<i4"), ("n_seed", "<i4"),
+                      ("sum_x", "<i8"), ("sum_y", "<i8")])
+assert JOB_DTYPE.itemsize == C.sizeof(L.CtdBalloonJob) == 32
+assert ROW_DTYPE.itemsize == C.sizeof(L.CtdBalloonRow) == 48
+
+
+def check_params(grow, tol, reach, reach_min) -> L.CtdBalloonParams:
+    vals = (grow, tol, reach, reach_min)
+    if not all(isinstance(v, (int, np.integer)) and not isinstance(v, bool) for v in vals):
+        raise ValueError("grow, tol, reach and reach_min are integers")
+    if not (0 <= grow <= L.ERASE_MAX_GROW and 0 <= tol <= 255 and 0 <= reach <= L.BALLOON_MAX_REACH
+            and L.BALLOON_MIN_REACH_MIN <= reach_min <= L.BALLOON_MAX_REACH_MIN):
+        raise ValueError("grow in 0..8, tol in 0..255, reach in 0..32, reach_min in 8..1024")
+    return L.CtdBalloonParams(int(grow), int(tol), int(reach), int(reach_min), 0)
+
+
+def balloon_tables(boxes: Sequence[np.ndarray], shapes: Sequence, reach: int = 8, reach_min: int = 32) -> tuple:
+    """What the host decides from the boxes alone, for pages of `shapes` = (H, W) with `boxes[i]` (n_i, 4), blocks in page
+    order: (windows (n, 4) i64 x1, y1, x2, y2 in page coordinates, x2 and y2 exclusive, all 0 where the clipped box is empty;
+    nw (n,) words a window row; word0 (n,) the block's first word of the bit buffer; the buffer's word count; too_large (n,)
+    bool: the window holds more than `BALLOON_MAX_WORDS` words and the block owns none)."""
+    check_params(0, 0, reach, reach_min)
+    counts = np.array([len(b) for b in boxes], np.int64)
+    n = int(counts.sum())
+    win = np.zeros((n, 4), np.int64)
+    if n:
+        xy = np.concatenate([np.asarray(b, np.int64).reshape(-1, 4) for b in boxes])
+        H = np.repeat(np.array([s[0] for s in shapes], np.int64), counts)
+        W = np.repeat(np.array([s[1] for s in shapes], np.int64), counts)
+        x1, y1 = np.maximum(xy[:, 0], 0), np.maximum(xy[:, 1], 0)
+        x2, y2 = np.minimum(xy[:, 2], W), np.minimum(xy[:, 3], H)
+        some = (x1 < x2) & (y1 < y2)
+        ex = np.maximum(reach_min, ((x2 - x1) * reach) >> 3)
+        ey = np.maximum(reach_min, ((y2 - y1) * reach) >> 3)
+        win = np.stack([np.maximum(x1 - ex, 0), np.maximum(y1 - ey, 0), np.minimum(x2 + ex, W), np.minimum(y2 + ey, H)], axis=1)
+        win[~some] = 0
+    nw = (win[:, 2] - win[:, 0] + 63) >> 6
+    words = nw * (win[:, 3] - win[:, 1])
+    too_large = words > L.BALLOON_MAX_WORDS
+    owned = np.where(too_large, 0, words)
+    return win, nw, np.cumsum(owned) - owned, int(owned.sum()), too_large
+
+
+class BalloonRegions:
+    """The result of `balloon_regions`.  Per block, in order: `index[j] = (page, block)`, `rows` the kernel's records
+    (`ROW_DTYPE`), `status[j]` = `_lib.BALLOON_OK` / `BALLOON_NOT_PLAIN` (the erase rule does not call the block's background
+    one colour: no region) / `BALLOON_TOO_LARGE` (the window holds more than 8192 words), `ok[j]` bool, `area[j]` pixels,
+    `bbox[j]` x1, y1, x2, y2 in page coordinates (exclusive), `center[j]` = (sum_x // area, sum_y // area) where `ok`, else
+    -1, `flags[j]`: bits 0..3 (`_lib.BALLOON_CUT_LEFT / TOP / RIGHT / BOTTOM`) the region reaches that side of its window --
+    it was cut by the window, or it leaked through a gap in the balloon's outline -- bits 4..7 the same where that side is
+    the page's edge.  `windows[j]` x1, y1, x2, y2 of the block's window, `nw[j]`, `word0[j]`: its words in `bits`, the device
+    u64 buffer of all regions (window row y, columns 64 k .. 64 k + 63 in word `word0 + y * nw + k`, least significant bit
+    first); `mask(j)` unpacks one.  `erase_rows`: the blocks' `erase.ROW_DTYPE` rows that decided plain / not plain."""
+
+    def __init__(self, index, rows, windows, nw, word0, too_large, bits, erase_rows):
+        self.index = np.asarray(index, np.int32).reshape(-1, 2)
+        self.rows, self.windows, self.nw, self.word0, self.too_large = rows, windows, nw, word0, too_large
+        self.bits, self.erase_rows = bits, erase_rows
+        if len(self.index) != len(rows):
+            raise ValueError("one index row per block")
+        self.status = rows["status"]
+        self.ok = self.status == L.BALLOON_OK
+        self.area, self.bbox, self.flags = rows["area"], rows["bbox"], rows["flags"]
+        den = np.where(self.ok, np.maximum(rows["area"], 1), 1).astype(np.int64)
+        self.center = np.where(self.ok[:, None], np.stack([rows["sum_x"] // den, rows["sum_y"] // den], axis=1), -1)
+
+    def __len__(self) -> int:
+        return len(self.index)
+
+    def mask(self, j: int) -> torch.Tensor:
+        """Block j's region as a (wh, ww) bool device tensor over its window (all False where the block is not `ok`)."""
+        x1, y1, x2, y2 = (int(v) for v in self.windows[j])
+        if self.too_large[j]:
+            raise ValueError("the block's window is too large: it has no bits")
+        nw, w0 = int(self.nw[j]), int(self.word0[j])
+        words = self.bits.view(torch.int64)[w0: w0 + nw * (y2 - y1)].view(y2 - y1, nw, 1)
+        shifts = torch.arange(64, device=words.device, dtype=torch.int64)
+        return ((words >> shifts) & 1).bool().view(y2 - y1, nw * 64)[:, : x2 - x1]
+
+    def to_host(self):
+        """(rows, bits) as numpy arrays; bits is u64."""
+        return self.rows, self.bits.view(torch.int64).cpu().numpy().view(np.uint64)
+
+    def __repr__(self) -> str:
+        return f"BalloonRegions({len(self)} blocks, {int(self.ok.sum())} ok)"
+
+
+def balloon_regions(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequence, erased: Optional[E.ErasedPages] = None,
+                    grow: int = 2, tol: int = 12, reach: int = 8, reach_min: int = 32,
+                    stream: Optional[torch.cuda.Stream] = None, device=None) -> BalloonRegions:
+    """The balloon region of EVERY block of EVERY page of a batch: one table upload, one `ctd_balloon_regions` launch, one
+    small download.  pages, masks, blk_lists as for `erase.erase_text`.  erased: the `ErasedPages` of an `erase_text` call
+    on the same pages, masks and blocks with the same `grow` (its rows are uploaded); without it the erase rule's stats launch
+    runs first on the same stream, with `grow`, `tol` and the erase defaults, and its rows never leave the device in between.
+    grow: as in `erase_text`; tol: how far from the block's background colour an open pixel may lie, per channel; reach: the
+    window is the box grown by reach / 8 of its side, but at least by reach_min pixels.  Runs on `stream` (default: the
+    current stream of the pages' device) and waits for the result; see `BalloonRegions`."""
+    prm = check_params(grow, tol, reach, reach_min)
+    if len(pages) != len(blk_lists) or len(masks) != len(pages):
+        raise ValueError("one mask and one blk_list per page")
+    for p, m in zip(pages, masks):
+        (ps, pu8), (ms, mu8) = _shape_of(p), _shape_of(m)
+        if not pu8 or len(ps) != 3 or ps[2] != 3:
+            raise ValueError("pages must be uint8 BGR (H,W,3)")
+        if not mu8 or ms != ps[:2]:
+            raise ValueError("a mask must be uint8 and have the shape of its page")
+        if ps[0] < 1 or ps[1] < 1:
+            raise ValueError("empty page")
+    lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in blk_lists]
+    boxes = [E._page_boxes(b) for b in lists]
+    shapes = [tuple(p.shape[:2]) for p in pages]
+    ejobs, block0, counts, _, _ = E.erase_tables(boxes, shapes)
+    n, n_pages = len(ejobs), len(pages)
+    index = np.stack([ejobs["page"], np.arange(n) - np.repeat(block0, counts)], axis=1).astype(np.int32) if n else \
+        np.zeros((0, 2), np.int32)
+    if erased is not None and (len(erased) != n or not np.array_equal(erased.index, index)):
+        raise ValueError("`erased` is not the result of erase_text on these pages and blocks")
+    win, nw, word0, total, too_large = balloon_tables(boxes, shapes, reach, reach_min)
+    if total >= 2 ** 31:
+        raise ValueError("too many window words for one call")
+    if n_pages == 0:
+        return BalloonRegions(index, np.zeros((0,), ROW_DTYPE), win, nw, word0, too_large, torch.zeros((0,), dtype=torch.uint64),
+                              np.zeros((0,), E.ROW_DTYPE))
+    if not torch.cuda.is_available():
+        raise L.CtdError("balloon regions run on the GPU and there is none (no CPU fallback)")
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        pages, _, device = _device_pages(pages, device)
+        masks = _device_pages(masks, device)[0]
+        with torch.cuda.device(device):
+            st = torch.cuda.current_stream(device)
+            W = np.array([p.shape[1] for p in pages], np.int64)
+            pitch = np.array([p.stride(0) for p in pages], np.int64)
+            mpitch = np.array([m.stride(0) for m in masks], np.int64)
+            if max(pitch.max(), mpitch.max(), (3 * W).max()) >= 2 ** 31:
+                raise ValueError("row pitch beyond int32")
+            # one upload: erase jobs, balloon jobs, pages, and the erase rows where the caller has them
+            js, ps, rs = E.JOB_DTYPE.itemsize, E.PAGE_DTYPE.itemsize, E.ROW_DTYPE.itemsize
+            o_jobs, o_pages, o_rows = n * js, n * (js + JOB_DTYPE.itemsize), n * (js + JOB_DTYPE.itemsize) + n_pages * ps
+            table = np.zeros((o_rows + (n * rs if erased is not None else 0),), np.uint8)
+            table[:o_jobs] = ejobs.view(np.uint8)
+            jt = table[o_jobs:o_pages].view(JOB_DTYPE)
+            jt["page"], jt["xyxy"], jt["erase_row"], jt["word0"] = ejobs["page"], ejobs["xyxy"], np.arange(n), word0
+            pt = table[o_pages:o_rows].view(E.PAGE_DTYPE)
+            pt["page_dev"] = [p.data_ptr() for p in pages]
+            pt["mask_dev"] = [m.data_ptr() for m in masks]
+            pt["H"], pt["W"], pt["pitch"], pt["mask_pitch"] = [s[0] for s in shapes], W, pitch, mpitch
+            pt["block0"], pt["n_blocks"] = block0, counts
+            if erased is not None:
+                table[o_rows:] = np.ascontiguousarray(erased.rows).view(np.uint8)
+            tab = torch.from_numpy(table).to(device)
+            # one buffer behind both row tables: balloon rows, then erase rows
+            res = torch.empty((max(n, 1) * (ROW_DTYPE.itemsize + rs),), dtype=torch.uint8, device=device)
+            bits = torch.empty((max(total, 1),), dtype=torch.int64, device=device)[:total].view(torch.uint64)
+            if n:
+                lib = L.lib()
+                erows_ptr = tab.data_ptr() + o_rows
+                if erased is None:
+                    eprm = E.check_params(grow, 4, tol, 16)             # n_tiles = 0: the stats launch alone
+                    erows_ptr = res.data_ptr() + n * ROW_DTYPE.itemsize
+                    L.check(lib.ctd_erase_text(tab.data_ptr(), n, tab.data_ptr() + o_pages, n_pages, C.byref(eprm), erows_ptr,
+                                               st.cuda_stream), "ctd_erase_text")
+                owned = (nw * (win[:, 3] - win[:, 1]))[~too_large]
+                prm.max_words = int(owned.max()) if len(owned) else 0
+                L.check(lib.ctd_balloon_regions(tab.data_ptr() + o_jobs, n, tab.data_ptr() + o_pages, n_pages, erows_ptr,
+                                                C.byref(prm), res.data_ptr(), bits.data_ptr() if total else None, st.cuda_stream),
+                        "ctd_balloon_regions")
+            host = res.cpu().numpy()                                    # stream-ordered: behind the launches
+            st.synchronize()
+    rows = host[: n * ROW_DTYPE.itemsize].view(ROW_DTYPE)
+    erows = erased.rows if erased is not None else host[n * ROW_DTYPE.itemsize: n * (ROW_DTYPE.itemsize + rs)].view(E.ROW_DTYPE)
+    if erased is not None and not np.array_equal(rows["n_seed"][rows["status"] == L.BALLOON_OK],
+                                                 erows["n_fill"][rows["status"] == L.BALLOON_OK]):
+        raise ValueError("`erased` was made with another `grow`, or from other pages, masks or blocks")
+    return BalloonRegions(index, rows, win, nw, word0, too_large, bits, erows)

@@ -184,5 +184,12 @@ void launch_erase_stats(const ctd_erase_job* jobs, int n_blocks, const ctd_erase
 void launch_erase_paint(const ctd_erase_job* jobs, int n_blocks, const ctd_erase_page* pages, int n_pages,
                         const ctd_erase_params& prm, const ctd_erase_row* rows, hipStream_t st);
 
+// ---- kernels_balloon.hip --------------------------------------------------------
+// ctd_balloon_regions' one launch (one workgroup per block; n >= 1, prm checked by the caller): raises the kernel's dynamic
+// LDS limit once per device, launches, and returns what hipGetLastError says right after the launch
+hipError_t launch_balloon_regions(const ctd_balloon_job* jobs, int n, const ctd_erase_page* pages, int n_pages,
+                                  const ctd_erase_row* erase_rows, const ctd_balloon_params& prm, ctd_balloon_row* rows,
+                                  uint64_t* bits, hipStream_t st);
+
 // ---- mfma layout probe (selftest) -------------------------------------------
 void launch_mfma_probe(const half_t* a, const half_t* b, float* out, hipStream_t st);

@@ -575,5 +575,24 @@ class TextDetector:
             torch.cuda.current_stream(dev).wait_event(ev)
         return erase.erase_text(pages, masks, blk_lists, device=dev, **kw)
 
+    def balloons(self, pages: Sequence[Page], results, erased=None, **kw):
+        """The balloon region of every block of a detected batch -- the free area around the text of each block that stands
+        on a plain background: area, bounding box, centre, cut flags and the region as a bit plane -- in one launch on the
+        detector's device (`balloons.balloon_regions` and its keywords `grow`, `tol`, `reach`, `reach_min`; returns its
+        `BalloonRegions`).  `results`: what `detect_batch` / `detect_stream` returned for `pages`; the masks are their
+        `mask_refined`.  `erased`: the `ErasedPages` of `erase_text(pages, results)` with the same `grow`, where the caller
+        has it; otherwise the erase rule's stats launch runs first.  Builds no `TextBlock` of a `BlockList`.  Host pages are
+        uploaded through the pinned staging ring (`_stage`)."""
+        from . import balloons
+        masks = [r[1] for r in results]
+        blk_lists = [r[2] for r in results]
+        balloons.check_params(*(kw.get(k, d) for k, d in (("grow", 2), ("tol", 12), ("reach", 8), ("reach_min", 32))))
+        dev = self.net.device
+        if len(pages) and not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
+                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
+            pages, ev = self._stage(pages)
+            torch.cuda.current_stream(dev).wait_event(ev)
+        return balloons.balloon_regions(pages, masks, blk_lists, erased=erased, device=dev, **kw)
+
     def __call__(self, img: np.ndarray, refine_mode=REFINEMASK_INPAINT, keep_undetected_mask=False):
         return self.detect_batch([img], refine_mode, keep_undetected_mask)[0]

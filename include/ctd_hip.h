@@ -517,6 +517,94 @@ typedef struct ctd_erase_row {
 int ctd_erase_text(const ctd_erase_job* blocks_dev, int32_t n_blocks, const ctd_erase_page* pages_dev, int32_t n_pages,
                    const ctd_erase_params* params, ctd_erase_row* rows_dev, void* stream);
 
+/* ---- balloon regions: the free area around every plain block (added within ABI v10) ------------------------------- */
+
+/* An addition to ABI v10 like the two above: one entry point, three structs, nothing existing changes.
+ * A caller that puts translated text back needs the extent of the free area the old text stood in: the balloon.
+ * Downstream tools flood-fill on the host from the text outwards over pixels of the balloon's colour and read the bounding
+ * box, the area and the centre of the fill.  This is that step for every block of a batch, this library's own rule, integers
+ * only; a connected component does not depend on the order in which it is found, so the result is a function of (page,
+ * mask, boxes, erase rows, parameters) to the bit.  Restated in numpy with a queue flood fill in tests/balloon_ref.py.
+ * It reuses the erase section's definitions M, D_k, X_b, T_b and F_b = D_g(T_b).
+ * Per page: the page and the text mask as in ctd_erase_text, and the page's blocks with their xyxy.  Per block: its
+ * ctd_erase_row of a ctd_erase_text call on the same page, mask and box with the same `grow`, read on the device.
+ * Parameters (ctd_balloon_params): grow g (0 .. 8, default 2; the value the erase rows were made with), tol (0 .. 255,
+ * default 12), reach (0 .. 32, default 8; window growth in eighths of the box side), reach_min (8 .. 1024, default 32;
+ * the least window growth in pixels).
+ *   Win_b   the window: with w, h the sides of the clipped box X_b, ex = max(reach_min, (w * reach) >> 3) and
+ *           ey = max(reach_min, (h * reach) >> 3) (in 64 bits), X_b grown by ex to the left and right and by ey up and down,
+ *           then clipped to the page; ww x wh pixels from (wx1, wy1), nw = ceil(ww / 64) words a row.  Where X_b is empty
+ *           the window is empty (ww = wh = nw = 0).  The window depends on xyxy, H, W, reach and reach_min alone.
+ *           reach_min >= 8 >= g: F_b lies inside the window.
+ *   O_b     the open pixels: the p of Win_b with |page[p][c] - med_c| <= tol for c = 0, 1 and 2 (med of the block's erase
+ *           row), or p in F_b.  Other blocks' text is not open: it is a hole.
+ *   B_b     the region: the union of the 4-CONNECTED components of O_b, taken inside the window only, that contain a pixel
+ *           of F_b.
+ * status, the first that applies:
+ *   CTD_BALLOON_NOT_PLAIN  the job's page or erase_row is no row of its table, or the erase row's status is not
+ *                          CTD_ERASE_PLAIN: every other field of the row is 0 and the block's words are all 0.
+ *   CTD_BALLOON_TOO_LARGE  nw * wh > CTD_BALLOON_MAX_WORDS (8192: two bit planes of 64 KB in LDS), or > params.max_words:
+ *                          every other field of the row is 0.
+ *   CTD_BALLOON_OK
+ * Row per block (ctd_balloon_row, 48 bytes, no padding): status; area = |B_b|; bbox = x1, y1, x2, y2 of B_b in page
+ * coordinates, x2 and y2 exclusive; n_seed = |F_b| (= the erase row's n_fill); sum_x, sum_y = the sums of the page
+ * coordinates over B_b (the centre is sum / area); flags:
+ *   bits 0 .. 3  left, top, right, bottom: B_b has a pixel in the window's outermost column / row on that side and that
+ *                side is NOT the page's edge: the region was cut by the window, or it leaked through a gap in the outline.
+ *   bits 4 .. 7  the same order: B_b has such a pixel and that side IS the page's edge.
+ * Bits: a block with nw * wh <= CTD_BALLOON_MAX_WORDS owns the words word0 .. word0 + nw * wh - 1 of bits_dev, whatever
+ * its status (the caller lays the buffer out from the boxes alone); a block beyond that owns none.  Word word0 + y nw + j
+ * covers window row y, window columns 64 j .. 64 j + 63; bit i (the least significant is 0) is window column 64 j + i and
+ * is set iff that pixel lies in B_b; bits beyond ww are 0.  Every owned word of an OK or NOT_PLAIN block is written
+ * exactly once, nothing else of the buffer is touched.
+ * Limits: a balloon whose outline has a gap leaks (the cut flags show it); a balloon with a gradient is TEXTURED for the
+ * erase rule and so NOT_PLAIN here; a window holds at most 8192 words (e.g. 512 x 1024 pixels). */
+#define CTD_BALLOON_OK 0
+#define CTD_BALLOON_NOT_PLAIN 1
+#define CTD_BALLOON_TOO_LARGE 2
+#define CTD_BALLOON_MAX_WORDS 8192
+#define CTD_BALLOON_MAX_REACH 32
+#define CTD_BALLOON_MIN_REACH_MIN 8
+#define CTD_BALLOON_MAX_REACH_MIN 1024
+#define CTD_BALLOON_CUT_LEFT 1 /* flags; the page-edge flags are these << 4 */
+#define CTD_BALLOON_CUT_TOP 2
+#define CTD_BALLOON_CUT_RIGHT 4
+#define CTD_BALLOON_CUT_BOTTOM 8
+
+/* One block of a ctd_balloon_regions call (a row of the device job table).  The page table is ctd_erase_page as it stands
+ * (page_dev, mask_dev, H, W, pitch, mask_pitch are read; the out / rest / block / tile fields are not). */
+typedef struct ctd_balloon_job {
+  int32_t page;      /* row of the page table                          */
+  int32_t xyxy[4];   /* x1, y1, x2, y2                                 */
+  int32_t erase_row; /* the block's row of the erase rows table        */
+  int64_t word0;     /* the block's first word of bits_dev             */
+} ctd_balloon_job;
+
+typedef struct ctd_balloon_params {
+  int32_t grow, tol, reach, reach_min;
+  int32_t max_words; /* the largest nw * wh <= CTD_BALLOON_MAX_WORDS among the call's blocks: sizes the launch's LDS */
+  int32_t pad_[3];
+} ctd_balloon_params;
+
+/* One row of the result. */
+typedef struct ctd_balloon_row {
+  int32_t status; /* CTD_BALLOON_* */
+  int32_t area;
+  int32_t bbox[4];
+  int32_t flags;
+  int32_t n_seed;
+  int64_t sum_x, sum_y;
+} ctd_balloon_row;
+
+/* The rule above for n blocks in ONE launch on `stream`, one workgroup per block: rows_dev[i] and the owned words of
+ * bits_dev are job i's.  erase_rows_dev may be the rows_dev of a ctd_erase_text call earlier on the same stream (no host
+ * step between them).  `params` is read on the host during the call.  n = 0 launches nothing.  A parameter outside its
+ * bounds, a negative count, blocks without pages or a missing table is an error rc and launches nothing (bits_dev may be
+ * NULL where no block owns a word). */
+int ctd_balloon_regions(const ctd_balloon_job* jobs_dev, int32_t n, const ctd_erase_page* pages_dev, int32_t n_pages,
+                        const ctd_erase_row* erase_rows_dev, const ctd_balloon_params* params, ctd_balloon_row* rows_dev,
+                        uint64_t* bits_dev, void* stream);
+
 /* ---- the detector tail ------------------------------------------------------ */
 
 /* Everything `TextDetector.__call__` does after `self.net(img_in)` (reference inference.py:148-178) for a
