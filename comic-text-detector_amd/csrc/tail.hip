@@ -689,10 +689,27 @@ int undetected_pass(ctd_tail* t, const std::vector<std::vector<int32_t>>& blk_xy
     GET(t->h_tab, (size_t)B * nmax * 5 * 4, int, sth);
     T_TRY(hipMemcpy2DAsync(sth, (size_t)nmax * 20, st_dev, (size_t)cap * 20, (size_t)nmax * 20, B, hipMemcpyDeviceToHost, st));
     T_TRY(hipStreamSynchronize(st));
+    // A page with more components than `cap` (speckle above the text, network noise on a large page): the labelling wrote
+    // no statistics beyond row `cap`, and labels are ranked by first pixel, so whatever lies below the speckle would never
+    // become a window.  Such a page is labelled again, alone, with a table of all its n_host[b] rows (the count is exact;
+    // the table above is on the host by now, so its device buffer is free to grow).  No page over `cap`: nothing here runs.
+    std::vector<std::vector<int>> whole;
     for (int b = 0; b < B; ++b) {
-      const int n = std::min(n_host[b], cap);
+      if (n_host[b] <= cap) continue;
+      const int n = n_host[b];
+      whole.resize(B);
+      GET(t->d_ccl_small, 16 + (size_t)n * 20, int, again);                 // [n (1) | pad | stats (n,5)]
+      launch_ccl(pmask + t->poff[b], 1, t->pages[b].im_h, t->pages[b].im_w, 30, 4, lab, again, again + 4, n, ws, st, 0, nullptr, 1);
+      T_TRY(hipGetLastError());
+      whole[b].resize((size_t)n * 5);
+      T_TRY(hipMemcpyAsync(whole[b].data(), again + 4, (size_t)n * 20, hipMemcpyDeviceToHost, st));
+      T_TRY(hipStreamSynchronize(st));
+    }
+    for (int b = 0; b < B; ++b) {
+      const bool again = !whole.empty() && !whole[b].empty();
+      const int n = again ? (int)(whole[b].size() / 5) : n_host[b];
       const int im_w = t->pages[b].im_w, im_h = t->pages[b].im_h;
-      const int* s = sth + (size_t)b * nmax * 5;
+      const int* s = again ? whole[b].data() : sth + (size_t)b * nmax * 5;
       long long fg = 0;
       for (int l = 0; l < n; ++l) fg += s[5 * l + 4];
       // the reference's stats include the background row 0; `valid_labels[1:]` drops the FIRST row with

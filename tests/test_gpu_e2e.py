@@ -269,7 +269,8 @@ def test_refine_mask_batch_equals_single_pages():
 def test_db_stage_on_device_tables_matches_oracle_and_falls_back_on_overflow():
     """`SegRepresenter` (two labelling passes + contour tables on the GPU, geometry on the host) against the
     oracle's contour walk on speckle maps; a map with more components than the compact tables hold takes
-    the label-image path and must give the same answer."""
+    the label-image path (the overflow flag of the trace is asserted) and must give the same answer -- here on a map whose
+    boxes all score 0; tests/test_gpu_tail_caps.py checks that path on maps whose last components decide boxes that score."""
     from scipy import ndimage
     p = pkg()
     rep = p.postproc.SegRepresenter()
@@ -284,13 +285,22 @@ def test_db_stage_on_device_tables_matches_oracle_and_falls_back_on_overflow():
         rb, rs = R.boxes_from_bitmap(probs[b], probs[b] > 0.3, 256, 192)
         np.testing.assert_array_equal(boxes[b], rb)
         np.testing.assert_allclose(scores[b], rs, rtol=0, atol=1e-6)
-    # > 65536 single-pixel components + one solid block
-    big = np.full((516, 516), 0.05, np.float32)
-    big[::2, ::2] = 0.9
-    big[100:140, 200:330] = 0.95
+    # > 65536 single-pixel components + one solid block: `tail_trace_cases.overflow_map`, 524 a side (67 259 components; the
+    # 516-a-side map this test had has 65 179 and fits).  `rep` runs on the calling thread's tail: its trace shows the flag.
+    from tail_trace_cases import COMP_CAP, db_counts, overflow_map
+    big = overflow_map()
+    side = big.shape[0]
+    assert big.shape == (side, side) and db_counts(big)[0] > COMP_CAP
     bt = torch.from_numpy(big)[None].cuda()
-    boxes, scores = rep(bt, (bt > 0.3).to(torch.uint8))
-    rb, rs = R.boxes_from_bitmap(big, big > 0.3, 516, 516)
+    tail = p.tail.thread_tail(bt.device)
+    tail.set_trace(True)
+    try:
+        boxes, scores = rep(bt, (bt > 0.3).to(torch.uint8))
+        (page,) = tail.trace_db()
+    finally:
+        tail.set_trace(False)
+    assert int(page["hdr"][3]) == 1 and int(page["hdr"][0]) == COMP_CAP, page["hdr"]
+    rb, rs = R.boxes_from_bitmap(big, big > 0.3, side, side)
     np.testing.assert_array_equal(boxes[0], rb)
     np.testing.assert_allclose(scores[0], rs, rtol=0, atol=1e-6)
 
