@@ -34,6 +34,8 @@ ERASE_TILE_W, ERASE_TILE_H = 64, 32
 BALLOON_OK, BALLOON_NOT_PLAIN, BALLOON_TOO_LARGE = range(3)
 BALLOON_MAX_WORDS, BALLOON_MAX_REACH, BALLOON_MIN_REACH_MIN, BALLOON_MAX_REACH_MIN = 8192, 32, 8, 1024
 BALLOON_CUT_LEFT, BALLOON_CUT_TOP, BALLOON_CUT_RIGHT, BALLOON_CUT_BOTTOM = 1, 2, 4, 8
+FILL_OK, FILL_NO_HOLE, FILL_NO_KNOWN = range(3)
+FILL_MAX_SIDE, FILL_TILE = 8192, 64
 
 
 class CtdTensor(C.Structure):
@@ -136,6 +138,21 @@ class CtdBalloonRow(C.Structure):
                 ("sum_x", C.c_int64), ("sum_y", C.c_int64)]
 
 
+class CtdFillPage(C.Structure):
+    _fields_ = [("page_dev", C.c_void_p), ("hole_dev", C.c_void_p), ("out_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32),
+                ("pitch", C.c_int32), ("hole_pitch", C.c_int32), ("out_pitch", C.c_int32), ("tile0", C.c_int32),
+                ("lvl0", C.c_int64)]
+
+
+class CtdFillParams(C.Structure):
+    _fields_ = [("n_tiles", C.c_int32), ("pad_", C.c_int32 * 7)]
+
+
+class CtdFillRow(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_hole", C.c_int32), ("levels", C.c_int32), ("top", C.c_uint8 * 3),
+                ("pad_", C.c_uint8 * 17)]
+
+
 # every symbol include/ctd_hip.h declares: (restype, argtypes)
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -167,6 +184,7 @@ SYMBOLS = {
     "ctd_line_colors": (_i32, [_vp, _i32, _vp, _vp]),
     "ctd_erase_text": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(CtdEraseParams), _vp, _vp]),
     "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
+    "ctd_fill_rest": (_i32, [_vp, _i32, C.POINTER(CtdFillParams), _vp, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),
     "ctd_tail_destroy": (None, [_vp]),

@@ -1417,4 +1417,30 @@ int ctd_balloon_regions(const ctd_balloon_job* jobs_dev, int32_t n, const ctd_er
   return CTD_OK;
 }
 
+int ctd_fill_rest(const ctd_fill_page* pages_dev, int32_t n_pages, const ctd_fill_params* params, void* scratch_dev,
+                  ctd_fill_row* rows_dev, void* stream) {
+  if (n_pages < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (n_pages == 0) return CTD_OK;
+  if (!pages_dev || !params || !scratch_dev || !rows_dev) return fail(CTD_ERR_INVALID, "null pointer");
+  // the shapes decide the grid and what the kernels may touch: the table is checked here, before anything launches
+  std::vector<ctd_fill_page> tab((size_t)n_pages);
+  HIP_TRY(hipMemcpyAsync(tab.data(), pages_dev, tab.size() * sizeof(ctd_fill_page), hipMemcpyDefault, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  long long tiles = 0;
+  for (int32_t i = 0; i < n_pages; ++i) {
+    const ctd_fill_page& p = tab[(size_t)i];
+    const std::string at = "fill: page " + std::to_string(i) + ": ";
+    if (!p.page_dev || !p.hole_dev || !p.out_dev) return fail(CTD_ERR_INVALID, at + "null pointer");
+    if (p.H < 1 || p.W < 1 || p.H > CTD_FILL_MAX_SIDE || p.W > CTD_FILL_MAX_SIDE)
+      return fail(CTD_ERR_INVALID, at + "sides 1 .. " + std::to_string(CTD_FILL_MAX_SIDE));
+    if (p.pitch < 3 * p.W || p.hole_pitch < p.W || p.out_pitch < 3 * p.W) return fail(CTD_ERR_INVALID, at + "a pitch below the row size");
+    if (p.tile0 != tiles || p.lvl0 < 0) return fail(CTD_ERR_INVALID, at + "tile0 is the tiles of the pages before it, lvl0 >= 0");
+    tiles += (long long)((p.W + CTD_FILL_TILE - 1) / CTD_FILL_TILE) * ((p.H + CTD_FILL_TILE - 1) / CTD_FILL_TILE);
+    if (tiles > 0x7fffffffll) return fail(CTD_ERR_INVALID, "fill: too many tiles for one call");
+  }
+  if (params->n_tiles != tiles) return fail(CTD_ERR_INVALID, "fill: n_tiles is the tiles of all pages");
+  HIP_TRY(launch_fill_rest(pages_dev, n_pages, (int)tiles, scratch_dev, rows_dev, (hipStream_t)stream));
+  return CTD_OK;
+}
+
 }  // extern "C"

@@ -191,5 +191,12 @@ hipError_t launch_balloon_regions(const ctd_balloon_job* jobs, int n, const ctd_
                                   const ctd_erase_row* erase_rows, const ctd_balloon_params& prm, ctd_balloon_row* rows,
                                   uint64_t* bits, hipStream_t st);
 
+// ---- kernels_fill.hip -----------------------------------------------------------
+// ctd_fill_rest's three launches (pull per tile, the page launch, push per tile; n_pages >= 1, n_tiles >= 1 and the page
+// table checked by the caller): raises the page kernel's dynamic LDS limit once per device and returns what hipGetLastError
+// says right after the first launch that failed
+hipError_t launch_fill_rest(const ctd_fill_page* pages, int n_pages, int n_tiles, void* scratch, ctd_fill_row* rows,
+                            hipStream_t st);
+
 // ---- mfma layout probe (selftest) -------------------------------------------
 void launch_mfma_probe(const half_t* a, const half_t* b, float* out, hipStream_t st);

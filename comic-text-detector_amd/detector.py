@@ -594,5 +594,16 @@ class TextDetector:
             torch.cuda.current_stream(dev).wait_event(ev)
         return balloons.balloon_regions(pages, masks, blk_lists, erased=erased, device=dev, **kw)
 
+    def fill_rest(self, pages: Sequence[Page], results, erased=None, **erase_kw):
+        """The pages of a detected batch with NO text left, on the detector's device: the text on plain backgrounds erased
+        (`erase_text`) and the mask that leaves filled smoothly by pull-push (`fill.fill_rest` on the erased pages and their
+        rest masks; returns its `FilledPages`).  `results`: what `detect_batch` / `detect_stream` returned for `pages`.
+        `erased`: the `ErasedPages` of `erase_text(pages, results)` where the caller has it; otherwise that runs first, with
+        `erase_kw`.  Builds no `TextBlock` of a `BlockList`."""
+        from . import fill
+        if erased is None:
+            erased = self.erase_text(pages, results, **erase_kw)
+        return fill.fill_rest(erased.pages, erased.rest, device=self.net.device)
+
     def __call__(self, img: np.ndarray, refine_mode=REFINEMASK_INPAINT, keep_undetected_mask=False):
         return self.detect_batch([img], refine_mode, keep_undetected_mask)[0]

@@ -605,6 +605,95 @@ int ctd_balloon_regions(const ctd_balloon_job* jobs_dev, int32_t n, const ctd_er
                         const ctd_erase_row* erase_rows_dev, const ctd_balloon_params* params, ctd_balloon_row* rows_dev,
                         uint64_t* bits_dev, void* stream);
 
+/* ---- fill what erase leaves: smooth pull-push fill of a hole mask (added within ABI v10) --------------------------- */
+
+/* An addition to ABI v10 like the three above: one entry point, three structs, nothing existing changes.
+ * ctd_erase_text cleans a page only where the background is one colour; text on a gradient or a screentone, text that
+ * touches the balloon's outline and text outside every box come back as its `rest` mask.  This is the step that fills that
+ * mask: a deterministic smooth fill by pull-push, this library's own rule, integers only, so the result is a function of
+ * (page, hole mask) to the byte.  Pull builds an image pyramid of the known pixels; push fills the hole from coarse to fine
+ * by bilinear upsampling.  Restated in numpy in tests/fill_ref.py.
+ *
+ * Inputs, per page: P (H x W x 3 u8, any pitch) and a hole mask R (H x W u8, any pitch).  A pixel is a HOLE where R != 0
+ * and KNOWN otherwise.
+ * Levels: level 0 is H x W; level l + 1 is ceil(H_l / 2) x ceil(W_l / 2).  The top level T is the first that is 1 x 1 (a
+ *   1 x 1 page has T = 0).  Every level pixel carries a colour c[3] (u8) and a flag k.
+ * Pull: at level 0, k = KNOWN and c = P.  At level l + 1, pixel (y, x) looks at its up to four children (2y + dy, 2x + dx),
+ *   dy, dx in {0, 1}, that lie inside level l and have k = 1; n is their count and S their per-channel sum.
+ *     n > 0: k = 1 and c = (2 S + n) / (2 n), integer division, per channel (round half up, the colour code's formula);
+ *     n = 0: k = 0.
+ * Push: from level T - 1 down to 0.  At level l a pixel (y, x) with k = 0 takes a value bilinearly upsampled from the
+ *   FINISHED level l + 1: py = y >> 1, px = x >> 1, ny = clamp(py + (y & 1 ? 1 : -1), 0, H_{l+1} - 1), nx likewise from x
+ *   and W_{l+1}, and
+ *     c = (9 c[py][px] + 3 c[py][nx] + 3 c[ny][px] + c[ny][nx] + 8) >> 4, per channel;
+ *   the pixel then counts as finished.  Pixels with k = 1 keep their pulled colour.
+ * Output: `out` is P on KNOWN pixels and the pushed level-0 colour on HOLE pixels.
+ * Row per page (ctd_fill_row, 32 bytes, padding 0): status; n_hole, the number of hole pixels; levels = T; top[3], the
+ * colour of the top pixel in PAGE channel order, or 0 where it has k = 0.  status:
+ *   CTD_FILL_OK        filled by the rule
+ *   CTD_FILL_NO_HOLE   n_hole = 0: `out` is a copy of P
+ *   CTD_FILL_NO_KNOWN  no known pixel: `out` is a copy of P
+ * Properties: every filled value lies within [min, max] of the page's known pixels, per channel; a page whose known pixels
+ * all have one colour c is filled with exactly c ((16 c + 8) >> 4 = c); with one known pixel the whole page takes its colour.
+ * Limit: a side above CTD_FILL_MAX_SIDE (8192) is an error rc, decided by the shapes alone, and nothing launches.
+ * What the rule cannot do: it does not reproduce texture (screentone comes back as its local mean); it does not continue
+ * lines or panel borders through the hole; a hole at the page's edge is extrapolated from one side only; the hole is R as
+ * given, so anti-aliased fringes outside the mask stay (ctd_erase_text's `grow`, or the INPAINT refine mode's dilation, is
+ * where to widen it).
+ *
+ * Scratch: the launches hand each other the pyramid through scratch_dev, 4-byte aligned, dwords.  One dword a level pixel:
+ * c[0] | c[1] << 8 | c[2] << 16 | k << 24, and 0 where k = 0.  With tiles(page) = ceil(H / 64) * ceil(W / 64) and
+ * dim(n, l) = ceil(n / 2^l):
+ *   dwords 0 .. n_tiles - 1                 the hole count of every 64 x 64 tile, tile tile0 + ty * ceil(W / 64) + tx
+ *   dwords lvl0 .. lvl0 + plane(page) - 1   the page's levels 1 .. 6, one after the other, each row-major,
+ *                                           plane(page) = sum over l = 1 .. 6 of dim(H, l) * dim(W, l)
+ * where a page's tile0 is the sum of tiles() of the pages before it and its lvl0 is n_tiles plus the sum of plane() of the
+ * pages before it: scratch_dev holds n_tiles + sum of plane() dwords.  Levels 7 .. T never leave the chip; where T < 6 the
+ * levels T + 1 .. 6 are 1 x 1 copies of the top, which changes nothing of the rule.  The contents after the call are not
+ * part of the interface. */
+#define CTD_FILL_OK 0
+#define CTD_FILL_NO_HOLE 1
+#define CTD_FILL_NO_KNOWN 2
+#define CTD_FILL_MAX_SIDE 8192
+#define CTD_FILL_TILE 64
+
+/* One page of a ctd_fill_rest call (a row of the device page table). */
+typedef struct ctd_fill_page {
+  const uint8_t* page_dev; /* 3 x u8 a pixel, rows `pitch` bytes apart                                      */
+  const uint8_t* hole_dev; /* u8, rows `hole_pitch` bytes apart                                             */
+  uint8_t* out_dev;        /* H x W x 3, rows `out_pitch` bytes apart; overlaps no input                    */
+  int32_t H, W;            /* 1 .. CTD_FILL_MAX_SIDE                                                        */
+  int32_t pitch, hole_pitch, out_pitch; /* >= 3 W, W, 3 W                                                   */
+  int32_t tile0;           /* tiles of the pages before this one                                            */
+  int64_t lvl0;            /* the page's first pyramid dword of scratch_dev                                 */
+} ctd_fill_page;
+
+typedef struct ctd_fill_params {
+  int32_t n_tiles; /* tiles of all pages (tile0 of a page after the last) */
+  int32_t pad_[7];
+} ctd_fill_params;
+
+/* One row of the result. */
+typedef struct ctd_fill_row {
+  int32_t status; /* CTD_FILL_* */
+  int32_t n_hole;
+  int32_t levels;
+  uint8_t top[3];
+  uint8_t pad_[17];
+} ctd_fill_row;
+
+/* The rule above for all pages of a batch in THREE launches on `stream`, whatever the number and sizes of the pages, with no
+ * host wait between them: a pull launch (one workgroup per tile: levels 1 .. 6 and the tile's hole count), a page launch
+ * (one workgroup per page: levels 7 .. T, the push down to level 6, rows_dev[i] for page i) and a push launch (one
+ * workgroup per tile) that writes every byte of every page's `out` exactly once.  n_hole is a sum of integers: no result
+ * depends on an order.  The page table and `params` are read on the host during the call (the table is fetched from the
+ * device behind whatever `stream` holds, before the first launch).  n_pages = 0 launches nothing and returns CTD_OK.  A
+ * null table, row or scratch pointer with n_pages > 0, a negative count, a null page, hole or out pointer, a side < 1 or
+ * > CTD_FILL_MAX_SIDE, a pitch below the row size, a negative lvl0, or tile0 / n_tiles that are not the sums above is an
+ * error rc and launches nothing. */
+int ctd_fill_rest(const ctd_fill_page* pages_dev, int32_t n_pages, const ctd_fill_params* params, void* scratch_dev,
+                  ctd_fill_row* rows_dev, void* stream);
+
 /* ---- the detector tail ------------------------------------------------------ */
 
 /* Everything `TextDetector.__call__` does after `self.net(img_in)` (reference inference.py:148-178) for a
