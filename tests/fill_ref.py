@@ -7,7 +7,9 @@
                one pixel at coordinates clamped to the level.
 
 All three return (out, row): `out` (H,W,3) u8 and `row` = {status, n_hole, levels, top}.  Integers only, so every comparison
-with them is exact.  `material()` is the pages the tests of the rule and of the kernels share."""
+with them is exact.  `material()` is the pages the tests of the rule and of the kernels share, `large_material()` the pages at
+the sizes the page launch is sized for (up to T = 13 and 378 tiles), and `fill_blocks` the rule on a page that is constant on
+aligned 2^s x 2^s blocks, where it scales exactly: the reference of the 8192 x 8192 pages of `capacity_blocks()`."""
 import numpy as np
 
 OK, NO_HOLE, NO_KNOWN = range(3)
@@ -314,3 +316,180 @@ def reference():
             o.setflags(write=False)
         _REFERENCE["r"] = res
     return _REFERENCE["r"]
+
+
+# ---- 5. pages at the sizes the page launch is sized for ------------------------------------------------------------------------
+
+LARGE_SIZES = ((1, 8192), (8192, 1), (65, 8129), (1024, 1024), (1025, 1025), (1100, 1300))
+# what each size gets (about 40 cases in all: `fill_vec` takes a quarter of a second a megapixel); the thin pages have two corners
+_LARGE_PICK = {
+    (1, 8192): ("all", "random0.5", "one_known_0_0", "one_known_0_8191", "islands"),
+    (8192, 1): ("none", "random0.5", "one_known_0_0", "one_known_8191_0", "islands"),
+    (65, 8129): ("random0.5", "one_known_0_0", "one_known_0_8128", "one_known_64_0", "one_known_64_8128", "islands", "big", "seams"),
+    (1024, 1024): ("random0.5", "one_known_0_0", "one_known_1023_1023", "islands", "big", "seams"),
+    (1025, 1025): ("all", "none", "random0.5", "one_known_0_0", "one_known_0_1024", "one_known_1024_0", "one_known_1024_1024",
+                   "islands", "big", "seams"),
+    (1100, 1300): ("none", "random0.5", "one_known_0_1299", "one_known_1099_0", "islands", "big", "seams"),
+}
+
+
+def known_plane(R, l):
+    """k of level l after the pull, from the hole mask alone: a level pixel is known where any child is."""
+    k = R == 0
+    for _ in range(l):
+        h, w = k.shape
+        kp = np.zeros((2 * ((h + 1) // 2), 2 * ((w + 1) // 2)), bool)
+        kp[:h, :w] = k
+        k = kp.reshape(kp.shape[0] // 2, 2, kp.shape[1] // 2, 2).any(axis=(1, 3))
+    return k
+
+
+def _tile_span(n, t0, t1):
+    """Pixels of the whole tiles t0 .. t1 - 1 of an axis of n pixels, or the whole axis where it has too few tiles."""
+    return (t0 * TILE, t1 * TILE) if _dim(n, 6) >= t1 + 2 else (0, n)
+
+
+def large_holes_of(H, W, rng):
+    """{name: R} for one of LARGE_SIZES, every pattern the size allows."""
+    out = {"all": np.full((H, W), 255, np.uint8), "none": np.zeros((H, W), np.uint8)}
+    out["random0.5"] = ((rng.random((H, W)) < 0.5) * rng.integers(1, 256, (H, W))).astype(np.uint8)
+    for cy, cx in dict.fromkeys(((0, 0), (0, W - 1), (H - 1, 0), (H - 1, W - 1))):
+        R = np.full((H, W), 1, np.uint8)
+        R[cy, cx] = 0
+        out[f"one_known_{cy}_{cx}"] = R
+    R = np.full((H, W), 7, np.uint8)                                 # all hole but a few dozen single known pixels
+    R[rng.integers(0, H, 40), rng.integers(0, W, 40)] = 0
+    out["islands"] = R
+    R = np.zeros((H, W), np.uint8)                                   # whole aligned tiles: tile rows 2 .. 7, tile columns 4 .. 9,
+    (ya, yb), (xa, xb) = _tile_span(H, 2, 8), _tile_span(W, 4, 10)   # which hold the aligned 4 x 4 tiles (4 .. 7, 4 .. 7)
+    R[ya:yb, xa:xb] = 255
+    R[max(H - 130, 0):, max(W - 200, 0):] = 255                      # and one flush with the bottom-right corner
+    out["big"] = R
+    R = np.zeros((H, W), np.uint8)                                   # thin bars astride every fourth tile seam
+    for x in range(256, W, 256):
+        R[min(10, H - 1):max(H - 10, 1), x - 2:x + 3] = 255
+    for y in (range(256, H, 256) if H > 256 else range(64, H, 64)):
+        R[y - 1:y + 2, 5:max(W - 5, 6)] = 200
+    out["seams"] = R
+    return out
+
+
+def large_material():
+    """[(name, page, hole mask)] at LARGE_SIZES; pages of noise, the ramp page and a flat colour in turn, the ramp page under
+    the big holes.  Made once, read-only."""
+    if "l" not in _MATERIAL:
+        rng = np.random.default_rng(1419)
+        out = []
+        for H, W in LARGE_SIZES:
+            holes = large_holes_of(H, W, rng)
+            for i, name in enumerate(_LARGE_PICK[(H, W)]):
+                kind = 1 if name == "big" else i % 3
+                page = (rng.integers(0, 256, (H, W, 3), dtype=np.uint8), ramp_page(H, W),
+                        np.full((H, W, 3), (17, 250, 133), np.uint8))[kind]
+                page.setflags(write=False)
+                holes[name].setflags(write=False)
+                out.append((f"{H}x{W}-{name}-{('noise', 'ramp', 'flat')[kind]}", page, holes[name]))
+        _MATERIAL["l"] = out
+    return _MATERIAL["l"]
+
+
+def large_reference():
+    """[(out, row)] of `fill_vec` on `large_material()`: computed once, shared, never changed."""
+    if "l" not in _REFERENCE:
+        res = [fill_vec(p, r) for _, p, r in large_material()]
+        for o, _ in res:
+            o.setflags(write=False)
+        _REFERENCE["l"] = res
+    return _REFERENCE["l"]
+
+
+# ---- 6. pages that are constant on aligned 2^s x 2^s blocks: the rule scales -----------------------------------------------------
+
+def repeat_blocks(A, s):
+    """Every pixel of A as a 2^s x 2^s block."""
+    return np.repeat(np.repeat(A, 1 << s, axis=0), 1 << s, axis=1)
+
+
+def _push_window(fin, c, k):
+    """`push_level` on a WINDOW of the levels: `fin` the finished level l + 1 over some rows and columns, (c, k) level l as
+    pulled over twice as many from twice the origin.  ny and nx are clamped to the window: at an edge of the level that is the
+    rule's clamp, elsewhere it makes the window's outermost rows and columns wrong (see `fill_blocks`)."""
+    n_r, n_c = fin.shape[:2]
+    py, ny = _neighbours(2 * n_r, n_r)
+    px, nx = _neighbours(2 * n_c, n_c)
+    v = (9 * fin[py][:, px] + 3 * fin[py][:, nx] + 3 * fin[ny][:, px] + fin[ny][:, nx] + 8) >> 4
+    return np.where(k[:, :, None], c, v)
+
+
+def fill_blocks(Q, M, s, win=8):
+    """(out, row) of `fill_vec(repeat_blocks(Q, s), repeat_blocks(M, s))` without a full-size plane.  Levels 1 .. s of the pull
+    are the coarser repeats of Q (a mean of equal known values is that value) and level s is (Q, M == 0), so the row is
+    `fill_vec(Q, M)`'s with 4^s times the holes and s more levels, and the finished level s is `fill_vec(Q, M)`'s output; the
+    levels s - 1 .. 0 are plain pushes from it.  These run on windows of Q around the hole blocks (runs of `win` x `win`
+    blocks that hold one) widened by ONE block: a level-l pixel needs its parent and the parent's neighbour, so of a window
+    whose level-(l + 1) rows from r on are right the level-l rows from 2 r - 1 on are right, and 2 (2^j y0 - 1) - 1 stays
+    below 2^(j + 1) y0: what the window's clamp spoils never reaches the rows and columns that are kept."""
+    f = 1 << s
+    H, W = M.shape
+    o, r = fill_vec(Q, M)
+    out = repeat_blocks(Q, s)
+    row = dict(r, n_hole=r["n_hole"] * f * f, levels=r["levels"] + s)
+    if row["status"] != OK or s == 0:
+        return (out if s else o), row
+    known = M == 0
+    gh, gw = (H + win - 1) // win, (W + win - 1) // win
+    pad = np.zeros((gh * win, gw * win), bool)
+    pad[:H, :W] = ~known
+    grid = pad.reshape(gh, win, gw, win).any(axis=(1, 3))
+    for i in range(gh):
+        edges = np.flatnonzero(np.diff(np.concatenate(([0], grid[i].astype(np.int8), [0]))))
+        for j0, j1 in zip(edges[::2], edges[1::2]):                  # a run of windows with a hole block
+            y0, y1, x0, x1 = win * i, min(win * (i + 1), H), win * int(j0), min(win * int(j1), W)
+            a0, a1, b0, b1 = max(y0 - 1, 0), min(y1 + 1, H), max(x0 - 1, 0), min(x1 + 1, W)
+            fin = o[a0:a1, b0:b1].astype(np.int32)
+            for l in range(s - 1, -1, -1):
+                fin = _push_window(fin, repeat_blocks(Q[a0:a1, b0:b1], s - l).astype(np.int32), repeat_blocks(known[a0:a1, b0:b1], s - l))
+            out[f * y0:f * y1, f * x0:f * x1] = fin[f * (y0 - a0):f * (y1 - a0), f * (x0 - b0):f * (x1 - b0)]
+    return out, row
+
+
+def block_mask(n, rng):
+    """The hole blocks of the capacity page, n x n (n = 1024 for the page of 8192 x 8192 at s = 3; a smaller n has the same
+    parts in proportion): a large hole at an offset that is no multiple of 8 blocks, so that it covers whole tiles and cuts
+    others; a square hole flush with each corner; a bar one block wide along the whole right and bottom edge; scattered single
+    hole blocks."""
+    M = np.zeros((n, n), np.uint8)
+    y, x, h, w, c = 301 * n // 1024, 227 * n // 1024, 160 * n // 1024, 200 * n // 1024, 24 * n // 1024
+    M[y:y + h, x:x + w] = 255
+    for ys in (slice(0, c), slice(n - c, n)):
+        for xs in (slice(0, c), slice(n - c, n)):
+            M[ys, xs] = 9
+    M[:, n - 1] = 1
+    M[n - 1, :] = 128
+    k = max(300 * n * n // (1024 * 1024), 4)
+    M[rng.integers(0, n, k), rng.integers(0, n, k)] = 77
+    return M
+
+
+def capacity_blocks(deep=False):
+    """(Q, M, s) of the capacity page, 8192 x 8192 = `repeat_blocks` of 1024 x 1024 noise and `block_mask(1024)` at s = 3: every
+    64 x 64 tile holds 64 block colours.  Noise averages out, though: from level 10 on every pixel of that page is known and
+    127 or 128, so a wrong layout of the top levels would go unseen.  `deep` is its companion: a ramp under weak noise, whose
+    means differ from place to place, and aligned square holes of 4096, 2048 and 1024 pixels, so that levels 6 .. 12 all have
+    unknown pixels and a quarter of the page hangs on the top level alone.  Made once, read-only."""
+    key = "d" if deep else "c"
+    if key not in _MATERIAL:
+        rng = np.random.default_rng(8192 + deep)
+        if deep:
+            Q = (ramp_page(1024, 1024).astype(np.int64) * 7 // 8 + rng.integers(0, 32, (1024, 1024, 3))).astype(np.uint8)
+            M = np.zeros((1024, 1024), np.uint8)
+            M[512:, :512] = 255                                      # a pixel of level 12
+            M[:256, 512:768] = 2                                     # of level 11
+            M[384:512, 128:256] = 1                                  # of level 10
+            M[rng.integers(0, 1024, 300), rng.integers(0, 1024, 300)] = 77
+        else:
+            Q, M = rng.integers(0, 256, (1024, 1024, 3), dtype=np.uint8), block_mask(1024, rng)
+        Q.setflags(write=False)
+        M.setflags(write=False)
+        _MATERIAL[key] = (Q, M, 3)
+    return _MATERIAL[key]

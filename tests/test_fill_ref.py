@@ -118,6 +118,139 @@ def test_fill_tables_plans_the_levels_and_the_scratch():
     assert F.PAGE_DTYPE.itemsize == 56 and F.ROW_DTYPE.itemsize == 32 and F.PAGE_DTYPE.fields["lvl0"][1] == 48
 
 
+def test_large_material_is_what_the_page_launch_needs():
+    """The six sizes plan T = 13, 13, 13, 10, 11, 11 and 128, 128, 256, 256, 289, 378 tiles; every pattern of every size is
+    there once; all three statuses occur; every size above 256 tiles has an OK page whose level-6 plane has unknown pixels,
+    and so has one at 256; the pages and masks are read-only."""
+    F = pkg().fill
+    tile0, n_tiles, lvl0, dwords, levels = F.fill_tables(R.LARGE_SIZES)
+    tiles = [128, 128, 2 * 128, 16 * 16, 17 * 17, 18 * 21]
+    assert levels.tolist() == [13, 13, 13, 10, 11, 11] and n_tiles == sum(tiles)
+    assert tile0.tolist() == [sum(tiles[:i]) for i in range(6)]
+    assert [len(R.level_shapes(h, w)) - 1 for h, w in R.LARGE_SIZES] == levels.tolist()
+    assert [R.level_shapes(h, w)[6] for h, w in R.LARGE_SIZES] == [(1, 128), (128, 1), (2, 128), (16, 16), (17, 17), (18, 21)]
+    assert all(a % 2 for lv in R.level_shapes(65, 8129)[1:6] for a in lv[1:]) and R.level_shapes(65, 8129)[6][1] == 128
+    assert [lv[0] for lv in R.level_shapes(1025, 1025)[6:]] == [17, 9, 5, 3, 2, 1]
+    material, want = R.large_material(), R.large_reference()
+    names = [m[0] for m in material]
+    assert len(names) == len(set(names)) <= 42 and len(want) == len(names)
+    assert R.large_material() is material and R.large_reference() is want
+    deep = {}
+    for (name, page, hole), (out, row) in zip(material, want):
+        assert not page.flags.writeable and not hole.flags.writeable and not out.flags.writeable
+        assert (hole.shape in R.LARGE_SIZES) and page.shape == hole.shape + (3,) and name.startswith("%dx%d-" % hole.shape)
+        assert row["n_hole"] == int((hole != 0).sum()) and row["levels"] == len(R.level_shapes(*hole.shape)) - 1
+        assert np.array_equal(out[hole == 0], page[hole == 0]), name
+        k6 = R.known_plane(hole, 6)
+        assert k6.shape == R.level_shapes(*hole.shape)[6]
+        if row["status"] == R.OK and not k6.all():
+            deep.setdefault(hole.shape, []).append(name)
+        if "-one_known_" in name:
+            cy, cx = np.argwhere(hole == 0)[0]
+            assert (out == page[cy, cx]).all() and row["top"] == page[cy, cx].tolist() and int(k6.sum()) == 1, name
+        if name.endswith("-flat") and row["status"] == R.OK:
+            assert (out == page).all(), name
+    assert sorted({w[1]["status"] for w in want}) == [R.OK, R.NO_HOLE, R.NO_KNOWN]
+    assert set(deep) == set(R.LARGE_SIZES), deep
+    for size in R.LARGE_SIZES[3:]:
+        assert any("-big-" in n for n in deep[size]) and any("-islands-" in n for n in deep[size]), deep[size]
+    # the big holes leave unknown pixels next to known ones on every level below the top (the corner one: the last row and
+    # column of the odd planes), the islands mix n = 1, 2, 3 above level 6
+    i = names.index("1025x1025-big-ramp")
+    for l in (6, 7, 8, 9, 10):
+        k = R.known_plane(material[i][2], l)
+        assert k.any() and not k.all(), l
+    i = names.index("1025x1025-islands-" + ("noise", "ramp", "flat")[7 % 3])
+    k = R.known_plane(material[i][2], 6)
+    kp = np.zeros((18, 18), int)
+    kp[:17, :17] = k
+    assert {1, 2, 3} <= set(kp.reshape(9, 2, 9, 2).sum(axis=(1, 3)).ravel().tolist())
+
+
+def test_the_emulated_launches_equal_the_rule_on_the_large_pages():
+    """`fill_emul` -- strided tile loops, the halo's index ranges, the level layout -- against `fill_vec` on every large case
+    of at most 70 000 pixels, and on the two `one_known` cases of 1025 x 1025 at opposite corners (the emulation is slow)."""
+    material, want = R.large_material(), R.large_reference()
+    n = 0
+    for (name, page, hole), (out, row) in zip(material, want):
+        if hole.size <= 70000 or name in ("1025x1025-one_known_0_0-noise", "1025x1025-one_known_1024_1024-noise"):
+            o2, r2 = R.fill_emul(page, hole)
+            assert r2 == row and np.array_equal(o2, out), name
+            n += 1
+    assert n == 12
+
+
+def _block_cases():
+    """[(name, Q, M)]: Q from 1 x 1 to 130 x 170 under the hole patterns of `holes_of` (the random ones, the checker, one known
+    pixel at a corner, single holes at every edge and corner), and the capacity page's parts at 128 x 128."""
+    rng = np.random.default_rng(77)
+    out = []
+    for H, W in ((1, 1), (1, 7), (9, 1), (5, 6), (17, 23), (63, 65), (130, 170)):
+        for i, (name, M) in enumerate(R.holes_of(H, W, rng)):
+            if (H, W) == (130, 170) and name in ("all", "none", "random0.02", "random0.98", "singles01", "singles10"):
+                continue
+            Q = (rng.integers(0, 256, (H, W, 3), dtype=np.uint8), R.ramp_page(H, W))[i % 2]
+            out.append((f"{H}x{W}-{name}", Q, M))
+    M = np.zeros((40, 50), np.uint8)                                # holes flush with every edge and corner, and one inside
+    M[:3, :4] = M[:5, -2:] = M[-1:, :9] = M[-6:, -7:] = M[17:22, :1] = M[:2, 20:31] = M[-3:, 25:27] = M[11:19, -1:] = M[9:25, 13:30] = 3
+    out.append(("40x50-edges", rng.integers(0, 256, (40, 50, 3), dtype=np.uint8), M))
+    out.append(("128x128-capacity-parts", rng.integers(0, 256, (128, 128, 3), dtype=np.uint8), R.block_mask(128, rng)))
+    M = np.zeros((128, 128), np.uint8)                              # and its companion's: aligned squares, a quarter of the page
+    M[64:, :64], M[:32, 64:96], M[48:64, 16:32] = 255, 2, 1
+    M[rng.integers(0, 128, 5), rng.integers(0, 128, 5)] = 77
+    out.insert(-1, ("128x128-deep-parts", R.ramp_page(128, 128), M))
+    return out
+
+
+@pytest.mark.parametrize("s", [1, 2, 3])
+def test_fill_blocks_equals_the_rule_on_the_repeated_page(s):
+    """`fill_blocks(Q, M, s)` == `fill_vec(repeat(Q), repeat(M))`, every byte and the row: the reference of the capacity page
+    is the rule itself."""
+    n_ok = 0
+    for name, Q, M in _block_cases():
+        out, row = R.fill_blocks(Q, M, s)
+        o2, r2 = R.fill_vec(R.repeat_blocks(Q, s), R.repeat_blocks(M, s))
+        assert row == r2, (name, row, r2)
+        assert out.dtype == np.uint8 and np.array_equal(out, o2), (name, int((out != o2).any(axis=2).sum()))
+        n_ok += row["status"] == R.OK
+    assert n_ok >= 40
+    Q, M = _block_cases()[-1][1:]
+    for win in (1, 3, 200):                                          # whatever the windows
+        assert np.array_equal(R.fill_blocks(Q, M, s, win=win)[0], R.fill_blocks(Q, M, s)[0])
+    assert np.array_equal(R.fill_blocks(Q, M, 0)[0], R.fill_vec(Q, M)[0])
+
+
+def test_capacity_blocks_reach_every_level_of_the_page_launch():
+    """The capacity page's blocks: 1024 x 1024 at s = 3 is 8192 x 8192 with T = 13 and 16 384 tiles; the large hole starts at no
+    multiple of 8 blocks, covers whole tiles and cuts others, and leaves unknown pixels on levels 6 .. 9 but not 10; every
+    corner and the whole right and bottom edge are hole; a tile holds 64 block colours."""
+    Q, M, s = R.capacity_blocks()
+    assert Q.shape == (1024, 1024, 3) and M.shape == (1024, 1024) and s == 3 and R.capacity_blocks()[0] is Q
+    plan = pkg().fill.fill_tables([(8192, 8192)])
+    assert plan[1] == 16384 and plan[4].tolist() == [13]
+    ys, xs = np.flatnonzero((M == 255).any(axis=1)), np.flatnonzero((M == 255).any(axis=0))
+    assert (ys[0] % 8, xs[0] % 8, len(ys), len(xs)) == (5, 3, 160, 200)
+    assert [bool(R.known_plane(M, l - 3).all()) for l in (6, 7, 8, 9, 10)] == [False, False, False, False, True]
+    holes_per_tile = (M != 0).reshape(128, 8, 128, 8).sum(axis=(1, 3))
+    assert (holes_per_tile == 64).sum() >= 19 * 24 and ((holes_per_tile > 0) & (holes_per_tile < 64)).sum() > 300
+    assert M[0, 0] and M[0, -1] and M[-1, 0] and M[-1, -1] and M[:, -1].all() and M[-1, :].all()
+    assert 250 <= int((M == 77).sum()) <= 300
+    assert len(np.unique(Q[:8, :8].reshape(64, 3), axis=0)) == 64
+    out, row = R.fill_vec(Q, M)
+    assert row["status"] == R.OK and row["levels"] == 10
+    # noise averages out: the top levels of that page are all alike, and its companion's are not
+    c, k = Q.astype(np.int64), M == 0
+    for _ in range(7):
+        c, k = R.pull_level(c, k)
+    assert k.all() and int(np.ptp(c)) <= 8                          # means of >= 5000 bytes of noise each: sigma about 1
+    Q2, M2, s2 = R.capacity_blocks(deep=True)
+    assert s2 == 3 and [bool(R.known_plane(M2, l - 3).all()) for l in range(6, 14)] == [False] * 7 + [True]
+    c, k = Q2.astype(np.int64), M2 == 0
+    for _ in range(7):
+        c, k = R.pull_level(c, k)
+    assert not k.all() and int(np.ptp(c[k][:, 0])) > 100 and R.fill_vec(Q2, M2)[1]["status"] == R.OK
+
+
 def test_fill_rest_refuses_bad_arguments():
     F = pkg().fill
     page, hole = np.zeros((20, 30, 3), np.uint8), np.zeros((20, 30), np.uint8)
