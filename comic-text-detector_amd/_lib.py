@@ -36,6 +36,8 @@ BALLOON_MAX_WORDS, BALLOON_MAX_REACH, BALLOON_MIN_REACH_MIN, BALLOON_MAX_REACH_M
 BALLOON_CUT_LEFT, BALLOON_CUT_TOP, BALLOON_CUT_RIGHT, BALLOON_CUT_BOTTOM = 1, 2, 4, 8
 FILL_OK, FILL_NO_HOLE, FILL_NO_KNOWN = range(3)
 FILL_MAX_SIDE, FILL_TILE = 8192, 64
+LAYOUT_OK, LAYOUT_NO_REGION, LAYOUT_EMPTY = range(3)
+LAYOUT_MAX_INSET = 16
 
 
 class CtdTensor(C.Structure):
@@ -138,6 +140,19 @@ class CtdBalloonRow(C.Structure):
                 ("sum_x", C.c_int64), ("sum_y", C.c_int64)]
 
 
+class CtdLayoutJob(C.Structure):
+    _fields_ = [("win", C.c_int32 * 4), ("ax", C.c_int32), ("ay", C.c_int32), ("word0", C.c_int64)]
+
+
+class CtdLayoutParams(C.Structure):
+    _fields_ = [("inset", C.c_int32), ("max_words", C.c_int32), ("n_rows", C.c_int32), ("pad_", C.c_int32)]
+
+
+class CtdLayoutRow(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_inner", C.c_int32), ("area", C.c_int32), ("rect", C.c_int32 * 4),
+                ("a_area", C.c_int32), ("a_rect", C.c_int32 * 4)]
+
+
 class CtdFillPage(C.Structure):
     _fields_ = [("page_dev", C.c_void_p), ("hole_dev", C.c_void_p), ("out_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32),
                 ("pitch", C.c_int32), ("hole_pitch", C.c_int32), ("out_pitch", C.c_int32), ("tile0", C.c_int32),
@@ -184,6 +199,7 @@ SYMBOLS = {
     "ctd_line_colors": (_i32, [_vp, _i32, _vp, _vp]),
     "ctd_erase_text": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(CtdEraseParams), _vp, _vp]),
     "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
+    "ctd_layout_boxes": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdLayoutParams), _vp, _vp]),
     "ctd_fill_rest": (_i32, [_vp, _i32, C.POINTER(CtdFillParams), _vp, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),

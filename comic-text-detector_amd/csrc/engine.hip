@@ -1417,6 +1417,20 @@ int ctd_balloon_regions(const ctd_balloon_job* jobs_dev, int32_t n, const ctd_er
   return CTD_OK;
 }
 
+int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloon_row* balloon_rows_dev,
+                     const uint64_t* bits_dev, const ctd_layout_params* params, ctd_layout_row* rows_dev, void* stream) {
+  if (n < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
+  const ctd_layout_params prm = *params;
+  if (prm.inset < 0 || prm.inset > CTD_LAYOUT_MAX_INSET || prm.max_words < 0 || prm.max_words > CTD_BALLOON_MAX_WORDS ||
+      prm.n_rows < 0)
+    return fail(CTD_ERR_INVALID, "layout: inset 0..16, max_words 0..8192, n_rows >= 0");
+  if (n == 0) return CTD_OK;
+  if (!jobs_dev || !balloon_rows_dev || !rows_dev || (prm.max_words > 0 && !bits_dev)) return fail(CTD_ERR_INVALID, "null pointer");
+  HIP_TRY(launch_layout_boxes(jobs_dev, n, balloon_rows_dev, bits_dev, prm, rows_dev, (hipStream_t)stream));
+  return CTD_OK;
+}
+
 int ctd_fill_rest(const ctd_fill_page* pages_dev, int32_t n_pages, const ctd_fill_params* params, void* scratch_dev,
                   ctd_fill_row* rows_dev, void* stream) {
   if (n_pages < 0) return fail(CTD_ERR_INVALID, "bad sizes");

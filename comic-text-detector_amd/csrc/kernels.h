@@ -191,6 +191,12 @@ hipError_t launch_balloon_regions(const ctd_balloon_job* jobs, int n, const ctd_
                                   const ctd_erase_row* erase_rows, const ctd_balloon_params& prm, ctd_balloon_row* rows,
                                   uint64_t* bits, hipStream_t st);
 
+// ---- kernels_layout.hip ---------------------------------------------------------
+// ctd_layout_boxes' one launch (one workgroup per block; n >= 1, prm checked by the caller): raises the kernel's dynamic
+// LDS limit once per device, launches, and returns what hipGetLastError says right after the launch
+hipError_t launch_layout_boxes(const ctd_layout_job* jobs, int n, const ctd_balloon_row* balloon_rows,
+                               const uint64_t* bits, const ctd_layout_params& prm, ctd_layout_row* rows, hipStream_t st);
+
 // ---- kernels_fill.hip -----------------------------------------------------------
 // ctd_fill_rest's three launches (pull per tile, the page launch, push per tile; n_pages >= 1, n_tiles >= 1 and the page
 // table checked by the caller): raises the page kernel's dynamic LDS limit once per device and returns what hipGetLastError

@@ -594,6 +594,23 @@ class TextDetector:
             torch.cuda.current_stream(dev).wait_event(ev)
         return balloons.balloon_regions(pages, masks, blk_lists, erased=erased, device=dev, **kw)
 
+    def layout_boxes(self, pages: Sequence[Page], results, erased=None, regions=None, inset: int = 2, **balloon_kw):
+        """The box a typesetter lays the translated text into, for every block of a detected batch: the largest axis-aligned
+        rectangle inside the block's balloon region, `inset` pixels off its outline, and the largest one that contains the
+        centre of the block's box, ((x1 + x2) >> 1, (y1 + y2) >> 1) of the box clipped to the page -- one launch behind the
+        balloon launch (`layout.layout_boxes`; returns its `LayoutBoxes`).  `results`: what `detect_batch` / `detect_stream`
+        returned for `pages`.  `regions`: the `BalloonRegions` of `balloons(pages, results)` where the caller has them;
+        otherwise that runs first, with `erased` and `balloon_kw`.  Builds no `TextBlock` of a `BlockList`."""
+        from . import erase, layout
+        layout.check_params(inset)
+        if regions is None:
+            regions = self.balloons(pages, results, erased=erased, **balloon_kw)
+        boxes = [erase._page_boxes(r[2]) for r in results]
+        anchors = layout.box_anchors(boxes, [tuple(p.shape[:2]) for p in pages])
+        if len(anchors) != len(regions):
+            raise ValueError("`regions` is not the result of balloons on these pages and blocks")
+        return layout.layout_boxes(regions, anchors, inset=inset)
+
     def fill_rest(self, pages: Sequence[Page], results, erased=None, **erase_kw):
         """The pages of a detected batch with NO text left, on the detector's device: the text on plain backgrounds erased
         (`erase_text`) and the mask that leaves filled smoothly by pull-push (`fill.fill_rest` on the erased pages and their

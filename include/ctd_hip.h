@@ -694,6 +694,72 @@ typedef struct ctd_fill_row {
 int ctd_fill_rest(const ctd_fill_page* pages_dev, int32_t n_pages, const ctd_fill_params* params, void* scratch_dev,
                   ctd_fill_row* rows_dev, void* stream);
 
+/* ---- layout boxes: the largest free rectangle in every balloon (added within ABI v10) ------------------------------- */
+
+/* An addition to ABI v10 like the four above: one entry point, three structs, nothing existing changes.
+ * A typesetter lays translated text into a box, not into a bit plane.  This is the step from the balloon section's region
+ * to that box, for every block of a batch, this library's own rule, integers only: the largest axis-aligned rectangle
+ * inside the region, and the largest one that still contains the spot the old text stood on, both with a margin to the
+ * outline.  Restated in numpy in tests/layout_ref.py.  It builds on the balloon section's Win_b (ww x wh pixels at
+ * (wx1, wy1), nw words a row), B_b and word0.
+ * Parameters: inset m (0 .. CTD_LAYOUT_MAX_INSET, default 2), the margin in pixels.
+ *   E_b     the inner plane: a pixel p of Win_b is in E_b when every pixel q with |qx - px| <= m and |qy - py| <= m lies
+ *           inside the window and in B_b: the erosion of B_b by a (2m + 1)-square, clipped at the window.  A page edge
+ *           erodes like any other edge.  With m = 0, E_b = B_b.
+ *   rectangles  x1, y1, x2, y2 with x2 and y2 exclusive, x1 < x2, y1 < y2, every pixel in E_b.
+ *   order   rectangle R is better than S when it has the larger area; at equal area the smaller y1 wins, then the smaller
+ *           x1, then the smaller y2.  The order is total and a best rectangle is a maximal one, so the answer is a
+ *           function of the plane alone, whatever scheme enumerates the candidates.
+ *   rect    the best rectangle of E_b.
+ *   a_rect  the best rectangle among those that contain the block's anchor pixel (ax, ay), given in page coordinates.
+ *           Where the anchor is no pixel of E_b (or lies outside the window) a_area = 0 and a_rect is all 0.
+ * status, the first that applies:
+ *   CTD_LAYOUT_NO_REGION  the job's index is no row of the balloon row table (it is params.n_rows or more), the block's
+ *                         balloon row has a status other than CTD_BALLOON_OK, or the window holds more than
+ *                         params.max_words words (its balloon row is TOO_LARGE anyway): every other field of the row is 0.
+ *   CTD_LAYOUT_EMPTY      E_b has no pixel: every other field of the row is 0.
+ *   CTD_LAYOUT_OK
+ * Row per block, 48 bytes, twelve int32, no padding: status; n_inner = |E_b|; area and rect; a_area and a_rect.  Rectangles
+ * are in page coordinates.  Areas fit int32: a window has at most 8192 x 64 pixels.
+ * Limits: an L-shaped balloon gets its larger arm; rotated text gets an axis-aligned box; a region that leaked through a gap
+ * in the outline gives a box cut at the window, and the balloon row's flags say so. */
+#define CTD_LAYOUT_OK 0
+#define CTD_LAYOUT_NO_REGION 1
+#define CTD_LAYOUT_EMPTY 2
+#define CTD_LAYOUT_MAX_INSET 16
+
+/* One block of a layout call (a row of the device job table).  Job i belongs to row i of the balloon row table. */
+typedef struct ctd_layout_job {
+  int32_t win[4]; /* the block's window x1, y1, x2, y2 in page coordinates, as the balloon call's caller laid it out */
+  int32_t ax, ay; /* the anchor, page coordinates                                                                      */
+  int64_t word0;  /* the block's first word of bits_dev                                                                */
+} ctd_layout_job;
+
+typedef struct ctd_layout_params {
+  int32_t inset;
+  int32_t max_words; /* the largest nw * wh <= CTD_BALLOON_MAX_WORDS among the call's blocks: sizes the launch's LDS */
+  int32_t n_rows;    /* the rows of balloon_rows_dev: a job at or beyond it is NO_REGION and reads none of the table  */
+  int32_t pad_;
+} ctd_layout_params;
+
+/* One row of the result. */
+typedef struct ctd_layout_row {
+  int32_t status; /* CTD_LAYOUT_* */
+  int32_t n_inner;
+  int32_t area;
+  int32_t rect[4];
+  int32_t a_area;
+  int32_t a_rect[4];
+} ctd_layout_row;
+
+/* The rule above for n blocks in ONE launch on `stream`, one workgroup per block: rows_dev[i] is job i's.
+ * balloon_rows_dev and bits_dev may be the rows_dev and bits_dev of a balloon call earlier on the same stream (no host step
+ * between them); bits_dev is read only, 8-byte aligned; rows_dev needs 4-byte alignment.  `params` is read on the host during
+ * the call.  n = 0 launches nothing.  inset outside 0 .. 16, max_words outside 0 .. 8192, a negative n or n_rows, or a missing
+ * table with n > 0 is an error rc and launches nothing (bits_dev may be NULL where max_words is 0). */
+int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloon_row* balloon_rows_dev,
+                     const uint64_t* bits_dev, const ctd_layout_params* params, ctd_layout_row* rows_dev, void* stream);
+
 /* ---- the detector tail ------------------------------------------------------ */
 
 /* Everything `TextDetector.__call__` does after `self.net(img_in)` (reference inference.py:148-178) for a
