@@ -38,6 +38,8 @@ FILL_OK, FILL_NO_HOLE, FILL_NO_KNOWN = range(3)
 FILL_MAX_SIDE, FILL_TILE = 8192, 64
 LAYOUT_OK, LAYOUT_NO_REGION, LAYOUT_EMPTY = range(3)
 LAYOUT_MAX_INSET = 16
+TYPESET_MAX_SIDE, TYPESET_MAX_RADIUS, TYPESET_TILE_W, TYPESET_TILE_H = 8192, 12, 64, 32
+TYPESET_OK, TYPESET_EMPTY, TYPESET_OUTSIDE = range(3)          # typeset.typeset_tables' status column (not part of the ABI)
 
 
 class CtdTensor(C.Structure):
@@ -153,6 +155,29 @@ class CtdLayoutRow(C.Structure):
                 ("a_area", C.c_int32), ("a_rect", C.c_int32 * 4)]
 
 
+class CtdTypesetPage(C.Structure):
+    _fields_ = [("page_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int64)]
+
+
+class CtdTypesetLayer(C.Structure):
+    _fields_ = [("cov0", C.c_int64), ("page", C.c_int32), ("x0", C.c_int32), ("y0", C.c_int32), ("w", C.c_int32), ("h", C.c_int32),
+                ("cov_pitch", C.c_int32), ("clip", C.c_int32 * 4), ("fill", C.c_uint8 * 3), ("stroke", C.c_uint8 * 3),
+                ("radius", C.c_uint8), ("pad_", C.c_uint8)]
+
+
+class CtdTypesetTile(C.Structure):
+    _fields_ = [("page", C.c_int32), ("tx", C.c_int32), ("ty", C.c_int32), ("first", C.c_int32)]
+
+
+class CtdTypesetParams(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("n_pages", C.c_int32), ("n_tiles", C.c_int32), ("n_entries", C.c_int32),
+                ("cov_bytes", C.c_int64), ("pad_", C.c_int64)]
+
+
+class CtdTypesetRow(C.Structure):
+    _fields_ = [("n_fill", C.c_int32), ("n_stroke", C.c_int32)]
+
+
 class CtdFillPage(C.Structure):
     _fields_ = [("page_dev", C.c_void_p), ("hole_dev", C.c_void_p), ("out_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32),
                 ("pitch", C.c_int32), ("hole_pitch", C.c_int32), ("out_pitch", C.c_int32), ("tile0", C.c_int32),
@@ -200,6 +225,7 @@ SYMBOLS = {
     "ctd_erase_text": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(CtdEraseParams), _vp, _vp]),
     "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
     "ctd_layout_boxes": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdLayoutParams), _vp, _vp]),
+    "ctd_typeset": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(CtdTypesetParams), _vp, _vp]),
     "ctd_fill_rest": (_i32, [_vp, _i32, C.POINTER(CtdFillParams), _vp, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),

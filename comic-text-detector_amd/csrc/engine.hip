@@ -1431,6 +1431,23 @@ int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloo
   return CTD_OK;
 }
 
+int ctd_typeset(const ctd_typeset_page* pages_dev, const ctd_typeset_layer* layers_dev, const ctd_typeset_tile* tiles_dev,
+                const int32_t* entries_dev, const uint8_t* cov_dev, const ctd_typeset_params* params,
+                ctd_typeset_row* rows_dev, void* stream) {
+  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
+  const ctd_typeset_params prm = *params;
+  if (prm.n_layers < 0 || prm.n_pages < 0 || prm.n_tiles < 0 || prm.n_entries < 0 || prm.cov_bytes < 0)
+    return fail(CTD_ERR_INVALID, "bad sizes");
+  if ((prm.n_pages > 0 && !pages_dev) || (prm.n_layers > 0 && (!layers_dev || !rows_dev)) || (prm.n_tiles > 0 && !tiles_dev) ||
+      (prm.n_entries > 0 && !entries_dev) || (prm.cov_bytes > 0 && !cov_dev))
+    return fail(CTD_ERR_INVALID, "null pointer");
+  if (prm.n_layers == 0) return CTD_OK;
+  HIP_TRY(hipMemsetAsync(rows_dev, 0, (size_t)prm.n_layers * sizeof(ctd_typeset_row), (hipStream_t)stream));
+  if (prm.n_tiles == 0) return CTD_OK;
+  HIP_TRY(launch_typeset(pages_dev, layers_dev, tiles_dev, entries_dev, cov_dev, prm, rows_dev, (hipStream_t)stream));
+  return CTD_OK;
+}
+
 int ctd_fill_rest(const ctd_fill_page* pages_dev, int32_t n_pages, const ctd_fill_params* params, void* scratch_dev,
                   ctd_fill_row* rows_dev, void* stream) {
   if (n_pages < 0) return fail(CTD_ERR_INVALID, "bad sizes");

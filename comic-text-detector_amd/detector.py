@@ -611,6 +611,39 @@ class TextDetector:
             raise ValueError("`regions` is not the result of balloons on these pages and blocks")
         return layout.layout_boxes(regions, anchors, inset=inset)
 
+    def typeset(self, pages: Sequence[Page], boxes, bitmaps, fill=(0, 0, 0), stroke=(255, 255, 255), radius=0,
+                prefer: str = "a_rect", inplace: bool = False):
+        """The translated text back in the pages, on the detector's device: one layer per block of `boxes` (the `LayoutBoxes`
+        of `layout_boxes`) that is `ok` and has a bitmap, composited with an outline in one launch (`typeset.typeset_pages`;
+        returns its `TypesetPages`).  `pages`: normally `fill_rest(...).pages`.  `bitmaps[j]`: block j's text rendered by any
+        font engine as a (h, w) uint8 coverage array, or None to skip the block.  A bitmap is centred (`typeset.place`) in the
+        block's `a_rect` where `prefer` is "a_rect" and `a_area > 0`, else in its `rect`, and clipped to the page.  fill /
+        stroke (RGB) and radius: one for all blocks or one per block.  The result's `layer_of[j]` is block j's layer, -1
+        where it was skipped; `fits[i]` says whether layer i with its outline fits its rectangle."""
+        from . import typeset as ts
+        if prefer not in ("a_rect", "rect"):
+            raise ValueError('prefer: "a_rect" or "rect"')
+        nb = len(boxes)
+        if len(bitmaps) != nb:
+            raise ValueError("one bitmap (or None) per block of `boxes`")
+        take = np.array([bool(boxes.ok[j]) and bitmaps[j] is not None for j in range(nb)], bool)
+        idx = np.flatnonzero(take)
+        layer_of = np.full((nb,), -1, np.int64)
+        layer_of[idx] = np.arange(len(idx))
+        fill, stroke = ts._per_layer(fill, nb, 3, "fill")[idx], ts._per_layer(stroke, nb, 3, "stroke")[idx]
+        radius = ts._per_layer(radius, nb, 1, "radius")[idx, 0]
+        maps = [bitmaps[j] for j in idx]
+        for b in maps:
+            if not isinstance(b, np.ndarray) or b.ndim != 2:
+                raise ValueError("a bitmap is a (h, w) uint8 numpy array")
+        anchored = (np.asarray(boxes.a_area) > 0) if prefer == "a_rect" else np.zeros((nb,), bool)
+        rects = np.where(anchored[:, None], boxes.a_rect, boxes.rect).reshape(nb, 4)[idx]
+        xy, fits = ts.place(rects, np.array([b.shape for b in maps], np.int64).reshape(len(idx), 2), radius)
+        out = ts.typeset_pages(pages, boxes.index[idx, 0], maps, xy, fill=fill, stroke=stroke, radius=radius, inplace=inplace,
+                               device=self.net.device)
+        out.layer_of, out.fits = layer_of, fits
+        return out
+
     def fill_rest(self, pages: Sequence[Page], results, erased=None, **erase_kw):
         """The pages of a detected batch with NO text left, on the detector's device: the text on plain backgrounds erased
         (`erase_text`) and the mask that leaves filled smoothly by pull-push (`fill.fill_rest` on the erased pages and their

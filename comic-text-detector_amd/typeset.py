@@ -1,0 +1,278 @@
+"""Typeset: text layers with outlines composited into pages, on the GPU.
+
+`layout_boxes` gives the box to lay the translated text into; any font engine renders that text into 8-bit coverage bitmaps.
+This is the step that puts them into the device pages, with the outline that is the standard manga treatment:
+
+    tp = typeset_pages(fp.pages, page_of, bitmaps, xy, fill=(0, 0, 0), stroke=(255, 255, 255), radius=3)
+    tp.pages[i]                                          # or TextDetector.typeset(fp.pages, lb, bitmaps, radius=3)
+
+packs the bitmaps into one buffer, builds the tile table with numpy (`typeset_tables`: the touched 64 x 32 tiles of all pages
+and, per tile, its layers in ascending order), uploads coverage and tables once, makes ONE `ctd_typeset` call
+(csrc/kernels_typeset.hip: one launch, one workgroup per touched tile, the coverage patch of each layer in LDS) and downloads
+one small table.  The rule is integers only and stated in include/ctd_hip.h (restated in numpy in tests/typeset_ref.py;
+DESIGN.md section 4.21 has its limits): the outline S is the max of the coverage F over a disk of `radius` pixels, and a
+pixel becomes blend(blend(page, stroke, S), fill, F) with blend(c, k, a) = (c (255 - a) + k a + 127) / 255; layers are applied
+in the order given.  Glyph rasterisation stays a font engine's job.  There is no per-layer Python beyond packing the bitmaps
+and no CPU fallback: without a GPU it raises `CtdError` like the rest of the package.
+"""
+from __future__ import annotations
+
+import contextlib
+import ctypes as C
+from typing import List, Optional, Sequence
+
+import numpy as np
+import torch
+
+from . import _lib as L
+from .colors import _shape_of
+from .regions import Page, _device_pages
+
+__all__ = ["typeset_pages", "TypesetPages", "typeset_tables", "place", "PAGE_DTYPE", "LAYER_DTYPE", "TILE_DTYPE", "ROW_DTYPE"]
+
+# numpy views of `ctd_typeset_page` / `_layer` / `_tile` / `_row` (include/ctd_hip.h; the _lib.CtdTypeset* mirrors)
+PAGE_DTYPE = np.dtype([("page_dev", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i8")])
+LAYER_DTYPE = np.dtype([("cov0", "<i8"), ("page", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"),
+                        ("cov_pitch", "<i4"), ("clip", "<i4", (4,)), ("fill", "u1", (3,)), ("stroke", "u1", (3,)),
+                        ("radius", "u1"), ("pad_", "u1")])
+TILE_DTYPE = np.dtype([("page", "<i4"), ("tx", "<i4"), ("ty", "<i4"), ("first", "<i4")])
+ROW_DTYPE = np.dtype([("n_fill", "<i4"), ("n_stroke", "<i4")])
+assert PAGE_DTYPE.itemsize == C.sizeof(L.CtdTypesetPage) == 24
+assert LAYER_DTYPE.itemsize == C.sizeof(L.CtdTypesetLayer) == 56
+assert TILE_DTYPE.itemsize == C.sizeof(L.CtdTypesetTile) == 16
+assert ROW_DTYPE.itemsize == C.sizeof(L.CtdTypesetRow) == 8
+assert C.sizeof(L.CtdTypesetParams) == 32
+
+MAX_COORD = 1 << 29
+
+
+def _ints(a, shape, what) -> np.ndarray:
+    """`a` as an int64 array of `shape` (-1: any length); ValueError where it holds anything but whole numbers."""
+    a = np.asarray(a)
+    if a.dtype.kind not in "iu" and a.size:
+        raise ValueError(f"{what}: integers")
+    try:
+        return a.astype(np.int64).reshape(shape)
+    except ValueError:
+        raise ValueError(f"{what}: expected shape {shape}") from None
+
+
+def _per_layer(v, n, width, what) -> np.ndarray:
+    """One value (of `width` numbers) for all layers or one per layer -> (n, width) int64."""
+    a = np.asarray(v)
+    if a.dtype.kind not in "iu" or a.dtype == bool:
+        raise ValueError(f"{what}: integers")
+    a = a.astype(np.int64)
+    if a.shape == ((width,) if width > 1 else ()):
+        return np.broadcast_to(a.reshape(1, width), (n, width)).copy()
+    if a.shape in ((n, width),) + (((n,),) if width == 1 else ()):
+        return a.reshape(n, width)
+    raise ValueError(f"{what}: one value for all layers or one per layer")
+
+
+def typeset_tables(shapes: Sequence, page_of, sizes, xy, radius=0, clip=None) -> tuple:
+    """The tile table and the entry list of a typeset call: (tiles, entries, status).  shapes[p] = (H, W) of page p; per
+    layer page_of[i], sizes[i] = (h, w) of its bitmap, xy[i] = (x0, y0) of the bitmap's top-left pixel in page coordinates,
+    radius (one for all or one per layer), clip[i] = (x1, y1, x2, y2) exclusive (one for all, one per layer, default: the
+    page).  A layer is entered in every tile that its rectangle grown by its radius, cut to the page and the clip, meets.
+    tiles: `TILE_DTYPE`, n_tiles + 1 rows, every touched tile once in page-major, row-major order, the last row's `first` the
+    entry count.  entries: int32 layer indices, ascending within a tile.  status[i], the first that applies:
+    `_lib.TYPESET_EMPTY` (w or h is 0), `TYPESET_OUTSIDE` (that rectangle is empty), `TYPESET_OK`.  Numpy only."""
+    H = _ints([s[0] for s in shapes], (-1,), "shapes")
+    W = _ints([s[1] for s in shapes], (-1,), "shapes")
+    if len(H) and (min(H.min(), W.min()) < 1 or max(H.max(), W.max()) > L.TYPESET_MAX_SIDE):
+        raise ValueError(f"page sides must be 1 .. {L.TYPESET_MAX_SIDE}")
+    page_of = _ints(page_of, (-1,), "page_of")
+    n = len(page_of)
+    sizes, xy = _ints(sizes, (n, 2), "sizes"), _ints(xy, (n, 2), "xy")
+    r = _per_layer(radius, n, 1, "radius")[:, 0]
+    if n and (page_of.min() < 0 or page_of.max() >= len(H)):
+        raise ValueError("page_of: an index of `shapes`")
+    if n and (sizes.min() < 0 or sizes.max() > L.TYPESET_MAX_SIDE):
+        raise ValueError(f"bitmap sides must be 0 .. {L.TYPESET_MAX_SIDE}")
+    if n and (r.min() < 0 or r.max() > L.TYPESET_MAX_RADIUS):
+        raise ValueError(f"radius in 0 .. {L.TYPESET_MAX_RADIUS}")
+    if n and np.abs(xy).max() > MAX_COORD:
+        raise ValueError("xy beyond 2^29")
+    pw, ph = W[page_of], H[page_of]
+    if clip is None:
+        clip = np.stack([np.zeros_like(pw), np.zeros_like(ph), pw, ph], axis=1)
+    clip = _per_layer(clip, n, 4, "clip")
+    if n and (clip.min() < -2 ** 31 or clip.max() >= 2 ** 31):
+        raise ValueError("clip beyond int32")
+    h, w = sizes[:, 0], sizes[:, 1]
+    x1 = np.maximum(np.maximum(xy[:, 0] - r, clip[:, 0]), 0)
+    y1 = np.maximum(np.maximum(xy[:, 1] - r, clip[:, 1]), 0)
+    x2 = np.minimum(np.minimum(xy[:, 0] + w + r, clip[:, 2]), pw)
+    y2 = np.minimum(np.minimum(xy[:, 1] + h + r, clip[:, 3]), ph)
+    status = np.where((w == 0) | (h == 0), L.TYPESET_EMPTY,
+                      np.where((x1 >= x2) | (y1 >= y2), L.TYPESET_OUTSIDE, L.TYPESET_OK)).astype(np.int32)
+    lay = np.flatnonzero(status == L.TYPESET_OK)
+    tw, th = L.TYPESET_TILE_W, L.TYPESET_TILE_H
+    tx1, ty1 = x1[lay] // tw, y1[lay] // th
+    nx, ny = (x2[lay] - 1) // tw + 1 - tx1, (y2[lay] - 1) // th + 1 - ty1
+    cnt = nx * ny
+    total = int(cnt.sum())
+    if total >= 2 ** 31:
+        raise ValueError("too many tile entries for one call")
+    k = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)     # the entry's number within its layer
+    nxr = np.repeat(nx, cnt)
+    tx, ty = np.repeat(tx1, cnt) + k % np.maximum(nxr, 1), np.repeat(ty1, cnt) + k // np.maximum(nxr, 1)
+    layer = np.repeat(lay, cnt)
+    pg = page_of[layer]
+    tiles_x = (W + tw - 1) // tw
+    per_page = tiles_x * ((H + th - 1) // th)
+    key = (np.cumsum(per_page) - per_page)[pg] + ty * tiles_x[pg] + tx
+    order = np.argsort(key, kind="stable")                 # stable: the layers of a tile stay in ascending order
+    first = np.flatnonzero(np.diff(key[order], prepend=-1)) if total else np.zeros((0,), np.int64)
+    tiles = np.zeros((len(first) + 1,), TILE_DTYPE)
+    at = order[first]
+    tiles["page"][:-1], tiles["tx"][:-1], tiles["ty"][:-1], tiles["first"][:-1] = pg[at], tx[at], ty[at], first
+    tiles["first"][-1] = total
+    return tiles, layer[order].astype(np.int32), status
+
+
+def place(rects, sizes, radius=0) -> tuple:
+    """Bitmaps of sizes[i] = (h, w) centred in rects[i] = (x1, y1, x2, y2), exclusive: (xy, fits) with xy[i] = (x0, y0),
+    x0 = x1 + ((x2 - x1 - w) >> 1) and likewise y0 (the odd pixel of slack goes right and down; a bitmap larger than its box
+    overhangs it evenly), and fits[i] where the bitmap plus 2 radius fits the rectangle both ways.  Numpy."""
+    rects = _ints(rects, (-1, 4), "rects")
+    n = len(rects)
+    sizes = _ints(sizes, (n, 2), "sizes")
+    r = _per_layer(radius, n, 1, "radius")[:, 0]
+    bw, bh = rects[:, 2] - rects[:, 0], rects[:, 3] - rects[:, 1]
+    xy = np.stack([rects[:, 0] + ((bw - sizes[:, 1]) >> 1), rects[:, 1] + ((bh - sizes[:, 0]) >> 1)], axis=1)
+    return xy, (sizes[:, 1] + 2 * r <= bw) & (sizes[:, 0] + 2 * r <= bh)
+
+
+class TypesetPages:
+    """The result of `typeset_pages`.  `pages[i]` (H,W,3) u8 in the page's channel order, on the device: views of ONE new
+    allocation, or the caller's own pages where `inplace` was set.  Per layer: `rows` the kernel's records (`ROW_DTYPE`),
+    `n_fill[i]` the pixels written with coverage above 0, `n_stroke[i]` those written with outline above 0, `status[i]` =
+    `_lib.TYPESET_OK` / `TYPESET_EMPTY` (a bitmap without pixels) / `TYPESET_OUTSIDE` (nothing of it on the page and in the
+    clip), `xy[i]` where the bitmap went.  `TextDetector.typeset` adds `layer_of[j]`, block j's layer or -1, and `fits[i]`."""
+
+    def __init__(self, pages: List[torch.Tensor], rows: np.ndarray, status: np.ndarray, xy: np.ndarray):
+        self.pages, self.rows, self.status, self.xy = pages, rows, status, xy
+        if len(rows) != len(status) or len(xy) != len(rows):
+            raise ValueError("one row, one status and one position per layer")
+        self.n_fill, self.n_stroke = rows["n_fill"], rows["n_stroke"]
+        self.layer_of = self.fits = None
+
+    def __len__(self) -> int:
+        return len(self.rows)
+
+    def to_host(self):
+        """The pages as a list of numpy arrays."""
+        return [p.cpu().numpy() for p in self.pages]
+
+    def __repr__(self) -> str:
+        return f"TypesetPages({len(self.pages)} pages, {len(self)} layers, {int((self.status == L.TYPESET_OK).sum())} drawn)"
+
+
+def _align(n: int, a: int = 256) -> int:
+    return (n + a - 1) // a * a
+
+
+def _dense(t) -> bool:
+    return t.stride(2) == 1 and t.stride(1) == 3 and t.stride(0) >= 3 * t.shape[1]
+
+
+def _copies(pages, device):
+    """The pages copied into views of ONE new allocation, each on a 256-byte boundary: one device copy where they already lie
+    like that in one buffer (as `FilledPages.pages` do), else one copy (or upload) a page."""
+    sizes = [int(p.shape[0]) * int(p.shape[1]) * 3 for p in pages]
+    offs = np.cumsum([0] + [_align(s) for s in sizes])
+    store = torch.empty((int(offs[-1]),), dtype=torch.uint8, device=device)
+    out = [store[int(offs[i]): int(offs[i]) + sizes[i]].view(int(p.shape[0]), int(p.shape[1]), 3) for i, p in enumerate(pages)]
+    dev = [p for p in pages if isinstance(p, torch.Tensor) and p.device == device and p.is_contiguous()]
+    if len(dev) == len(pages) and all(p.untyped_storage().data_ptr() == dev[0].untyped_storage().data_ptr() and
+                                      p.data_ptr() - dev[0].data_ptr() == int(offs[i]) for i, p in enumerate(dev)):
+        used = int(offs[len(pages) - 1]) + sizes[-1]
+        src = torch.empty((0,), dtype=torch.uint8, device=device).set_(dev[0].untyped_storage(), dev[0].storage_offset(), (used,))
+        store[:used].copy_(src)
+    else:
+        for o, p in zip(out, pages):
+            o.copy_(p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p)))
+    return out
+
+
+def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray], xy, fill=(0, 0, 0), stroke=(255, 255, 255),
+                  radius=0, clip=None, inplace: bool = False, stream: Optional[torch.cuda.Stream] = None,
+                  device=None) -> TypesetPages:
+    """Composite layers into the pages of a batch by the typeset rule: one upload of coverage and tables, one `ctd_typeset`
+    launch, one small download.  pages: uint8 (H,W,3) pages of any mix of sizes, on the device or on the host; per layer
+    page_of[i], bitmaps[i] a (h, w) uint8 numpy array of coverage, xy[i] = (x0, y0) of its top-left pixel in page
+    coordinates; fill / stroke: RGB, one triple for all layers or one per layer (reversed into the pages' BGR order); radius:
+    the outline's, 0 .. 12, one for all or one per layer; clip: (x1, y1, x2, y2) exclusive, one for all or one per layer,
+    default the page.  Layers are applied in the order given.  inplace=False composites into a copy, views of one new
+    allocation; inplace=True writes the given pages, which must then be device tensors with dense rows (any row pitch).
+    Bad arguments raise ValueError before anything is uploaded.  Runs on `stream` (default: the current stream of the pages'
+    device) and waits for the result; see `TypesetPages`."""
+    for p in pages:
+        ps, pu8 = _shape_of(p)
+        if not pu8 or len(ps) != 3 or ps[2] != 3:
+            raise ValueError("pages must be uint8 (H,W,3)")
+        if inplace and not (isinstance(p, torch.Tensor) and p.is_cuda and _dense(p)):
+            raise ValueError("inplace=True needs device pages with dense rows")
+    shapes = [tuple(int(v) for v in p.shape[:2]) for p in pages]
+    page_of = _ints(page_of, (-1,), "page_of")
+    n = len(page_of)
+    if len(bitmaps) != n:
+        raise ValueError("one bitmap per layer")
+    for b in bitmaps:
+        if not isinstance(b, np.ndarray) or b.dtype != np.uint8 or b.ndim != 2:
+            raise ValueError("a bitmap is a (h, w) uint8 numpy array")
+    sizes = np.array([b.shape for b in bitmaps], np.int64).reshape(n, 2)
+    xy = _ints(xy, (n, 2), "xy")
+    colours = []
+    for name, v in (("fill", fill), ("stroke", stroke)):
+        c = _per_layer(v, n, 3, name)
+        if n and (c.min() < 0 or c.max() > 255):
+            raise ValueError(f"{name}: 0 .. 255")
+        colours.append(c[:, ::-1])
+    r = _per_layer(radius, n, 1, "radius")[:, 0]
+    tiles, entries, status = typeset_tables(shapes, page_of, sizes, xy, r, clip)
+    clip4 = _per_layer(clip, n, 4, "clip") if clip is not None else np.array([(0, 0, shapes[p][1], shapes[p][0]) for p in page_of],
+                                                                            np.int64).reshape(n, 4)
+    if not torch.cuda.is_available():
+        raise L.CtdError("typesetting runs on the GPU and there is none (no CPU fallback)")
+    area = sizes[:, 0] * sizes[:, 1]
+    cov0 = np.cumsum(area) - area
+    cov = np.concatenate([b.ravel() for b in bitmaps]) if n else np.zeros((0,), np.uint8)
+    n_pages, n_tiles = len(pages), len(tiles) - 1
+    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
+        if device is None:
+            device = next((p.device for p in pages if isinstance(p, torch.Tensor) and p.is_cuda), torch.device("cuda", 0))
+        device = torch.device(device)
+        with torch.cuda.device(device):
+            st = torch.cuda.current_stream(device)
+            if inplace:
+                out = _device_pages(pages, device)[0] if n_pages else []
+                if any(o.data_ptr() != p.data_ptr() for o, p in zip(out, pages)):
+                    raise ValueError("inplace=True needs pages on the device the call runs on")
+            else:
+                out = _copies(pages, device) if n_pages else []
+            rows = np.zeros((n,), ROW_DTYPE)
+            if n and n_pages:
+                pt = np.zeros((n_pages,), PAGE_DTYPE)
+                pt["page_dev"] = [o.data_ptr() for o in out]
+                pt["H"], pt["W"], pt["pitch"] = [s[0] for s in shapes], [s[1] for s in shapes], [o.stride(0) for o in out]
+                lt = np.zeros((n,), LAYER_DTYPE)
+                lt["cov0"], lt["page"], lt["x0"], lt["y0"], lt["h"], lt["w"] = cov0, page_of, xy[:, 0], xy[:, 1], sizes[:, 0], sizes[:, 1]
+                lt["cov_pitch"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = sizes[:, 1], clip4, colours[0], colours[1], r
+                # one upload: the four tables and the coverage, each part on an 8-byte boundary
+                parts = [pt.view(np.uint8), lt.view(np.uint8), tiles.view(np.uint8), entries.view(np.uint8), cov]
+                at = np.cumsum([0] + [_align(len(x), 8) for x in parts])
+                blob = np.zeros((int(at[-1]),), np.uint8)
+                for a, x in zip(at, parts):
+                    blob[int(a): int(a) + len(x)] = x
+                tab = torch.from_numpy(blob).to(device)
+                rows_dev = torch.empty((n * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=device)
+                prm = L.CtdTypesetParams(n, n_pages, n_tiles, len(entries), len(cov), 0)
+                ptr = [tab.data_ptr() + int(a) for a in at]
+                L.check(L.lib().ctd_typeset(ptr[0], ptr[1], ptr[2], ptr[3] if len(entries) else None, ptr[4] if len(cov) else None,
+                                            C.byref(prm), rows_dev.data_ptr(), st.cuda_stream), "ctd_typeset")
+                rows = rows_dev.cpu().numpy().view(ROW_DTYPE)           # stream-ordered: behind the launch
+            st.synchronize()
+    return TypesetPages(out, rows, status, xy)

@@ -760,6 +760,99 @@ typedef struct ctd_layout_row {
 int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloon_row* balloon_rows_dev,
                      const uint64_t* bits_dev, const ctd_layout_params* params, ctd_layout_row* rows_dev, void* stream);
 
+/* ---- typeset: text layers with outlines composited into pages (added within ABI v10) ---------------------------------- */
+
+/* An addition to ABI v10 like the five above: one entry point, six structs, nothing existing changes.
+ * The layout section ends at the box; the translated text, rendered by any font engine into 8-bit coverage bitmaps, goes
+ * back into the device pages here, with the outline that is the standard manga treatment.  This library's own rule,
+ * integers only, so a result is a function of its inputs to the byte.  Restated in numpy in tests/typeset_ref.py.
+ *   page    P, H x W x 3 u8 at any pitch and any byte alignment, sides 1 .. CTD_TYPESET_MAX_SIDE; modified in place.
+ *   layer   a coverage bitmap cov, h x w u8 (h and w 1 .. CTD_TYPESET_MAX_SIDE), rows cov_pitch >= 0 bytes apart from byte
+ *           cov0 >= 0 of ONE packed coverage buffer; its page; the page coordinates (x0, y0) of the bitmap's top-left pixel
+ *           (any int32 with |x0|, |y0| <= 2^29); a fill colour f[3] and a stroke colour s[3] in the page's channel order; a
+ *           stroke radius r, 0 .. CTD_TYPESET_MAX_RADIUS; a clip rectangle cx1, cy1, cx2, cy2, exclusive, page coordinates.
+ *   F(p)    cov(p - (x0, y0)), and 0 outside the bitmap.
+ *   S(p)    for r > 0 the max of F(q) over all q with (qx - px)^2 + (qy - py)^2 <= r^2: a grey-scale dilation by a disk
+ *           of 5, 13, 29, 49, 81, 113, 149, 197, 253, 317, 377, 441 pixels for r = 1 .. 12.  For r = 0, S = 0.
+ *   blend   blend(c, k, a) = (c (255 - a) + k a + 127) / 255, integer division, per channel: a = 0 gives c, a = 255 gives
+ *           k, and the result always lies between c and k.
+ *   one layer   every pixel p inside the page, the clip and the bitmap's rectangle grown by r on every side becomes
+ *           blend(blend(P(p), s, S(p)), f, F(p)): the stroke goes on first and the fill over it.  No other pixel changes.
+ *   several layers   the layers of one call are applied in the order of the layer table.  Where they overlap the later one
+ *           sees the earlier one's result, so swapping two overlapping layers changes bytes.
+ *   row     per layer two int32: n_fill, the pixels written with F > 0, and n_stroke, the pixels written with S > 0.  Sums
+ *           of integers: they depend on no order.
+ *   invalid a layer draws nothing and counts nothing, and none of its coverage is read, when its page is not one of
+ *           0 .. n_pages - 1, w or h is 0 or above CTD_TYPESET_MAX_SIDE, r is above CTD_TYPESET_MAX_RADIUS, cov0 or
+ *           cov_pitch is negative, or cov0 + (h - 1) cov_pitch + w is more than params.cov_bytes.
+ * The launch works on page tiles of CTD_TYPESET_TILE_W x CTD_TYPESET_TILE_H pixels, one workgroup per tile of the tile
+ * table, which walks the tile's entries (layer indices) in table order.  The caller lists the touched tiles only (tile
+ * (tx, ty) of a page covers x in tx TILE_W .. and y in ty TILE_H ..) and, per tile, in ascending order every layer whose
+ * grown rectangle, cut to page and clip, meets it.
+ * PRECONDITION: a page tile appears at most once in the tile table, and the pages of one call do not overlap in memory.
+ * The entry point cannot see device tables; typeset.typeset_tables is their producer.  Short of that the tables are free:
+ * a tile that is no tile of its page, an entry that names no layer, a layer of another page or one that does not meet the
+ * tile contribute nothing, and entry ranges are cut to 0 .. n_entries.  A wrong table costs pixels and never faults.
+ * Limits: the radius is a whole number of pixels, and a max over an anti-aliased bitmap gives an outline whose edge is as
+ * smooth as the glyph's and no smoother; no resampling and no rotation, the caller renders at the final size and angle; no
+ * gamma; a layer is opaque text, there is no per-layer opacity. */
+#define CTD_TYPESET_MAX_SIDE 8192
+#define CTD_TYPESET_MAX_RADIUS 12
+#define CTD_TYPESET_TILE_W 64
+#define CTD_TYPESET_TILE_H 32
+
+/* One page of a typeset call (a row of the device page table), 24 bytes. */
+typedef struct ctd_typeset_page {
+  void* page_dev; /* H x W x 3 u8, written in place                                */
+  int32_t H, W;
+  int64_t pitch;  /* bytes from a row to the next, at least 3 W                    */
+} ctd_typeset_page;
+
+/* One layer (a row of the device layer table), 56 bytes. */
+typedef struct ctd_typeset_layer {
+  int64_t cov0;      /* the bitmap's first byte of cov_dev                         */
+  int32_t page;
+  int32_t x0, y0;    /* page coordinates of the bitmap's top-left pixel            */
+  int32_t w, h;
+  int32_t cov_pitch;
+  int32_t clip[4];   /* x1, y1, x2, y2, exclusive, page coordinates                */
+  uint8_t fill[3];   /* page channel order                                         */
+  uint8_t stroke[3];
+  uint8_t radius;
+  uint8_t pad_;
+} ctd_typeset_layer;
+
+/* One touched tile (a row of the device tile table, n_tiles + 1 rows), 16 bytes.  The tile's entries are
+ * entries_dev[first .. the next row's first); the last row's `first` is the entry count, its other fields are unused. */
+typedef struct ctd_typeset_tile {
+  int32_t page, tx, ty;
+  int32_t first;
+} ctd_typeset_tile;
+
+typedef struct ctd_typeset_params {
+  int32_t n_layers, n_pages, n_tiles, n_entries;
+  int64_t cov_bytes; /* the size of cov_dev: no layer reads beyond it                */
+  int64_t pad_;
+} ctd_typeset_params;
+
+/* One row of the result. */
+typedef struct ctd_typeset_row {
+  int32_t n_fill, n_stroke;
+} ctd_typeset_row;
+
+/* The rule above for all pages of a batch in ONE launch on `stream`, one workgroup per row of the tile table: a workgroup
+ * reads its tile of the page once, applies the tile's layers in table order on chip (the coverage patch of each in LDS) and
+ * writes the tile once, so a page byte is read once and written once whatever the number of layers, and the order of
+ * overlapping layers is exact without an atomic on a pixel.  There is no cap on the layers of a tile.  All tables are on the
+ * device (entries_dev: int32 layer indices; rows_dev: n_layers rows, 4-byte aligned, cleared by the call before the launch,
+ * summed into by integer atomics); `params` is read on the host during the call.  n_layers = 0 or n_tiles = 0 launches
+ * nothing (the rows are still cleared).  A negative count or cov_bytes, a missing table where its count is positive
+ * (pages_dev: n_pages; layers_dev and rows_dev: n_layers; tiles_dev: n_tiles; entries_dev: n_entries), or cov_dev NULL with
+ * cov_bytes > 0 is an error rc and launches nothing. */
+int ctd_typeset(const ctd_typeset_page* pages_dev, const ctd_typeset_layer* layers_dev, const ctd_typeset_tile* tiles_dev,
+                const int32_t* entries_dev, const uint8_t* cov_dev, const ctd_typeset_params* params,
+                ctd_typeset_row* rows_dev, void* stream);
+
 /* ---- the detector tail ------------------------------------------------------ */
 
 /* Everything `TextDetector.__call__` does after `self.net(img_in)` (reference inference.py:148-178) for a
