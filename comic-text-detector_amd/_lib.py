@@ -178,6 +178,24 @@ class CtdTypesetRow(C.Structure):
     _fields_ = [("n_fill", C.c_int32), ("n_stroke", C.c_int32)]
 
 
+class CtdGlyphLayer(C.Structure):
+    _fields_ = [("page", C.c_int32), ("clip", C.c_int32 * 4), ("fill", C.c_uint8 * 3), ("stroke", C.c_uint8 * 3),
+                ("radius", C.c_uint8), ("pad_", C.c_uint8), ("pad2_", C.c_int32)]
+
+
+class CtdGlyphPlace(C.Structure):
+    _fields_ = [("layer", C.c_int32), ("glyph", C.c_int32), ("x", C.c_int32), ("y", C.c_int32)]
+
+
+class CtdGlyphRecord(C.Structure):
+    _fields_ = [("off", C.c_int64), ("w", C.c_int32), ("h", C.c_int32)]
+
+
+class CtdGlyphParams(C.Structure):
+    _fields_ = [("n_layers", C.c_int32), ("n_pages", C.c_int32), ("n_tiles", C.c_int32), ("n_entries", C.c_int32),
+                ("n_places", C.c_int32), ("n_glyphs", C.c_int32), ("atlas_bytes", C.c_int64)]
+
+
 class CtdFillPage(C.Structure):
     _fields_ = [("page_dev", C.c_void_p), ("hole_dev", C.c_void_p), ("out_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32),
                 ("pitch", C.c_int32), ("hole_pitch", C.c_int32), ("out_pitch", C.c_int32), ("tile0", C.c_int32),
@@ -226,6 +244,7 @@ SYMBOLS = {
     "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
     "ctd_layout_boxes": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdLayoutParams), _vp, _vp]),
     "ctd_typeset": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(CtdTypesetParams), _vp, _vp]),
+    "ctd_typeset_glyphs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdGlyphParams), _vp, _vp]),
     "ctd_fill_rest": (_i32, [_vp, _i32, C.POINTER(CtdFillParams), _vp, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),

@@ -1448,6 +1448,25 @@ int ctd_typeset(const ctd_typeset_page* pages_dev, const ctd_typeset_layer* laye
   return CTD_OK;
 }
 
+int ctd_typeset_glyphs(const ctd_typeset_page* pages_dev, const ctd_glyph_layer* layers_dev, const ctd_glyph_place* places_dev,
+                       const ctd_glyph_record* glyphs_dev, const ctd_typeset_tile* tiles_dev, const int32_t* entries_dev,
+                       const uint8_t* atlas_dev, const ctd_glyph_params* params, ctd_typeset_row* rows_dev, void* stream) {
+  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
+  const ctd_glyph_params prm = *params;
+  if (prm.n_layers < 0 || prm.n_pages < 0 || prm.n_tiles < 0 || prm.n_entries < 0 || prm.n_places < 0 || prm.n_glyphs < 0 ||
+      prm.atlas_bytes < 0)
+    return fail(CTD_ERR_INVALID, "bad sizes");
+  if ((prm.n_pages > 0 && !pages_dev) || (prm.n_layers > 0 && (!layers_dev || !rows_dev)) || (prm.n_places > 0 && !places_dev) ||
+      (prm.n_glyphs > 0 && !glyphs_dev) || (prm.n_tiles > 0 && !tiles_dev) || (prm.n_entries > 0 && !entries_dev) ||
+      (prm.atlas_bytes > 0 && !atlas_dev))
+    return fail(CTD_ERR_INVALID, "null pointer");
+  if (prm.n_tiles == 0 || prm.n_layers == 0) return CTD_OK;
+  HIP_TRY(hipMemsetAsync(rows_dev, 0, (size_t)prm.n_layers * sizeof(ctd_typeset_row), (hipStream_t)stream));
+  HIP_TRY(launch_typeset_glyphs(pages_dev, layers_dev, places_dev, glyphs_dev, tiles_dev, entries_dev, atlas_dev, prm, rows_dev,
+                                (hipStream_t)stream));
+  return CTD_OK;
+}
+
 int ctd_fill_rest(const ctd_fill_page* pages_dev, int32_t n_pages, const ctd_fill_params* params, void* scratch_dev,
                   ctd_fill_row* rows_dev, void* stream) {
   if (n_pages < 0) return fail(CTD_ERR_INVALID, "bad sizes");

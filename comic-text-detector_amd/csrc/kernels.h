@@ -204,6 +204,13 @@ hipError_t launch_typeset(const ctd_typeset_page* pages, const ctd_typeset_layer
                           const int32_t* entries, const uint8_t* cov, const ctd_typeset_params& prm, ctd_typeset_row* rows,
                           hipStream_t st);
 
+// ---- kernels_glyphs.hip ---------------------------------------------------------
+// ctd_typeset_glyphs' one launch (one workgroup per row of the tile table; n_tiles >= 1, n_layers >= 1, the counts and
+// pointers checked and the rows cleared by the caller): returns what hipGetLastError says right after the launch
+hipError_t launch_typeset_glyphs(const ctd_typeset_page* pages, const ctd_glyph_layer* layers, const ctd_glyph_place* places,
+                                 const ctd_glyph_record* glyphs, const ctd_typeset_tile* tiles, const int32_t* entries,
+                                 const uint8_t* atlas, const ctd_glyph_params& prm, ctd_typeset_row* rows, hipStream_t st);
+
 // ---- kernels_fill.hip -----------------------------------------------------------
 // ctd_fill_rest's three launches (pull per tile, the page launch, push per tile; n_pages >= 1, n_tiles >= 1 and the page
 // table checked by the caller): raises the page kernel's dynamic LDS limit once per device and returns what hipGetLastError

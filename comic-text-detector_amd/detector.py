@@ -644,6 +644,41 @@ class TextDetector:
         out.layer_of, out.fits = layer_of, fits
         return out
 
+    def typeset_glyphs(self, pages: Sequence[Page], boxes, atlas, runs, fill=(0, 0, 0), stroke=(255, 255, 255), radius=0,
+                       prefer: str = "a_rect", inplace: bool = False, **flow_kw):
+        """`typeset` from a glyph atlas: one layer per block of `boxes` that is `ok` and has a run, its glyphs placed by
+        `glyphs.flow` (keywords: `flow_kw`) in the rectangle `typeset` would centre a bitmap in (`a_rect` where `prefer` is
+        "a_rect" and `a_area > 0`, else `rect`), clipped to the page, all composited in one launch (`glyphs.typeset_glyphs`;
+        returns its `TypesetPages`).  `atlas`: a `glyphs.GlyphAtlas`; `runs[j]`: block j's glyph ids as an int array, or None
+        to skip the block.  fill / stroke (RGB) and radius: one for all blocks or one per block.  The result's `layer_of[j]`
+        is block j's layer, -1 where it was skipped; `fits[i]` says whether layer i's lines stay inside its rectangle."""
+        from . import glyphs as gl, typeset as ts
+        if prefer not in ("a_rect", "rect"):
+            raise ValueError('prefer: "a_rect" or "rect"')
+        nb = len(boxes)
+        if len(runs) != nb:
+            raise ValueError("one run (or None) per block of `boxes`")
+        take = np.array([bool(boxes.ok[j]) and runs[j] is not None for j in range(nb)], bool)
+        idx = np.flatnonzero(take)
+        layer_of = np.full((nb,), -1, np.int64)
+        layer_of[idx] = np.arange(len(idx))
+        fill, stroke = ts._per_layer(fill, nb, 3, "fill")[idx], ts._per_layer(stroke, nb, 3, "stroke")[idx]
+        radius = ts._per_layer(radius, nb, 1, "radius")[idx, 0]
+        anchored = (np.asarray(boxes.a_area) > 0) if prefer == "a_rect" else np.zeros((nb,), bool)
+        rects = np.where(anchored[:, None], boxes.a_rect, boxes.rect).reshape(nb, 4)[idx]
+        ids, xy, fits = [], [], []
+        for i, j in enumerate(idx):
+            run = ts._ints(runs[j], (-1,), "runs")
+            p, f = gl.flow(run, atlas, rects[i], **flow_kw)
+            ids.append(run), xy.append(p), fits.append(f)
+        count = [len(a) for a in ids]
+        ids = np.concatenate(ids) if ids else np.zeros((0,), np.int64)
+        xy = np.concatenate(xy) if xy else np.zeros((0, 2), np.int64)
+        out = gl.typeset_glyphs(pages, atlas, boxes.index[idx, 0], np.repeat(np.arange(len(idx)), count), ids, xy, fill=fill,
+                                stroke=stroke, radius=radius, inplace=inplace, device=self.net.device)
+        out.layer_of, out.fits = layer_of, np.array(fits, bool)
+        return out
+
     def fill_rest(self, pages: Sequence[Page], results, erased=None, **erase_kw):
         """The pages of a detected batch with NO text left, on the detector's device: the text on plain backgrounds erased
         (`erase_text`) and the mask that leaves filled smoothly by pull-push (`fill.fill_rest` on the erased pages and their

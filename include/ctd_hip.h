@@ -853,6 +853,80 @@ int ctd_typeset(const ctd_typeset_page* pages_dev, const ctd_typeset_layer* laye
                 const int32_t* entries_dev, const uint8_t* cov_dev, const ctd_typeset_params* params,
                 ctd_typeset_row* rows_dev, void* stream);
 
+/* ---- typeset from a glyph atlas: glyph runs composited into pages (added within ABI v10) ------------------------------- */
+
+/* An addition to ABI v10 like the ones above: one entry point, four structs, nothing existing changes.
+ * The section above takes one coverage bitmap per layer; a font engine gives one bitmap per GLYPH plus metrics.  Here every
+ * distinct glyph lies once in an atlas on the device, a layer is a run of placements, and the layer's coverage is assembled
+ * on chip.  Everything but the coverage is the typeset rule above, unchanged.  Restated in tests/glyph_ref.py.
+ *   glyph   an atlas record (off, w, h): dense rows of w bytes from byte off of the atlas, sides 0 .. CTD_TYPESET_MAX_SIDE.
+ *           A side of 0 is legal (a space) and draws nothing.
+ *   layer   a page, a fill colour, a stroke colour, a stroke radius r of 0 .. CTD_TYPESET_MAX_RADIUS and a clip rectangle:
+ *           the bitmap layer's fields minus the bitmap.
+ *   placement   (layer, glyph, x, y): (x, y) the page coordinates of the glyph bitmap's top-left pixel.
+ *   F(p)    the MAX over the layer's placements of the glyph's coverage at p, and 0 where no glyph lies.  A max, not a
+ *           saturating sum: it needs no order and is idempotent, so a glyph placed twice at one position counts once.
+ *   S, blend, one layer, several layers, row   as above, with this F: S is the disk max of F, a pixel inside the page and the
+ *           clip becomes blend(blend(P, s, S), f, F), layers apply in table order, the row counts the pixels with F > 0 and
+ *           with S > 0.  (Where F = S = 0 the blend returns the pixel, so "the rectangle grown by r" needs no statement.)
+ * The result is by definition what ctd_typeset gives for the block bitmap that the max-paste of the glyphs produces.
+ *   invalid a placement contributes nothing, and none of its coverage is read, when its layer or its glyph index is out of
+ *           range, its layer is on another page than the tile (or has r above CTD_TYPESET_MAX_RADIUS), its glyph record has
+ *           a side above CTD_TYPESET_MAX_SIDE or a negative one, off < 0 or off + w h > params.atlas_bytes, or |x| or |y|
+ *           is above 2^29.
+ * The launch is ctd_typeset's: one workgroup per row of the tile table (ctd_typeset_tile, the same tiles).  A tile's entries
+ * are int32 PLACEMENT indices, ascending, so the placements of one layer are consecutive and layers ascend; the workgroup
+ * groups consecutive entries of equal layer.  The caller lists, per touched tile, every placement whose rectangle grown by
+ * its layer's r, cut to page and clip, meets it.  The PRECONDITION above holds here too (a page tile at most once, pages do
+ * not overlap in memory); glyphs.glyph_tables is the producer.  Short of that the tables are free: a tile that is none of its
+ * page returns, an entry that names no placement or a placement that misses the tile contributes nothing, entry ranges are
+ * cut to 0 .. n_entries, and entries of one layer that are not consecutive merely apply that layer twice.  A wrong table
+ * costs pixels and never faults.
+ * Limits beyond those above: overlap within a layer is max, not sum; one colour per layer, so a coloured word is a layer of
+ * its own; no kerning, shaping or rasterisation, which stay a font engine's. */
+
+/* One glyph layer (a row of the device layer table), 32 bytes. */
+typedef struct ctd_glyph_layer {
+  int32_t page;
+  int32_t clip[4];   /* x1, y1, x2, y2, exclusive, page coordinates                */
+  uint8_t fill[3];   /* page channel order                                         */
+  uint8_t stroke[3];
+  uint8_t radius;
+  uint8_t pad_;
+  int32_t pad2_;
+} ctd_glyph_layer;
+
+/* One placement (a row of the device placement table), 16 bytes. */
+typedef struct ctd_glyph_place {
+  int32_t layer, glyph;
+  int32_t x, y;      /* page coordinates of the glyph bitmap's top-left pixel      */
+} ctd_glyph_place;
+
+/* One glyph of the atlas (a row of the device record table), 16 bytes. */
+typedef struct ctd_glyph_record {
+  int64_t off;       /* the glyph's first byte of atlas_dev; rows are w bytes apart */
+  int32_t w, h;
+} ctd_glyph_record;
+
+typedef struct ctd_glyph_params {
+  int32_t n_layers, n_pages, n_tiles, n_entries;
+  int32_t n_places, n_glyphs;
+  int64_t atlas_bytes; /* the size of atlas_dev: no placement reads beyond it        */
+} ctd_glyph_params;
+
+/* The rule above for all pages of a batch in ONE launch on `stream`, one workgroup per row of the tile table, which reads
+ * its tile of the page once, assembles each layer's coverage patch in LDS from the atlas, runs the outline and the blend of
+ * ctd_typeset on it and writes the tile once.  There is no cap on the placements of a tile or of a layer.  All tables are on
+ * the device (pages_dev: ctd_typeset_page; tiles_dev: ctd_typeset_tile, n_tiles + 1 rows; entries_dev: int32 placement
+ * indices; rows_dev: n_layers ctd_typeset_row, 4-byte aligned, cleared by the call before the launch, summed into by integer
+ * atomics); `params` is read on the host during the call.  n_tiles = 0 or n_layers = 0 does nothing at all: no launch, and
+ * the rows are not touched.  A negative count or atlas_bytes, a missing table where its count is positive (pages_dev:
+ * n_pages; layers_dev and rows_dev: n_layers; places_dev: n_places; glyphs_dev: n_glyphs; tiles_dev: n_tiles; entries_dev:
+ * n_entries), or atlas_dev NULL with atlas_bytes > 0 is an error rc and launches nothing. */
+int ctd_typeset_glyphs(const ctd_typeset_page* pages_dev, const ctd_glyph_layer* layers_dev, const ctd_glyph_place* places_dev,
+                       const ctd_glyph_record* glyphs_dev, const ctd_typeset_tile* tiles_dev, const int32_t* entries_dev,
+                       const uint8_t* atlas_dev, const ctd_glyph_params* params, ctd_typeset_row* rows_dev, void* stream);
+
 /* ---- the detector tail ------------------------------------------------------ */
 
 /* Everything `TextDetector.__call__` does after `self.net(img_in)` (reference inference.py:148-178) for a
