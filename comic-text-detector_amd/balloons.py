@@ -28,8 +28,7 @@ import torch
 
 from . import _lib as L
 from . import erase as E
-from .colors import _shape_of
-from .regions import Page, _device_pages
+from .regions import Page, _check_pages, _device_pages
 
 __all__ = ["balloon_regions", "BalloonRegions", "balloon_tables", "check_params", "JOB_DTYPE", "ROW_DTYPE"]
 
@@ -136,14 +135,7 @@ def balloon_regions(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Seq
     prm = check_params(grow, tol, reach, reach_min)
     if len(pages) != len(blk_lists) or len(masks) != len(pages):
         raise ValueError("one mask and one blk_list per page")
-    for p, m in zip(pages, masks):
-        (ps, pu8), (ms, mu8) = _shape_of(p), _shape_of(m)
-        if not pu8 or len(ps) != 3 or ps[2] != 3:
-            raise ValueError("pages must be uint8 BGR (H,W,3)")
-        if not mu8 or ms != ps[:2]:
-            raise ValueError("a mask must be uint8 and have the shape of its page")
-        if ps[0] < 1 or ps[1] < 1:
-            raise ValueError("empty page")
+    _check_pages(pages, masks, "BGR ")
     lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in blk_lists]
     boxes = [E._page_boxes(b) for b in lists]
     shapes = [tuple(p.shape[:2]) for p in pages]

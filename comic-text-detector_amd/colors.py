@@ -25,7 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .regions import Page, _batch_lines, _device_pages
+from .regions import Page, _batch_lines, _check_pages, _device_pages
 
 __all__ = ["line_colors", "LineColors", "BlockColors", "color_rows", "JOB_DTYPE", "OUT_DTYPE"]
 
@@ -134,10 +134,6 @@ class LineColors:
         return f"LineColors({len(self)} lines, {int((self.status == L.COLOR_OK).sum())} ok)"
 
 
-def _shape_of(a):
-    return tuple(a.shape), (a.dtype == torch.uint8 if isinstance(a, torch.Tensor) else np.asarray(a).dtype == np.uint8)
-
-
 def line_colors(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequence,
                 stream: Optional[torch.cuda.Stream] = None, device=None) -> LineColors:
     """Fill and surround colour of EVERY line of EVERY block of a batch: one table upload, one kernel launch, one small
@@ -152,12 +148,7 @@ def line_colors(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequenc
     `COLOR_NO_CONTRAST`, the second as the mean of whatever falls on each side of the grey split."""
     if len(pages) != len(blk_lists) or len(masks) != len(pages):
         raise ValueError("one mask and one blk_list per page")
-    for p, m in zip(pages, masks):
-        (ps, pu8), (ms, mu8) = _shape_of(p), _shape_of(m)
-        if not pu8 or len(ps) != 3 or ps[2] != 3:
-            raise ValueError("pages must be uint8 BGR (H,W,3)")
-        if not mu8 or ms != ps[:2]:
-            raise ValueError("a mask must be uint8 and have the shape of its page")
+    _check_pages(pages, masks, "BGR ", nonempty=False)
     index, quads = _batch_lines(blk_lists)[:2]
     if len(index) == 0:
         return LineColors(index, np.zeros((0,), OUT_DTYPE))

@@ -1,8 +1,8 @@
 // Typeset from a glyph atlas (`ctd_typeset_glyphs`; the rule is stated in include/ctd_hip.h and restated in numpy in
 // tests/glyph_ref.py): a layer is a run of placements (layer, glyph, x, y) of atlas glyphs, its coverage F the MAX of the
 // glyphs' coverage, and from there on the typeset rule of kernels_typeset.hip: outline S = disk max of F, r <= 12,
-// pixel = blend(blend(P, s, S), f, F).  Integers only.  The device helpers of kernels_typeset.hip (blend, the half-width
-// planes) are duplicated here, not shared: that file stays as it is.
+// pixel = blend(blend(P, s, S), f, F).  Integers only.  The tile, the outline and the blend are typeset_tile.h's, shared
+// with kernels_typeset.hip; staging the placements and gathering the patch are this file's.
 //
 // glyphs_kernel, ONE launch, one workgroup of 256 threads per row of the tile table (a TILE_W x TILE_H tile of one page):
 //   load    the tile of the page into registers, as typeset_kernel does.
@@ -26,20 +26,14 @@
 // LDS: 4928 (patch) + TS_PLANES * 3584 (planes / staged records) + small tables.
 #include <climits>
 
-#include "kernels.h"
+#include "typeset_tile.h"
 
 namespace {
 
-constexpr int TW = CTD_TYPESET_TILE_W, TH = CTD_TYPESET_TILE_H, RMAX = CTD_TYPESET_MAX_RADIUS;
-constexpr int TS_THREADS = 256;
-constexpr int PX = TW * TH / TS_THREADS;                   // pixels a thread
-constexpr int CW = TW + 2 * RMAX, CH = TH + 2 * RMAX;      // the coverage patch
 constexpr int NC = TS_THREADS;                             // staged records a chunk: one a thread
 constexpr int PB = 11;                                     // patch bytes a thread resolves at a time: CH * CW <= 2 PB threads
 static_assert(CH * CW <= 2 * PB * TS_THREADS && CW <= 128, "two batches cover the patch; a patch column fits 7 bits");
 constexpr int MAX_COORD = 1 << 29;
-static_assert(TW == 64 && TS_THREADS % TW == 0 && (TW * TH) % TS_THREADS == 0 && TH % (TS_THREADS / TW) == 0,
-              "a wave is one tile row; every thread has PX pixels");
 static_assert(sizeof(ctd_glyph_layer) == 32 && sizeof(ctd_glyph_place) == 16 && sizeof(ctd_glyph_record) == 16 &&
               sizeof(ctd_glyph_params) == 32, "glyph typeset ABI sizes (glyphs.py dtypes)");
 static_assert(offsetof(ctd_glyph_layer, clip) == 4 && offsetof(ctd_glyph_layer, fill) == 20 &&
@@ -47,30 +41,11 @@ static_assert(offsetof(ctd_glyph_layer, clip) == 4 && offsetof(ctd_glyph_layer, 
               offsetof(ctd_glyph_params, n_places) == 16 && offsetof(ctd_glyph_params, atlas_bytes) == 24,
               "glyph typeset ABI offsets");
 
-constexpr int half_width(int r, int dy) {
-  int k = 0;
-  while ((k + 1) * (k + 1) + dy * dy <= r * r) ++k;
-  return k;
-}
-constexpr int distinct_half_widths(int r) {
-  int n = 0;
-  for (int dy = 0; dy <= r; ++dy) n += dy == 0 || half_width(r, dy) != half_width(r, dy - 1);
-  return n;
-}
-constexpr int max_planes() {
-  int n = 0;
-  for (int r = 1; r <= RMAX; ++r) n = distinct_half_widths(r) > n ? distinct_half_widths(r) : n;
-  return n;
-}
-constexpr int TS_PLANES = max_planes();
-
 struct Staged {                                            // a checked placement; w == 0: contributes nothing
   long long off;
   int x, y, w, h;
 };
 static_assert(sizeof(Staged) == 24 && NC * sizeof(Staged) <= (size_t)TS_PLANES * CH * TW, "the staged records fit the planes");
-
-__device__ __forceinline__ int blend(int c, int k, int a) { return (c * (255 - a) + k * a + 127) / 255; }
 
 __global__ __launch_bounds__(TS_THREADS) void glyphs_kernel(const ctd_typeset_page* __restrict__ pages,
                                                             const ctd_glyph_layer* __restrict__ layers,
@@ -92,32 +67,13 @@ __global__ __launch_bounds__(TS_THREADS) void glyphs_kernel(const ctd_typeset_pa
   unsigned char(*plane)[CH][TW] = reinterpret_cast<unsigned char(*)[CH][TW]>(plane_raw);
   Staged* staged = reinterpret_cast<Staged*>(plane_raw);
   const int t = threadIdx.x, lane = t & 63;
-  const int lx = t % TW, ly = t / TW;                      // this thread's pixels: (lx, ly + j * LYS)
-  constexpr int LYS = TS_THREADS / TW;
 
-  // ---- the tile (block-uniform; a tile that is no tile of its page does nothing)
-  const ctd_typeset_tile T = tiles[blockIdx.x];
-  if (T.page < 0 || T.page >= prm.n_pages || T.tx < 0 || T.ty < 0) return;
-  const ctd_typeset_page P = pages[T.page];
-  if (P.H < 1 || P.W < 1 || P.H > CTD_TYPESET_MAX_SIDE || P.W > CTD_TYPESET_MAX_SIDE) return;
-  if ((long long)T.tx * TW >= P.W || (long long)T.ty * TH >= P.H) return;
-  const int tx0 = T.tx * TW, ty0 = T.ty * TH;
-  const int e_begin = min(max(T.first, 0), prm.n_entries), e_end = min(max(tiles[blockIdx.x + 1].first, 0), prm.n_entries);
-  if (e_begin >= e_end) return;
-
-  // ---- load
-  unsigned char* __restrict__ base = (unsigned char*)P.page_dev;
+  ctd_typeset_tile T;
+  ctd_typeset_page P;
+  int tx0, ty0, e_begin, e_end;
+  if (!open_tile(tiles, pages, prm.n_pages, prm.n_entries, T, P, tx0, ty0, e_begin, e_end)) return;
   unsigned pix[PX];
-  const int gx = tx0 + lx;
-#pragma unroll
-  for (int j = 0; j < PX; ++j) {
-    const int gy = ty0 + ly + j * LYS;
-    pix[j] = 0;
-    if (gx < P.W && gy < P.H) {
-      const unsigned char* q = base + (long long)gy * P.pitch + 3 * gx;
-      pix[j] = (unsigned)q[0] | ((unsigned)q[1] << 8) | ((unsigned)q[2] << 16);
-    }
-  }
+  load_tile(P, tx0, ty0, t, pix);
 
   // ---- groups
   int e = e_begin;
@@ -177,16 +133,7 @@ __global__ __launch_bounds__(TS_THREADS) void glyphs_kernel(const ctd_typeset_pa
         pr1 = cy1 - ty0;                                   // the patch rows a pixel of that rectangle can see: pr1 ..
         n_bytes = (cy2 - cy1 + 2 * r) * CW;
         px0 = tx0 - r, py0 = ty0 - r;                      // patch (0, 0) in page coordinates
-        if (t == 0 && r > 0) {                             // read behind the barriers below
-          for (int k = 0; k <= r; ++k) slot[k] = -1;
-          int ns = 0;
-          for (int dy = 0; dy <= r; ++dy) {
-            int k = 0;
-            while ((k + 1) * (k + 1) + dy * dy <= r * r) ++k;
-            if (slot[k] < 0) slot[k] = (signed char)ns++;  // half-widths fall as dy grows: ns <= TS_PLANES
-            slot_dy[dy] = slot[k];
-          }
-        }
+        if (t == 0 && r > 0) slot_table(r, slot, slot_dy); // read behind the barriers below
       }
       // the group's length within the chunk: up to the first entry of another layer; its box
       const unsigned long long others = __ballot(t < n && lay != li);
@@ -262,65 +209,14 @@ __global__ __launch_bounds__(TS_THREADS) void glyphs_kernel(const ctd_typeset_pa
     __syncthreads();                                       // cov is whole; the staged records are done with
     const int rr1 = ay1 - ty0, rr2 = ay2 - ty0 + 2 * r;    // the patch rows an active pixel can see (within pr1 ..)
     if (r > 0) {
-      for (int i = t; i < (rr2 - rr1) * TW; i += TS_THREADS) {
-        const int py = rr1 + i / TW, x = i % TW;
-        const unsigned char* __restrict__ row = &cov[py][x + r];
-        int m = row[0];
-        if (slot[0] >= 0) plane[slot[0]][py][x] = (unsigned char)m;
-        for (int k = 1; k <= r; ++k) {
-          m = max(m, max((int)row[-k], (int)row[k]));
-          const int s = slot[k];
-          if (s >= 0) plane[s][py][x] = (unsigned char)m;
-        }
-      }
-      __syncthreads();
+      rows_pass(cov, plane, slot, r, rr1, rr2, t);
+      __syncthreads();                                     // the planes are whole
     }
-
-    // ---- blend
     const ctd_glyph_layer Ly = s_layer;                    // s_layer is next written behind the next group's first barrier
-    const int f0 = Ly.fill[0], f1 = Ly.fill[1], f2 = Ly.fill[2], s0 = Ly.stroke[0], s1 = Ly.stroke[1], s2 = Ly.stroke[2];
-    int n_fill = 0, n_stroke = 0;
-    if (gx >= ax1 && gx < ax2) {
-#pragma unroll
-      for (int j = 0; j < PX; ++j) {
-        const int yy = ly + j * LYS, gy = ty0 + yy;
-        if (gy < ay1 || gy >= ay2) continue;
-        const int F = cov[yy + r][lx + r];
-        int S = 0;
-        if (r > 0) {
-          S = plane[slot_dy[0]][yy + r][lx];
-          for (int dy = 1; dy <= r; ++dy) {
-            const int s = slot_dy[dy];
-            S = max(S, max((int)plane[s][yy + r - dy][lx], (int)plane[s][yy + r + dy][lx]));
-          }
-        }
-        const unsigned c = pix[j];
-        const int c0 = blend(blend(c & 255, s0, S), f0, F);
-        const int c1 = blend(blend((c >> 8) & 255, s1, S), f1, F);
-        const int c2 = blend(blend((c >> 16) & 255, s2, S), f2, F);
-        pix[j] = (unsigned)c0 | ((unsigned)c1 << 8) | ((unsigned)c2 << 16) | 0x1000000u;   // bit 24: written
-        n_fill += F > 0, n_stroke += S > 0;
-      }
-    }
-#pragma unroll
-    for (int d = 32; d >= 1; d >>= 1) {
-      n_fill += __shfl_down(n_fill, d, 64);
-      n_stroke += __shfl_down(n_stroke, d, 64);
-    }
-    if (lane == 0) {
-      if (n_fill) atomicAdd(&rows[li].n_fill, n_fill);
-      if (n_stroke) atomicAdd(&rows[li].n_stroke, n_stroke);
-    }
+    blend_count(r, ax1, ay1, ax2, ay2, Ly.fill, Ly.stroke, cov, plane, slot_dy, tx0, ty0, t, pix, rows, li);
   }
 
-  // ---- store, once: the pixels some layer wrote
-#pragma unroll
-  for (int j = 0; j < PX; ++j) {
-    if (pix[j] >> 24) {
-      unsigned char* q = base + (long long)(ty0 + ly + j * LYS) * P.pitch + 3 * gx;
-      q[0] = (unsigned char)pix[j], q[1] = (unsigned char)(pix[j] >> 8), q[2] = (unsigned char)(pix[j] >> 16);
-    }
-  }
+  store_tile(P, tx0, ty0, t, pix);
 }
 
 }  // namespace

@@ -25,8 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .colors import _shape_of
-from .regions import Page, _device_pages
+from .regions import Page, _check_pages, _device_pages, _views
 from .textblock import BlockList
 
 __all__ = ["erase_text", "ErasedPages", "erase_tables", "JOB_DTYPE", "PAGE_DTYPE", "ROW_DTYPE"]
@@ -111,10 +110,6 @@ class ErasedPages:
         return f"ErasedPages({len(self.pages)} pages, {len(self)} blocks, {int(self.plain.sum())} plain)"
 
 
-def _align(n: int, a: int = 256) -> int:
-    return (n + a - 1) // a * a
-
-
 def erase_text(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequence, grow: int = 2, ring: int = 4, tol: int = 12,
                min_ring: int = 16, stream: Optional[torch.cuda.Stream] = None, device=None) -> ErasedPages:
     """Decide for EVERY block of EVERY page of a batch whether it stands on a plain background, fill the plain ones and make
@@ -128,14 +123,7 @@ def erase_text(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequence
     prm = check_params(grow, ring, tol, min_ring)
     if len(pages) != len(blk_lists) or len(masks) != len(pages):
         raise ValueError("one mask and one blk_list per page")
-    for p, m in zip(pages, masks):
-        (ps, pu8), (ms, mu8) = _shape_of(p), _shape_of(m)
-        if not pu8 or len(ps) != 3 or ps[2] != 3:
-            raise ValueError("pages must be uint8 BGR (H,W,3)")
-        if not mu8 or ms != ps[:2]:
-            raise ValueError("a mask must be uint8 and have the shape of its page")
-        if ps[0] < 1 or ps[1] < 1:
-            raise ValueError("empty page")
+    _check_pages(pages, masks, "BGR ")
     lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in blk_lists]
     boxes = [_page_boxes(b) for b in lists]
     jobs, block0, counts, tile0, n_tiles = erase_tables(boxes, [tuple(p.shape[:2]) for p in pages])
@@ -158,19 +146,15 @@ def erase_text(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequence
             if max(pitch.max(), mpitch.max(), (3 * W).max()) >= 2 ** 31:
                 raise ValueError("row pitch beyond int32")
             # one buffer behind all the outputs: the pages, then the rest masks, each on a 256-byte boundary
-            sizes = [_align(int(h * w * 3)) for h, w in zip(H, W)] + [_align(int(h * w)) for h, w in zip(H, W)]
-            offs = np.cumsum([0] + sizes)
-            store = torch.empty((int(offs[-1]),), dtype=torch.uint8, device=device)
-            out = [store[int(offs[i]): int(offs[i]) + int(H[i] * W[i] * 3)].view(int(H[i]), int(W[i]), 3) for i in range(n_pages)]
-            rest = [store[int(offs[n_pages + i]): int(offs[n_pages + i]) + int(H[i] * W[i])].view(int(H[i]), int(W[i]))
-                    for i in range(n_pages)]
+            views = _views([(int(h), int(w), 3) for h, w in zip(H, W)] + [(int(h), int(w)) for h, w in zip(H, W)], device)[1]
+            out, rest = views[:n_pages], views[n_pages:]
             table = np.zeros((n * JOB_DTYPE.itemsize + n_pages * PAGE_DTYPE.itemsize,), np.uint8)   # jobs, then pages: one upload
             table[: n * JOB_DTYPE.itemsize] = jobs.view(np.uint8)
             pt = table[n * JOB_DTYPE.itemsize:].view(PAGE_DTYPE)
             pt["page_dev"] = [p.data_ptr() for p in pages]
             pt["mask_dev"] = [m.data_ptr() for m in masks]
-            pt["out_dev"] = store.data_ptr() + offs[:n_pages]
-            pt["rest_dev"] = store.data_ptr() + offs[n_pages: 2 * n_pages]
+            pt["out_dev"] = [o.data_ptr() for o in out]
+            pt["rest_dev"] = [r.data_ptr() for r in rest]
             pt["H"], pt["W"], pt["pitch"], pt["mask_pitch"], pt["out_pitch"], pt["rest_pitch"] = H, W, pitch, mpitch, 3 * W, W
             pt["block0"], pt["n_blocks"], pt["tile0"] = block0, counts, tile0
             prm.n_tiles = n_tiles

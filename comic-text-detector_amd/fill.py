@@ -25,8 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .colors import _shape_of
-from .regions import Page, _device_pages
+from .regions import Page, _check_pages, _device_pages, _views
 
 __all__ = ["fill_rest", "FilledPages", "fill_tables", "level_shapes", "PAGE_DTYPE", "ROW_DTYPE"]
 
@@ -101,10 +100,6 @@ class FilledPages:
         return f"FilledPages({len(self.pages)} pages, {int((self.status == L.FILL_OK).sum())} filled)"
 
 
-def _align(n: int, a: int = 256) -> int:
-    return (n + a - 1) // a * a
-
-
 def fill_rest(pages: Sequence[Page], holes: Sequence[Page], stream: Optional[torch.cuda.Stream] = None, device=None) -> FilledPages:
     """Fill the hole pixels of EVERY page of a batch by the pull-push rule: one table upload, one `ctd_fill_rest` call (three
     launches), one small download.  pages: uint8 (H,W,3) pages of any mix of sizes, holes: uint8 (H,W) masks of the same
@@ -113,14 +108,7 @@ def fill_rest(pages: Sequence[Page], holes: Sequence[Page], stream: Optional[tor
     the pages' device) and waits for the result; see `FilledPages`."""
     if len(holes) != len(pages):
         raise ValueError("one hole mask per page")
-    for p, m in zip(pages, holes):
-        (ps, pu8), (ms, mu8) = _shape_of(p), _shape_of(m)
-        if not pu8 or len(ps) != 3 or ps[2] != 3:
-            raise ValueError("pages must be uint8 (H,W,3)")
-        if not mu8 or ms != ps[:2]:
-            raise ValueError("a hole mask must be uint8 and have the shape of its page")
-        if ps[0] < 1 or ps[1] < 1:
-            raise ValueError("empty page")
+    _check_pages(pages, holes, mask="hole mask")
     tile0, n_tiles, lvl0, scratch_dwords, _ = fill_tables([tuple(p.shape[:2]) for p in pages])
     n_pages = len(pages)
     if n_pages == 0:
@@ -139,13 +127,11 @@ def fill_rest(pages: Sequence[Page], holes: Sequence[Page], stream: Optional[tor
             if max(pitch.max(), hpitch.max()) >= 2 ** 31:
                 raise ValueError("row pitch beyond int32")
             # one buffer behind all the outputs, each on a 256-byte boundary
-            offs = np.cumsum([0] + [_align(int(h * w * 3)) for h, w in zip(H, W)])
-            store = torch.empty((int(offs[-1]),), dtype=torch.uint8, device=device)
-            out = [store[int(offs[i]): int(offs[i]) + int(H[i] * W[i] * 3)].view(int(H[i]), int(W[i]), 3) for i in range(n_pages)]
+            out = _views([(int(h), int(w), 3) for h, w in zip(H, W)], device)[1]
             pt = np.zeros((n_pages,), PAGE_DTYPE)
             pt["page_dev"] = [p.data_ptr() for p in pages]
             pt["hole_dev"] = [m.data_ptr() for m in holes]
-            pt["out_dev"] = store.data_ptr() + offs[:n_pages]
+            pt["out_dev"] = [o.data_ptr() for o in out]
             pt["H"], pt["W"], pt["pitch"], pt["hole_pitch"], pt["out_pitch"] = H, W, pitch, hpitch, 3 * W
             pt["tile0"], pt["lvl0"] = tile0, lvl0
             tab = torch.from_numpy(pt.view(np.uint8)).to(device)

@@ -33,9 +33,9 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .colors import _shape_of
-from .regions import Page, _device_pages
-from .typeset import MAX_COORD, PAGE_DTYPE, ROW_DTYPE, TILE_DTYPE, TypesetPages, _align, _copies, _dense, _ints, _per_layer
+from .regions import Page
+from .typeset import (MAX_COORD, ROW_DTYPE, TILE_DTYPE, TypesetPages, _bin_tiles, _ints, _layer_args, _layers, _open_pages, _pack,
+                      _rects)
 
 __all__ = ["GlyphAtlas", "glyph_tables", "typeset_glyphs", "flow", "LAYER_DTYPE", "PLACE_DTYPE", "RECORD_DTYPE"]
 
@@ -137,67 +137,21 @@ def glyph_tables(shapes: Sequence, page_of, layer_of, sizes, xy, radius=0, clip=
     entries: int32 placement indices, ascending within a tile, so the placements of a layer are consecutive.  status[l], the
     first that applies: `_lib.TYPESET_EMPTY` (no placement has a glyph with pixels), `TYPESET_OUTSIDE` (no such placement's
     rectangle grown by r meets page and clip), `TYPESET_OK`.  Numpy only."""
-    H = _ints([s[0] for s in shapes], (-1,), "shapes")
-    W = _ints([s[1] for s in shapes], (-1,), "shapes")
-    if len(H) and (min(H.min(), W.min()) < 1 or max(H.max(), W.max()) > L.TYPESET_MAX_SIDE):
-        raise ValueError(f"page sides must be 1 .. {L.TYPESET_MAX_SIDE}")
-    page_of = _ints(page_of, (-1,), "page_of")
+    H, W, page_of, r, clip = _layers(shapes, page_of, radius, clip)
     nl = len(page_of)
     layer_of = _ints(layer_of, (-1,), "layer_of")
     n = len(layer_of)
-    sizes, xy = _ints(sizes, (n, 2), "sizes"), _ints(xy, (n, 2), "xy")
-    r = _per_layer(radius, nl, 1, "radius")[:, 0]
-    if nl and (page_of.min() < 0 or page_of.max() >= len(H)):
-        raise ValueError("page_of: an index of `shapes`")
     if n and (layer_of.min() < 0 or layer_of.max() >= nl):
         raise ValueError("layer_of: an index of the layers")
     if n and (np.diff(layer_of) < 0).any():
         raise ValueError("layer_of must be non-decreasing: the placements of a layer are consecutive")
-    if n and (sizes.min() < 0 or sizes.max() > L.TYPESET_MAX_SIDE):
-        raise ValueError(f"glyph sides must be 0 .. {L.TYPESET_MAX_SIDE}")
-    if nl and (r.min() < 0 or r.max() > L.TYPESET_MAX_RADIUS):
-        raise ValueError(f"radius in 0 .. {L.TYPESET_MAX_RADIUS}")
-    if n and np.abs(xy).max() > MAX_COORD:
-        raise ValueError("xy beyond 2^29")
-    pw, ph = W[page_of], H[page_of]
-    if clip is None:
-        clip = np.stack([np.zeros_like(pw), np.zeros_like(ph), pw, ph], axis=1)
-    clip = _per_layer(clip, nl, 4, "clip")
-    if nl and (clip.min() < -2 ** 31 or clip.max() >= 2 ** 31):
-        raise ValueError("clip beyond int32")
-    h, w = sizes[:, 0], sizes[:, 1]
-    rp, cp = r[layer_of], clip[layer_of]
-    x1 = np.maximum(np.maximum(xy[:, 0] - rp, cp[:, 0]), 0)
-    y1 = np.maximum(np.maximum(xy[:, 1] - rp, cp[:, 1]), 0)
-    x2 = np.minimum(np.minimum(xy[:, 0] + w + rp, cp[:, 2]), pw[layer_of])
-    y2 = np.minimum(np.minimum(xy[:, 1] + h + rp, cp[:, 3]), ph[layer_of])
-    inked = (w > 0) & (h > 0)
+    pg = page_of[layer_of]
+    sizes, xy, x1, y1, x2, y2 = _rects(n, sizes, xy, r[layer_of], clip[layer_of], W[pg], H[pg], "glyph")
+    inked = (sizes[:, 0] > 0) & (sizes[:, 1] > 0)
     drawn = inked & (x1 < x2) & (y1 < y2)
     n_inked, n_drawn = np.bincount(layer_of[inked], minlength=nl), np.bincount(layer_of[drawn], minlength=nl)
     status = np.where(n_inked == 0, L.TYPESET_EMPTY, np.where(n_drawn == 0, L.TYPESET_OUTSIDE, L.TYPESET_OK)).astype(np.int32)
-    pl = np.flatnonzero(drawn)
-    tw, th = L.TYPESET_TILE_W, L.TYPESET_TILE_H
-    tx1, ty1 = x1[pl] // tw, y1[pl] // th
-    nx, ny = (x2[pl] - 1) // tw + 1 - tx1, (y2[pl] - 1) // th + 1 - ty1
-    cnt = nx * ny
-    total = int(cnt.sum())
-    if total >= 2 ** 31:
-        raise ValueError("too many tile entries for one call")
-    k = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)     # the entry's number within its placement
-    nxr = np.repeat(nx, cnt)
-    tx, ty = np.repeat(tx1, cnt) + k % np.maximum(nxr, 1), np.repeat(ty1, cnt) + k // np.maximum(nxr, 1)
-    place = np.repeat(pl, cnt)
-    pg = page_of[layer_of[place]]
-    tiles_x = (W + tw - 1) // tw
-    per_page = tiles_x * ((H + th - 1) // th)
-    key = (np.cumsum(per_page) - per_page)[pg] + ty * tiles_x[pg] + tx
-    order = np.argsort(key, kind="stable")                 # stable: the placements of a tile stay in ascending order
-    first = np.flatnonzero(np.diff(key[order], prepend=-1)) if total else np.zeros((0,), np.int64)
-    tiles = np.zeros((len(first) + 1,), TILE_DTYPE)
-    at = order[first]
-    tiles["page"][:-1], tiles["tx"][:-1], tiles["ty"][:-1], tiles["first"][:-1] = pg[at], tx[at], ty[at], first
-    tiles["first"][-1] = total
-    return tiles, place[order].astype(np.int32), status
+    return _bin_tiles(H, W, pg, x1, y1, x2, y2, np.flatnonzero(drawn)) + (status,)
 
 
 def flow(ids, atlas, rect, line: Optional[int] = None, gap: int = 0, vertical: bool = False, breaks=None,
@@ -281,14 +235,7 @@ def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, 
     as in `typeset_pages`.  Bad arguments raise ValueError before anything is uploaded.  Runs on `stream` (default: the
     current stream of the atlas's device) and waits for the result: a `TypesetPages` with one row and one status per
     LAYER, whose `xy` is per PLACEMENT and which also carries `place_layer` (= layer_of) and `place_glyph`."""
-    for p in pages:
-        ps, pu8 = _shape_of(p)
-        if not pu8 or len(ps) != 3 or ps[2] != 3:
-            raise ValueError("pages must be uint8 (H,W,3)")
-        if inplace and not (isinstance(p, torch.Tensor) and p.is_cuda and _dense(p)):
-            raise ValueError("inplace=True needs device pages with dense rows")
-    shapes = [tuple(int(v) for v in p.shape[:2]) for p in pages]
-    page_of = _ints(page_of, (-1,), "page_of")
+    shapes, page_of, fill, stroke, r = _layer_args(pages, page_of, fill, stroke, radius, inplace)
     nl = len(page_of)
     layer_of = _ints(layer_of, (-1,), "layer_of")
     n = len(layer_of)
@@ -297,16 +244,7 @@ def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, 
         raise ValueError("atlas: an open GlyphAtlas")
     if n and (glyph.min() < 0 or glyph.max() >= len(atlas)):
         raise ValueError("glyph: an id of the atlas")
-    colours = []
-    for name, v in (("fill", fill), ("stroke", stroke)):
-        c = _per_layer(v, nl, 3, name)
-        if nl and (c.min() < 0 or c.max() > 255):
-            raise ValueError(f"{name}: 0 .. 255")
-        colours.append(c[:, ::-1])
-    r = _per_layer(radius, nl, 1, "radius")[:, 0]
     tiles, entries, status = glyph_tables(shapes, page_of, layer_of, atlas.sizes[glyph], xy, r, clip)
-    clip4 = _per_layer(clip, nl, 4, "clip") if clip is not None else np.array([(0, 0, shapes[p][1], shapes[p][0]) for p in page_of],
-                                                                             np.int64).reshape(nl, 4)
     n_pages, n_tiles = len(pages), len(tiles) - 1
     device = atlas.device if device is None else torch.device(device)
     if device != atlas.device:
@@ -314,27 +252,14 @@ def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, 
     with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
         with torch.cuda.device(device):
             st = torch.cuda.current_stream(device)
-            if inplace:
-                out = _device_pages(pages, device)[0] if n_pages else []
-                if any(o.data_ptr() != p.data_ptr() for o, p in zip(out, pages)):
-                    raise ValueError("inplace=True needs pages on the device the call runs on")
-            else:
-                out = _copies(pages, device) if n_pages else []
+            out, pt, clip4 = _open_pages(pages, shapes, page_of, clip, inplace, device)
             rows = np.zeros((nl,), ROW_DTYPE)
             if n_tiles:
-                pt = np.zeros((n_pages,), PAGE_DTYPE)
-                pt["page_dev"] = [o.data_ptr() for o in out]
-                pt["H"], pt["W"], pt["pitch"] = [s[0] for s in shapes], [s[1] for s in shapes], [o.stride(0) for o in out]
                 lt = np.zeros((nl,), LAYER_DTYPE)
-                lt["page"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = page_of, clip4, colours[0], colours[1], r
+                lt["page"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = page_of, clip4, fill, stroke, r
                 qt = np.zeros((n,), PLACE_DTYPE)
                 qt["layer"], qt["glyph"], qt["x"], qt["y"] = layer_of, glyph, xy[:, 0], xy[:, 1]
-                # one upload: the tables and the placements, each part on an 8-byte boundary
-                parts = [pt.view(np.uint8), lt.view(np.uint8), qt.view(np.uint8), tiles.view(np.uint8), entries.view(np.uint8)]
-                at = np.cumsum([0] + [_align(len(x), 8) for x in parts])
-                blob = np.zeros((int(at[-1]),), np.uint8)
-                for a, x in zip(at, parts):
-                    blob[int(a): int(a) + len(x)] = x
+                blob, at = _pack([pt, lt, qt, tiles, entries])     # one upload: the tables and the placements
                 tab = torch.from_numpy(blob).to(device)
                 rows_dev = torch.empty((nl * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=device)
                 prm = L.CtdGlyphParams(nl, n_pages, n_tiles, len(entries), n, len(atlas), atlas.nbytes)

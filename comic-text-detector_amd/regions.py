@@ -23,6 +23,7 @@ What is restated from cv2 here (four-point homography, the fixed-point linear wa
 from __future__ import annotations
 
 import ctypes as C
+import math
 from collections import namedtuple
 from typing import List, Optional, Sequence, Union
 
@@ -120,6 +121,40 @@ class LineRegions:
     def __repr__(self) -> str:
         return (f"LineRegions({len(self)} lines, {int((~self.valid).sum())} invalid, textheight {self.textheight}, "
                 f"{self.packed.numel()} bytes)")
+
+
+def _shape_of(a):
+    return tuple(a.shape), (a.dtype == torch.uint8 if isinstance(a, torch.Tensor) else np.asarray(a).dtype == np.uint8)
+
+
+def _check_pages(pages: Sequence[Page], masks: Optional[Sequence[Page]] = None, order: str = "", mask: str = "mask",
+                 nonempty: bool = True) -> None:
+    """The page arguments of the tail calls, on the host or on the device: ValueError unless every page is uint8 (H,W,3),
+    its mask (where masks are given, one a page) uint8 (H,W) of the page's size and, with `nonempty`, no side is 0.  `order`
+    ("BGR ") and `mask` ("hole mask") only word the message."""
+    for i, p in enumerate(pages):
+        ps, pu8 = _shape_of(p)
+        if not pu8 or len(ps) != 3 or ps[2] != 3:
+            raise ValueError(f"pages must be uint8 {order}(H,W,3)")
+        if masks is not None:
+            ms, mu8 = _shape_of(masks[i])
+            if not mu8 or ms != ps[:2]:
+                raise ValueError(f"a {mask} must be uint8 and have the shape of its page")
+        if nonempty and (ps[0] < 1 or ps[1] < 1):
+            raise ValueError("empty page")
+
+
+def _align(n: int, a: int = 256) -> int:
+    return (n + a - 1) // a * a
+
+
+def _views(shapes: Sequence[tuple], device) -> tuple:
+    """Uninitialised uint8 device tensors of `shapes`: views of ONE new allocation, in the order given, each on a 256-byte
+    boundary.  Returns (store, views)."""
+    sizes = [math.prod(s) for s in shapes]
+    offs = np.cumsum([0] + [_align(n) for n in sizes]).tolist()
+    store = torch.empty((offs[-1],), dtype=torch.uint8, device=device)
+    return store, [store[o: o + n].view(s) for o, n, s in zip(offs, sizes, shapes)]
 
 
 def _device_pages(pages: Sequence[Page], device=None):

@@ -25,8 +25,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .colors import _shape_of
-from .regions import Page, _device_pages
+from .regions import Page, _align, _check_pages, _device_pages, _views
 
 __all__ = ["typeset_pages", "TypesetPages", "typeset_tables", "place", "PAGE_DTYPE", "LAYER_DTYPE", "TILE_DTYPE", "ROW_DTYPE"]
 
@@ -70,6 +69,73 @@ def _per_layer(v, n, width, what) -> np.ndarray:
     raise ValueError(f"{what}: one value for all layers or one per layer")
 
 
+def _layers(shapes: Sequence, page_of, radius, clip) -> tuple:
+    """The per-layer arguments that `typeset_tables` and `glyphs.glyph_tables` share, checked: (H, W, page_of, r, clip) with
+    H, W per page, the others per layer, all int64; the default clip is the layer's page."""
+    H = _ints([s[0] for s in shapes], (-1,), "shapes")
+    W = _ints([s[1] for s in shapes], (-1,), "shapes")
+    if len(H) and (min(H.min(), W.min()) < 1 or max(H.max(), W.max()) > L.TYPESET_MAX_SIDE):
+        raise ValueError(f"page sides must be 1 .. {L.TYPESET_MAX_SIDE}")
+    page_of = _ints(page_of, (-1,), "page_of")
+    n = len(page_of)
+    r = _per_layer(radius, n, 1, "radius")[:, 0]
+    if n and (page_of.min() < 0 or page_of.max() >= len(H)):
+        raise ValueError("page_of: an index of `shapes`")
+    if n and (r.min() < 0 or r.max() > L.TYPESET_MAX_RADIUS):
+        raise ValueError(f"radius in 0 .. {L.TYPESET_MAX_RADIUS}")
+    pw, ph = W[page_of], H[page_of]
+    if clip is None:
+        clip = np.stack([np.zeros_like(pw), np.zeros_like(ph), pw, ph], axis=1)
+    clip = _per_layer(clip, n, 4, "clip")
+    if n and (clip.min() < -2 ** 31 or clip.max() >= 2 ** 31):
+        raise ValueError("clip beyond int32")
+    return H, W, page_of, r, clip
+
+
+def _rects(n: int, sizes, xy, r, clip, pw, ph, what: str) -> tuple:
+    """n bitmaps of sizes[i] = (h, w) at xy[i], checked (`what` words the message), and the rectangle of each grown by
+    r[i], cut to clip[i] and to its page of pw[i] x ph[i]: (sizes, xy, x1, y1, x2, y2); empty where x1 >= x2 or y1 >= y2."""
+    sizes, xy = _ints(sizes, (n, 2), "sizes"), _ints(xy, (n, 2), "xy")
+    if n and (sizes.min() < 0 or sizes.max() > L.TYPESET_MAX_SIDE):
+        raise ValueError(f"{what} sides must be 0 .. {L.TYPESET_MAX_SIDE}")
+    if n and np.abs(xy).max() > MAX_COORD:
+        raise ValueError("xy beyond 2^29")
+    x1 = np.maximum(np.maximum(xy[:, 0] - r, clip[:, 0]), 0)
+    y1 = np.maximum(np.maximum(xy[:, 1] - r, clip[:, 1]), 0)
+    x2 = np.minimum(np.minimum(xy[:, 0] + sizes[:, 1] + r, clip[:, 2]), pw)
+    y2 = np.minimum(np.minimum(xy[:, 1] + sizes[:, 0] + r, clip[:, 3]), ph)
+    return sizes, xy, x1, y1, x2, y2
+
+
+def _bin_tiles(H, W, page_of_item, x1, y1, x2, y2, items) -> tuple:
+    """The tile binner of both typeset calls: (tiles, entries).  `items` (ascending indices) lie on page page_of_item[i] of
+    H[p] x W[p] pixels and cover the non-empty rectangle x1[i] .. y2[i], exclusive, within it.  tiles: `TILE_DTYPE`, every
+    tile that an item's rectangle meets once, in page-major, row-major order, and a closing row whose `first` is the entry
+    count; entries: int32, the items of each tile in ascending order."""
+    tw, th = L.TYPESET_TILE_W, L.TYPESET_TILE_H
+    tx1, ty1 = x1[items] // tw, y1[items] // th
+    nx, ny = (x2[items] - 1) // tw + 1 - tx1, (y2[items] - 1) // th + 1 - ty1
+    cnt = nx * ny
+    total = int(cnt.sum())
+    if total >= 2 ** 31:
+        raise ValueError("too many tile entries for one call")
+    k = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)     # the entry's number within its item
+    nxr = np.repeat(nx, cnt)
+    tx, ty = np.repeat(tx1, cnt) + k % np.maximum(nxr, 1), np.repeat(ty1, cnt) + k // np.maximum(nxr, 1)
+    item = np.repeat(items, cnt)
+    pg = page_of_item[item]
+    tiles_x = (W + tw - 1) // tw
+    per_page = tiles_x * ((H + th - 1) // th)
+    key = (np.cumsum(per_page) - per_page)[pg] + ty * tiles_x[pg] + tx
+    order = np.argsort(key, kind="stable")                 # stable: the items of a tile stay in ascending order
+    first = np.flatnonzero(np.diff(key[order], prepend=-1)) if total else np.zeros((0,), np.int64)
+    tiles = np.zeros((len(first) + 1,), TILE_DTYPE)
+    at = order[first]
+    tiles["page"][:-1], tiles["tx"][:-1], tiles["ty"][:-1], tiles["first"][:-1] = pg[at], tx[at], ty[at], first
+    tiles["first"][-1] = total
+    return tiles, item[order].astype(np.int32)
+
+
 def typeset_tables(shapes: Sequence, page_of, sizes, xy, radius=0, clip=None) -> tuple:
     """The tile table and the entry list of a typeset call: (tiles, entries, status).  shapes[p] = (H, W) of page p; per
     layer page_of[i], sizes[i] = (h, w) of its bitmap, xy[i] = (x0, y0) of the bitmap's top-left pixel in page coordinates,
@@ -78,58 +144,11 @@ def typeset_tables(shapes: Sequence, page_of, sizes, xy, radius=0, clip=None) ->
     tiles: `TILE_DTYPE`, n_tiles + 1 rows, every touched tile once in page-major, row-major order, the last row's `first` the
     entry count.  entries: int32 layer indices, ascending within a tile.  status[i], the first that applies:
     `_lib.TYPESET_EMPTY` (w or h is 0), `TYPESET_OUTSIDE` (that rectangle is empty), `TYPESET_OK`.  Numpy only."""
-    H = _ints([s[0] for s in shapes], (-1,), "shapes")
-    W = _ints([s[1] for s in shapes], (-1,), "shapes")
-    if len(H) and (min(H.min(), W.min()) < 1 or max(H.max(), W.max()) > L.TYPESET_MAX_SIDE):
-        raise ValueError(f"page sides must be 1 .. {L.TYPESET_MAX_SIDE}")
-    page_of = _ints(page_of, (-1,), "page_of")
-    n = len(page_of)
-    sizes, xy = _ints(sizes, (n, 2), "sizes"), _ints(xy, (n, 2), "xy")
-    r = _per_layer(radius, n, 1, "radius")[:, 0]
-    if n and (page_of.min() < 0 or page_of.max() >= len(H)):
-        raise ValueError("page_of: an index of `shapes`")
-    if n and (sizes.min() < 0 or sizes.max() > L.TYPESET_MAX_SIDE):
-        raise ValueError(f"bitmap sides must be 0 .. {L.TYPESET_MAX_SIDE}")
-    if n and (r.min() < 0 or r.max() > L.TYPESET_MAX_RADIUS):
-        raise ValueError(f"radius in 0 .. {L.TYPESET_MAX_RADIUS}")
-    if n and np.abs(xy).max() > MAX_COORD:
-        raise ValueError("xy beyond 2^29")
-    pw, ph = W[page_of], H[page_of]
-    if clip is None:
-        clip = np.stack([np.zeros_like(pw), np.zeros_like(ph), pw, ph], axis=1)
-    clip = _per_layer(clip, n, 4, "clip")
-    if n and (clip.min() < -2 ** 31 or clip.max() >= 2 ** 31):
-        raise ValueError("clip beyond int32")
-    h, w = sizes[:, 0], sizes[:, 1]
-    x1 = np.maximum(np.maximum(xy[:, 0] - r, clip[:, 0]), 0)
-    y1 = np.maximum(np.maximum(xy[:, 1] - r, clip[:, 1]), 0)
-    x2 = np.minimum(np.minimum(xy[:, 0] + w + r, clip[:, 2]), pw)
-    y2 = np.minimum(np.minimum(xy[:, 1] + h + r, clip[:, 3]), ph)
-    status = np.where((w == 0) | (h == 0), L.TYPESET_EMPTY,
+    H, W, page_of, r, clip = _layers(shapes, page_of, radius, clip)
+    sizes, xy, x1, y1, x2, y2 = _rects(len(page_of), sizes, xy, r, clip, W[page_of], H[page_of], "bitmap")
+    status = np.where((sizes[:, 0] == 0) | (sizes[:, 1] == 0), L.TYPESET_EMPTY,
                       np.where((x1 >= x2) | (y1 >= y2), L.TYPESET_OUTSIDE, L.TYPESET_OK)).astype(np.int32)
-    lay = np.flatnonzero(status == L.TYPESET_OK)
-    tw, th = L.TYPESET_TILE_W, L.TYPESET_TILE_H
-    tx1, ty1 = x1[lay] // tw, y1[lay] // th
-    nx, ny = (x2[lay] - 1) // tw + 1 - tx1, (y2[lay] - 1) // th + 1 - ty1
-    cnt = nx * ny
-    total = int(cnt.sum())
-    if total >= 2 ** 31:
-        raise ValueError("too many tile entries for one call")
-    k = np.arange(total, dtype=np.int64) - np.repeat(np.cumsum(cnt) - cnt, cnt)     # the entry's number within its layer
-    nxr = np.repeat(nx, cnt)
-    tx, ty = np.repeat(tx1, cnt) + k % np.maximum(nxr, 1), np.repeat(ty1, cnt) + k // np.maximum(nxr, 1)
-    layer = np.repeat(lay, cnt)
-    pg = page_of[layer]
-    tiles_x = (W + tw - 1) // tw
-    per_page = tiles_x * ((H + th - 1) // th)
-    key = (np.cumsum(per_page) - per_page)[pg] + ty * tiles_x[pg] + tx
-    order = np.argsort(key, kind="stable")                 # stable: the layers of a tile stay in ascending order
-    first = np.flatnonzero(np.diff(key[order], prepend=-1)) if total else np.zeros((0,), np.int64)
-    tiles = np.zeros((len(first) + 1,), TILE_DTYPE)
-    at = order[first]
-    tiles["page"][:-1], tiles["tx"][:-1], tiles["ty"][:-1], tiles["first"][:-1] = pg[at], tx[at], ty[at], first
-    tiles["first"][-1] = total
-    return tiles, layer[order].astype(np.int32), status
+    return _bin_tiles(H, W, page_of, x1, y1, x2, y2, np.flatnonzero(status == L.TYPESET_OK)) + (status,)
 
 
 def place(rects, sizes, radius=0) -> tuple:
@@ -170,10 +189,6 @@ class TypesetPages:
         return f"TypesetPages({len(self.pages)} pages, {len(self)} layers, {int((self.status == L.TYPESET_OK).sum())} drawn)"
 
 
-def _align(n: int, a: int = 256) -> int:
-    return (n + a - 1) // a * a
-
-
 def _dense(t) -> bool:
     return t.stride(2) == 1 and t.stride(1) == 3 and t.stride(0) >= 3 * t.shape[1]
 
@@ -181,20 +196,66 @@ def _dense(t) -> bool:
 def _copies(pages, device):
     """The pages copied into views of ONE new allocation, each on a 256-byte boundary: one device copy where they already lie
     like that in one buffer (as `FilledPages.pages` do), else one copy (or upload) a page."""
-    sizes = [int(p.shape[0]) * int(p.shape[1]) * 3 for p in pages]
-    offs = np.cumsum([0] + [_align(s) for s in sizes])
-    store = torch.empty((int(offs[-1]),), dtype=torch.uint8, device=device)
-    out = [store[int(offs[i]): int(offs[i]) + sizes[i]].view(int(p.shape[0]), int(p.shape[1]), 3) for i, p in enumerate(pages)]
+    store, out = _views([(int(p.shape[0]), int(p.shape[1]), 3) for p in pages], device)
     dev = [p for p in pages if isinstance(p, torch.Tensor) and p.device == device and p.is_contiguous()]
     if len(dev) == len(pages) and all(p.untyped_storage().data_ptr() == dev[0].untyped_storage().data_ptr() and
-                                      p.data_ptr() - dev[0].data_ptr() == int(offs[i]) for i, p in enumerate(dev)):
-        used = int(offs[len(pages) - 1]) + sizes[-1]
+                                      p.data_ptr() - dev[0].data_ptr() == o.data_ptr() - out[0].data_ptr() for p, o in zip(dev, out)):
+        used = out[-1].data_ptr() - out[0].data_ptr() + out[-1].numel()
         src = torch.empty((0,), dtype=torch.uint8, device=device).set_(dev[0].untyped_storage(), dev[0].storage_offset(), (used,))
         store[:used].copy_(src)
     else:
         for o, p in zip(out, pages):
             o.copy_(p if isinstance(p, torch.Tensor) else torch.from_numpy(np.ascontiguousarray(p)))
     return out
+
+
+def _layer_args(pages, page_of, fill, stroke, radius, inplace: bool) -> tuple:
+    """What `typeset_pages` and `glyphs.typeset_glyphs` check first, ValueError where it is wrong: the pages, the per-layer
+    columns -> (shapes, page_of, fill (n, 3) BGR, stroke (n, 3) BGR, r)."""
+    _check_pages(pages, nonempty=False)                    # an empty page is the tables' "page sides" error
+    if inplace and not all(isinstance(p, torch.Tensor) and p.is_cuda and _dense(p) for p in pages):
+        raise ValueError("inplace=True needs device pages with dense rows")
+    shapes = [tuple(int(v) for v in p.shape[:2]) for p in pages]
+    page_of = _ints(page_of, (-1,), "page_of")
+    n = len(page_of)
+    colours = []
+    for name, v in (("fill", fill), ("stroke", stroke)):
+        c = _per_layer(v, n, 3, name)
+        if n and (c.min() < 0 or c.max() > 255):
+            raise ValueError(f"{name}: 0 .. 255")
+        colours.append(c[:, ::-1])
+    return shapes, page_of, colours[0], colours[1], _per_layer(radius, n, 1, "radius")[:, 0]
+
+
+def _open_pages(pages, shapes, page_of, clip, inplace: bool, device) -> tuple:
+    """Behind the tables, which have checked `page_of` and `clip`, and on the call's device and stream: (out, pt, clip4).
+    out: the pages the kernel writes, the caller's own where `inplace`, else copies (views of one new allocation); pt:
+    their `ctd_typeset_page` table; clip4: the clip of every layer, (n, 4), the page where none was given."""
+    n = len(page_of)
+    clip4 = _per_layer(clip, n, 4, "clip") if clip is not None else np.array([(0, 0, shapes[p][1], shapes[p][0]) for p in page_of],
+                                                                            np.int64).reshape(n, 4)
+    if not pages:
+        out = []
+    elif inplace:
+        out = _device_pages(pages, device)[0]
+        if any(o.data_ptr() != p.data_ptr() for o, p in zip(out, pages)):
+            raise ValueError("inplace=True needs pages on the device the call runs on")
+    else:
+        out = _copies(pages, device)
+    pt = np.zeros((len(out),), PAGE_DTYPE)
+    pt["page_dev"] = [o.data_ptr() for o in out]
+    pt["H"], pt["W"], pt["pitch"] = [s[0] for s in shapes], [s[1] for s in shapes], [o.stride(0) for o in out]
+    return out, pt, clip4
+
+
+def _pack(parts) -> tuple:
+    """The tables of a call as ONE byte array for one upload, each part on an 8-byte boundary: (blob, offsets)."""
+    parts = [x.view(np.uint8) for x in parts]
+    at = np.cumsum([0] + [_align(len(x), 8) for x in parts])
+    blob = np.zeros((int(at[-1]),), np.uint8)
+    for a, x in zip(at, parts):
+        blob[int(a): int(a) + len(x)] = x
+    return blob, at
 
 
 def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray], xy, fill=(0, 0, 0), stroke=(255, 255, 255),
@@ -209,14 +270,7 @@ def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray],
     allocation; inplace=True writes the given pages, which must then be device tensors with dense rows (any row pitch).
     Bad arguments raise ValueError before anything is uploaded.  Runs on `stream` (default: the current stream of the pages'
     device) and waits for the result; see `TypesetPages`."""
-    for p in pages:
-        ps, pu8 = _shape_of(p)
-        if not pu8 or len(ps) != 3 or ps[2] != 3:
-            raise ValueError("pages must be uint8 (H,W,3)")
-        if inplace and not (isinstance(p, torch.Tensor) and p.is_cuda and _dense(p)):
-            raise ValueError("inplace=True needs device pages with dense rows")
-    shapes = [tuple(int(v) for v in p.shape[:2]) for p in pages]
-    page_of = _ints(page_of, (-1,), "page_of")
+    shapes, page_of, fill, stroke, r = _layer_args(pages, page_of, fill, stroke, radius, inplace)
     n = len(page_of)
     if len(bitmaps) != n:
         raise ValueError("one bitmap per layer")
@@ -225,16 +279,7 @@ def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray],
             raise ValueError("a bitmap is a (h, w) uint8 numpy array")
     sizes = np.array([b.shape for b in bitmaps], np.int64).reshape(n, 2)
     xy = _ints(xy, (n, 2), "xy")
-    colours = []
-    for name, v in (("fill", fill), ("stroke", stroke)):
-        c = _per_layer(v, n, 3, name)
-        if n and (c.min() < 0 or c.max() > 255):
-            raise ValueError(f"{name}: 0 .. 255")
-        colours.append(c[:, ::-1])
-    r = _per_layer(radius, n, 1, "radius")[:, 0]
     tiles, entries, status = typeset_tables(shapes, page_of, sizes, xy, r, clip)
-    clip4 = _per_layer(clip, n, 4, "clip") if clip is not None else np.array([(0, 0, shapes[p][1], shapes[p][0]) for p in page_of],
-                                                                            np.int64).reshape(n, 4)
     if not torch.cuda.is_available():
         raise L.CtdError("typesetting runs on the GPU and there is none (no CPU fallback)")
     area = sizes[:, 0] * sizes[:, 1]
@@ -247,26 +292,13 @@ def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray],
         device = torch.device(device)
         with torch.cuda.device(device):
             st = torch.cuda.current_stream(device)
-            if inplace:
-                out = _device_pages(pages, device)[0] if n_pages else []
-                if any(o.data_ptr() != p.data_ptr() for o, p in zip(out, pages)):
-                    raise ValueError("inplace=True needs pages on the device the call runs on")
-            else:
-                out = _copies(pages, device) if n_pages else []
+            out, pt, clip4 = _open_pages(pages, shapes, page_of, clip, inplace, device)
             rows = np.zeros((n,), ROW_DTYPE)
             if n and n_pages:
-                pt = np.zeros((n_pages,), PAGE_DTYPE)
-                pt["page_dev"] = [o.data_ptr() for o in out]
-                pt["H"], pt["W"], pt["pitch"] = [s[0] for s in shapes], [s[1] for s in shapes], [o.stride(0) for o in out]
                 lt = np.zeros((n,), LAYER_DTYPE)
                 lt["cov0"], lt["page"], lt["x0"], lt["y0"], lt["h"], lt["w"] = cov0, page_of, xy[:, 0], xy[:, 1], sizes[:, 0], sizes[:, 1]
-                lt["cov_pitch"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = sizes[:, 1], clip4, colours[0], colours[1], r
-                # one upload: the four tables and the coverage, each part on an 8-byte boundary
-                parts = [pt.view(np.uint8), lt.view(np.uint8), tiles.view(np.uint8), entries.view(np.uint8), cov]
-                at = np.cumsum([0] + [_align(len(x), 8) for x in parts])
-                blob = np.zeros((int(at[-1]),), np.uint8)
-                for a, x in zip(at, parts):
-                    blob[int(a): int(a) + len(x)] = x
+                lt["cov_pitch"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = sizes[:, 1], clip4, fill, stroke, r
+                blob, at = _pack([pt, lt, tiles, entries, cov])    # one upload: the four tables and the coverage
                 tab = torch.from_numpy(blob).to(device)
                 rows_dev = torch.empty((n * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=device)
                 prm = L.CtdTypesetParams(n, n_pages, n_tiles, len(entries), len(cov), 0)

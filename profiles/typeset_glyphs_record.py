@@ -64,10 +64,7 @@ def host(fn):
 
 
 def blob(parts, dev):
-    at = np.cumsum([0] + [T._align(len(x), 8) for x in parts])
-    b = np.zeros((int(at[-1]),), np.uint8)
-    for a, x in zip(at, parts):
-        b[int(a): int(a) + len(x)] = x
+    b, at = T._pack(parts)
     tab = torch.from_numpy(b).to(dev)
     return tab, [tab.data_ptr() + int(a) for a in at], len(b)
 

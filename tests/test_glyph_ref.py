@@ -90,6 +90,41 @@ def test_glyph_tables_against_a_brute_force_loop():
     assert len(t0) == 1 and len(e0) == 0 and s0.tolist() == [TR.EMPTY, TR.EMPTY]
 
 
+def test_one_placement_per_layer_gives_the_tables_of_typeset_tables():
+    """Both calls bin through one `_bin_tiles`: a layer that is one glyph is a bitmap layer, so on the same rectangles
+    `glyph_tables` returns the bytes of `typeset_tables`: the tiles, the entries (a placement's index is its layer's) and
+    the status.  The hand-made layers of tests/typeset_ref.py (every radius, clips, empty and outside ones) and seeded
+    random ones, a third with a clip of their own, on `TR.SHAPES` and a page of several tiles both ways."""
+    p = pkg()
+    G, T = p.glyphs, p.typeset
+    assert G._bin_tiles is T._bin_tiles
+    rng = np.random.default_rng(7)
+    shapes = TR.SHAPES + [(200, 300)]
+    layers = TR.small_layers()
+    for i in range(120):
+        pg = int(rng.integers(0, len(shapes)))
+        H, W = shapes[pg]
+        clip = None
+        if i % 3 == 0:
+            cx, cy = sorted(rng.integers(-20, W + 20, 2)), sorted(rng.integers(-20, H + 20, 2))
+            clip = (int(cx[0]), int(cy[0]), int(cx[1]), int(cy[1]))
+        layers.append(TR.layer(pg, np.zeros((int(rng.integers(0, 90)), int(rng.integers(0, 90))), np.uint8),
+                               int(rng.integers(-100, W + 20)), int(rng.integers(-100, H + 20)), int(rng.integers(0, 13)), clip=clip))
+    page_of, radius = [ly["page"] for ly in layers], [ly["r"] for ly in layers]
+    sizes, xy = [ly["cov"].shape for ly in layers], [(ly["x0"], ly["y0"]) for ly in layers]
+    seen, most = set(), 0
+    for clip in (_clips(layers, shapes), None, (10, 10, 60, 60)):
+        for r in (radius, 0, 12):
+            t1, e1, s1 = T.typeset_tables(shapes, page_of, sizes, xy, r, clip)
+            t2, e2, s2 = G.glyph_tables(shapes, page_of, np.arange(len(layers)), sizes, xy, r, clip)
+            assert t1.dtype == t2.dtype and t1.tobytes() == t2.tobytes() and len(t1) > 1
+            assert e1.dtype == e2.dtype == np.int32 and e1.tobytes() == e2.tobytes() and len(e1) > len(t1)
+            assert s1.dtype == s2.dtype and s1.tolist() == s2.tolist()
+            seen |= set(s1.tolist())
+            most = max(most, len(t1))
+    assert seen == {TR.OK, TR.EMPTY, TR.OUTSIDE} and most > 40           # the page clips: tiles of every page
+
+
 def test_glyph_tables_refusals():
     G = pkg().glyphs
     ok = dict(shapes=TR.SHAPES, page_of=[0, 0], layer_of=[0, 1], sizes=[(3, 3), (3, 3)], xy=[(0, 0), (5, 5)], radius=0, clip=None)
