@@ -136,11 +136,10 @@ def test_two_layers_overlapping_on_one_tile_in_both_orders():
 
 # ---- 2. the caller's buffers ----------------------------------------------------------------------------------------------------
 
-def test_views_at_an_odd_offset_and_pitch_and_untouched_guards():
-    """The small pages as views at an odd byte offset with an odd pitch inside one larger buffer: `inplace=False` leaves every
-    byte of it as it was; `inplace=True` writes the views and nothing around or between their rows."""
-    p = pkg()
-    pages, bitmaps, layers, places, want, want_rows, bl = _small()
+def _odd_views(pages, want):
+    """The pages as views at an odd byte offset with an odd pitch inside ONE buffer of GUARD bytes: (host, expect, buf,
+    views) with host the buffer holding `pages`, expect the same buffer holding `want`, buf a device copy of host and views
+    the pages inside buf."""
     pitch = [(3 * pg.shape[1] + 7) | 1 for pg in pages]
     offs, at = [], 33
     for pg, pt in zip(pages, pitch):
@@ -155,6 +154,15 @@ def test_views_at_an_odd_offset_and_pitch_and_untouched_guards():
         np.lib.stride_tricks.as_strided(expect[o:], (H, W, 3), (pt, 3, 1))[...] = w
     buf = torch.from_numpy(host).cuda()
     views = [torch.as_strided(buf, (pg.shape[0], pg.shape[1], 3), (pt, 3, 1), o) for pg, o, pt in zip(pages, offs, pitch)]
+    return host, expect, buf, views
+
+
+def test_views_at_an_odd_offset_and_pitch_and_untouched_guards():
+    """The small pages as views at an odd byte offset with an odd pitch inside one larger buffer: `inplace=False` leaves every
+    byte of it as it was; `inplace=True` writes the views and nothing around or between their rows."""
+    p = pkg()
+    pages, bitmaps, layers, places, want, want_rows, bl = _small()
+    host, expect, buf, views = _odd_views(pages, want)
     atlas = _atlas(p, bitmaps)
     kw = _args(pages, layers, places)
     tp = p.glyphs.typeset_glyphs(views, atlas, **kw)
