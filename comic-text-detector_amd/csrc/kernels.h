@@ -157,8 +157,11 @@ void launch_ccl(const uint8_t* img, int B, int H, int W, int thresh, int conn, i
                 int* stats, int max_labels, void* ws, hipStream_t st, int invert = 0, int* first = nullptr, int bg_negative = 0);
 // Foreground (img > thresh, 8-connected) and background (4-connected) components in one union-find:
 // labels (B,H,W) signed (+id / -id, per-class raster order), n / stats / first per class, same workspace.
+// seg_live (B, ceil(H*W / 64)) or null: one byte per 64 consecutive linear pixels of a page, 1 where some pixel of the
+// segment has a label other than -1 (the background component that holds the page's first background pixel).
 void launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* labels, int* n_f, int* n_b, int* st_f,
-                     int* st_b, int* first_f, int* first_b, int max_labels, void* ws, hipStream_t st);
+                     int* st_b, int* first_f, int* first_b, int max_labels, void* ws, hipStream_t st,
+                     uint8_t* seg_live = nullptr);
 
 // ---- kernels_pre.hip ----------------------------------------------------------
 // cv2.resize(INTER_LINEAR) u8 (C = 1 or 3) into the top-left (dH,dW) of a zero-padded canvas

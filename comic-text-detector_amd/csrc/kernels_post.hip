@@ -992,9 +992,11 @@ __global__ __launch_bounds__(256) void ccl2_rank_kernel(const unsigned long long
 }
 
 // signed final labels + the statistics of both classes (aggregation as in ccl_label_kernel)
+// seg_live (null: not wanted): a wave's 64 pixels are one 64-aligned segment of the page's linear index (chunks and steps
+// are multiples of 256), and the wave has their labels in registers: lane 0 notes whether any differs from -1.
 __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels_all, const int* __restrict__ ids_all, int B, int H,
                                                          int W, int chunks, int* __restrict__ st_f, int* __restrict__ st_b,
-                                                         int max_labels) {
+                                                         int max_labels, uint8_t* __restrict__ seg_live) {
   constexpr int EMPTY = (int)0x80000000;
   __shared__ int hkey[LB_SLOTS];
   __shared__ int hst[LB_SLOTS * 5];
@@ -1032,6 +1034,11 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
       const bool live = p < p_end;
       const int id = idv[u];                                  // 0 = dead lane (every pixel has a class, so no real id is 0)
       const int x = live ? p % W : 0, y = live ? p / W : 0;
+      if (seg_live) {
+        const unsigned long long other = __ballot(live && id != -1);
+        const int q0 = p0 + ((int)threadIdx.x & ~63);
+        if (lane == 0 && q0 < p_end) seg_live[(size_t)b * ((hw + 63) >> 6) + (q0 >> 6)] = other ? 1 : 0;
+      }
       const int prev = __shfl_up(id, 1);
       const bool head = lane == 0 || prev != id || x == 0;
       const unsigned long long heads = __ballot(head);
@@ -1074,9 +1081,9 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
 // waves per SIMD next to the network, not all of them
 __global__ __launch_bounds__(256) void ccl2_label_kernel(int* __restrict__ labels_all, const int* __restrict__ ids_all, int B, int H,
                                                          int W, int chunks, int* __restrict__ st_f, int* __restrict__ st_b,
-                                                         int max_labels, int nvb) {
+                                                         int max_labels, int nvb, uint8_t* __restrict__ seg_live) {
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl2_label_body(vb, labels_all, ids_all, B, H, W, chunks, st_f, st_b, max_labels);
+    ccl2_label_body(vb, labels_all, ids_all, B, H, W, chunks, st_f, st_b, max_labels, seg_live);
     __syncthreads();
   }
 }
@@ -1160,7 +1167,7 @@ void launch_ccl(const uint8_t* img, int B, int H, int W, int thresh, int conn, i
 }
 
 void launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* labels, int* n_f, int* n_b, int* st_f,
-                     int* st_b, int* first_f, int* first_b, int max_labels, void* ws, hipStream_t st) {
+                     int* st_b, int* first_f, int* first_b, int max_labels, void* ws, hipStream_t st, uint8_t* seg_live) {
   const int hw = H * W;
   const long long total = (long long)B * hw;
   const int nchunks = (hw + RK_CHUNK - 1) / RK_CHUNK;
@@ -1183,7 +1190,7 @@ void launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* l
   hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(sgrid, B), dim3(256), 0, st, st_b, n_b, max_labels, H, W);
   const int lchunks = (hw + LB_CHUNK - 1) / LB_CHUNK;
   hipLaunchKernelGGL(ccl2_label_kernel, dim3(capped(B * lchunks)), dim3(256), 0, st, labels, ids, B, H, W, lchunks, st_f, st_b,
-                     max_labels, B * lchunks);
+                     max_labels, B * lchunks, seg_live);
   hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, st_f, n_f, max_labels);
   hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, st_b, n_b, max_labels);
 }

@@ -67,7 +67,7 @@ __global__ __launch_bounds__(256) void dbc_scan_kernel(DbcTables t) {
   __shared__ int sh[4];
   const int b = blockIdx.x;
   const int nf = min(t.n_f[b], t.cap), nb = min(t.n_b[b], t.cap);
-  int carry = 0;
+  int carry = 0, carry_f = 0;
   for (int pass = 0; pass < 2; ++pass) {
     int* a = (pass ? t.off_b : t.off_f) + (size_t)b * t.cap;
     const int n = pass ? nb : nf;
@@ -79,9 +79,11 @@ __global__ __launch_bounds__(256) void dbc_scan_kernel(DbcTables t) {
       if (i < n) a[i] = carry + e;
       carry += total;
     }
+    if (pass == 0) carry_f = carry;
   }
   if (threadIdx.x == 0) {
     int* h = t.hdr + b * 4;
+    t.hole_rows[b] = carry - carry_f;
     h[0] = nf, h[1] = nb, h[2] = carry;
     h[3] = (t.n_f[b] > t.cap || t.n_b[b] > t.cap || carry > t.rcap) ? 1 : 0;
   }
@@ -105,15 +107,41 @@ __global__ __launch_bounds__(256) void dbc_accum_kernel(DbcTables t) {
   // loads that nearly every wave needs only to find out that it has nothing to add.  One step at a time a thread spent
   // its ~44 steps waiting for one load after the other.
   constexpr int DU = 4;
+  // Label -1 is the background component that holds the page's first background pixel: on nearly every page the outer
+  // background, no hole, most of the page.  A wave's 64 pixels are one 64-aligned segment of the linear index (every step
+  // is a multiple of 256), and the label pass left a flag per segment: where the flag is clear and -1 is no hole the wave
+  // knows its labels (-1) and their ring (none) without loading either.  A page whose -1 IS a hole (a foreground frame
+  // around the page) is swept in full.  The flags of a batch are fetched one batch ahead: they are not one more round
+  // trip in front of the labels.
+  // A page without any hole (`hole_rows` = 0: the usual text-line map) has no ring and no hole sum: no `par_b` gather, and
+  // below no look at a foreground pixel's four neighbours.
+  const bool rings = t.hole_rows[b] > 0;
+  const uint8_t* seg = t.seg_live ? t.seg_live + (size_t)b * ((hw + 63) >> 6) : nullptr;
+  const bool outer_plain = seg && !(rings && t.hdr[b * 4 + 1] > 0 && t.par_b[cb] > 0);
+  auto flags_of = [&](long long pb, int* some) {
+#pragma unroll
+    for (int u = 0; u < DU; ++u) {
+      const long long q0 = pb + (long long)u * span + ((int)threadIdx.x & ~63);
+      some[u] = (outer_plain && q0 < hw) ? seg[q0 >> 6] : 1;
+    }
+  };
+  int some[DU];
+  flags_of((long long)blockIdx.x * 256, some);
   for (long long pb = (long long)blockIdx.x * 256; pb < hw; pb += (long long)span * DU) {
-    int keys[DU], pars[DU];
+    int keys[DU], pars[DU], ahead[DU];
+    float prv[DU];
+    flags_of(pb + (long long)span * DU, ahead);
 #pragma unroll
     for (int u = 0; u < DU; ++u) {
       const long long q = pb + (long long)u * span + (int)threadIdx.x;
-      keys[u] = q < hw ? t.lab[(long long)b * hw + q] : 0;   // +foreground id / -background id
+      keys[u] = q < hw ? (some[u] ? t.lab[(long long)b * hw + q] : -1) : 0;   // +foreground id / -background id
+      prv[u] = (q < hw && some[u]) ? t.prob[(long long)b * t.prob_stride + q] : 0.f;
     }
 #pragma unroll
-    for (int u = 0; u < DU; ++u) pars[u] = (keys[u] < 0 && -keys[u] <= t.cap) ? t.par_b[cb + (-keys[u]) - 1] : 0;
+    for (int u = 0; u < DU; ++u)
+      pars[u] = (rings && some[u] && keys[u] < 0 && -keys[u] <= t.cap) ? t.par_b[cb + (-keys[u]) - 1] : 0;
+#pragma unroll
+    for (int u = 0; u < DU; ++u) some[u] = ahead[u];
 #pragma unroll
     for (int u = 0; u < DU; ++u) {
       if (pb + (long long)u * span >= hw) break;
@@ -128,7 +156,7 @@ __global__ __launch_bounds__(256) void dbc_accum_kernel(DbcTables t) {
       // the f64 scan below (14 cross-lane moves) is what this kernel's time goes into.
       const bool hole = live && lf <= 0 && lb > 0 && lb <= t.cap && pars[u] > 0;
       if (!__ballot(live && (lf > 0 || hole))) continue;
-      const double pr = live ? (double)t.prob[(long long)b * t.prob_stride + p] : 0.0;
+      const double pr = live ? (double)prv[u] : 0.0;
       // horizontal runs of one label inside the wave: the first lane of a run acts for it
       const int prev = __shfl_up(key, 1);
       const bool head = lane == 0 || prev != key || x == 0;
@@ -151,6 +179,7 @@ __global__ __launch_bounds__(256) void dbc_accum_kernel(DbcTables t) {
           atomicMin(t.row_lo + rb + row, x);
           atomicMax(t.row_hi + rb + row, x + len - 1);
         }
+        if (!rings) continue;
         // border ring of a hole: foreground pixels of the ringing component that 4-touch the hole (the four neighbours'
         // labels, then the four rings, are fetched together: one pixel has up to eight dependent loads here otherwise)
         int seen[4];

@@ -19,11 +19,13 @@ struct DbcTables {
   const int* st_b;
   const int* first_f;         // (B,cap) linear index of the component's first pixel
   const int* first_b;
+  const uint8_t* seg_live;    // (B, ceil(H*W/64)) launch_ccl_dual's segment flags, or null: 0 = the 64 pixels all carry label -1
   int* par_f;                 // (B,cap) background label left of the first pixel (0: page edge)
   int* par_b;                 // (B,cap) foreground label left of the first pixel of a HOLE (0: not a hole)
   int* off_f;                 // (B,cap) first row-table entry of the component (h entries)
   int* off_b;                 // (B,cap) first row-table entry of the hole's border ring (h + 2 entries)
   int* hdr;                   // (B,4) [min(n_f,cap), min(n_b,cap), rows used, overflow flag]
+  int* hole_rows;             // (B) row-table entries of the page's holes (0: the page has no hole, so no ring either)
   int* row_lo;                // (B,rcap) leftmost x of the component / ring in that row
   int* row_hi;                // (B,rcap) rightmost x
   double* sum_f;              // (B,cap) sum of prob over the component

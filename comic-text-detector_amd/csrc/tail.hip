@@ -801,7 +801,8 @@ struct DbStage {
   long long prob_stride = 0;
   int *lab = nullptr, *n_f = nullptr, *n_b = nullptr, *st_f = nullptr, *st_b = nullptr;
   int *first_f = nullptr, *first_b = nullptr, *par_f = nullptr, *par_b = nullptr, *off_f = nullptr, *off_b = nullptr;
-  int *hdr = nullptr, *ring_cnt = nullptr, *row_lo = nullptr, *row_hi = nullptr;
+  int *hdr = nullptr, *ring_cnt = nullptr, *row_lo = nullptr, *row_hi = nullptr, *hole_rows = nullptr;
+  uint8_t* seg_live = nullptr;
   double *sum_f = nullptr, *sum_b = nullptr, *ring_sum = nullptr;
   int* hhdr = nullptr;
 };
@@ -816,9 +817,10 @@ int db_enqueue(ctd_tail* t, DbStage& d, int B, int Hn, int Wn, const float* prob
   d.B = B, d.Hn = Hn, d.Wn = Wn, d.prob = prob_dev, d.prob_stride = prob_stride;
   GET(t->d_lab_f, (size_t)B * hw * 4, int, lab);
   GET(t->d_ccl_ws, ccl_workspace_bytes(B, Hn, Wn), uint8_t, ccl_ws);
-  // int tables: n_f, n_b (B each) | st_f, st_b (B,cap,5) | first, par, off x2 (B,cap) | hdr (B,4) | ring_cnt (B,cap)
-  const size_t bc = (size_t)B * cap;
-  GET(t->d_dbc_i, (2 * (size_t)B + 10 * bc + 6 * bc + 4 * (size_t)B + bc) * 4, int, ti);
+  // int tables: n_f, n_b (B each) | st_f, st_b (B,cap,5) | first, par, off x2 (B,cap) | hdr (B,4) | ring_cnt (B,cap) |
+  // hole_rows (B) | seg_live (B, ceil(hw / 64)) bytes
+  const size_t bc = (size_t)B * cap, nseg = (hw + 63) / 64;
+  GET(t->d_dbc_i, (2 * (size_t)B + 10 * bc + 6 * bc + 4 * (size_t)B + bc + (size_t)B) * 4 + (size_t)B * nseg, int, ti);
   d.lab = lab;
   d.n_f = ti;
   d.n_b = d.n_f + B;
@@ -832,6 +834,8 @@ int db_enqueue(ctd_tail* t, DbStage& d, int B, int Hn, int Wn, const float* prob
   d.off_b = d.off_f + bc;
   d.hdr = d.off_b + bc;
   d.ring_cnt = d.hdr + 4 * (size_t)B;
+  d.hole_rows = d.ring_cnt + bc;
+  d.seg_live = (uint8_t*)(d.hole_rows + B);
   GET(t->d_dbc_d, 3 * bc * 8, double, td);
   d.sum_f = td, d.sum_b = td + bc, d.ring_sum = td + 2 * bc;
   GET(t->d_rows, 2 * (size_t)B * rcap * 4, int, rows);
@@ -840,13 +844,14 @@ int db_enqueue(ctd_tail* t, DbStage& d, int B, int Hn, int Wn, const float* prob
   pre.fill(td, 0, 3 * bc * 8);
   pre.fill(d.ring_cnt, 0, bc * 4);
   pre.flush();
-  launch_ccl_dual(bitmap_dev, B, Hn, Wn, 0, lab, d.n_f, d.n_b, d.st_f, d.st_b, d.first_f, d.first_b, cap, ccl_ws, st);
+  launch_ccl_dual(bitmap_dev, B, Hn, Wn, 0, lab, d.n_f, d.n_b, d.st_f, d.st_b, d.first_f, d.first_b, cap, ccl_ws, st,
+                  d.seg_live);
   DbcTables dt;
   dt.B = B, dt.H = Hn, dt.W = Wn, dt.cap = cap, dt.rcap = rcap;
   dt.prob = prob_dev, dt.prob_stride = prob_stride;
   dt.lab = lab, dt.n_f = d.n_f, dt.n_b = d.n_b, dt.st_f = d.st_f, dt.st_b = d.st_b;
-  dt.first_f = d.first_f, dt.first_b = d.first_b, dt.par_f = d.par_f, dt.par_b = d.par_b, dt.off_f = d.off_f;
-  dt.off_b = d.off_b, dt.hdr = d.hdr, dt.row_lo = d.row_lo, dt.row_hi = d.row_hi, dt.sum_f = d.sum_f, dt.sum_b = d.sum_b;
+  dt.first_f = d.first_f, dt.first_b = d.first_b, dt.seg_live = d.seg_live, dt.par_f = d.par_f, dt.par_b = d.par_b, dt.off_f = d.off_f;
+  dt.off_b = d.off_b, dt.hdr = d.hdr, dt.hole_rows = d.hole_rows, dt.row_lo = d.row_lo, dt.row_hi = d.row_hi, dt.sum_f = d.sum_f, dt.sum_b = d.sum_b;
   dt.ring_sum = d.ring_sum, dt.ring_cnt = d.ring_cnt;
   launch_dbc(dt, st);
   GET(t->h_hdr, (size_t)B * 4 * 4, int, hhdr);
