@@ -40,6 +40,11 @@ LAYOUT_OK, LAYOUT_NO_REGION, LAYOUT_EMPTY = range(3)
 LAYOUT_MAX_INSET = 16
 TYPESET_MAX_SIDE, TYPESET_MAX_RADIUS, TYPESET_TILE_W, TYPESET_TILE_H = 8192, 12, 64, 32
 TYPESET_OK, TYPESET_EMPTY, TYPESET_OUTSIDE = range(3)          # typeset.typeset_tables' status column (not part of the ABI)
+RASTER_MAX_SIDE, RASTER_MAX_SCALE = 1024, 1 << 22
+RASTER_OK, RASTER_EMPTY, RASTER_REFUSED = range(3)
+# the shape of the raster launch (csrc/kernels.h RS_*; not part of the ABI, no result depends on it): pixel rows a band, pixel
+# columns a chunk, segments a staging pass, workgroups a job.  The tests put sizes on both sides of each.
+RASTER_BAND_H, RASTER_CHUNK_W, RASTER_SEG_CHUNK, RASTER_BANDS_Y = 4, 128, 32, 8
 
 
 class CtdTensor(C.Structure):
@@ -196,6 +201,11 @@ class CtdGlyphParams(C.Structure):
                 ("n_places", C.c_int32), ("n_glyphs", C.c_int32), ("atlas_bytes", C.c_int64)]
 
 
+class CtdRasterJob(C.Structure):
+    _fields_ = [("off", C.c_int64), ("w", C.c_int32), ("h", C.c_int32), ("bx", C.c_int32), ("by", C.c_int32),
+                ("seg_first", C.c_int32), ("seg_count", C.c_int32), ("scale", C.c_int32), ("pad_", C.c_int32)]
+
+
 class CtdFillPage(C.Structure):
     _fields_ = [("page_dev", C.c_void_p), ("hole_dev", C.c_void_p), ("out_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32),
                 ("pitch", C.c_int32), ("hole_pitch", C.c_int32), ("out_pitch", C.c_int32), ("tile0", C.c_int32),
@@ -245,6 +255,7 @@ SYMBOLS = {
     "ctd_layout_boxes": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdLayoutParams), _vp, _vp]),
     "ctd_typeset": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(CtdTypesetParams), _vp, _vp]),
     "ctd_typeset_glyphs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdGlyphParams), _vp, _vp]),
+    "ctd_rasterise_glyphs": (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
     "ctd_fill_rest": (_i32, [_vp, _i32, C.POINTER(CtdFillParams), _vp, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),

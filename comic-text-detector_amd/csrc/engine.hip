@@ -1467,6 +1467,17 @@ int ctd_typeset_glyphs(const ctd_typeset_page* pages_dev, const ctd_glyph_layer*
   return CTD_OK;
 }
 
+int ctd_rasterise_glyphs(const int32_t* segs_dev, int64_t n_segs, const ctd_raster_job* jobs_dev, int32_t n_jobs,
+                         uint8_t* atlas_dev, int64_t atlas_bytes, int32_t* status_dev, void* stream) {
+  if (n_segs < 0 || n_jobs < 0 || atlas_bytes < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (n_jobs > (1 << 24)) return fail(CTD_ERR_INVALID, "raster: at most 2^24 jobs a call");
+  if ((n_jobs > 0 && (!jobs_dev || !status_dev)) || (n_segs > 0 && !segs_dev) || (atlas_bytes > 0 && !atlas_dev))
+    return fail(CTD_ERR_INVALID, "null pointer");
+  if (n_jobs == 0) return CTD_OK;
+  HIP_TRY(launch_rasterise_glyphs(segs_dev, n_segs, jobs_dev, n_jobs, atlas_dev, atlas_bytes, status_dev, (hipStream_t)stream));
+  return CTD_OK;
+}
+
 int ctd_fill_rest(const ctd_fill_page* pages_dev, int32_t n_pages, const ctd_fill_params* params, void* scratch_dev,
                   ctd_fill_row* rows_dev, void* stream) {
   if (n_pages < 0) return fail(CTD_ERR_INVALID, "bad sizes");

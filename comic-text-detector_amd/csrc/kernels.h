@@ -214,6 +214,15 @@ hipError_t launch_typeset_glyphs(const ctd_typeset_page* pages, const ctd_glyph_
                                  const ctd_glyph_record* glyphs, const ctd_typeset_tile* tiles, const int32_t* entries,
                                  const uint8_t* atlas, const ctd_glyph_params& prm, ctd_typeset_row* rows, hipStream_t st);
 
+// ---- kernels_raster.hip ---------------------------------------------------------
+// the shape of ctd_rasterise_glyphs' launch (mirrored in _lib.py for the tests, which probe every boundary; no result
+// depends on any of them): pixel rows a band, pixel columns a chunk, segments a staging pass, workgroups a job
+constexpr int RS_BAND_H = 4, RS_CHUNK_W = 128, RS_SEG_CHUNK = 32, RS_BANDS_Y = 8;
+// ctd_rasterise_glyphs' one launch (RS_BANDS_Y workgroups per job; 1 <= n_jobs <= 2^24, the counts and pointers checked by
+// the caller): returns what hipGetLastError says right after the launch
+hipError_t launch_rasterise_glyphs(const int32_t* segs, int64_t n_segs, const ctd_raster_job* jobs, int n_jobs, uint8_t* atlas,
+                                   int64_t atlas_bytes, int32_t* status, hipStream_t st);
+
 // ---- kernels_fill.hip -----------------------------------------------------------
 // ctd_fill_rest's three launches (pull per tile, the page launch, push per tile; n_pages >= 1, n_tiles >= 1 and the page
 // table checked by the caller): raises the page kernel's dynamic LDS limit once per device and returns what hipGetLastError

@@ -679,6 +679,43 @@ class TextDetector:
         out.layer_of, out.fits = layer_of, np.array(fits, bool)
         return out
 
+    def typeset_text(self, pages: Sequence[Page], boxes, font, atlas, runs, sizes, fill=(0, 0, 0), stroke=(255, 255, 255),
+                     radius=3, prefer: str = "a_rect", inplace: bool = False, **flow_kw):
+        """`typeset_glyphs` from outlines, at the size that fits: per block of `boxes` that is `ok` and has a run,
+        `glyphs.fit` picks the largest of the ascending `sizes` (pixels an em) at which the run flows into the block's
+        rectangle (the one `typeset_glyphs` uses); ONE `atlas.rasterise` launch then makes every (glyph, size) instance
+        of the batch that the atlas does not hold yet; `glyphs.flow_outlines` places each run, and `glyphs.typeset_glyphs`
+        composites all of them in one launch (returns its `TypesetPages`).  `font`: a `glyphs.OutlineFont`; `runs[j]`:
+        block j's gids OF THE FONT, or None to skip the block.  The result's `layer_of[j]` is block j's layer, -1 where it was skipped; `size[i]` the size chosen for layer
+        i and `fits[i]` whether its lines stay inside its rectangle at that size (False: not even `sizes[0]` fits, which is
+        then used)."""
+        from . import glyphs as gl, typeset as ts
+        if prefer not in ("a_rect", "rect"):
+            raise ValueError('prefer: "a_rect" or "rect"')
+        nb = len(boxes)
+        if len(runs) != nb:
+            raise ValueError("one run (or None) per block of `boxes`")
+        take = np.array([bool(boxes.ok[j]) and runs[j] is not None for j in range(nb)], bool)
+        idx = np.flatnonzero(take)
+        layer_of = np.full((nb,), -1, np.int64)
+        layer_of[idx] = np.arange(len(idx))
+        fill, stroke = ts._per_layer(fill, nb, 3, "fill")[idx], ts._per_layer(stroke, nb, 3, "stroke")[idx]
+        radius = ts._per_layer(radius, nb, 1, "radius")[idx, 0]
+        anchored = (np.asarray(boxes.a_area) > 0) if prefer == "a_rect" else np.zeros((nb,), bool)
+        rects = np.where(anchored[:, None], boxes.a_rect, boxes.rect).reshape(nb, 4)[idx]
+        run_of = [ts._ints(runs[j], (-1,), "runs") for j in idx]
+        chosen = [gl.fit(run, font, rects[i], sizes, **flow_kw) for i, run in enumerate(run_of)]
+        count = [len(a) for a in run_of]
+        ids = atlas.rasterise(font, np.concatenate(run_of) if run_of else np.zeros((0,), np.int64),
+                              np.repeat(np.array([c[0] for c in chosen], np.float64), count))
+        xy = [gl.flow_outlines(run, font, rects[i], chosen[i][0], **flow_kw)[0] for i, run in enumerate(run_of)]
+        xy = np.concatenate(xy) if xy else np.zeros((0, 2), np.int64)
+        out = gl.typeset_glyphs(pages, atlas, boxes.index[idx, 0], np.repeat(np.arange(len(idx)), count), ids, xy, fill=fill,
+                                stroke=stroke, radius=radius, inplace=inplace, device=self.net.device)
+        out.layer_of, out.fits = layer_of, np.array([c[1] for c in chosen], bool)
+        out.size = np.array([c[0] for c in chosen])
+        return out
+
     def fill_rest(self, pages: Sequence[Page], results, erased=None, **erase_kw):
         """The pages of a detected batch with NO text left, on the detector's device: the text on plain backgrounds erased
         (`erase_text`) and the mask that leaves filled smoothly by pull-push (`fill.fill_rest` on the erased pages and their

@@ -18,8 +18,13 @@ tiles and, per tile, its placements in ascending order), tables and placements g
 launch (csrc/kernels_glyphs.hip) assembles each layer's coverage on chip, one small download.  No CPU fallback: without a
 GPU `GlyphAtlas` and `typeset_glyphs` raise `CtdError` like the rest of the package.
 
-What this is not: no kerning, no shaping (ligatures, bidi, contextual forms), no hyphenation, no font-size search and no
-rasterisation.  `flow` is a greedy breaker on integer advances; anything smarter computes `xy` itself and calls
+Where the glyphs come from outlines, the atlas fills itself: `OutlineFont` keeps quadratic outlines on the device,
+`atlas.rasterise(font, gids, size)` rasterises every (glyph, size) instance it does not hold yet straight into its buffer in ONE
+`ctd_rasterise_glyphs` launch (csrc/kernels_raster.hip; an unhinted integer rule, include/ctd_hip.h, tests/raster_ref.py,
+DESIGN.md section 4.25), and `fit` picks the largest size whose flow fits a box, on the host, from metrics only.
+
+What this is not: no kerning, no shaping (ligatures, bidi, contextual forms), no hyphenation, no hinting and no cubic
+outlines.  `flow` is a greedy breaker on integer advances; anything smarter computes `xy` itself and calls
 `typeset_glyphs`.  Overlapping glyphs of a layer combine by max, not by sum; a layer has one colour, so a coloured word is a
 layer of its own.
 """
@@ -37,7 +42,8 @@ from .regions import Page
 from .typeset import (MAX_COORD, ROW_DTYPE, TILE_DTYPE, TypesetPages, _bin_tiles, _ints, _layer_args, _layers, _open_pages, _pack,
                       _rects)
 
-__all__ = ["GlyphAtlas", "glyph_tables", "typeset_glyphs", "flow", "LAYER_DTYPE", "PLACE_DTYPE", "RECORD_DTYPE"]
+__all__ = ["GlyphAtlas", "glyph_tables", "typeset_glyphs", "flow", "LAYER_DTYPE", "PLACE_DTYPE", "RECORD_DTYPE", "OutlineFont",
+           "segments_from_ops", "outline_boxes", "flow_outlines", "fit", "RASTER_JOB_DTYPE"]
 
 # numpy views of `ctd_glyph_layer` / `_place` / `_record` (include/ctd_hip.h; the _lib.CtdGlyph* mirrors)
 LAYER_DTYPE = np.dtype([("page", "<i4"), ("clip", "<i4", (4,)), ("fill", "u1", (3,)), ("stroke", "u1", (3,)), ("radius", "u1"),
@@ -48,6 +54,10 @@ assert LAYER_DTYPE.itemsize == C.sizeof(L.CtdGlyphLayer) == 32
 assert PLACE_DTYPE.itemsize == C.sizeof(L.CtdGlyphPlace) == 16
 assert RECORD_DTYPE.itemsize == C.sizeof(L.CtdGlyphRecord) == 16
 assert C.sizeof(L.CtdGlyphParams) == 32
+# `ctd_raster_job` (the _lib.CtdRasterJob mirror)
+RASTER_JOB_DTYPE = np.dtype([("off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("bx", "<i4"), ("by", "<i4"), ("seg_first", "<i4"),
+                             ("seg_count", "<i4"), ("scale", "<i4"), ("pad_", "<i4")])
+assert RASTER_JOB_DTYPE.itemsize == C.sizeof(L.CtdRasterJob) == 40
 
 
 class GlyphAtlas:
@@ -56,7 +66,8 @@ class GlyphAtlas:
     device buffer of dense rows, grown by doubling with a device copy, so only the appended bytes are ever uploaded; the record
     table (`RECORD_DTYPE`: off, w, h) is kept on the device beside it and on the host as `sizes[i] = (h, w)` and `offsets[i]`.
     `advance[i] = (ax, ay)` (default (w, h)) and `bearing[i] = (bx, by)` (default 0) are host-side integer metrics that only
-    `flow` reads.  `len(atlas)` glyphs, `nbytes` of coverage; `close()` frees the device buffers."""
+    `flow` reads.  `len(atlas)` glyphs, `nbytes` of coverage; `close()` frees the device buffers.
+    `rasterise(font, gids, size)` appends instances of an `OutlineFont`'s glyphs without any coverage crossing the bus."""
 
     def __init__(self, device=None):
         if not torch.cuda.is_available():
@@ -69,6 +80,7 @@ class GlyphAtlas:
         self.nbytes = 0
         self._cov = torch.empty((4096,), dtype=torch.uint8, device=self.device)
         self._rec = torch.empty((256 * RECORD_DTYPE.itemsize,), dtype=torch.uint8, device=self.device)
+        self._instances = {}                               # (font, gid, S) -> id: what `rasterise` has made
 
     def __len__(self) -> int:
         return len(self.offsets)
@@ -120,8 +132,79 @@ class GlyphAtlas:
         torch.cuda.current_stream(self.device).synchronize()                # a later call may run on any stream
         return np.arange(n0, n0 + k, dtype=np.int32)
 
+    def rasterise(self, font: "OutlineFont", gids, size) -> np.ndarray:
+        """The atlas ids of the font's glyphs `gids` at `size` pixels an em (one for all or one per gid; S = round(size 65536
+        / upem)).  Instances the
+        atlas already holds, (font, gid, S), keep their ids; the missing ones are rasterised from the font's device outlines
+        straight into the coverage buffer in ONE `ctd_rasterise_glyphs` launch: the buffer is grown first, only the job table
+        (40 bytes an instance) and the new records go up, no coverage does.  Records and metrics are appended as `add`
+        appends them: `sizes` (h, w) of the rule's box, `advance` (ax, ascent + descent) and the horizontal `bearing`
+        (bx, baseline + by) of `font.metrics`.  A box side above `_lib.RASTER_MAX_SIDE` raises ValueError before anything
+        changes.  Runs on the current stream of the atlas's device and waits for it, as `add` does."""
+        if self._cov is None:
+            raise L.CtdError("the atlas is closed")
+        if not isinstance(font, OutlineFont):
+            raise ValueError("font: an OutlineFont")
+        gids = font._gids(gids)
+        size = np.asarray(size, np.float64)
+        if size.ndim > 1 or (size.ndim == 1 and len(size) != len(gids)):
+            raise ValueError("size: one for all gids or one per gid")
+        scale_of = {float(v): font.scale(v) for v in np.unique(size)}
+        keys = [(font, g, scale_of[float(v)]) for g, v in zip(gids.tolist(), np.broadcast_to(size, gids.shape).tolist())]
+        new = [key for key in dict.fromkeys(keys) if key not in self._instances]   # the missing instances, each once, in order
+        k = len(new)
+        if k:
+            new_g, new_S = np.array([key[1] for key in new], np.int64), np.array([key[2] for key in new], np.int64)
+            box, adv, bear = np.zeros((k, 4), np.int64), np.zeros((k, 2), np.int64), np.zeros((k, 2), np.int64)
+            for S in np.unique(new_S):                     # host metrics, one pass a distinct scale
+                at = np.flatnonzero(new_S == S)
+                m = font._metrics_at(new_g[at], int(S), False)
+                box[at], adv[at], bear[at] = m.box, m.advance, m.bearing
+            if box[:, 2:].max() > L.RASTER_MAX_SIDE:
+                raise ValueError(f"an instance's box side is above {L.RASTER_MAX_SIDE} pixels")
+            if max(np.abs(adv).max(), np.abs(bear).max()) > MAX_COORD:
+                raise ValueError("advance / bearing beyond 2^29")
+            n0 = len(self)
+            if n0 + k >= 2 ** 31:
+                raise ValueError("too many glyphs")
+            area = box[:, 2] * box[:, 3]
+            off = self.nbytes + np.cumsum(area) - area
+            total = int(area.sum())
+            jobs = np.zeros((k,), RASTER_JOB_DTYPE)
+            jobs["off"], jobs["w"], jobs["h"], jobs["bx"], jobs["by"] = off, box[:, 2], box[:, 3], box[:, 0], box[:, 1]
+            jobs["seg_first"], jobs["seg_count"], jobs["scale"] = font.seg_first[new_g], font.seg_count[new_g], new_S
+            rec = np.zeros((k,), RECORD_DTYPE)
+            rec["off"], rec["h"], rec["w"] = off, box[:, 3], box[:, 2]
+            segs_dev = font._sync()
+            if font.device != self.device:
+                raise ValueError("the font's outlines live on another device")
+            want = np.where((area == 0) | (font.seg_count[new_g] == 0), L.RASTER_EMPTY, L.RASTER_OK)
+            with torch.cuda.device(self.device):
+                st = torch.cuda.current_stream(self.device)
+                cov = self._grown(self._cov, self.nbytes, self.nbytes + total)
+                recs = self._grown(self._rec, n0 * RECORD_DTYPE.itemsize, (n0 + k) * RECORD_DTYPE.itemsize)
+                blob, at = _pack([jobs, rec])               # one upload: the job table and the new records
+                tab = torch.from_numpy(blob).to(self.device)
+                status_dev = torch.empty((k,), dtype=torch.int32, device=self.device)
+                L.check(L.lib().ctd_rasterise_glyphs(segs_dev.data_ptr(), font.n_segs, tab.data_ptr() + int(at[0]), k, cov.data_ptr(),
+                                                     self.nbytes + total, status_dev.data_ptr(), st.cuda_stream),
+                        "ctd_rasterise_glyphs")
+                recs[n0 * RECORD_DTYPE.itemsize: (n0 + k) * RECORD_DTYPE.itemsize].copy_(tab[int(at[1]): int(at[1]) + rec.nbytes])
+                status = status_dev.cpu().numpy()           # stream-ordered: behind the launch
+                st.synchronize()
+            if not np.array_equal(status, want):
+                raise L.CtdError(f"ctd_rasterise_glyphs: status {status.tolist()} where {want.tolist()} was expected")
+            self._cov, self._rec = cov, recs
+            self.sizes, self.offsets = np.concatenate([self.sizes, box[:, [3, 2]]]), np.concatenate([self.offsets, off])
+            self.advance, self.bearing = np.concatenate([self.advance, adv]), np.concatenate([self.bearing, bear])
+            self.nbytes += total
+            for i, key in enumerate(new):
+                self._instances[key] = n0 + i
+        return np.array([self._instances[key] for key in keys], np.int32)
+
     def close(self) -> None:
         self._cov = self._rec = None
+        self._instances = {}
 
     def __repr__(self) -> str:
         return f"GlyphAtlas({len(self)} glyphs, {self.nbytes} bytes on {self.device})"
@@ -272,3 +355,260 @@ def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, 
     tp = TypesetPages(out, rows, status, np.zeros((nl, 2), np.int64))
     tp.xy, tp.place_layer, tp.place_glyph = xy, layer_of, glyph             # per placement here, not per layer
     return tp
+
+
+# ---- outlines rasterised into the atlas (include/ctd_hip.h, "glyph outlines rasterised into the atlas")
+
+def _sround(v, S):
+    """A font-unit length at scale S (16.16 pixels per font unit), rounded to pixels."""
+    return (np.asarray(v, np.int64) * int(S) + 32768) >> 16
+
+
+def _scale_of(size, upem) -> int:
+    S = int(round(float(size) * 65536 / upem))
+    if not 0 < S <= L.RASTER_MAX_SCALE:
+        raise ValueError(f"size: the scale {S} / 65536 pixels per font unit is not in 1 .. 2^22")
+    return S
+
+
+def segments_from_ops(ops) -> np.ndarray:
+    """Pen-style operations -> the (n, 6) int32 segment rows (x0, y0, cx, cy, x1, y1) of the raster rule.  `ops` is a sequence
+    of (name, points) as a fontTools `RecordingPen` records them (no font library is imported here): `moveTo` ((x, y),),
+    `lineTo` ((x, y),), `qCurveTo` (off, ..., off, on) with TrueType's implied on-curve points between consecutive off-curve
+    points (a last point of None: a contour of off-curve points only, which starts at the implied point between its last and
+    its first), `closePath` / `endPath` (). A line is stored with its control point on its start.  A fill needs closed
+    contours, so both `closePath` and `endPath` add the line back to the contour's start where the pen is not there.
+    Coordinates are integers; an implied point between a and b is (a + b + 1) >> 1, at most half a font unit from the exact
+    one.  `curveTo` raises ValueError: cubics are not accepted, convert them first (cu2qu).  Pure numpy."""
+    rows, cur, start = [], None, None
+
+    def pt(p):
+        x, y = p
+        if int(x) != x or int(y) != y:
+            raise ValueError("outline coordinates are integers (font units)")
+        if max(abs(int(x)), abs(int(y))) > 1 << 15:
+            raise ValueError("outline coordinates beyond 2^15")
+        return int(x), int(y)
+
+    def mid(a, b):
+        return (a[0] + b[0] + 1) >> 1, (a[1] + b[1] + 1) >> 1
+
+    def close():
+        nonlocal cur, start
+        if cur is not None and start is not None and cur != start:
+            rows.append(cur + cur + start)
+        cur = start = None
+
+    for name, args in ops:
+        if name == "moveTo":
+            close()
+            cur = start = pt(args[0])
+        elif name == "lineTo":
+            if cur is None:
+                raise ValueError("lineTo before moveTo")
+            p = pt(args[0])
+            rows.append(cur + cur + p)
+            cur = p
+        elif name == "qCurveTo":
+            if len(args) < 1:
+                raise ValueError("qCurveTo: at least one point")
+            if args[-1] is None:                           # off-curve points only: start at an implied point
+                off = [pt(a) for a in args[:-1]]
+                if not off:
+                    raise ValueError("qCurveTo: no points")
+                close()
+                cur = start = mid(off[-1], off[0])
+                last = start
+            else:
+                if cur is None:
+                    raise ValueError("qCurveTo before moveTo")
+                off, last = [pt(a) for a in args[:-1]], pt(args[-1])
+            for i, c in enumerate(off):
+                end = mid(c, off[i + 1]) if i + 1 < len(off) else last
+                rows.append(cur + c + end)
+                cur = end
+            if not off:
+                rows.append(cur + cur + last)
+                cur = last
+        elif name in ("closePath", "endPath"):
+            close()
+        elif name == "curveTo":
+            raise ValueError("curveTo: cubic curves are not accepted; convert them to quadratics first (cu2qu)")
+        else:
+            raise ValueError(f"unknown pen operation {name!r}")
+    close()
+    return np.array(rows, np.int32).reshape(-1, 6)
+
+
+def outline_boxes(points: Sequence[np.ndarray], S: int) -> np.ndarray:
+    """The raster rule's box of each outline at scale S: rows (bx, by, w, h), int64.  points[i]: the (n, 6) segments of glyph
+    i.  X = (x S + 512) >> 10, Y = (-y S + 512) >> 10 over ALL points, controls included; floor of the minimum, ceil of the
+    maximum, in pixels of 64; no segments: zeros."""
+    out = np.zeros((len(points), 4), np.int64)
+    for i, sg in enumerate(points):
+        if len(sg) == 0:
+            continue
+        sg = np.asarray(sg, np.int64).reshape(-1, 3, 2)
+        X, Y = (sg[..., 0] * S + 512) >> 10, (-sg[..., 1] * S + 512) >> 10
+        bx, by = int(X.min()) >> 6, int(Y.min()) >> 6
+        out[i] = bx, by, ((int(X.max()) + 63) >> 6) - bx, ((int(Y.max()) + 63) >> 6) - by
+    return out
+
+
+class OutlineFont:
+    """Quadratic glyph outlines, kept on the device once.  `upem` font units per em; `ascent` and `descent` the line's extent
+    above and below the baseline, both >= 0, font units.  `add(segments_list, advance)` appends glyphs ((n, 6) int32 arrays
+    as `segments_from_ops` returns them; an empty one is a space) with their horizontal advances in font units and returns
+    their gids, which never change.  The segments live in ONE int32 device buffer grown by doubling with a device copy, so
+    only appended rows are uploaded; host copies are kept, and everything but `GlyphAtlas.rasterise` works from those,
+    without a GPU (the upload then waits for the first `rasterise`)."""
+
+    def __init__(self, upem: int, ascent: int, descent: int, device=None):
+        if not (0 < int(upem) <= 1 << 15 and 0 <= int(ascent) <= 1 << 15 and 0 <= int(descent) <= 1 << 15):
+            raise ValueError("upem 1 .. 2^15, ascent and descent 0 .. 2^15")
+        self.upem, self.ascent, self.descent = int(upem), int(ascent), int(descent)
+        self.device = None if device is None else torch.device(device)
+        self.segments = []                                 # per gid: (n, 6) int32
+        self.seg_first = np.zeros((0,), np.int64)
+        self.seg_count = np.zeros((0,), np.int64)
+        self.advance = np.zeros((0,), np.int64)
+        self.n_segs = 0
+        self._dev, self._on_dev = None, 0                  # the device buffer (bytes) and the segment rows it holds
+        self._host = None                                  # every segment's points, (n_segs, 3, 2) int64: made when boxes are asked for
+
+    def __len__(self) -> int:
+        return len(self.segments)
+
+    def add(self, segments_list: Sequence[np.ndarray], advance) -> np.ndarray:
+        k = len(segments_list)
+        advance = _ints(advance, (k,), "advance")
+        if k and (advance.min() < 0 or advance.max() > 1 << 15):
+            raise ValueError("advance: 0 .. 2^15 font units")
+        segs = []
+        for sg in segments_list:
+            sg = np.asarray(sg)
+            if sg.dtype.kind not in "iu" or sg.ndim != 2 or sg.shape[1] != 6:
+                raise ValueError("a glyph is a (n, 6) integer array of segments")
+            if sg.size and np.abs(sg.astype(np.int64)).max() > 1 << 15:
+                raise ValueError("outline coordinates beyond 2^15")
+            segs.append(np.ascontiguousarray(sg, np.int32))
+        count = np.array([len(sg) for sg in segs], np.int64)
+        if self.n_segs + int(count.sum()) >= 2 ** 31 or len(self) + k >= 2 ** 31:
+            raise ValueError("too many segments")
+        n0 = len(self)
+        self.seg_first = np.concatenate([self.seg_first, self.n_segs + np.cumsum(count) - count])
+        self.seg_count = np.concatenate([self.seg_count, count])
+        self.advance = np.concatenate([self.advance, advance])
+        self.segments += segs
+        self.n_segs += int(count.sum())
+        if torch.cuda.is_available():
+            self._sync()
+        return np.arange(n0, n0 + k, dtype=np.int32)
+
+    def _sync(self):
+        """The device buffer with every segment row in it: the rows added since the last call go up, nothing else."""
+        if not torch.cuda.is_available():
+            raise L.CtdError("the outlines are rasterised on the GPU and there is none (no CPU fallback)")
+        if self.device is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        if self._dev is None:
+            self._dev = torch.empty((4096 * 24,), dtype=torch.uint8, device=self.device)
+        if self._on_dev < self.n_segs:
+            with torch.cuda.device(self.device):
+                self._dev = GlyphAtlas._grown(self._dev, self._on_dev * 24, self.n_segs * 24)
+                g0 = int(np.searchsorted(self.seg_first, self._on_dev, side="left"))   # whole glyphs were uploaded
+                new = np.concatenate([sg.ravel() for sg in self.segments[g0:]])
+                self._dev[self._on_dev * 24: self.n_segs * 24].copy_(torch.from_numpy(new.view(np.uint8)))
+                torch.cuda.current_stream(self.device).synchronize()
+            self._on_dev = self.n_segs
+        return self._dev
+
+    def scale(self, size) -> int:
+        """S = round(size 65536 / upem): the 16.16 scale at which `size` pixels make an em."""
+        return _scale_of(size, self.upem)
+
+    def boxes(self, gids, S: int) -> np.ndarray:
+        """`outline_boxes` of the font's glyphs `gids` at scale S, all at once: rows (bx, by, w, h)."""
+        gids = self._gids(gids)
+        out = np.zeros((len(gids), 4), np.int64)
+        count = self.seg_count[gids]
+        inked = np.flatnonzero(count)
+        if len(inked):
+            if self._host is None or len(self._host) != self.n_segs:
+                self._host = np.concatenate(self.segments).astype(np.int64).reshape(-1, 3, 2)
+            c = count[inked]
+            starts = np.cumsum(c) - c
+            sg = self._host[np.repeat(self.seg_first[gids[inked]] - starts, c) + np.arange(int(c.sum()))]
+            X, Y = (sg[..., 0] * int(S) + 512) >> 10, (-sg[..., 1] * int(S) + 512) >> 10
+            lo = [np.minimum(np.minimum(v[:, 0], v[:, 1]), v[:, 2]) for v in (X, Y)]      # over a segment's three points
+            hi = [np.maximum(np.maximum(v[:, 0], v[:, 1]), v[:, 2]) for v in (X, Y)]
+            bx, by = np.minimum.reduceat(lo[0], starts) >> 6, np.minimum.reduceat(lo[1], starts) >> 6
+            out[inked, 0], out[inked, 1] = bx, by
+            out[inked, 2] = ((np.maximum.reduceat(hi[0], starts) + 63) >> 6) - bx
+            out[inked, 3] = ((np.maximum.reduceat(hi[1], starts) + 63) >> 6) - by
+        return out
+
+    def _gids(self, gids):
+        gids = _ints(gids, (-1,), "gids")
+        if len(gids) and (gids.min() < 0 or gids.max() >= len(self)):
+            raise ValueError("gids: glyphs of the font")
+        return gids
+
+    def metrics(self, gids, size, vertical: bool = False):
+        """What `flow` reads, for `gids` at `size` pixels an em, from the outlines by the raster rule, on the host: an object
+        with `sizes[i] = (h, w)`, `advance[i] = (ax, ay)` and `bearing[i]` of gids[i] (so a run indexes it by POSITION in
+        `gids`), plus `box[i] = (bx, by, w, h)`, `scale`, `baseline` (the scaled ascent) and `line` (the scaled ascent plus
+        the scaled descent; vertical: the scaled em, a column's width).  ax = (adv S + 32768) >> 16 and ay = `line` of the
+        horizontal case.  Horizontal bearing: (bx, baseline + by), so a line's top is `baseline` above the pen's baseline.
+        vertical=True: bearing (0, baseline + by); `flow` centres a glyph in its column."""
+        return self._metrics_at(gids, self.scale(size), vertical)
+
+    def _metrics_at(self, gids, S: int, vertical: bool):
+        import types
+        gids = self._gids(gids)
+        box = self.boxes(gids, S)
+        base, down = int(_sround(self.ascent, S)), int(_sround(self.descent, S))
+        adv = np.stack([_sround(self.advance[gids], S), np.full((len(gids),), base + down, np.int64)], axis=1)
+        bear = np.stack([np.zeros((len(gids),), np.int64) if vertical else box[:, 0], base + box[:, 1]], axis=1)
+        return types.SimpleNamespace(sizes=box[:, [3, 2]].copy(), advance=adv.reshape(-1, 2), bearing=bear.reshape(-1, 2), box=box,
+                                     scale=S, baseline=base, line=int(_sround(self.upem, S)) if vertical else base + down)
+
+    def close(self) -> None:
+        self._dev, self._on_dev = None, 0
+
+    def __repr__(self) -> str:
+        return f"OutlineFont({len(self)} glyphs, {self.n_segs} segments, upem {self.upem})"
+
+
+def _run_metrics(run_gids, font, size, vertical):
+    run = _ints(run_gids, (-1,), "run")
+    uniq, pos = np.unique(run, return_inverse=True)
+    return font.metrics(uniq, size, vertical=vertical), uniq, pos.reshape(-1)
+
+
+def flow_outlines(run_gids, font: OutlineFont, rect, size, **flow_kwargs) -> tuple:
+    """`flow` of a run of the FONT's gids at `size`, on `font.metrics`: (xy, fits).  `line` defaults to the metrics' `line`
+    (ascent + descent, scaled; vertical: the scaled em), not to the run's tallest glyph: the bearings are measured from it."""
+    m, _, pos = _run_metrics(run_gids, font, size, bool(flow_kwargs.get("vertical", False)))
+    kw = dict(flow_kwargs)
+    if kw.get("line") is None:
+        kw["line"] = m.line
+    return flow(pos, m, rect, **kw)
+
+
+def fit(run_gids, font: OutlineFont, rect, sizes, **flow_kwargs) -> tuple:
+    """The largest of the ascending `sizes` (pixels an em) at which the run, flowed by `flow_outlines` into `rect`, fits:
+    (size, True), or (sizes[0], False) where none does.  Bisection: the greedy breaker's `fits` is monotone in the size on
+    these metrics (tests/test_raster_ref.py holds it against a linear scan on seeded cases).  Host only, metrics only:
+    nothing is rasterised."""
+    sizes = list(sizes)
+    if not sizes or any(b <= a for a, b in zip(sizes, sizes[1:])):
+        raise ValueError("sizes: ascending, at least one")
+    lo, hi = -1, len(sizes)                                # sizes[lo] fits (or lo = -1), sizes[hi] does not (or hi = len)
+    while hi - lo > 1:
+        k = (lo + hi) >> 1
+        if flow_outlines(run_gids, font, rect, sizes[k], **flow_kwargs)[1]:
+            lo = k
+        else:
+            hi = k
+    return (sizes[lo], True) if lo >= 0 else (sizes[0], False)

@@ -12,7 +12,7 @@ and, per tile, its layers in ascending order), uploads coverage and tables once,
 one small table.  The rule is integers only and stated in include/ctd_hip.h (restated in numpy in tests/typeset_ref.py;
 DESIGN.md section 4.21 has its limits): the outline S is the max of the coverage F over a disk of `radius` pixels, and a
 pixel becomes blend(blend(page, stroke, S), fill, F) with blend(c, k, a) = (c (255 - a) + k a + 127) / 255; layers are applied
-in the order given.  Glyph rasterisation stays a font engine's job.  There is no per-layer Python beyond packing the bitmaps
+in the order given.  Glyph rasterisation is not done here (a font engine's job, or `glyphs.GlyphAtlas.rasterise`).  There is no per-layer Python beyond packing the bitmaps
 and no CPU fallback: without a GPU it raises `CtdError` like the rest of the package.
 """
 from __future__ import annotations

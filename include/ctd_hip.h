@@ -883,7 +883,7 @@ int ctd_typeset(const ctd_typeset_page* pages_dev, const ctd_typeset_layer* laye
  * cut to 0 .. n_entries, and entries of one layer that are not consecutive merely apply that layer twice.  A wrong table
  * costs pixels and never faults.
  * Limits beyond those above: overlap within a layer is max, not sum; one colour per layer, so a coloured word is a layer of
- * its own; no kerning, shaping or rasterisation, which stay a font engine's. */
+ * its own; no kerning or shaping, which stay a font engine's (rasterisation: the section after this one). */
 
 /* One glyph layer (a row of the device layer table), 32 bytes. */
 typedef struct ctd_glyph_layer {
@@ -926,6 +926,69 @@ typedef struct ctd_glyph_params {
 int ctd_typeset_glyphs(const ctd_typeset_page* pages_dev, const ctd_glyph_layer* layers_dev, const ctd_glyph_place* places_dev,
                        const ctd_glyph_record* glyphs_dev, const ctd_typeset_tile* tiles_dev, const int32_t* entries_dev,
                        const uint8_t* atlas_dev, const ctd_glyph_params* params, ctd_typeset_row* rows_dev, void* stream);
+
+/* ---- glyph outlines rasterised into the atlas (added within ABI v10) ------------------------------------------------------ */
+
+/* An addition to ABI v10 like the ones above: one entry point, one struct, nothing existing changes.
+ * The section above composites glyphs that already lie in the atlas.  This one puts them there: quadratic outlines are kept
+ * on the device, and any number of (glyph, size) instances are rasterised straight into the atlas's own buffer in ONE
+ * launch.  All integers, so the kernel and the restatement (tests/raster_ref.py) agree on every byte.
+ *   outline   a glyph is n segments, each a row of 6 int32 in font units, y up: (x0, y0, cx, cy, x1, y1), |v| <= 2^15 (the
+ *             kernel clamps a value beyond that).  A segment whose control point equals either end point (in font units) is
+ *             a straight line; any other is a quadratic Bezier.  Contours are closed by the caller's segments; the rule
+ *             never adds an edge.  Cubic curves are not accepted.
+ *   instance  a glyph at scale S, 16.16 pixels per font unit, 0 < S <= CTD_RASTER_MAX_SCALE = 2^22.  A point maps to 26.6
+ *             fixed point, y down: X = (x S + 512) >> 10, Y = (-y S + 512) >> 10, arithmetic shifts on int64.
+ *   box       from ALL transformed points, controls included: bx = floor(minX / 64), by = floor(minY / 64),
+ *             w = ceil(maxX / 64) - bx, h = ceil(maxY / 64) - by.  A glyph without segments has w = h = 0.  Sides above
+ *             CTD_RASTER_MAX_SIDE are refused.
+ *   flatten   for a curve, dd = max(|X0 - 2 X1 + X2|, |Y0 - 2 Y1 + Y2|), L the smallest of 0 .. 5 with (dd >> 2L) <= 16 (5 if
+ *             none), N = 1 << L, Q_k = ((N-k)^2 P0 + 2 k (N-k) P1 + k^2 P2 + (N^2 >> 1)) >> 2L for k = 0 .. N, the edges
+ *             Q_k -> Q_k+1.  A line is one edge.  Rounded convex combinations of integers stay inside the control box, so
+ *             no edge leaves the box.
+ *   coverage  a pixel row py has 16 sample rows at Ys = 64 (by + py) + 4 k + 2, k = 0 .. 15.  An edge with ends lo, hi
+ *             ordered by Y, lo.Y != hi.Y, crosses a sample row iff lo.Y <= Ys < hi.Y; its direction d is +1 if the edge runs
+ *             down (its first point is lo), else -1; its crossing, in 1/256 pixel from the box's left, is
+ *             Xc = floor(4 (lo.X (hi.Y - Ys) + hi.X (Ys - lo.Y)) / (hi.Y - lo.Y)) - 256 bx (int64; 0 <= Xc <= 256 w always).
+ *             A_k(px) = sum over edges of d clamp(256 (px + 1) - Xc, 0, 256), and the byte is
+ *             c(px, py) = (255 sum_k min(|A_k(px)|, 256) + 2048) >> 12.
+ * |.| makes the two contour orientations equal.  The clamp is how overlapping contours are handled: exact where the winding
+ * is 0 or +-1 on a sample row, saturating elsewhere.
+ * What the rule cannot do: no hinting (stems are not moved to the pixel grid; it is an unhinted rasteriser of ordinary
+ * quality); no sub-pixel positioning (an instance is rasterised at the origin's pixel phase only); no cubics (convert them
+ * first, e.g. with cu2qu); 16 vertical samples, so a horizontal edge is placed to 1/16 pixel (horizontally the area is exact
+ * to 1/256); overlapping contours saturate instead of following a fill rule.
+ * A job is one instance: the host computes off, w, h, bx, by with the rule above (it must, to lay out the atlas) and the
+ * kernel trusts none of it.  Status per job, the first that applies:
+ *   CTD_RASTER_REFUSED  the segment range leaves 0 .. n_segs, the record off .. off + w h leaves 0 .. atlas_bytes, a side is
+ *                       negative or above CTD_RASTER_MAX_SIDE, or the scale is not in 1 .. CTD_RASTER_MAX_SCALE.  Nothing is
+ *                       written.
+ *   CTD_RASTER_EMPTY    w or h is 0, or there are no segments.  Nothing is written.
+ *   CTD_RASTER_OK       the w h bytes of the record are written, dense rows of w bytes, every one of them.
+ * A crossing outside 0 .. 256 w is clamped, and X - 64 bx is clamped to +-2^30: a wrong table costs pixels and never faults.
+ * Records of different jobs must not overlap (the caller's to see to, as for the pages of ctd_typeset). */
+#define CTD_RASTER_MAX_SIDE 1024
+#define CTD_RASTER_MAX_SCALE (1 << 22)
+#define CTD_RASTER_OK 0
+#define CTD_RASTER_EMPTY 1
+#define CTD_RASTER_REFUSED 2
+
+/* One instance (a row of the device job table), 40 bytes. */
+typedef struct ctd_raster_job {
+  int64_t off;       /* the record's first byte of atlas_dev; rows are w bytes apart */
+  int32_t w, h;      /* the box, pixels                                            */
+  int32_t bx, by;    /* the box's top-left pixel relative to the glyph's origin    */
+  int32_t seg_first, seg_count; /* the glyph's rows of segs_dev                    */
+  int32_t scale;     /* S, 16.16 pixels per font unit                              */
+  int32_t pad_;
+} ctd_raster_job;
+
+/* The rule above for all jobs in ONE launch on `stream`.  segs_dev: n_segs rows of 6 int32; jobs_dev: n_jobs rows;
+ * status_dev: n_jobs int32, every one written; atlas_dev: atlas_bytes bytes, of which only the records of the OK jobs are
+ * written.  n_jobs = 0 does nothing at all.  A negative count or atlas_bytes, jobs_dev or status_dev NULL, segs_dev NULL with
+ * n_segs > 0 or atlas_dev NULL with atlas_bytes > 0 is an error rc (plus ctd_last_error) and launches nothing. */
+int ctd_rasterise_glyphs(const int32_t* segs_dev, int64_t n_segs, const ctd_raster_job* jobs_dev, int32_t n_jobs,
+                         uint8_t* atlas_dev, int64_t atlas_bytes, int32_t* status_dev, void* stream);
 
 /* ---- the detector tail ------------------------------------------------------ */
 
