@@ -1,6 +1,7 @@
 // Post-processing kernels: class-aware greedy NMS and connected-component
 // labelling with statistics.  Integer / comparison work, HBM- and latency-bound.
 #include <algorithm>
+#include <cstdint>
 
 #include "kernels.h"
 
@@ -715,157 +716,292 @@ __global__ void ccl_stats_final_kernel(int* __restrict__ stats, const int* __res
 // disjoint, so one parent array, one border merge, one flattening, one ranking sweep and one label pass serve
 // both -- the two separate launches read and wrote every int32 plane twice.  Output: ONE signed label image
 // (+id foreground, -id background, ids per class in raster order of the first pixel) and per-class stats.
+//
+// The union-find runs over ROW RUNS, not pixels.  A run is a maximal horizontal stretch of one class
+// inside a row; a page of speckle has a tenth as many runs as pixels, a real page far fewer.  With the page as
+// wp = ceil(W / 32) words per row:
+//   bits[word]    bit i = pixel 32 * wx + i is foreground (0 beyond W)
+//   starts[word]  bit i = that pixel starts a run: x == 0 or class(x) != class(x - 1) (0 beyond W)
+//   base[word]    exclusive prefix sum of popcount(starts) over the page's words
+//   run of bit i  base[word] + popcount(starts[word] & ((2u << i) - 1)) - 1   -- ids in raster order of the runs' first pixels
+// Unions happen only between a row and the row above, group of set bits against group of set bits (8-connected for
+// the foreground: one halo bit from each neighbouring word above; 4-connected for the background).  The smaller root
+// wins, so a component's root is the run that holds its first pixel, and ranking the roots of each class in run order
+// gives the ids of the per-pixel labelling.  Kernels, in launch order:
+//   ccl2_pack          u8 -> bits, starts, the start count of every 128 words
+//   ccl2_run_scan      base, and the page's run count R (stays on the device: every kernel over runs is sized for
+//                      R <= H * W and exits on R)
+//   ccl2_band          unions inside a band of RB_ROWS full-width rows in LDS, rparent[] and the class byte of every
+//                      run; a band with more than RB_CAP runs does the same unions on rparent[] in global memory
+//   ccl2_band_border   the same unions for rows 32k, k >= 1, on rparent[]   (full-width bands: no vertical borders)
+//   ccl2_flatten_count / ccl2_scan_chunks / ccl2_rank / ccl2_spread         rlabel[run] = 2 * (+-id) + root, over runs
+//   ccl2_label         paints the plane from base / starts / rlabel, once; statistics, first pixels, seg_live
+// rparent[] lives in the label plane (R <= H * W) and is dead before the paint overwrites it.
 // ======================================================================================================
-__device__ __forceinline__ void ccl2_local_body(int vb, const uint8_t* __restrict__ img, int* __restrict__ parent_all,
-                                                         int H, int W, int tiles_x, int tiles_y, int thresh) {
-  __shared__ int lp[CT * CT];
-  __shared__ unsigned mrow[2][CT];                 // row masks: [0] foreground, [1] background (pixels inside the image)
-  int bid = vb;
-  const int tx = bid % tiles_x;
-  bid /= tiles_x;
-  const int ty = bid % tiles_y;
-  const int b = bid / tiles_y;
-  const size_t base = (size_t)b * H * W;
-  const int x0 = tx * CT, y0 = ty * CT;
-  const int lane = threadIdx.x & 63;
-  const int lx = threadIdx.x & 31;
-  int pix[CT * CT / 256];                                   // loads first, ballots second (see ccl_local_body)
-#pragma unroll
-  for (int k = 0; k < CT * CT / 256; ++k) {
-    const int gx = x0 + lx, gy = y0 + ((threadIdx.x + 256 * k) >> 5);
-    pix[k] = img[base + (gx < W && gy < H ? (size_t)gy * W + gx : (size_t)0)];
-  }
-#pragma unroll
-  for (int k = 0; k < CT * CT / 256; ++k) {
-    const int li = threadIdx.x + 256 * k;
-    const int ly = li >> 5;
-    const int gx = x0 + lx, gy = y0 + ly;
-    const bool valid = gx < W && gy < H;
-    const bool fg = valid && pix[k] > thresh;
-    const unsigned long long balf = __ballot(fg), balv = __ballot(valid);
-    const unsigned mf = (unsigned)(lane < 32 ? balf : balf >> 32);
-    const unsigned mv = (unsigned)(lane < 32 ? balv : balv >> 32);
-    const unsigned mb = mv & ~mf;
-    const unsigned mine = fg ? mf : mb;
-    const unsigned below = ~mine & ((1u << lx) - 1u);
-    const int start = below ? 32 - __clz(below) : 0;
-    lp[li] = valid ? (ly << 5) + start : -1;
-    if (lx == 0) mrow[0][ly] = mf, mrow[1][ly] = mb;
-  }
+// what the paint reads (all of it in the workspace)
+struct RunTables {
+  const unsigned* starts;              // (B, H, wp)
+  const unsigned* base;                // (B, H, wp)
+  const int* rlabel;                   // (B, H * W), the first R of a page in use: 2 * (+-id) + (the run is a root)
+  int wp;
+};
+constexpr int RB_ROWS = 32;    // rows of a band: a row's word is 32 pixels, a band's words are 32 x 32 pixel tiles as before
+constexpr int RB_THREADS = 1024;   // of a band's block: a 1024-wide band is 1024 words, one per thread and one round trip
+constexpr int RB_CAP = 8192;   // runs a band's LDS table holds (32 KB).  The benchmark's 1024-wide speckle pages have at most
+                               // 4 264 runs in a band (mean 3 000-3 500); alternating pixels have 32 768 and go through global memory.
+
+// four pixels per thread, eight lanes per word; a virtual block is a segment of PK_SEG consecutive words of one page and
+// leaves the segment's number of starts for the scan
+constexpr int PK_U = 4;   // steps of 256 groups = 32 words each per virtual block: all their loads first
+constexpr int PK_SEG = 32 * PK_U;
+__device__ __forceinline__ void ccl2_pack_body(int vb, const uint8_t* __restrict__ img, unsigned* __restrict__ bits_all,
+                                                        unsigned* __restrict__ starts_all, int* __restrict__ segsum, int nseg, int H,
+                                                        int W, int wp, int thresh, int aligned4) {
+  __shared__ int segc;
+  const int nw = H * wp;
+  const size_t hw = (size_t)H * W;
+  const int b = vb / nseg, seg = vb - b * nseg;
+  if (threadIdx.x == 0) segc = 0;
   __syncthreads();
+  unsigned px[PK_U];
+  int prev[PK_U], xs[PK_U], ws[PK_U];
 #pragma unroll
-  for (int k = 0; k < CT * CT / 256; ++k) {
-    const int li = threadIdx.x + 256 * k;
-    const int ly = li >> 5;
-    if (ly == 0) continue;
-    const int cls = ((mrow[0][ly] >> lx) & 1u) ? 0 : 1;
-    const unsigned m = mrow[cls][ly], ma = mrow[cls][ly - 1];
-    if (!((m >> lx) & 1u) || (lx > 0 && ((m >> (lx - 1)) & 1u))) continue;   // heads of this class's runs only
-    const unsigned from = m >> lx;
-    const int len = (~from) ? __ffs(~from) - 1 : 32 - lx;
-    unsigned run = (len >= 32 ? 0xffffffffu : ((1u << len) - 1u)) << lx;
-    if (cls == 0) run |= (run << 1) | (run >> 1);                            // foreground: 8-connected
-    unsigned ov = ma & run;
-    while (ov) {
-      const int bpos = __ffs(ov) - 1;
-      const unsigned belowa = ~ma & ((1u << bpos) - 1u);
-      const int sa = belowa ? 32 - __clz(belowa) : 0;
-      lds_union(lp, li, ((ly - 1) << 5) + sa);
-      const unsigned froma = ma >> bpos;
-      const int lena = (~froma) ? __ffs(~froma) - 1 : 32 - bpos;
-      ov &= ~((lena >= 32 ? 0xffffffffu : ((1u << lena) - 1u)) << bpos);
+  for (int u = 0; u < PK_U; ++u) {
+    const int g = (int)threadIdx.x;                                       // group of 4 pixels of the padded rows
+    const int rem = seg * PK_SEG + u * 32 + (g >> 3);                     // word of the page
+    const bool valid = rem < nw;
+    const int y = valid ? rem / wp : 0, wx = valid ? rem - y * wp : 0;
+    const int x = wx * 32 + 4 * (g & 7);
+    const uint8_t* row = img + (size_t)b * hw + (size_t)y * W;
+    unsigned v = 0;
+    if (valid && x < W) {
+      if (aligned4) {
+        v = *reinterpret_cast<const unsigned*>(row + x);
+      } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+          if (x + k < W) v |= (unsigned)row[x + k] << (8 * k);
+      }
+    }
+    px[u] = v;
+    prev[u] = (valid && ((int)g & 7) == 0 && wx > 0) ? (int)row[x - 1] : -1;   // the left word's last pixel
+    xs[u] = x;
+    ws[u] = valid ? rem : -1;
+  }
+  unsigned* bits = bits_all + (size_t)b * nw;
+  unsigned* starts = starts_all + (size_t)b * nw;
+  int nstart = 0;
+#pragma unroll
+  for (int u = 0; u < PK_U; ++u) {
+    const int x = xs[u];
+    unsigned nib = 0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+      if (x + k < W && (int)((px[u] >> (8 * k)) & 255u) > thresh) nib |= 1u << k;
+    unsigned v = nib << (4 * (threadIdx.x & 7));
+    v |= __shfl_xor(v, 1);
+    v |= __shfl_xor(v, 2);
+    v |= __shfl_xor(v, 4);
+    if ((threadIdx.x & 7) == 0 && ws[u] >= 0) {
+      const int nbit = min(32, W - x);                                  // x = the word's first pixel here
+      const unsigned vmask = nbit >= 32 ? 0xffffffffu : ((1u << nbit) - 1u);
+      const unsigned pb = prev[u] >= 0 ? (prev[u] > thresh ? 1u : 0u) : (~v & 1u);   // x == 0 always starts a run
+      const unsigned s = (v ^ ((v << 1) | pb)) & vmask;
+      bits[ws[u]] = v;
+      starts[ws[u]] = s;
+      nstart += __popc(s);
     }
   }
+  if (nstart) atomicAdd(&segc, nstart);                                   // LDS: the 32 word owners of the block
   __syncthreads();
-#pragma unroll
-  for (int k = 0; k < CT * CT / 256; ++k) {
-    const int li = threadIdx.x + 256 * k;
-    const int gx = x0 + lx, gy = y0 + (li >> 5);
-    if (gx >= W || gy >= H) continue;
-    const int r = lds_find(lp, lp[li]);
-    parent_all[base + (size_t)gy * W + gx] = (y0 + (r >> 5)) * W + x0 + (r & 31);
-  }
+  if (threadIdx.x == 0) segsum[vb] = segc;
 }
-// a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
-// waves per SIMD next to the network, not all of them
-__global__ __launch_bounds__(256) void ccl2_local_kernel(const uint8_t* __restrict__ img, int* __restrict__ parent_all,
-                                                         int H, int W, int tiles_x, int tiles_y, int thresh, int nvb) {
+__global__ __launch_bounds__(256) void ccl2_pack_kernel(const uint8_t* __restrict__ img, unsigned* __restrict__ bits_all,
+                                                        unsigned* __restrict__ starts_all, int* __restrict__ segsum, int nseg, int H,
+                                                        int W, int wp, int thresh, int aligned4, int nvb) {
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl2_local_body(vb, img, parent_all, H, W, tiles_x, tiles_y, thresh);
+    ccl2_pack_body(vb, img, bits_all, starts_all, segsum, nseg, H, W, wp, thresh, aligned4);
     __syncthreads();
   }
 }
 
-// Border links of both classes (pruned to one link per pair of overlapping runs, see ccl_border_*_kernel):
-// foreground pixels follow the 8-connected rules, background pixels the 4-connected ones.
-__global__ __launch_bounds__(256) void ccl2_border_h_kernel(int* __restrict__ parent_all, const uint8_t* __restrict__ img_all,
-                                                            int thresh, int H, int W) {
-  const int x = blockIdx.x * 256 + threadIdx.x;
-  const int y = CT * (blockIdx.y + 1);
-  if (x >= W || y >= H) return;
-  int* parent = parent_all + (size_t)blockIdx.z * H * W;
-  const uint8_t* img = img_all + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;
-  const bool me = (int)img[p] > thresh;
-  auto same = [&](int q) { return ((int)img[q] > thresh) == me; };
-  const bool q = x > 0 && same(p - 1);
-  const bool up = same(p - W);
-  const bool ul = x > 0 && same(p - W - 1);
-  if (!me) {                                      // background: 4-connected
-    if (up && !(q && ul)) uf_union(parent, p, p - W);
+// base[]: a block scans one tile of SC_TILE words of one page, 16 consecutive words per thread in one round trip; what
+// lies before the tile is the sum of the pack's segment counts before it.  The block of a page's last tile leaves the
+// page's run count.  (One block per page and a sweep over its words was 44 us for eight pages: eight blocks, nothing to
+// hide a round trip behind.)
+constexpr int SC_TILE = 4096;
+static_assert(SC_TILE % PK_SEG == 0 && SC_TILE == 256 * 16, "whole segments; 16 words per thread");
+__device__ __forceinline__ void ccl2_run_scan_body(int vb, const unsigned* __restrict__ starts_all, const int* __restrict__ segsum,
+                                                            unsigned* __restrict__ base_all, int* __restrict__ rcount, int nw, int nseg,
+                                                            int ntiles) {
+  __shared__ int sh[4];
+  const int b = vb / ntiles, tile = vb - b * ntiles;
+  const unsigned* starts = starts_all + (size_t)b * nw;
+  unsigned* base = base_all + (size_t)b * nw;
+  const int i0 = tile * SC_TILE + 16 * (int)threadIdx.x;
+  unsigned sv[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) sv[k] = i0 + k < nw ? starts[i0 + k] : 0u;
+  int before = 0;
+  for (int i = threadIdx.x; i < tile * (SC_TILE / PK_SEG); i += 256) before += segsum[(size_t)b * nseg + i];
+  int mine = 0;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) mine += __popc(sv[k]);
+  int prefix, total;
+  block_exclusive_scan(before, sh, &prefix);                // only its total: the starts before this tile
+  int e = prefix + block_exclusive_scan(mine, sh, &total);
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (i0 + k < nw) base[i0 + k] = (unsigned)e;
+    e += __popc(sv[k]);
+  }
+  if (tile == ntiles - 1 && threadIdx.x == 0) rcount[b] = prefix + total;
+}
+__global__ __launch_bounds__(256) void ccl2_run_scan_kernel(const unsigned* __restrict__ starts_all, const int* __restrict__ segsum,
+                                                            unsigned* __restrict__ base_all, int* __restrict__ rcount, int nw, int nseg,
+                                                            int ntiles, int nvb) {
+  for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
+    ccl2_run_scan_body(vb, starts_all, segsum, base_all, rcount, nw, nseg, ntiles);
+    __syncthreads();
+  }
+}
+
+// The unions of word (y, wx), y >= 1, with the row above: every group of set bits of either class against every group of
+// the same class above that it touches, one union per pair.  `unite(a, b)` gets two run ids of the page.
+template <class U>
+__device__ __forceinline__ void ccl2_word_unions(const unsigned* __restrict__ bits, const unsigned* __restrict__ starts,
+                                                          const unsigned* __restrict__ base, int y, int wx, int wp, int W, U&& unite) {
+  const int w = y * wp + wx, wa = w - wp;
+  const bool hl = wx > 0, hr = wx + 1 < wp;
+  // every load first (the halo words of the foreground too), their use after
+  const unsigned c = bits[w], sc = starts[w], a = bits[wa], sa = starts[wa];
+  const int bc = (int)base[w], ba = (int)base[wa];
+  const unsigned al = hl ? bits[wa - 1] : 0u, sal = hl ? starts[wa - 1] : 0u;
+  const int bal = hl ? (int)base[wa - 1] : 0;
+  const unsigned ar = hr ? bits[wa + 1] : 0u, sar = hr ? starts[wa + 1] : 0u;
+  const int bar = hr ? (int)base[wa + 1] : 0;
+  const int nbit = min(32, W - 32 * wx);
+  const unsigned vmask = nbit >= 32 ? 0xffffffffu : ((1u << nbit) - 1u);
+#pragma unroll
+  for (int cls = 0; cls < 2; ++cls) {                       // 1 = foreground
+    const unsigned m = (cls ? c : ~c) & vmask, ma = (cls ? a : ~a) & vmask;
+    unsigned rest = m;
+    while (rest) {
+      const int lo = __ffs(rest) - 1;
+      const unsigned from = m >> lo;
+      const int len = (~from) ? __ffs(~from) - 1 : 32 - lo;
+      const unsigned g = (len >= 32 ? 0xffffffffu : ((1u << len) - 1u)) << lo;
+      rest &= ~g;
+      const int me = bc + __popc(sc & ((2u << lo) - 1u)) - 1;
+      const bool cont = lo == 0 && !(sc & 1u);              // my run began in an earlier word
+      unsigned reach = g;
+      if (cls) reach |= (g << 1) | (g >> 1);                // 8-connected: the diagonal neighbours above
+      unsigned ov = ma & reach;
+      while (ov) {
+        const int bpos = __ffs(ov) - 1;
+        // both runs come over from the word to the left: that word has united them
+        if (!(cont && bpos == 0 && !(sa & 1u))) unite(me, ba + __popc(sa & ((2u << bpos) - 1u)) - 1);
+        const unsigned froma = ma >> bpos;                  // clear the rest of that group above
+        const int lena = (~froma) ? __ffs(~froma) - 1 : 32 - bpos;
+        ov &= ~((lena >= 32 ? 0xffffffffu : ((1u << lena) - 1u)) << bpos);
+      }
+      if (cls) {                                            // the halo bits: last pixel of the word above-left, first of above-right
+        if (lo == 0 && (al >> 31)) unite(me, bal + __popc(sal) - 1);
+        if (lo + len == 32 && (ar & 1u)) unite(me, bar + (int)(sar & 1u) - 1);
+      }
+    }
+  }
+}
+
+__device__ __forceinline__ void ccl2_band_body(int vb, const unsigned* __restrict__ bits_all, const unsigned* __restrict__ starts_all,
+                                                        const unsigned* __restrict__ base_all, const int* __restrict__ rcount,
+                                                        int* __restrict__ rparent_all, uint8_t* __restrict__ rcls_all, int H, int W,
+                                                        int wp, int nbands) {
+  __shared__ int lp[RB_CAP];
+  const int b = vb / nbands, k = vb % nbands;
+  const int y0 = k * RB_ROWS, y1 = min(H, y0 + RB_ROWS);
+  const size_t nw = (size_t)H * wp, hw = (size_t)H * W;
+  const unsigned* bits = bits_all + b * nw;
+  const unsigned* starts = starts_all + b * nw;
+  const unsigned* base = base_all + b * nw;
+  int* rparent = rparent_all + b * hw;
+  uint8_t* rcls = rcls_all + b * hw;
+  // a band's runs are contiguous in id space: local id = id - gbase
+  const int gbase = (int)base[y0 * wp];
+  const int n = (y1 < H ? (int)base[y1 * wp] : rcount[b]) - gbase;
+  const bool in_lds = n <= RB_CAP;                          // the same for the whole block
+  if (in_lds) {
+    for (int i = threadIdx.x; i < n; i += RB_THREADS) lp[i] = i;
+  } else {
+    for (int i = threadIdx.x; i < n; i += RB_THREADS) rparent[gbase + i] = gbase + i;
+    __threadfence();
+  }
+  __syncthreads();
+  for (int wi = y0 * wp + threadIdx.x; wi < y1 * wp; wi += RB_THREADS) {
+    const int y = wi / wp, wx = wi - y * wp;
+    unsigned s = starts[wi];
+    const unsigned c = bits[wi];
+    int id = (int)base[wi];
+    while (s) {                                             // the class byte of every run that starts in this word
+      const int pos = __ffs(s) - 1;
+      s &= s - 1u;
+      rcls[id++] = (uint8_t)((c >> pos) & 1u);
+    }
+    if (y == y0) continue;
+    if (in_lds)
+      ccl2_word_unions(bits, starts, base, y, wx, wp, W, [&](int p, int q) { lds_union(lp, p - gbase, q - gbase); });
+    else
+      ccl2_word_unions(bits, starts, base, y, wx, wp, W, [&](int p, int q) { uf_union(rparent, p, q); });
+  }
+  __syncthreads();
+  if (in_lds)
+    for (int i = threadIdx.x; i < n; i += RB_THREADS) rparent[gbase + i] = gbase + lds_find(lp, i);
+}
+// a block walks several bands: the launcher caps the grid (tail_max_blocks counts blocks of 256 threads) so that these
+// kernels hold a few waves per SIMD next to the network, not all of them
+__global__ __launch_bounds__(RB_THREADS) void ccl2_band_kernel(const unsigned* __restrict__ bits_all, const unsigned* __restrict__ starts_all,
+                                                        const unsigned* __restrict__ base_all, const int* __restrict__ rcount,
+                                                        int* __restrict__ rparent_all, uint8_t* __restrict__ rcls_all, int H, int W,
+                                                        int wp, int nbands, int nvb) {
+  for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
+    ccl2_band_body(vb, bits_all, starts_all, base_all, rcount, rparent_all, rcls_all, H, W, wp, nbands);
+    __syncthreads();
+  }
+}
+
+// rows y = RB_ROWS * k, k >= 1, with the last row of the band above: one thread per word
+__global__ __launch_bounds__(256) void ccl2_band_border_kernel(const unsigned* __restrict__ bits_all,
+                                                               const unsigned* __restrict__ starts_all,
+                                                               const unsigned* __restrict__ base_all, int* __restrict__ rparent_all,
+                                                               int B, int H, int W, int wp, int nbord) {
+  int t = blockIdx.x * 256 + threadIdx.x;
+  if (t >= B * nbord * wp) return;
+  const int wx = t % wp;
+  t /= wp;
+  const int k = t % nbord, b = t / nbord;
+  const size_t nw = (size_t)H * wp;
+  int* rparent = rparent_all + (size_t)b * H * W;
+  ccl2_word_unions(bits_all + b * nw, starts_all + b * nw, base_all + b * nw, RB_ROWS * (k + 1), wx, wp, W,
+                   [&](int p, int q) { uf_union(rparent, p, q); });
+}
+
+// Flattening, root count and root bitmaps over the page's R runs (the scheme of ccl_flatten_count_body on the run table:
+// parent = rparent[], a chunk = RK_CHUNK runs; a chunk beyond R counts nothing).
+// chunk_cnt: (B, 2, nchunks) -- class 0 = foreground roots, 1 = background roots
+__device__ __forceinline__ void ccl2_flatten_count_body(int vb, int* __restrict__ parent_all, const uint8_t* __restrict__ rcls_all,
+                                                                 const int* __restrict__ rcount, int B, int hw, int nchunks,
+                                                                 int* __restrict__ chunk_cnt, unsigned long long* __restrict__ rootmask) {
+  __shared__ int sh[4];
+  // chunk-major: the chunks that hold runs are the first few of every page, and a capped grid walks virtual blocks with a
+  // stride -- page-major, the same few blocks got the live chunks of every page and the rest of the grid none
+  const int b = vb % B, ch = vb / B;
+  const int R = rcount[b];
+  if (ch * RK_CHUNK >= R) {                     // the whole block
+    if (threadIdx.x == 0) chunk_cnt[((size_t)b * 2 + 0) * nchunks + ch] = 0, chunk_cnt[((size_t)b * 2 + 1) * nchunks + ch] = 0;
     return;
   }
-  const bool ur = x + 1 < W && same(p - W + 1);
-  if (q) {
-    if (ur && !up) uf_union(parent, p, p - W + 1);
-  } else if (up) {
-    uf_union(parent, p, p - W);
-  } else {
-    if (ul) uf_union(parent, p, p - W - 1);
-    if (ur) uf_union(parent, p, p - W + 1);
-  }
-}
-
-__global__ __launch_bounds__(256) void ccl2_border_v_kernel(int* __restrict__ parent_all, const uint8_t* __restrict__ img_all,
-                                                            int thresh, int H, int W) {
-  const int y = blockIdx.x * 256 + threadIdx.x;
-  const int x = CT * (blockIdx.y + 1);
-  if (y >= H || x >= W) return;
-  int* parent = parent_all + (size_t)blockIdx.z * H * W;
-  const uint8_t* img = img_all + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;
-  const bool ua = y > 0, same_tile = (y % CT) != 0;
-  const bool fme = (int)img[p] > thresh, fleft = (int)img[p - 1] > thresh;
-  const bool fmu = ua && (int)img[p - W] > thresh, flu = ua && (int)img[p - W - 1] > thresh;
-  // background, 4-connected: only the horizontal pair
-  {
-    const bool me = !fme, left = !fleft, mu = ua && !fmu, lu = ua && !flu;
-    if (me && left && !(same_tile && mu && lu)) uf_union(parent, p, p - 1);
-  }
-  // foreground, 8-connected
-  {
-    const bool me = fme, left = fleft, mu = fmu, lu = flu;
-    if (!me && !left) return;
-    if (!same_tile) {
-      if (me && left) uf_union(parent, p, p - 1);
-      if (me && lu) uf_union(parent, p, p - W - 1);
-      if (left && mu) uf_union(parent, p - 1, p - W);
-      return;
-    }
-    if (me && left && !(mu && lu)) uf_union(parent, p, p - 1);
-    if (me && lu && !left && !mu) uf_union(parent, p, p - W - 1);
-    if (left && mu && !me && !lu) uf_union(parent, p - 1, p - W);
-  }
-}
-
-// chunk_cnt: (B, 2, nchunks) -- class 0 = foreground roots, 1 = background roots
-__device__ __forceinline__ void ccl2_flatten_count_body(int vb, int* __restrict__ parent_all, const uint8_t* __restrict__ img_all,
-                                                                 int thresh, int hw, int nchunks, int* __restrict__ chunk_cnt,
-                                                                 unsigned long long* __restrict__ rootmask) {
-  __shared__ int sh[4];
-  const int b = vb / nchunks, ch = vb % nchunks;
   int* parent = parent_all + (size_t)b * hw;
-  const uint8_t* img = img_all + (size_t)b * hw;
+  const uint8_t* rcls = rcls_all + (size_t)b * hw;
   const int p0 = ch * RK_CHUNK + threadIdx.x;
   int lf = 0, lb = 0;
   constexpr int FU = 4;                         // hop by hop over four pixels (see ccl_flatten_count_body)
@@ -875,8 +1011,8 @@ __device__ __forceinline__ void ccl2_flatten_count_body(int vb, int* __restrict_
 #pragma unroll
     for (int j = 0; j < FU; ++j) {
       const int p = p0 + 256 * (j0 + j);
-      v[j] = p < hw ? uf_load(parent, p) : -1;  // every pixel of the image has a class: parents are never negative
-      px[j] = img[min(p, hw - 1)];
+      v[j] = p < R ? uf_load(parent, p) : -1;   // every run has a class: parents are never negative
+      px[j] = rcls[min(p, R - 1)];
     }
 #pragma unroll
     for (int j = 0; j < FU; ++j) g[j] = v[j] >= 0 ? uf_load(parent, v[j]) : -1;
@@ -887,8 +1023,12 @@ __device__ __forceinline__ void ccl2_flatten_count_body(int vb, int* __restrict_
       if (v[j] >= 0) {
         const int r = g[j] == v[j] ? v[j] : uf_find(parent, g[j]);
         if (r != v[j]) parent[p] = r;
+        // v is the root its band gave the run, r the component's: the band borders chain the band roots of a component
+        // that spans the page (the background: one hop per band), and every run of the band walks that chain unless the
+        // first to get there shortens it (no union runs next to this kernel: any ancestor is a valid parent)
+        if (g[j] != v[j] && r != g[j]) parent[v[j]] = r;
         if (r == p) {
-          if (px[j] > thresh) ++lf, rf = true; else ++lb, rb = true;
+          if (px[j]) ++lf, rf = true; else ++lb, rb = true;
         }
       }
       // root bitmaps per class (see ccl_flatten_count_body): (B, 2, nchunks, 64) words
@@ -910,11 +1050,12 @@ __device__ __forceinline__ void ccl2_flatten_count_body(int vb, int* __restrict_
 }
 // a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
 // waves per SIMD next to the network, not all of them
-__global__ __launch_bounds__(256) void ccl2_flatten_count_kernel(int* __restrict__ parent_all, const uint8_t* __restrict__ img_all,
-                                                                 int thresh, int hw, int nchunks, int* __restrict__ chunk_cnt,
-                                                                 unsigned long long* __restrict__ rootmask, int nvb) {
+__global__ __launch_bounds__(256) void ccl2_flatten_count_kernel(int* __restrict__ parent_all, const uint8_t* __restrict__ rcls_all,
+                                                                 const int* __restrict__ rcount, int B, int hw, int nchunks,
+                                                                 int* __restrict__ chunk_cnt, unsigned long long* __restrict__ rootmask,
+                                                                 int nvb) {
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl2_flatten_count_body(vb, parent_all, img_all, thresh, hw, nchunks, chunk_cnt, rootmask);
+    ccl2_flatten_count_body(vb, parent_all, rcls_all, rcount, B, hw, nchunks, chunk_cnt, rootmask);
     __syncthreads();
   }
 }
@@ -937,13 +1078,14 @@ __global__ __launch_bounds__(256) void ccl2_scan_chunks_kernel(int* __restrict__
   if (threadIdx.x == 0) ((blockIdx.x & 1) ? n_b : n_f)[blockIdx.x >> 1] = carry;
 }
 
-// ids: +rank for a foreground root, -rank for a background root (ranks per class, raster order)
-__device__ __forceinline__ void ccl2_rank_body(int vb, const unsigned long long* __restrict__ rootmask,
-                                                        int hw, int nchunks, const int* __restrict__ chunk_cnt,
-                                                        int* __restrict__ ids_all, int* __restrict__ first_f,
-                                                        int* __restrict__ first_b, int max_labels) {
+// rlabel of the root runs: 2 * id + 1, id = +rank for a foreground root, -rank for a background root (ranks per class, in run
+// order = raster order of the components' first pixels); the low bit says "root" to the paint
+__device__ __forceinline__ void ccl2_rank_body(int vb, const unsigned long long* __restrict__ rootmask, const int* __restrict__ rcount,
+                                                        int B, int hw, int nchunks, const int* __restrict__ chunk_cnt,
+                                                        int* __restrict__ ids_all) {
   __shared__ int sh[2][4];
-  const int b = vb / nchunks, ch = vb % nchunks;
+  const int b = vb % B, ch = vb / B;            // chunk-major (see ccl2_flatten_count_body)
+  if (ch * RK_CHUNK >= rcount[b]) return;       // the whole block: no run, no root bitmap
   const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int base = ch * RK_CHUNK + w * 1024 + lane;
   unsigned long long mf[16], mb[16];
@@ -968,12 +1110,10 @@ __device__ __forceinline__ void ccl2_rank_body(int vb, const unsigned long long*
     const int p = base + 64 * j;
     if ((mf[j] >> lane) & 1ull) {
       const int id = idf + __popcll(mf[j] & below) + 1;
-      ids[p] = id;
-      if (id <= max_labels) first_f[(size_t)b * max_labels + id - 1] = p;
+      ids[p] = 2 * id + 1;
     } else if ((mb[j] >> lane) & 1ull) {
       const int id = idb + __popcll(mb[j] & below) + 1;
-      ids[p] = -id;
-      if (id <= max_labels) first_b[(size_t)b * max_labels + id - 1] = p;
+      ids[p] = -2 * id + 1;
     }
     idf += __popcll(mf[j]);
     idb += __popcll(mb[j]);
@@ -981,22 +1121,56 @@ __device__ __forceinline__ void ccl2_rank_body(int vb, const unsigned long long*
 }
 // a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
 // waves per SIMD next to the network, not all of them
-__global__ __launch_bounds__(256) void ccl2_rank_kernel(const unsigned long long* __restrict__ rootmask,
-                                                        int hw, int nchunks, const int* __restrict__ chunk_cnt,
-                                                        int* __restrict__ ids_all, int* __restrict__ first_f,
-                                                        int* __restrict__ first_b, int max_labels, int nvb) {
+__global__ __launch_bounds__(256) void ccl2_rank_kernel(const unsigned long long* __restrict__ rootmask, const int* __restrict__ rcount,
+                                                        int B, int hw, int nchunks, const int* __restrict__ chunk_cnt,
+                                                        int* __restrict__ ids_all, int nvb) {
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl2_rank_body(vb, rootmask, hw, nchunks, chunk_cnt, ids_all, first_f, first_b, max_labels);
+    ccl2_rank_body(vb, rootmask, rcount, B, hw, nchunks, chunk_cnt, ids_all);
     __syncthreads();
   }
 }
 
-// signed final labels + the statistics of both classes (aggregation as in ccl_label_kernel)
+// rlabel of every other run: its root's without the root bit (rparent[] is flat by now).  After this the label plane that
+// held rparent[] is free.
+__global__ __launch_bounds__(256) void ccl2_spread_kernel(const int* __restrict__ rparent_all, const int* __restrict__ rcount, int B,
+                                                          int hw, int nchunks, int* __restrict__ rlabel_all, int nvb) {
+  for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
+    const int b = vb % B, ch = vb / B;          // chunk-major (see ccl2_flatten_count_body)
+    const int R = rcount[b];
+    const int* rparent = rparent_all + (size_t)b * hw;
+    int* rlabel = rlabel_all + (size_t)b * hw;
+    constexpr int SU = 4;                         // parents of four runs, then their labels
+    for (int j0 = 0; j0 < RK_PER_T && ch * RK_CHUNK + 256 * j0 < R; j0 += SU) {
+      int par[SU], lab[SU];
+#pragma unroll
+      for (int j = 0; j < SU; ++j) {
+        const int r = ch * RK_CHUNK + 256 * (j0 + j) + threadIdx.x;
+        par[j] = r < R ? rparent[r] : -1;
+      }
+#pragma unroll
+      for (int j = 0; j < SU; ++j) {
+        const int r = ch * RK_CHUNK + 256 * (j0 + j) + threadIdx.x;
+        lab[j] = (par[j] >= 0 && par[j] != r) ? rlabel[par[j]] : 0;
+      }
+#pragma unroll
+      for (int j = 0; j < SU; ++j) {
+        const int r = ch * RK_CHUNK + 256 * (j0 + j) + threadIdx.x;
+        if (par[j] >= 0 && par[j] != r) rlabel[r] = lab[j] & ~1;
+      }
+    }
+  }
+}
+
+// The paint: signed final labels + the statistics of both classes (aggregation as in ccl_label_kernel).  A pixel's label is
+// its run's: run = base[word] + popcount(starts[word] up to its bit) - 1, label = rlabel[run] >> 1.  The plane is written once
+// and never read.  The pixel that starts a root run (rlabel[run] & 1) is its component's first pixel in raster order: it
+// writes first_*.
 // seg_live (null: not wanted): a wave's 64 pixels are one 64-aligned segment of the page's linear index (chunks and steps
 // are multiples of 256), and the wave has their labels in registers: lane 0 notes whether any differs from -1.
-__device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels_all, const int* __restrict__ ids_all, int B, int H,
+__device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels_all, const RunTables t, int B, int H,
                                                          int W, int chunks, int* __restrict__ st_f, int* __restrict__ st_b,
-                                                         int max_labels, uint8_t* __restrict__ seg_live) {
+                                                         int* __restrict__ first_f, int* __restrict__ first_b, int max_labels,
+                                                         uint8_t* __restrict__ seg_live) {
   constexpr int EMPTY = (int)0x80000000;
   __shared__ int hkey[LB_SLOTS];
   __shared__ int hst[LB_SLOTS * 5];
@@ -1004,6 +1178,9 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
   const int b = vb / chunks, ch = vb % chunks;
   const int p_begin = ch * LB_CHUNK, p_end = min(hw, p_begin + LB_CHUNK);
   const size_t base = (size_t)b * hw;
+  const unsigned* starts = t.starts + (size_t)b * H * t.wp;
+  const unsigned* wbase = t.base + (size_t)b * H * t.wp;
+  const int* rlabel = t.rlabel + base;
   for (int s = threadIdx.x; s < LB_SLOTS; s += 256) {
     hkey[s] = EMPTY;
     hst[5 * s] = W, hst[5 * s + 1] = H, hst[5 * s + 2] = -1, hst[5 * s + 3] = -1, hst[5 * s + 4] = 0;
@@ -1011,16 +1188,33 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
   __syncthreads();
   const int lane = threadIdx.x & 63;
   auto row_of = [&](int id) { return (id > 0 ? st_f : st_b) + ((size_t)b * max_labels + ((id > 0 ? id : -id) - 1)) * 5; };
-  constexpr int LU = 4;                                     // four steps' roots, then their ids (see ccl_label_body)
+  // eight steps' words, then their runs' labels (see ccl_label_body): two memory round trips per 2048 pixels, and the
+  // capped grid leaves a block little else to hide them behind
+  constexpr int LU = 8;
+  static_assert(LB_CHUNK % (256 * LU) == 0, "whole batches");
   for (int pb = p_begin; pb < p_end; pb += 256 * LU) {
-    int root[LU], idv[LU];
+    unsigned sw[LU];
+    int run[LU], idv[LU];
 #pragma unroll
     for (int u = 0; u < LU; ++u) {
       const int p = pb + 256 * u + threadIdx.x;
-      root[u] = p < p_end ? labels_all[base + p] : -1;
+      const int y = p / W, w = y * t.wp + ((p - y * W) >> 5);
+      sw[u] = p < p_end ? starts[w] : 0u;
+      run[u] = p < p_end ? (int)wbase[w] : 0;
     }
 #pragma unroll
-    for (int u = 0; u < LU; ++u) idv[u] = root[u] >= 0 ? ids_all[base + root[u]] : 0;
+    for (int u = 0; u < LU; ++u) {
+      const int p = pb + 256 * u + threadIdx.x;
+      const int bit = (p % W) & 31;
+      run[u] += __popc(sw[u] & ((2u << bit) - 1u)) - 1;
+      idv[u] = p < p_end ? rlabel[run[u]] : 0;
+      sw[u] = (sw[u] >> bit) & 1u;                            // this pixel starts its run
+    }
+#pragma unroll
+    for (int u = 0; u < LU; ++u) {
+      sw[u] &= (unsigned)idv[u];                              // ... a root run: the component's first pixel
+      idv[u] >>= 1;
+    }
 #pragma unroll
     for (int u = 0; u < LU; ++u) {
       const int p = pb + 256 * u + threadIdx.x;
@@ -1043,6 +1237,7 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
       const bool head = lane == 0 || prev != id || x == 0;
       const unsigned long long heads = __ballot(head);
       const int mag = id > 0 ? id : -id;
+      if (sw[u] && mag <= max_labels) (id > 0 ? first_f : first_b)[(size_t)b * max_labels + mag - 1] = p;
       if (head && id != 0 && mag <= max_labels) {
         const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1));
         const int len = later ? __ffsll((long long)later) : 64 - lane;
@@ -1079,11 +1274,12 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
 }
 // a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
 // waves per SIMD next to the network, not all of them
-__global__ __launch_bounds__(256) void ccl2_label_kernel(int* __restrict__ labels_all, const int* __restrict__ ids_all, int B, int H,
+__global__ __launch_bounds__(256) void ccl2_label_kernel(int* __restrict__ labels_all, const RunTables t, int B, int H,
                                                          int W, int chunks, int* __restrict__ st_f, int* __restrict__ st_b,
-                                                         int max_labels, int nvb, uint8_t* __restrict__ seg_live) {
+                                                         int* __restrict__ first_f, int* __restrict__ first_b, int max_labels,
+                                                         int nvb, uint8_t* __restrict__ seg_live) {
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl2_label_body(vb, labels_all, ids_all, B, H, W, chunks, st_f, st_b, max_labels, seg_live);
+    ccl2_label_body(vb, labels_all, t, B, H, W, chunks, st_f, st_b, first_f, first_b, max_labels, seg_live);
     __syncthreads();
   }
 }
@@ -1130,8 +1326,14 @@ size_t ccl_workspace_bytes(int B, int H, int W) {
   // ids + chunk counts + root bitmaps (64 words per chunk; two planes of each for launch_ccl_dual) + the tiles' column masks
   // (two words per 32 x 32 tile; callers size for a pixel count and label any H x W within it: tiles <= hw / 1024 + (H + W) / 32 + 1)
   const size_t tiles_max = hw / (CT * CT) + (hw + 1) / CT + 2;
+  // launch_ccl_dual: no column masks, but a class byte per run (up to one per pixel), the bits / starts / base words of the
+  // page (H * ceil(W / 32) each), the pages' run counts and the start counts of the pages' 128-word segments (it labels the
+  // H x W it was sized for)
+  const size_t nw = (size_t)H * ((W + 31) / 32);
+  const size_t run_tables = (size_t)B * hw + 3 * (size_t)B * nw * sizeof(unsigned) + (size_t)B * sizeof(int) +
+                            (size_t)B * (nw / 128 + 1) * sizeof(int);
   return (size_t)B * hw * sizeof(int) + 2 * (size_t)B * nchunks * sizeof(int) + 2 * (size_t)B * nchunks * 64 * 8 +
-         (size_t)B * tiles_max * 2 * sizeof(unsigned) + 1280;
+         std::max((size_t)B * tiles_max * 2 * sizeof(unsigned), run_tables) + 2560;
 }
 
 void launch_ccl(const uint8_t* img, int B, int H, int W, int thresh, int conn, int* labels, int* n_out, int* stats,
@@ -1171,26 +1373,45 @@ void launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* l
   const int hw = H * W;
   const long long total = (long long)B * hw;
   const int nchunks = (hw + RK_CHUNK - 1) / RK_CHUNK;
-  int* ids = (int*)ws;
-  int* chunk_cnt = (int*)((char*)ws + ((size_t)total * sizeof(int) + 255) / 256 * 256);   // (B, 2, nchunks)
-  unsigned long long* rootmask = (unsigned long long*)((char*)chunk_cnt + (2 * (size_t)B * nchunks * sizeof(int) + 255) / 256 * 256);
-  const int tiles_x = (W + CT - 1) / CT, tiles_y = (H + CT - 1) / CT;
-  hipLaunchKernelGGL(ccl2_local_kernel, dim3(capped(B * tiles_x * tiles_y)), dim3(256), 0, st, img, labels, H, W, tiles_x, tiles_y,
-                     thresh, B * tiles_x * tiles_y);
-  const int nh = (H - 1) / CT, nv = (W - 1) / CT;
-  if (nh > 0) hipLaunchKernelGGL(ccl2_border_h_kernel, dim3((W + 255) / 256, nh, B), dim3(256), 0, st, labels, img, thresh, H, W);
-  if (nv > 0) hipLaunchKernelGGL(ccl2_border_v_kernel, dim3((H + 255) / 256, nv, B), dim3(256), 0, st, labels, img, thresh, H, W);
-  hipLaunchKernelGGL(ccl2_flatten_count_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, labels, img, thresh, hw, nchunks, chunk_cnt,
-                     rootmask, B * nchunks);
+  const int wp = (W + 31) / 32, nw = H * wp;
+  auto after = [](void* p, size_t bytes) { return (void*)((char*)p + (bytes + 255) / 256 * 256); };
+  int* rlabel = (int*)ws;                                                                    // (B, hw): R of a page in use
+  int* chunk_cnt = (int*)after(rlabel, (size_t)total * sizeof(int));                         // (B, 2, nchunks)
+  unsigned long long* rootmask = (unsigned long long*)after(chunk_cnt, 2 * (size_t)B * nchunks * sizeof(int));
+  uint8_t* rcls = (uint8_t*)after(rootmask, 2 * (size_t)B * nchunks * 64 * 8);               // (B, hw)
+  unsigned* bits = (unsigned*)after(rcls, (size_t)total);                                    // (B, H, wp) each
+  unsigned* starts = (unsigned*)after(bits, (size_t)B * nw * sizeof(unsigned));
+  unsigned* base = (unsigned*)after(starts, (size_t)B * nw * sizeof(unsigned));
+  int* rcount = (int*)after(base, (size_t)B * nw * sizeof(unsigned));                        // (B)
+  const int nseg = (nw + PK_SEG - 1) / PK_SEG, ntiles = (nw + SC_TILE - 1) / SC_TILE;
+  int* segsum = (int*)after(rcount, (size_t)B * sizeof(int));                                // (B, nseg)
+  int* rparent = labels;                                                                     // dead before the paint
+  const int aligned4 = (W % 4 == 0 && ((uintptr_t)img & 3) == 0) ? 1 : 0;
+  hipLaunchKernelGGL(ccl2_pack_kernel, dim3(capped(B * nseg)), dim3(256), 0, st, img, bits, starts, segsum, nseg, H, W, wp, thresh,
+                     aligned4, B * nseg);
+  hipLaunchKernelGGL(ccl2_run_scan_kernel, dim3(capped(B * ntiles)), dim3(256), 0, st, starts, segsum, base, rcount, nw, nseg, ntiles,
+                     B * ntiles);
+  const int nbands = (H + RB_ROWS - 1) / RB_ROWS;
+  const int band_grid = std::max(1, std::min(B * nbands, g_tail_max_blocks / (RB_THREADS / 256)));   // the cap counts 256 threads
+  hipLaunchKernelGGL(ccl2_band_kernel, dim3(band_grid), dim3(RB_THREADS), 0, st, bits, starts, base, rcount, rparent, rcls, H, W, wp,
+                     nbands, B * nbands);
+  if (nbands > 1)
+    hipLaunchKernelGGL(ccl2_band_border_kernel, dim3((B * (nbands - 1) * wp + 255) / 256), dim3(256), 0, st, bits, starts, base,
+                       rparent, B, H, W, wp, nbands - 1);
+  hipLaunchKernelGGL(ccl2_flatten_count_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rparent, rcls, rcount, B, hw, nchunks,
+                     chunk_cnt, rootmask, B * nchunks);
   hipLaunchKernelGGL(ccl2_scan_chunks_kernel, dim3(2 * B), dim3(256), 0, st, chunk_cnt, nchunks, n_f, n_b);
-  hipLaunchKernelGGL(ccl2_rank_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rootmask, hw, nchunks, chunk_cnt, ids,
-                     first_f, first_b, max_labels, B * nchunks);
+  hipLaunchKernelGGL(ccl2_rank_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rootmask, rcount, B, hw, nchunks, chunk_cnt, rlabel,
+                     B * nchunks);
+  hipLaunchKernelGGL(ccl2_spread_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rparent, rcount, B, hw, nchunks, rlabel,
+                     B * nchunks);
   const int sgrid = std::max(1, std::min(64, (max_labels + 255) / 256));
   hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(sgrid, B), dim3(256), 0, st, st_f, n_f, max_labels, H, W);
   hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(sgrid, B), dim3(256), 0, st, st_b, n_b, max_labels, H, W);
   const int lchunks = (hw + LB_CHUNK - 1) / LB_CHUNK;
-  hipLaunchKernelGGL(ccl2_label_kernel, dim3(capped(B * lchunks)), dim3(256), 0, st, labels, ids, B, H, W, lchunks, st_f, st_b,
-                     max_labels, B * lchunks, seg_live);
+  const RunTables t{starts, base, rlabel, wp};
+  hipLaunchKernelGGL(ccl2_label_kernel, dim3(capped(B * lchunks)), dim3(256), 0, st, labels, t, B, H, W, lchunks, st_f, st_b, first_f,
+                     first_b, max_labels, B * lchunks, seg_live);
   hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, st_f, n_f, max_labels);
   hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, st_b, n_b, max_labels);
 }
