@@ -1317,9 +1317,9 @@ int ctd_ccl(const uint8_t* img_dev, int32_t B, int32_t H, int32_t W, int32_t thr
   if (!img_dev || !labels_dev || !n_dev || !ws_dev) return fail(CTD_ERR_INVALID, "null pointer");
   if (connectivity != 4 && connectivity != 8) return fail(CTD_ERR_INVALID, "connectivity must be 4 or 8");
   if (B < 1 || H < 1 || W < 1 || (long long)H * W >= (1LL << 30)) return fail(CTD_ERR_INVALID, "bad sizes");
-  if (ws_bytes < ccl_workspace_bytes(B, H, W)) return fail(CTD_ERR_INVALID, "workspace too small");
-  launch_ccl(img_dev, B, H, W, thresh, connectivity, labels_dev, n_dev, stats_dev, max_labels, ws_dev,
-             (hipStream_t)stream);
+  if (launch_ccl(img_dev, B, H, W, thresh, connectivity, labels_dev, n_dev, stats_dev, max_labels, ws_dev, ws_bytes,
+                 (hipStream_t)stream) != hipSuccess)
+    return fail(CTD_ERR_INVALID, "workspace too small");
   HIP_TRY(hipGetLastError());
   return CTD_OK;
 }
@@ -1330,9 +1330,9 @@ int ctd_ccl_dual(const uint8_t* img_dev, int32_t B, int32_t H, int32_t W, int32_
   if (!img_dev || !labels_dev || !n_f_dev || !n_b_dev || !stats_f_dev || !stats_b_dev || !first_f_dev || !first_b_dev || !ws_dev)
     return fail(CTD_ERR_INVALID, "null pointer");
   if (B < 1 || H < 1 || W < 1 || (long long)H * W >= (1LL << 30) || max_labels < 1) return fail(CTD_ERR_INVALID, "bad sizes");
-  if (ws_bytes < ccl_workspace_bytes(B, H, W)) return fail(CTD_ERR_INVALID, "workspace too small");
-  launch_ccl_dual(img_dev, B, H, W, thresh, labels_dev, n_f_dev, n_b_dev, stats_f_dev, stats_b_dev, first_f_dev, first_b_dev,
-                  max_labels, ws_dev, (hipStream_t)stream);
+  if (launch_ccl_dual(img_dev, B, H, W, thresh, labels_dev, n_f_dev, n_b_dev, stats_f_dev, stats_b_dev, first_f_dev, first_b_dev,
+                      max_labels, ws_dev, ws_bytes, (hipStream_t)stream) != hipSuccess)
+    return fail(CTD_ERR_INVALID, "workspace too small");
   HIP_TRY(hipGetLastError());
   return CTD_OK;
 }

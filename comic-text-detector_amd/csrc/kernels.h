@@ -149,19 +149,22 @@ const char* launch_db_up(const void* src, bool f32in, int pitch, int q, int nbr,
 size_t nms_workspace_bytes(int B, int rows);
 void launch_nms(const float* blks, int B, int rows, int no, float conf, float iou, int max_det, int max_nms,
                 float max_wh, float* dets, int* counts, void* ws, hipStream_t st);
+// One labelling engine on row runs serves both launchers.  Its workspace is laid out for the (B, H, W) it was sized for --
+// a size for one shape serves no other, whatever its pixel count -- and both launchers take the size of the workspace
+// they are handed: with less than ccl_workspace_bytes(B, H, W) they return hipErrorInvalidValue and launch nothing.
 size_t ccl_workspace_bytes(int B, int H, int W);
-// invert: foreground = !(img > thresh); first (B,max_labels): linear index of every component's first pixel
-// in raster order (= its union-find root), or null; bg_negative: background pixels of `labels` keep the -1 the union-find
-// left there instead of being rewritten to 0 (callers that only test `label > 0`: 4 B less per background pixel)
-void launch_ccl(const uint8_t* img, int B, int H, int W, int thresh, int conn, int* labels, int* n_out,
-                int* stats, int max_labels, void* ws, hipStream_t st, int invert = 0, int* first = nullptr, int bg_negative = 0);
+// The components of img > thresh, 4- or 8-connected, ids in raster order of first pixels; n_out is exact, stats (rows
+// [x, y, w, h, area]) and first hold the first max_labels.  stats may be null.  first (B,max_labels): linear index of
+// every component's first pixel in raster order, or null; bg_negative: background pixels of `labels` get -1, not 0.
+hipError_t launch_ccl(const uint8_t* img, int B, int H, int W, int thresh, int conn, int* labels, int* n_out, int* stats,
+                      int max_labels, void* ws, size_t ws_bytes, hipStream_t st, int* first = nullptr, int bg_negative = 0);
 // Foreground (img > thresh, 8-connected) and background (4-connected) components in one union-find:
 // labels (B,H,W) signed (+id / -id, per-class raster order), n / stats / first per class, same workspace.
 // seg_live (B, ceil(H*W / 64)) or null: one byte per 64 consecutive linear pixels of a page, 1 where some pixel of the
 // segment has a label other than -1 (the background component that holds the page's first background pixel).
-void launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* labels, int* n_f, int* n_b, int* st_f,
-                     int* st_b, int* first_f, int* first_b, int max_labels, void* ws, hipStream_t st,
-                     uint8_t* seg_live = nullptr);
+hipError_t launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* labels, int* n_f, int* n_b, int* st_f,
+                           int* st_b, int* first_f, int* first_b, int max_labels, void* ws, size_t ws_bytes, hipStream_t st,
+                           uint8_t* seg_live = nullptr);
 
 // ---- kernels_pre.hip ----------------------------------------------------------
 // cv2.resize(INTER_LINEAR) u8 (C = 1 or 3) into the top-left (dH,dW) of a zero-padded canvas

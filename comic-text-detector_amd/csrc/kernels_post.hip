@@ -1,5 +1,6 @@
 // Post-processing kernels: class-aware greedy NMS and connected-component
-// labelling with statistics.  Integer / comparison work, HBM- and latency-bound.
+// labelling with statistics (one union-find engine on row runs behind `launch_ccl`
+// and `launch_ccl_dual`).  Integer / comparison work, HBM- and latency-bound.
 #include <algorithm>
 #include <cstdint>
 
@@ -213,10 +214,12 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_greedy_kernel(Cand* __restric
 
 // ===========================================================================
 // CCL with stats (replaces cv2.connectedComponentsWithStats, reference
-// utils/textmask.py:93,113,138).  Union-find over pixel indices with atomicMin
-// links (root = smallest linear index of the component = its first pixel in
-// raster order), then roots are ranked in raster order so label ids follow the
-// first-pixel order (OpenCV SAUF numbering for 4-connectivity).
+// utils/textmask.py:93,113,138, and the DB stage's two labellings).  ONE engine:
+// a union-find over row runs with atomicMin links (root = the run that holds the
+// component's first pixel in raster order), then the roots of a class are ranked
+// in run order, so label ids follow the first-pixel order (OpenCV SAUF numbering
+// for 4-connectivity).  `launch_ccl_dual` keeps both classes of its answer,
+// `launch_ccl` one.  First the pieces both share with nothing else in between.
 // ===========================================================================
 // (agent scope: every thread that links or flattens a parent array runs on this GPU; the default system scope made each
 // hop a load that bypasses the caches)
@@ -244,12 +247,7 @@ __device__ __forceinline__ void uf_union(int* parent, int a, int b) {
   }
 }
 
-// Phase 1: tile-local labelling in LDS.  Each 32x32 tile is resolved with a
-// union-find over LDS atomics (no HBM atomics, no cross-CU traffic); the result
-// written to HBM is parent[p] = global index of p's tile-local root (the first
-// pixel of its local component in raster order).
-constexpr int CT = 32;  // tile edge
-
+// the same on a table in LDS (a band's runs: no HBM atomics, no cross-CU traffic)
 __device__ __forceinline__ int lds_find(int* lp, int x) {
   int p = __atomic_load_n(lp + x, __ATOMIC_RELAXED);
   while (p != x) {
@@ -271,237 +269,8 @@ __device__ __forceinline__ void lds_union(int* lp, int a, int b) {
   }
 }
 
-constexpr int RK_CHUNK = 4096;  // pixels ranked per block
+constexpr int RK_CHUNK = 4096;  // runs flattened / ranked / spread per block
 constexpr int RK_PER_T = RK_CHUNK / 256;
-
-// Run-based: a row of a tile is 32 pixels = half a wavefront, so the horizontal runs of a row come from
-// one ballot -- every pixel is pre-labelled with the first pixel of its run without any atomic, and only run
-// HEADS take part in the union-find, each with the (few) runs of the row above it overlaps.  The per-pixel
-// version issued up to four LDS union chains per foreground pixel; on page backgrounds and window
-// complements (runs of 32) that was 30x the work (rocprofv3: 0.36 ms per 32 Mpixel launch before).
-template <int CONN>
-__device__ __forceinline__ void ccl_local_body(int vb, const uint8_t* __restrict__ img, int* __restrict__ parent_all,
-                                                        unsigned* __restrict__ colmask, int H, int W, int tiles_x, int tiles_y,
-                                                        int thresh, int invert) {
-  __shared__ int lp[CT * CT];
-  __shared__ unsigned rowmask[CT];
-  int bid = vb;
-  const int tx = bid % tiles_x;
-  bid /= tiles_x;
-  const int ty = bid % tiles_y;
-  const int b = bid / tiles_y;
-  const size_t base = (size_t)b * H * W;
-  const int x0 = tx * CT, y0 = ty * CT;
-  const int lane = threadIdx.x & 63;
-  const int lx = threadIdx.x & 31;
-  // the tile's four rows of this thread first, then the ballots: a ballot consumes its load, and interleaved the four
-  // were four memory round trips in a row (pixels outside the image read the image's first byte and are masked)
-  int pix[CT * CT / 256];
-#pragma unroll
-  for (int k = 0; k < CT * CT / 256; ++k) {
-    const int gx = x0 + lx, gy = y0 + ((threadIdx.x + 256 * k) >> 5);
-    pix[k] = img[base + (gx < W && gy < H ? (size_t)gy * W + gx : (size_t)0)];
-  }
-#pragma unroll
-  for (int k = 0; k < CT * CT / 256; ++k) {
-    const int li = threadIdx.x + 256 * k;
-    const int ly = li >> 5;
-    const int gx = x0 + lx, gy = y0 + ly;
-    const bool fg = gx < W && gy < H && ((pix[k] > thresh) != (invert != 0));
-    const unsigned long long bal = __ballot(fg);
-    const unsigned m = (unsigned)(lane < 32 ? bal : bal >> 32);          // this row's 32 pixels
-    // first pixel of my run: one past the highest clear bit below me
-    const unsigned below = ~m & ((1u << lx) - 1u);
-    const int start = below ? 32 - __clz(below) : 0;
-    lp[li] = fg ? (ly << 5) + start : -1;
-    if (lx == 0) rowmask[ly] = m;
-  }
-  __syncthreads();
-  // the tile's first and last column as bit masks (bit ly = foreground): all the vertical-boundary kernel needs to know
-  // where a link is due -- read from the parent plane, a column is one 64-B line per PIXEL (0.5 GB per 32 pages)
-  if (threadIdx.x < 64) {
-    const unsigned rm = rowmask[threadIdx.x & 31];
-    const unsigned long long bl = __ballot(threadIdx.x < 32 && (rm & 1u)), br = __ballot(threadIdx.x < 32 && (rm >> 31));
-    if (threadIdx.x == 0) {
-      unsigned* cm = colmask + ((size_t)b * tiles_y * tiles_x + (size_t)ty * tiles_x + tx) * 2;
-      cm[0] = (unsigned)bl, cm[1] = (unsigned)br;
-    }
-  }
-#pragma unroll
-  for (int k = 0; k < CT * CT / 256; ++k) {
-    const int li = threadIdx.x + 256 * k;
-    const int ly = li >> 5;
-    if (ly == 0) continue;
-    const unsigned m = rowmask[ly], ma = rowmask[ly - 1];
-    // run heads only -- decided from the row mask: lp[] is already being rewritten by other heads' unions
-    if (!((m >> lx) & 1u) || (lx > 0 && ((m >> (lx - 1)) & 1u))) continue;
-    // my run [lx, end]: the set bits of m from lx up to the next clear bit
-    const unsigned from = m >> lx;
-    const int len = (~from) ? __ffs(~from) - 1 : 32 - lx;
-    unsigned run = (len >= 32 ? 0xffffffffu : ((1u << len) - 1u)) << lx;
-    if (CONN == 8) run |= (run << 1) | (run >> 1);                       // diagonal neighbours in the row above
-    unsigned ov = ma & run;
-    while (ov) {
-      const int bpos = __ffs(ov) - 1;
-      const unsigned belowa = ~ma & ((1u << bpos) - 1u);
-      const int sa = belowa ? 32 - __clz(belowa) : 0;                    // head of that run in the row above
-      lds_union(lp, li, ((ly - 1) << 5) + sa);
-      const unsigned froma = ma >> bpos;                                 // clear the rest of that run
-      const int lena = (~froma) ? __ffs(~froma) - 1 : 32 - bpos;
-      ov &= ~((lena >= 32 ? 0xffffffffu : ((1u << lena) - 1u)) << bpos);
-    }
-  }
-  __syncthreads();
-#pragma unroll
-  for (int k = 0; k < CT * CT / 256; ++k) {
-    const int li = threadIdx.x + 256 * k;
-    const int gx = x0 + lx, gy = y0 + (li >> 5);
-    if (gx >= W || gy >= H) continue;
-    int v = -1;
-    if (lp[li] >= 0) {
-      const int r = lds_find(lp, lp[li]);
-      v = (y0 + (r >> 5)) * W + x0 + (r & 31);
-    }
-    parent_all[base + (size_t)gy * W + gx] = v;
-  }
-}
-// a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
-// waves per SIMD next to the network, not all of them
-template <int CONN>
-__global__ __launch_bounds__(256) void ccl_local_kernel(const uint8_t* __restrict__ img, int* __restrict__ parent_all,
-                                                        unsigned* __restrict__ colmask, int H, int W, int tiles_x, int tiles_y,
-                                                        int thresh, int invert, int nvb) {
-  for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl_local_body<CONN>(vb, img, parent_all, colmask, H, W, tiles_x, tiles_y, thresh, invert);
-    __syncthreads();
-  }
-}
-
-// Phase 2: merge across tile borders with HBM atomics.  Only border pixels take part (~3/32 of the image)
-// and every chain starts at a tile-local root.  Threads are enumerated over the border lines themselves
-// (blockIdx.y = which tile boundary, blockIdx.z = image): a flat grid-stride loop over all pixels spent its
-// time on 64-bit divisions to find the 3 border pixels in 32 (rocprofv3: 0.45-1.0 ms per launch at 32 x 1024^2).
-//   horizontal boundary y = CT*k : pixel (x, y) with the row above: (x, y-1) and, 8-connected, (x-1, y-1), (x+1, y-1)
-//   vertical boundary   x = CT*k : pixel (x, y) with (x-1, y) and, 8-connected, (x-1, y-1); and (x-1, y) with (x, y-1)
-template <int CONN>
-__global__ __launch_bounds__(256) void ccl_border_h_kernel(int* __restrict__ parent_all, int H, int W) {
-  const int x = blockIdx.x * 256 + threadIdx.x;
-  const int y = CT * (blockIdx.y + 1);
-  if (x >= W || y >= H) return;
-  int* parent = parent_all + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;
-  if (parent[p] < 0) return;
-  // Only one link per pair of overlapping runs: horizontally adjacent foreground pixels are already one
-  // set (tile-local labelling, or the vertical-boundary kernel, whose pruning never relies on this one),
-  // so when the left neighbour is foreground it has made -- or inherited -- the links to the row above.
-  const bool q = x > 0 && parent[p - 1] >= 0;
-  const bool up = parent[p - W] >= 0;
-  if (CONN == 4) {
-    if (up && !(q && parent[p - W - 1] >= 0)) uf_union(parent, p, p - W);
-  } else {
-    const bool ur = x + 1 < W && parent[p - W + 1] >= 0;
-    if (q) {
-      if (ur && !up) uf_union(parent, p, p - W + 1);
-    } else if (up) {
-      uf_union(parent, p, p - W);
-    } else {
-      if (x > 0 && parent[p - W - 1] >= 0) uf_union(parent, p, p - W - 1);
-      if (ur) uf_union(parent, p, p - W + 1);
-    }
-  }
-}
-
-template <int CONN>
-__global__ __launch_bounds__(256) void ccl_border_v_kernel(int* __restrict__ parent_all, const unsigned* __restrict__ colmask,
-                                                           int H, int W, int tiles_x, int tiles_y) {
-  const int y = blockIdx.x * 256 + threadIdx.x;
-  const int k = blockIdx.y;                              // boundary between tile columns k and k + 1
-  const int x = CT * (k + 1);
-  if (y >= H || x >= W) return;
-  int* parent = parent_all + (size_t)blockIdx.z * H * W;
-  const int p = y * W + x;
-  // which of the four pixels around (x, y) are foreground: from the column masks the tile-local kernel left (bit = row of
-  // the tile; [0] first column, [1] last column), not from the parent plane
-  const unsigned* cm = colmask + (size_t)blockIdx.z * tiles_y * tiles_x * 2;
-  auto fg = [&](int yy, int tile_x, int side) { return ((cm[((size_t)(yy >> 5) * tiles_x + tile_x) * 2 + side] >> (yy & 31)) & 1u) != 0; };
-  const bool me = fg(y, k + 1, 0), left = fg(y, k, 1);
-  if (!me && !left) return;
-  // Rows y-1 and y of one tile: vertical neighbours are already one set, so the 2x2 block needs a link only
-  // where the row above does not provide the connection.  On a horizontal tile boundary (y % CT == 0) nothing
-  // is assumed about the row above (that is the other kernel's job) and every adjacent pair is linked.
-  const bool ua = y > 0, same_tile = (y % CT) != 0;
-  const bool mu = ua && fg(y - 1, k + 1, 0), lu = ua && fg(y - 1, k, 1);
-  if (!same_tile) {
-    if (me && left) uf_union(parent, p, p - 1);
-    if (CONN == 8) {
-      if (me && lu) uf_union(parent, p, p - W - 1);
-      if (left && mu) uf_union(parent, p - 1, p - W);
-    }
-    return;
-  }
-  if (me && left && !(mu && lu)) uf_union(parent, p, p - 1);
-  if (CONN == 8) {
-    if (me && lu && !left && !mu) uf_union(parent, p, p - W - 1);
-    if (left && mu && !me && !lu) uf_union(parent, p - 1, p - W);
-  }
-}
-
-
-__device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int* total);
-
-// Path flattening fused with pass 1 of the ranking: a block owns one rank chunk, replaces every parent by
-// its root and counts the roots of the chunk (a pixel is a root iff it is its own parent).
-// ... and with the root bitmap of the chunk: bit (p % 64) of word (p / 64) of the image = pixel p is a root.  The ranking
-// kernel numbers the roots from these words (8 B per 64 pixels) instead of reading the parent plane again (256 B).
-__device__ __forceinline__ void ccl_flatten_count_body(int vb, int* __restrict__ parent_all, int hw, int nchunks,
-                                                                int* __restrict__ chunk_cnt, unsigned long long* __restrict__ rootmask) {
-  __shared__ int sh[4];
-  const int b = vb / nchunks, ch = vb % nchunks;
-  int* parent = parent_all + (size_t)b * hw;
-  const int p0 = ch * RK_CHUNK + threadIdx.x;
-  int local = 0;
-  // Four pixels per thread at a time, hop by hop: the parents of all four, then the parents' parents of all four -- after
-  // the tile-local labelling nearly every pixel is a root or points at one, i.e. done after these two loads -- and only
-  // what is left walks its chain alone.  One pixel at a time was a chain of 2-3 dependent loads, 16 times in a row.
-  constexpr int FU = 4;
-  static_assert(RK_PER_T % FU == 0, "whole batches");
-  for (int j0 = 0; j0 < RK_PER_T; j0 += FU) {
-    int v[FU], g[FU];
-#pragma unroll
-    for (int j = 0; j < FU; ++j) {
-      const int p = p0 + 256 * (j0 + j);        // coalesced: consecutive threads, consecutive pixels
-      v[j] = p < hw ? uf_load(parent, p) : -1;
-    }
-#pragma unroll
-    for (int j = 0; j < FU; ++j) g[j] = v[j] >= 0 ? uf_load(parent, v[j]) : -1;
-#pragma unroll
-    for (int j = 0; j < FU; ++j) {
-      const int p = p0 + 256 * (j0 + j);
-      bool root = false;
-      if (v[j] >= 0) {
-        const int r = g[j] == v[j] ? v[j] : uf_find(parent, g[j]);
-        if (r != v[j]) parent[p] = r;           // most pixels already point at their root (tile-local labelling)
-        root = r == p;
-        local += root;
-      }
-      const unsigned long long m = __ballot(root);                 // this wave's 64 consecutive pixels
-      if ((threadIdx.x & 63) == 0) rootmask[((size_t)b * nchunks + ch) * 64 + 4 * (j0 + j) + (threadIdx.x >> 6)] = m;
-    }
-  }
-  int total;
-  block_exclusive_scan(local, sh, &total);
-  if (threadIdx.x == 0) chunk_cnt[vb] = total;
-}
-// a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
-// waves per SIMD next to the network, not all of them
-__global__ __launch_bounds__(256) void ccl_flatten_count_kernel(int* __restrict__ parent_all, int hw, int nchunks,
-                                                                int* __restrict__ chunk_cnt, unsigned long long* __restrict__ rootmask,
-                                                                int nvb) {
-  for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl_flatten_count_body(vb, parent_all, hw, nchunks, chunk_cnt, rootmask);
-    __syncthreads();
-  }
-}
 
 __device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int* total) {
   // 256 threads
@@ -520,72 +289,6 @@ __device__ __forceinline__ int block_exclusive_scan(int v, int* sh, int* total) 
   return base + incl - v;
 }
 
-// pass 3: assign raster-order ids to the roots (pass 1, the per-chunk count, is fused into the flattening).
-__device__ __forceinline__ void ccl_rank_body(int vb, const unsigned long long* __restrict__ rootmask, int hw, int nchunks,
-                                                       const int* __restrict__ chunk_cnt, int* __restrict__ ids_all,
-                                                       int* __restrict__ first, int max_labels) {
-  // A wave owns 1024 consecutive pixels of the chunk, 64 at a time (coalesced); the root masks of the 16
-  // groups stay in scalar registers between the counting and the numbering sweep.
-  static_assert(RK_CHUNK == 4 * 16 * 64, "4 waves x 16 groups x 64 lanes");
-  __shared__ int sh[4];
-  const int b = vb / nchunks, ch = vb % nchunks;
-  const int lane = threadIdx.x & 63, w = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-  const int base = ch * RK_CHUNK + w * 1024 + lane;
-  unsigned long long m[16];
-  int cnt = 0;
-  // the root bitmap the flattening left: this wave's 16 words (pixels beyond the image are no roots there either)
-  const unsigned long long* words = rootmask + ((size_t)b * nchunks + ch) * 64 + w * 16;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    m[j] = words[j];
-    cnt += __popcll(m[j]);
-  }
-  if (lane == 0) sh[w] = cnt;
-  __syncthreads();
-  int id0 = chunk_cnt[vb];   // exclusive offset of the chunk (after ccl_scan_chunks_kernel)
-  for (int i = 0; i < w; ++i) id0 += sh[i];
-  int* ids = ids_all + (size_t)b * hw;
-  const unsigned long long below = lane ? (~0ull >> (64 - lane)) : 0ull;
-#pragma unroll
-  for (int j = 0; j < 16; ++j) {
-    if ((m[j] >> lane) & 1ull) {
-      const int p = base + 64 * j;
-      const int id = id0 + __popcll(m[j] & below) + 1;
-      ids[p] = id;
-      if (first && id <= max_labels) first[(size_t)b * max_labels + id - 1] = p;   // root = first pixel in raster order
-    }
-    id0 += __popcll(m[j]);
-  }
-}
-// a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
-// waves per SIMD next to the network, not all of them
-__global__ __launch_bounds__(256) void ccl_rank_kernel(const unsigned long long* __restrict__ rootmask, int hw, int nchunks,
-                                                       const int* __restrict__ chunk_cnt, int* __restrict__ ids_all,
-                                                       int* __restrict__ first, int max_labels, int nvb) {
-  for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl_rank_body(vb, rootmask, hw, nchunks, chunk_cnt, ids_all, first, max_labels);
-    __syncthreads();
-  }
-}
-
-// pass 2: per image exclusive scan of the chunk counts (one block per image)
-__global__ __launch_bounds__(256) void ccl_scan_chunks_kernel(int* __restrict__ chunk_cnt, int nchunks,
-                                                              int* __restrict__ n_out) {
-  __shared__ int sh[4];
-  int* c = chunk_cnt + (size_t)blockIdx.x * nchunks;
-  int carry = 0;
-  for (int base = 0; base < nchunks; base += 256) {
-    const int i = base + threadIdx.x;
-    const int v = i < nchunks ? c[i] : 0;
-    int total;
-    const int excl = block_exclusive_scan(v, sh, &total);
-    if (i < nchunks) c[i] = carry + excl;
-    carry += total;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) n_out[blockIdx.x] = carry;
-}
-
 // rows of labels that exist (1..n, capped at max_labels) only: n is on the device by now
 __global__ void ccl_stats_init_kernel(int* __restrict__ stats, const int* __restrict__ n_out, int max_labels, int H, int W) {
   const int b = blockIdx.y;
@@ -596,108 +299,8 @@ __global__ void ccl_stats_init_kernel(int* __restrict__ stats, const int* __rest
   }
 }
 
-// Final labels + statistics.  A block owns LB_CHUNK consecutive pixels of one image.  Statistics go
-// through two levels of aggregation before they reach HBM: (1) a wave covers 64 consecutive pixels, each
-// horizontal run of one label is handled by its first lane; (2) the runs of a block are merged per label in
-// a small LDS hash table that is flushed once at the end.  Big components (a page's background, a window's
-// complement) otherwise serialise tens of thousands of atomics on the same five words of `stats`
-// (rocprofv3: 1.2-2.7 ms per launch before the block-level table).
-constexpr int LB_CHUNK = 8192;
-constexpr int LB_SLOTS = 128;
-
-__device__ __forceinline__ void ccl_label_body(int vb, int* __restrict__ labels_all, const int* __restrict__ ids_all,
-                                                        int B, int H, int W, int chunks, int* __restrict__ stats,
-                                                        int max_labels, int bg_negative) {
-  __shared__ int hkey[LB_SLOTS];
-  __shared__ int hst[LB_SLOTS * 5];
-  const int hw = H * W;
-  const int b = vb / chunks, ch = vb % chunks;
-  const int p_begin = ch * LB_CHUNK, p_end = min(hw, p_begin + LB_CHUNK);
-  const size_t base = (size_t)b * hw;
-  if (stats) {
-    for (int s = threadIdx.x; s < LB_SLOTS; s += 256) {
-      hkey[s] = -1;
-      hst[5 * s] = W, hst[5 * s + 1] = H, hst[5 * s + 2] = -1, hst[5 * s + 3] = -1, hst[5 * s + 4] = 0;
-    }
-    __syncthreads();
-  }
-  const int lane = threadIdx.x & 63;
-  // Four 256-pixel steps at a time: their roots, then their ids (a dependent gather), then the statistics step by step.
-  // One step at a time was two memory round trips per step, 32 steps in a row.
-  constexpr int LU = 4;
-  for (int pb = p_begin; pb < p_end; pb += 256 * LU) {
-    int root[LU], idv[LU];
-#pragma unroll
-    for (int u = 0; u < LU; ++u) {
-      const int p = pb + 256 * u + threadIdx.x;
-      root[u] = p < p_end ? labels_all[base + p] : -1;
-    }
-#pragma unroll
-    for (int u = 0; u < LU; ++u) idv[u] = root[u] >= 0 ? ids_all[base + root[u]] : 0;
-#pragma unroll
-    for (int u = 0; u < LU; ++u) {
-      const int p = pb + 256 * u + threadIdx.x;
-      if (p < p_end && !(bg_negative && root[u] < 0)) labels_all[base + p] = idv[u];   // (a background pixel holds -1 already)
-    }
-    if (!stats) continue;
-#pragma unroll
-    for (int u = 0; u < LU; ++u) {
-      const int p0 = pb + 256 * u;
-      if (p0 >= p_end) break;
-      const int p = p0 + threadIdx.x;
-      const bool live = p < p_end;
-      const int id = idv[u];
-      const int x = live ? p % W : 0, y = live ? p / W : 0;
-      const int key = live ? id : -1;                         // dead lanes end a run
-      const int prev = __shfl_up(key, 1);
-      const bool head = lane == 0 || prev != key || x == 0;
-      const unsigned long long heads = __ballot(head);
-      if (head && id > 0 && id <= max_labels) {
-        const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1));
-        const int len = later ? __ffsll((long long)later) : 64 - lane;
-        int slot = -1;
-        unsigned hsh = ((unsigned)id * 2654435761u) >> 25;    // 7 bits
-        for (int probe = 0; probe < 4; ++probe) {
-          const int sidx = (hsh + probe) & (LB_SLOTS - 1);
-          const int old = atomicCAS(&hkey[sidx], -1, id);
-          if (old == -1 || old == id) {
-            slot = sidx;
-            break;
-          }
-        }
-        int* s = slot >= 0 ? hst + 5 * slot : stats + ((size_t)b * max_labels + (id - 1)) * 5;
-        atomicMin(s + 0, x);
-        atomicMin(s + 1, y);
-        atomicMax(s + 2, x + len - 1);
-        atomicMax(s + 3, y);
-        atomicAdd(s + 4, len);
-      }
-    }
-  }
-  if (stats) {
-    __syncthreads();
-    for (int sl = threadIdx.x; sl < LB_SLOTS; sl += 256) {
-      const int id = hkey[sl];
-      if (id <= 0) continue;
-      int* s = stats + ((size_t)b * max_labels + (id - 1)) * 5;
-      atomicMin(s + 0, hst[5 * sl]);
-      atomicMin(s + 1, hst[5 * sl + 1]);
-      atomicMax(s + 2, hst[5 * sl + 2]);
-      atomicMax(s + 3, hst[5 * sl + 3]);
-      atomicAdd(s + 4, hst[5 * sl + 4]);
-    }
-  }
-}
-// a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
-// waves per SIMD next to the network, not all of them
-__global__ __launch_bounds__(256) void ccl_label_kernel(int* __restrict__ labels_all, const int* __restrict__ ids_all,
-                                                        int B, int H, int W, int chunks, int* __restrict__ stats,
-                                                        int max_labels, int bg_negative, int nvb) {
-  for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl_label_body(vb, labels_all, ids_all, B, H, W, chunks, stats, max_labels, bg_negative);
-    __syncthreads();
-  }
-}
+constexpr int LB_CHUNK = 8192;  // pixels painted per block
+constexpr int LB_SLOTS = 128;   // labels a block aggregates in LDS before its statistics reach HBM
 
 __global__ void ccl_stats_final_kernel(int* __restrict__ stats, const int* __restrict__ n_out, int max_labels) {
   const int b = blockIdx.y;
@@ -737,6 +340,14 @@ __global__ void ccl_stats_final_kernel(int* __restrict__ stats, const int* __res
 //   ccl2_flatten_count / ccl2_scan_chunks / ccl2_rank / ccl2_spread         rlabel[run] = 2 * (+-id) + root, over runs
 //   ccl2_label         paints the plane from base / starts / rlabel, once; statistics, first pixels, seg_live
 // rparent[] lives in the label plane (R <= H * W) and is dead before the paint overwrites it.
+//
+// Single-class labelling (`launch_ccl`) is the same engine with half of its answer kept:
+//   conn 8   the foreground class of the page as it is
+//   conn 4   the BACKGROUND class of the flipped page (ccl2_pack sets a bit where (pixel > thresh) != flip): 4-connected,
+//            ranked in raster order of first pixels
+// Everything up to the paint runs on both classes as above; the other class's count goes to a scratch int of the
+// workspace, and ccl2_label<KEEP> paints |id| on the kept class, the caller's background value on the other, and
+// aggregates the kept class only.
 // ======================================================================================================
 // what the paint reads (all of it in the workspace)
 struct RunTables {
@@ -751,12 +362,13 @@ constexpr int RB_CAP = 8192;   // runs a band's LDS table holds (32 KB).  The be
                                // 4 264 runs in a band (mean 3 000-3 500); alternating pixels have 32 768 and go through global memory.
 
 // four pixels per thread, eight lanes per word; a virtual block is a segment of PK_SEG consecutive words of one page and
-// leaves the segment's number of starts for the scan
+// leaves the segment's number of starts for the scan.  flip: the classes change places, a bit is set where
+// (pixel > thresh) != flip (launch_ccl's 4-connected labelling; the dual call passes none)
 constexpr int PK_U = 4;   // steps of 256 groups = 32 words each per virtual block: all their loads first
 constexpr int PK_SEG = 32 * PK_U;
 __device__ __forceinline__ void ccl2_pack_body(int vb, const uint8_t* __restrict__ img, unsigned* __restrict__ bits_all,
                                                         unsigned* __restrict__ starts_all, int* __restrict__ segsum, int nseg, int H,
-                                                        int W, int wp, int thresh, int aligned4) {
+                                                        int W, int wp, int thresh, int flip, int aligned4) {
   __shared__ int segc;
   const int nw = H * wp;
   const size_t hw = (size_t)H * W;
@@ -797,7 +409,7 @@ __device__ __forceinline__ void ccl2_pack_body(int vb, const uint8_t* __restrict
     unsigned nib = 0;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
-      if (x + k < W && (int)((px[u] >> (8 * k)) & 255u) > thresh) nib |= 1u << k;
+      if (x + k < W && ((int)((px[u] >> (8 * k)) & 255u) > thresh) != (flip != 0)) nib |= 1u << k;
     unsigned v = nib << (4 * (threadIdx.x & 7));
     v |= __shfl_xor(v, 1);
     v |= __shfl_xor(v, 2);
@@ -805,7 +417,7 @@ __device__ __forceinline__ void ccl2_pack_body(int vb, const uint8_t* __restrict
     if ((threadIdx.x & 7) == 0 && ws[u] >= 0) {
       const int nbit = min(32, W - x);                                  // x = the word's first pixel here
       const unsigned vmask = nbit >= 32 ? 0xffffffffu : ((1u << nbit) - 1u);
-      const unsigned pb = prev[u] >= 0 ? (prev[u] > thresh ? 1u : 0u) : (~v & 1u);   // x == 0 always starts a run
+      const unsigned pb = prev[u] >= 0 ? ((prev[u] > thresh) != (flip != 0) ? 1u : 0u) : (~v & 1u);   // x == 0 always starts a run
       const unsigned s = (v ^ ((v << 1) | pb)) & vmask;
       bits[ws[u]] = v;
       starts[ws[u]] = s;
@@ -818,9 +430,9 @@ __device__ __forceinline__ void ccl2_pack_body(int vb, const uint8_t* __restrict
 }
 __global__ __launch_bounds__(256) void ccl2_pack_kernel(const uint8_t* __restrict__ img, unsigned* __restrict__ bits_all,
                                                         unsigned* __restrict__ starts_all, int* __restrict__ segsum, int nseg, int H,
-                                                        int W, int wp, int thresh, int aligned4, int nvb) {
+                                                        int W, int wp, int thresh, int flip, int aligned4, int nvb) {
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl2_pack_body(vb, img, bits_all, starts_all, segsum, nseg, H, W, wp, thresh, aligned4);
+    ccl2_pack_body(vb, img, bits_all, starts_all, segsum, nseg, H, W, wp, thresh, flip, aligned4);
     __syncthreads();
   }
 }
@@ -985,8 +597,11 @@ __global__ __launch_bounds__(256) void ccl2_band_border_kernel(const unsigned* _
                    [&](int p, int q) { uf_union(rparent, p, q); });
 }
 
-// Flattening, root count and root bitmaps over the page's R runs (the scheme of ccl_flatten_count_body on the run table:
-// parent = rparent[], a chunk = RK_CHUNK runs; a chunk beyond R counts nothing).
+// Path flattening fused with pass 1 of the ranking, over the page's R runs: a block owns one chunk of RK_CHUNK runs,
+// replaces every rparent[] by its root and counts the roots of the chunk per class (a run is a root iff it is its own
+// parent; a chunk beyond R counts nothing).  It also leaves the chunk's root bitmaps: bit (r % 64) of word (r / 64) = run
+// r is a root of that class.  The ranking numbers the roots from these words (8 B per 64 runs) instead of reading
+// rparent[] again (256 B).
 // chunk_cnt: (B, 2, nchunks) -- class 0 = foreground roots, 1 = background roots
 __device__ __forceinline__ void ccl2_flatten_count_body(int vb, int* __restrict__ parent_all, const uint8_t* __restrict__ rcls_all,
                                                                  const int* __restrict__ rcount, int B, int hw, int nchunks,
@@ -1004,7 +619,10 @@ __device__ __forceinline__ void ccl2_flatten_count_body(int vb, int* __restrict_
   const uint8_t* rcls = rcls_all + (size_t)b * hw;
   const int p0 = ch * RK_CHUNK + threadIdx.x;
   int lf = 0, lb = 0;
-  constexpr int FU = 4;                         // hop by hop over four pixels (see ccl_flatten_count_body)
+  // Four runs per thread at a time, hop by hop: the parents of all four, then the parents' parents of all four -- after
+  // the band kernel nearly every run is a root or points at one, i.e. done after these two loads -- and only what is
+  // left walks its chain alone.  One run at a time was a chain of 2-3 dependent loads, 16 times in a row.
+  constexpr int FU = 4;
   static_assert(RK_PER_T % FU == 0, "whole batches");
   for (int j0 = 0; j0 < RK_PER_T; j0 += FU) {
     int v[FU], g[FU], px[FU];
@@ -1031,7 +649,7 @@ __device__ __forceinline__ void ccl2_flatten_count_body(int vb, int* __restrict_
           if (px[j]) ++lf, rf = true; else ++lb, rb = true;
         }
       }
-      // root bitmaps per class (see ccl_flatten_count_body): (B, 2, nchunks, 64) words
+      // root bitmaps per class, from this wave's 64 consecutive runs: (B, 2, nchunks, 64) words
       const unsigned long long mf = __ballot(rf), mb = __ballot(rb);
       if ((threadIdx.x & 63) == 0) {
         const size_t wi = (size_t)ch * 64 + 4 * (j0 + j) + (threadIdx.x >> 6);
@@ -1079,7 +697,9 @@ __global__ __launch_bounds__(256) void ccl2_scan_chunks_kernel(int* __restrict__
 }
 
 // rlabel of the root runs: 2 * id + 1, id = +rank for a foreground root, -rank for a background root (ranks per class, in run
-// order = raster order of the components' first pixels); the low bit says "root" to the paint
+// order = raster order of the components' first pixels); the low bit says "root" to the paint.  A wave owns 1024
+// consecutive runs of the chunk, 64 at a time; the root masks of its 16 groups stay in registers between the counting and
+// the numbering sweep.
 __device__ __forceinline__ void ccl2_rank_body(int vb, const unsigned long long* __restrict__ rootmask, const int* __restrict__ rcount,
                                                         int B, int hw, int nchunks, const int* __restrict__ chunk_cnt,
                                                         int* __restrict__ ids_all) {
@@ -1161,16 +781,26 @@ __global__ __launch_bounds__(256) void ccl2_spread_kernel(const int* __restrict_
   }
 }
 
-// The paint: signed final labels + the statistics of both classes (aggregation as in ccl_label_kernel).  A pixel's label is
-// its run's: run = base[word] + popcount(starts[word] up to its bit) - 1, label = rlabel[run] >> 1.  The plane is written once
+// The paint: final labels + statistics.  A block owns LB_CHUNK consecutive pixels of one page.  A pixel's label is its
+// run's: run = base[word] + popcount(starts[word] up to its bit) - 1, label = rlabel[run] >> 1.  The plane is written once
 // and never read.  The pixel that starts a root run (rlabel[run] & 1) is its component's first pixel in raster order: it
 // writes first_*.
+// Statistics go through two levels of aggregation before they reach HBM: (1) a wave covers 64 consecutive pixels, each
+// horizontal stretch of one label is handled by its first lane; (2) the stretches of a block are merged per label in a
+// small LDS hash table that is flushed once at the end.  Big components (a page's background, a window's complement)
+// otherwise serialise tens of thousands of atomics on the same five words of `stats` (rocprofv3: 1.2-2.7 ms per launch
+// before the block-level table).
+// KEEP 0 (launch_ccl_dual): signed labels, the tables of both classes.  KEEP +1 / -1 (launch_ccl): the foreground /
+// background class alone -- its pixels get |id|, the other class's pixels get `other` (0, or the -1 of bg_negative) and
+// take no part in anything below; st_f / first_f are the kept class's tables and may be null, st_b / first_b / seg_live
+// are not used.
 // seg_live (null: not wanted): a wave's 64 pixels are one 64-aligned segment of the page's linear index (chunks and steps
 // are multiples of 256), and the wave has their labels in registers: lane 0 notes whether any differs from -1.
+template <int KEEP>
 __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels_all, const RunTables t, int B, int H,
                                                          int W, int chunks, int* __restrict__ st_f, int* __restrict__ st_b,
                                                          int* __restrict__ first_f, int* __restrict__ first_b, int max_labels,
-                                                         uint8_t* __restrict__ seg_live) {
+                                                         uint8_t* __restrict__ seg_live, int other) {
   constexpr int EMPTY = (int)0x80000000;
   __shared__ int hkey[LB_SLOTS];
   __shared__ int hst[LB_SLOTS * 5];
@@ -1188,7 +818,7 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
   __syncthreads();
   const int lane = threadIdx.x & 63;
   auto row_of = [&](int id) { return (id > 0 ? st_f : st_b) + ((size_t)b * max_labels + ((id > 0 ? id : -id) - 1)) * 5; };
-  // eight steps' words, then their runs' labels (see ccl_label_body): two memory round trips per 2048 pixels, and the
+  // eight steps' words, then their runs' labels (a dependent gather): two memory round trips per 2048 pixels, and the
   // capped grid leaves a block little else to hide them behind
   constexpr int LU = 8;
   static_assert(LB_CHUNK % (256 * LU) == 0, "whole batches");
@@ -1214,21 +844,24 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
     for (int u = 0; u < LU; ++u) {
       sw[u] &= (unsigned)idv[u];                              // ... a root run: the component's first pixel
       idv[u] >>= 1;
+      if (KEEP) idv[u] = (KEEP > 0 ? idv[u] > 0 : idv[u] < 0) ? (KEEP > 0 ? idv[u] : -idv[u]) : 0;   // the other class: 0
     }
 #pragma unroll
     for (int u = 0; u < LU; ++u) {
       const int p = pb + 256 * u + threadIdx.x;
-      if (p < p_end) labels_all[base + p] = idv[u];
+      if (p < p_end) labels_all[base + p] = (KEEP && !idv[u]) ? other : idv[u];
     }
+    if (KEEP && !st_f && !first_f) continue;
 #pragma unroll
     for (int u = 0; u < LU; ++u) {
       const int p0 = pb + 256 * u;
       if (p0 >= p_end) break;
       const int p = p0 + threadIdx.x;
       const bool live = p < p_end;
-      const int id = idv[u];                                  // 0 = dead lane (every pixel has a class, so no real id is 0)
+      // 0 = dead lane, or (KEEP) a pixel of the other class, set to 0 above: every pixel has a class, so no real id is 0
+      const int id = idv[u];
       const int x = live ? p % W : 0, y = live ? p / W : 0;
-      if (seg_live) {
+      if (!KEEP && seg_live) {
         const unsigned long long other = __ballot(live && id != -1);
         const int q0 = p0 + ((int)threadIdx.x & ~63);
         if (lane == 0 && q0 < p_end) seg_live[(size_t)b * ((hw + 63) >> 6) + (q0 >> 6)] = other ? 1 : 0;
@@ -1237,8 +870,9 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
       const bool head = lane == 0 || prev != id || x == 0;
       const unsigned long long heads = __ballot(head);
       const int mag = id > 0 ? id : -id;
-      if (sw[u] && mag <= max_labels) (id > 0 ? first_f : first_b)[(size_t)b * max_labels + mag - 1] = p;
-      if (head && id != 0 && mag <= max_labels) {
+      if (sw[u] && (!KEEP || (id != 0 && first_f)) && mag <= max_labels)
+        (id > 0 ? first_f : first_b)[(size_t)b * max_labels + mag - 1] = p;
+      if (head && id != 0 && mag <= max_labels && (!KEEP || st_f)) {
         const unsigned long long later = lane == 63 ? 0ull : (heads >> (lane + 1));
         const int len = later ? __ffsll((long long)later) : 64 - lane;
         int slot = -1;
@@ -1274,12 +908,13 @@ __device__ __forceinline__ void ccl2_label_body(int vb, int* __restrict__ labels
 }
 // a block walks several tiles / chunks: the launcher caps the grid (tail_max_blocks) so that these kernels hold a few
 // waves per SIMD next to the network, not all of them
+template <int KEEP>
 __global__ __launch_bounds__(256) void ccl2_label_kernel(int* __restrict__ labels_all, const RunTables t, int B, int H,
                                                          int W, int chunks, int* __restrict__ st_f, int* __restrict__ st_b,
                                                          int* __restrict__ first_f, int* __restrict__ first_b, int max_labels,
-                                                         int nvb, uint8_t* __restrict__ seg_live) {
+                                                         int nvb, uint8_t* __restrict__ seg_live, int other) {
   for (int vb = blockIdx.x; vb < nvb; vb += gridDim.x) {
-    ccl2_label_body(vb, labels_all, t, B, H, W, chunks, st_f, st_b, first_f, first_b, max_labels, seg_live);
+    ccl2_label_body<KEEP>(vb, labels_all, t, B, H, W, chunks, st_f, st_b, first_f, first_b, max_labels, seg_live, other);
     __syncthreads();
   }
 }
@@ -1293,15 +928,6 @@ inline int grid_for(long long total, int block = 256) {
   if (g > (long long)g_tail_max_blocks) g = g_tail_max_blocks;
   if (g < 1) g = 1;
   return (int)g;
-}
-
-template <int CONN>
-void launch_border(int* labels, const unsigned* colmask, int B, int H, int W, hipStream_t st) {
-  const int nh = (H - 1) / CT, nv = (W - 1) / CT;      // boundaries strictly inside the image
-  if (nh > 0) hipLaunchKernelGGL((ccl_border_h_kernel<CONN>), dim3((W + 255) / 256, nh, B), dim3(256), 0, st, labels, H, W);
-  if (nv > 0)
-    hipLaunchKernelGGL((ccl_border_v_kernel<CONN>), dim3((H + 255) / 256, nv, B), dim3(256), 0, st, labels, colmask, H, W,
-                       (W + CT - 1) / CT, (H + CT - 1) / CT);
 }
 
 }  // namespace
@@ -1320,98 +946,125 @@ void launch_nms(const float* blks, int B, int rows, int no, float conf, float io
                      dets, counts);
 }
 
-size_t ccl_workspace_bytes(int B, int H, int W) {
-  const size_t hw = (size_t)H * W;
-  const size_t nchunks = (hw + RK_CHUNK - 1) / RK_CHUNK;
-  // ids + chunk counts + root bitmaps (64 words per chunk; two planes of each for launch_ccl_dual) + the tiles' column masks
-  // (two words per 32 x 32 tile; callers size for a pixel count and label any H x W within it: tiles <= hw / 1024 + (H + W) / 32 + 1)
-  const size_t tiles_max = hw / (CT * CT) + (hw + 1) / CT + 2;
-  // launch_ccl_dual: no column masks, but a class byte per run (up to one per pixel), the bits / starts / base words of the
-  // page (H * ceil(W / 32) each), the pages' run counts and the start counts of the pages' 128-word segments (it labels the
-  // H x W it was sized for)
-  const size_t nw = (size_t)H * ((W + 31) / 32);
-  const size_t run_tables = (size_t)B * hw + 3 * (size_t)B * nw * sizeof(unsigned) + (size_t)B * sizeof(int) +
-                            (size_t)B * (nw / 128 + 1) * sizeof(int);
-  return (size_t)B * hw * sizeof(int) + 2 * (size_t)B * nchunks * sizeof(int) + 2 * (size_t)B * nchunks * 64 * 8 +
-         std::max((size_t)B * tiles_max * 2 * sizeof(unsigned), run_tables) + 2560;
+namespace {
+
+// The labelling's workspace, sub-buffer by sub-buffer in the order they are carved; each starts a multiple of 256 bytes
+// after `ws`.  With hw = H * W, nchunks = ceil(hw / RK_CHUNK), wp = ceil(W / 32), nw = H * wp, nseg = ceil(nw / PK_SEG):
+//   rlabel     (B, hw) int                 a run's 2 * (+-id) + root bit; the first R of a page in use
+//   chunk_cnt  (B, 2, nchunks) int         roots per chunk and class, then their exclusive scan
+//   rootmask   (B, 2, nchunks, 64) u64     root bitmaps per chunk and class
+//   rcls       (B, hw) u8                  a run's class
+//   bits, starts, base   (B, nw) u32 each  the page as words (the header of the engine above)
+//   rcount     (B) int                     runs of a page
+//   segsum     (B, nseg) int               starts per segment of PK_SEG words
+//   n_other    (B) int                     launch_ccl: the count of the class it does not keep
+// The tables are laid out for the H x W they were sized for: a workspace for one shape serves no other, whatever its
+// pixel count.  ccl_workspace_bytes is where this carve ends, so the two cannot disagree.
+struct CclWs {
+  int* rlabel;
+  int* chunk_cnt;
+  unsigned long long* rootmask;
+  uint8_t* rcls;
+  unsigned *bits, *starts, *base;
+  int *rcount, *segsum, *n_other;
+  size_t bytes;
+};
+CclWs ccl_carve(void* ws, int B, int H, int W) {
+  const size_t hw = (size_t)H * W, nchunks = (hw + RK_CHUNK - 1) / RK_CHUNK;
+  const size_t nw = (size_t)H * ((W + 31) / 32), nseg = (nw + PK_SEG - 1) / PK_SEG;
+  size_t off = 0;
+  auto take = [&](size_t bytes) {
+    void* p = (void*)((uintptr_t)ws + off);
+    off += (bytes + 255) / 256 * 256;
+    return p;
+  };
+  CclWs w;
+  w.rlabel = (int*)take(B * hw * sizeof(int));
+  w.chunk_cnt = (int*)take(2 * B * nchunks * sizeof(int));
+  w.rootmask = (unsigned long long*)take(2 * B * nchunks * 64 * 8);
+  w.rcls = (uint8_t*)take(B * hw);
+  w.bits = (unsigned*)take(B * nw * sizeof(unsigned));
+  w.starts = (unsigned*)take(B * nw * sizeof(unsigned));
+  w.base = (unsigned*)take(B * nw * sizeof(unsigned));
+  w.rcount = (int*)take(B * sizeof(int));
+  w.segsum = (int*)take(B * nseg * sizeof(int));
+  w.n_other = (int*)take(B * sizeof(int));
+  w.bytes = off;
+  return w;
 }
 
-void launch_ccl(const uint8_t* img, int B, int H, int W, int thresh, int conn, int* labels, int* n_out, int* stats,
-                int max_labels, void* ws, hipStream_t st, int invert, int* first, int bg_negative) {
+// The engine.  keep 0: both classes (launch_ccl_dual).  keep +1 / -1: the foreground / background class alone; the other
+// class's n_*, st_*, first_* are null and `other` is what its pixels get in the plane.  Refuses, launching nothing, a
+// workspace smaller than ccl_workspace_bytes(B, H, W).
+hipError_t ccl_on_runs(const uint8_t* img, int B, int H, int W, int thresh, int flip, int keep, int other, int* labels, int* n_f,
+                       int* n_b, int* st_f, int* st_b, int* first_f, int* first_b, int max_labels, void* ws, size_t ws_bytes,
+                       hipStream_t st, uint8_t* seg_live) {
+  const CclWs w = ccl_carve(ws, B, H, W);
+  if (ws_bytes < w.bytes) return hipErrorInvalidValue;
   const int hw = H * W;
-  const long long total = (long long)B * hw;
-  const int nchunks = (hw + RK_CHUNK - 1) / RK_CHUNK;
-  int* ids = (int*)ws;
-  int* chunk_cnt = (int*)((char*)ws + ((size_t)total * sizeof(int) + 255) / 256 * 256);
-  unsigned long long* rootmask = (unsigned long long*)((char*)chunk_cnt + ((size_t)B * nchunks * sizeof(int) + 255) / 256 * 256);
-  unsigned* colmask = (unsigned*)((char*)rootmask + ((size_t)B * nchunks * 64 * 8 + 255) / 256 * 256);
-  const int tiles_x = (W + CT - 1) / CT, tiles_y = (H + CT - 1) / CT;
-  if (conn == 8) {
-    hipLaunchKernelGGL((ccl_local_kernel<8>), dim3(capped(B * tiles_x * tiles_y)), dim3(256), 0, st, img, labels, colmask, H, W,
-                       tiles_x, tiles_y, thresh, invert, B * tiles_x * tiles_y);
-    launch_border<8>(labels, colmask, B, H, W, st);
-  } else {
-    hipLaunchKernelGGL((ccl_local_kernel<4>), dim3(capped(B * tiles_x * tiles_y)), dim3(256), 0, st, img, labels, colmask, H, W,
-                       tiles_x, tiles_y, thresh, invert, B * tiles_x * tiles_y);
-    launch_border<4>(labels, colmask, B, H, W, st);
-  }
-  hipLaunchKernelGGL(ccl_flatten_count_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, labels, hw, nchunks, chunk_cnt, rootmask,
-                     B * nchunks);
-  hipLaunchKernelGGL(ccl_scan_chunks_kernel, dim3(B), dim3(256), 0, st, chunk_cnt, nchunks, n_out);
-  hipLaunchKernelGGL(ccl_rank_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rootmask, hw, nchunks, chunk_cnt, ids, first,
-                     max_labels, B * nchunks);
-  const int sgrid = std::max(1, std::min(64, (max_labels + 255) / 256));
-  if (stats) hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(sgrid, B), dim3(256), 0, st, stats, n_out, max_labels, H, W);
-  const int lchunks = (hw + LB_CHUNK - 1) / LB_CHUNK;
-  hipLaunchKernelGGL(ccl_label_kernel, dim3(capped(B * lchunks)), dim3(256), 0, st, labels, ids, B, H, W, lchunks, stats, max_labels,
-                     bg_negative, B * lchunks);
-  if (stats) hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, stats, n_out, max_labels);
-}
-
-void launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* labels, int* n_f, int* n_b, int* st_f,
-                     int* st_b, int* first_f, int* first_b, int max_labels, void* ws, hipStream_t st, uint8_t* seg_live) {
-  const int hw = H * W;
-  const long long total = (long long)B * hw;
   const int nchunks = (hw + RK_CHUNK - 1) / RK_CHUNK;
   const int wp = (W + 31) / 32, nw = H * wp;
-  auto after = [](void* p, size_t bytes) { return (void*)((char*)p + (bytes + 255) / 256 * 256); };
-  int* rlabel = (int*)ws;                                                                    // (B, hw): R of a page in use
-  int* chunk_cnt = (int*)after(rlabel, (size_t)total * sizeof(int));                         // (B, 2, nchunks)
-  unsigned long long* rootmask = (unsigned long long*)after(chunk_cnt, 2 * (size_t)B * nchunks * sizeof(int));
-  uint8_t* rcls = (uint8_t*)after(rootmask, 2 * (size_t)B * nchunks * 64 * 8);               // (B, hw)
-  unsigned* bits = (unsigned*)after(rcls, (size_t)total);                                    // (B, H, wp) each
-  unsigned* starts = (unsigned*)after(bits, (size_t)B * nw * sizeof(unsigned));
-  unsigned* base = (unsigned*)after(starts, (size_t)B * nw * sizeof(unsigned));
-  int* rcount = (int*)after(base, (size_t)B * nw * sizeof(unsigned));                        // (B)
   const int nseg = (nw + PK_SEG - 1) / PK_SEG, ntiles = (nw + SC_TILE - 1) / SC_TILE;
-  int* segsum = (int*)after(rcount, (size_t)B * sizeof(int));                                // (B, nseg)
+  if (!n_f) n_f = w.n_other;
+  if (!n_b) n_b = w.n_other;
   int* rparent = labels;                                                                     // dead before the paint
   const int aligned4 = (W % 4 == 0 && ((uintptr_t)img & 3) == 0) ? 1 : 0;
-  hipLaunchKernelGGL(ccl2_pack_kernel, dim3(capped(B * nseg)), dim3(256), 0, st, img, bits, starts, segsum, nseg, H, W, wp, thresh,
-                     aligned4, B * nseg);
-  hipLaunchKernelGGL(ccl2_run_scan_kernel, dim3(capped(B * ntiles)), dim3(256), 0, st, starts, segsum, base, rcount, nw, nseg, ntiles,
-                     B * ntiles);
+  hipLaunchKernelGGL(ccl2_pack_kernel, dim3(capped(B * nseg)), dim3(256), 0, st, img, w.bits, w.starts, w.segsum, nseg, H, W, wp,
+                     thresh, flip, aligned4, B * nseg);
+  hipLaunchKernelGGL(ccl2_run_scan_kernel, dim3(capped(B * ntiles)), dim3(256), 0, st, w.starts, w.segsum, w.base, w.rcount, nw, nseg,
+                     ntiles, B * ntiles);
   const int nbands = (H + RB_ROWS - 1) / RB_ROWS;
   const int band_grid = std::max(1, std::min(B * nbands, g_tail_max_blocks / (RB_THREADS / 256)));   // the cap counts 256 threads
-  hipLaunchKernelGGL(ccl2_band_kernel, dim3(band_grid), dim3(RB_THREADS), 0, st, bits, starts, base, rcount, rparent, rcls, H, W, wp,
-                     nbands, B * nbands);
+  hipLaunchKernelGGL(ccl2_band_kernel, dim3(band_grid), dim3(RB_THREADS), 0, st, w.bits, w.starts, w.base, w.rcount, rparent, w.rcls, H,
+                     W, wp, nbands, B * nbands);
   if (nbands > 1)
-    hipLaunchKernelGGL(ccl2_band_border_kernel, dim3((B * (nbands - 1) * wp + 255) / 256), dim3(256), 0, st, bits, starts, base,
+    hipLaunchKernelGGL(ccl2_band_border_kernel, dim3((B * (nbands - 1) * wp + 255) / 256), dim3(256), 0, st, w.bits, w.starts, w.base,
                        rparent, B, H, W, wp, nbands - 1);
-  hipLaunchKernelGGL(ccl2_flatten_count_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rparent, rcls, rcount, B, hw, nchunks,
-                     chunk_cnt, rootmask, B * nchunks);
-  hipLaunchKernelGGL(ccl2_scan_chunks_kernel, dim3(2 * B), dim3(256), 0, st, chunk_cnt, nchunks, n_f, n_b);
-  hipLaunchKernelGGL(ccl2_rank_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rootmask, rcount, B, hw, nchunks, chunk_cnt, rlabel,
-                     B * nchunks);
-  hipLaunchKernelGGL(ccl2_spread_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rparent, rcount, B, hw, nchunks, rlabel,
+  hipLaunchKernelGGL(ccl2_flatten_count_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rparent, w.rcls, w.rcount, B, hw, nchunks,
+                     w.chunk_cnt, w.rootmask, B * nchunks);
+  hipLaunchKernelGGL(ccl2_scan_chunks_kernel, dim3(2 * B), dim3(256), 0, st, w.chunk_cnt, nchunks, n_f, n_b);
+  hipLaunchKernelGGL(ccl2_rank_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, w.rootmask, w.rcount, B, hw, nchunks, w.chunk_cnt,
+                     w.rlabel, B * nchunks);
+  hipLaunchKernelGGL(ccl2_spread_kernel, dim3(capped(B * nchunks)), dim3(256), 0, st, rparent, w.rcount, B, hw, nchunks, w.rlabel,
                      B * nchunks);
   const int sgrid = std::max(1, std::min(64, (max_labels + 255) / 256));
-  hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(sgrid, B), dim3(256), 0, st, st_f, n_f, max_labels, H, W);
-  hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(sgrid, B), dim3(256), 0, st, st_b, n_b, max_labels, H, W);
+  if (st_f) hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(sgrid, B), dim3(256), 0, st, st_f, n_f, max_labels, H, W);
+  if (st_b) hipLaunchKernelGGL(ccl_stats_init_kernel, dim3(sgrid, B), dim3(256), 0, st, st_b, n_b, max_labels, H, W);
   const int lchunks = (hw + LB_CHUNK - 1) / LB_CHUNK;
-  const RunTables t{starts, base, rlabel, wp};
-  hipLaunchKernelGGL(ccl2_label_kernel, dim3(capped(B * lchunks)), dim3(256), 0, st, labels, t, B, H, W, lchunks, st_f, st_b, first_f,
-                     first_b, max_labels, B * lchunks, seg_live);
-  hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, st_f, n_f, max_labels);
-  hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, st_b, n_b, max_labels);
+  const RunTables t{w.starts, w.base, w.rlabel, wp};
+  const dim3 lgrid(capped(B * lchunks));
+  if (keep == 0)
+    hipLaunchKernelGGL((ccl2_label_kernel<0>), lgrid, dim3(256), 0, st, labels, t, B, H, W, lchunks, st_f, st_b, first_f, first_b,
+                       max_labels, B * lchunks, seg_live, 0);
+  else if (keep > 0)
+    hipLaunchKernelGGL((ccl2_label_kernel<1>), lgrid, dim3(256), 0, st, labels, t, B, H, W, lchunks, st_f, nullptr, first_f, nullptr,
+                       max_labels, B * lchunks, nullptr, other);
+  else
+    hipLaunchKernelGGL((ccl2_label_kernel<-1>), lgrid, dim3(256), 0, st, labels, t, B, H, W, lchunks, st_b, nullptr, first_b, nullptr,
+                       max_labels, B * lchunks, nullptr, other);
+  if (st_f) hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, st_f, n_f, max_labels);
+  if (st_b) hipLaunchKernelGGL(ccl_stats_final_kernel, dim3(sgrid, B), dim3(256), 0, st, st_b, n_b, max_labels);
+  return hipSuccess;
+}
+
+}  // namespace
+
+size_t ccl_workspace_bytes(int B, int H, int W) { return ccl_carve(nullptr, B, H, W).bytes; }
+
+hipError_t launch_ccl(const uint8_t* img, int B, int H, int W, int thresh, int conn, int* labels, int* n_out, int* stats,
+                      int max_labels, void* ws, size_t ws_bytes, hipStream_t st, int* first, int bg_negative) {
+  const int other = bg_negative ? -1 : 0;
+  if (conn == 8)   // the foreground half of the dual labelling
+    return ccl_on_runs(img, B, H, W, thresh, 0, +1, other, labels, n_out, nullptr, stats, nullptr, first, nullptr, max_labels, ws,
+                       ws_bytes, st, nullptr);
+  // conn 4: the background half of the dual labelling of the flipped page
+  return ccl_on_runs(img, B, H, W, thresh, 1, -1, other, labels, nullptr, n_out, nullptr, stats, nullptr, first, max_labels, ws,
+                     ws_bytes, st, nullptr);
+}
+
+hipError_t launch_ccl_dual(const uint8_t* img, int B, int H, int W, int thresh, int* labels, int* n_f, int* n_b, int* st_f,
+                           int* st_b, int* first_f, int* first_b, int max_labels, void* ws, size_t ws_bytes, hipStream_t st,
+                           uint8_t* seg_live) {
+  return ccl_on_runs(img, B, H, W, thresh, 0, 0, 0, labels, n_f, n_b, st_f, st_b, first_f, first_b, max_labels, ws, ws_bytes, st,
+                     seg_live);
 }

@@ -1,7 +1,7 @@
 // Device kernels of the detector tail (reference inference.py:148-178 after the network):
 //
-//  * DB text-line stage (reference utils/db_utils.py:123-211): after the two labelling passes
-//    (`launch_ccl`: 8-connected foreground, 4-connected background) the per-contour quantities the
+//  * DB text-line stage (reference utils/db_utils.py:123-211): after the two labellings
+//    (`launch_ccl_dual`: 8-connected foreground, 4-connected background, one signed plane) the per-contour quantities the
 //    host geometry needs are compacted here, so no label image or probability map leaves the GPU:
 //      - containment links (which hole a component sits in, which component rings a hole),
 //      - sum of the probability map per component / per hole / per hole-border ring,
@@ -9,7 +9,8 @@
 //        pixel set is the hull of its row extremes.
 //  * mask refinement (reference utils/textmask.py:29-131): batched per-window kernels;
 //    every text-block window of a page batch is one entry of a window table, candidate masks and
-//    merged masks live as bands of packed canvases that `launch_ccl` labels in one launch.
+//    merged masks live as bands of packed canvases that `launch_ccl` (one class of the same labelling on row
+//    runs, kernels_post.hip) labels in one call.
 //
 // Integer / comparison work on u8 and i32 pixels: HBM- and latency-bound, no MFMA.
 #include <hip/amd_detail/amd_hip_unsafe_atomics.h>

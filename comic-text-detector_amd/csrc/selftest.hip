@@ -537,16 +537,17 @@ static void run_stem2_case(const char* name, int B, int H, int W, int in_fmt, in
       }
     uint8_t* dBm = dev_alloc<uint8_t>(bm.size());
     CK(hipMemcpy(dBm, bm.data(), bm.size(), hipMemcpyHostToDevice));
+    const size_t ccl_ws_bytes = ccl_workspace_bytes(cB, cH, cW);
     int* dLab[3]; int* dCnt[3]; void* dWs[3];               // one set per stream: concurrent labellings must not share a union-find
     for (int q = 0; q < 3; ++q) {
       dLab[q] = dev_alloc<int>((size_t)cB * cH * cW);
       dCnt[q] = dev_alloc<int>((size_t)cB * 2 + (size_t)cB * cL * 12 + 64);
-      CK(hipMalloc(&dWs[q], ccl_workspace_bytes(cB, cH, cW)));
+      CK(hipMalloc(&dWs[q], ccl_ws_bytes));
     }
     auto ccl_dual = [&](hipStream_t st, int q) {
       int* n_f = dCnt[q]; int* n_b = n_f + cB; int* st_f = n_f + 2 * cB; int* st_b = st_f + (size_t)cB * cL * 5;
       int* first_f = st_b + (size_t)cB * cL * 5; int* first_b = first_f + (size_t)cB * cL;
-      launch_ccl_dual(dBm, cB, cH, cW, 127, dLab[q], n_f, n_b, st_f, st_b, first_f, first_b, cL, dWs[q], st);
+      CK(launch_ccl_dual(dBm, cB, cH, cW, 127, dLab[q], n_f, n_b, st_f, st_b, first_f, first_b, cL, dWs[q], ccl_ws_bytes, st));
     };
     struct D { const char* name; int kind; };
     const D ds[] = {{"alone", -1}, {"valu, no LDS, 8 waves/SIMD", 0}, {"streaming copy 128 MB", 1}, {"contended atomics (64 words)", 2},

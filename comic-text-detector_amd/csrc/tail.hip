@@ -401,7 +401,10 @@ int refine_canvas(ctd_tail* t, const TWin* hw, const std::vector<TBand>& bands, 
   GET(t->d_canvas, cpx, uint8_t, canvas);
   GET(t->d_clab, cpx * 4, int, clab);
   GET(t->d_cstats, (size_t)cap1 * 5 * 4, int, cstats);
-  GET(t->d_ccl_ws, ccl_workspace_bytes(1, std::max(pc.H, pm.H), std::max(pc.W, pm.W)), uint8_t, ws);
+  // one workspace for both canvases: the formula grows with H and with W, so the larger of each covers either shape.
+  // The launchers get the size asked for here, not the buffer's capacity, and refuse (T_TRY) when it falls short.
+  const size_t ws_bytes = ccl_workspace_bytes(1, std::max(pc.H, pm.H), std::max(pc.W, pm.W));
+  GET(t->d_ccl_ws, ws_bytes, uint8_t, ws);
   GET(t->d_cnt, ((size_t)cap1 + 1) * 8, unsigned, counters);
   Batch bt(st);
   T_TRY(bt.h2d(dw, cw, sizeof(TWin) * n));
@@ -420,7 +423,7 @@ int refine_canvas(ctd_tail* t, const TWin* hw, const std::vector<TBand>& bands, 
   GpuChain chain(st, t->device, g_tail_chain >= 2);
   T_TRY(chain.begin());
   launch_tw_render(dw, db, nbands, max_pix, canvas, pc.W, st);
-  launch_ccl(canvas, 1, pc.H, pc.W, 0, 8, clab, n_dev, cstats, cap1, ws, st, 0, nullptr, 1);   // the window kernels test `label > 0`
+  T_TRY(launch_ccl(canvas, 1, pc.H, pc.W, 0, 8, clab, n_dev, cstats, cap1, ws, ws_bytes, st, nullptr, 1));   // the window kernels test `label > 0`
   launch_label_counters_zero(counters, n_dev, cap1, st);
   if (fused) {
     launch_tw_accept_all(dw, db, n, clab, pc.W, cstats, cap1, 3, merged_a, pm.W, counters, st);
@@ -433,7 +436,7 @@ int refine_canvas(ctd_tail* t, const TWin* hw, const std::vector<TBand>& bands, 
   GET(t->d_mlab, mpx * 4, int, mlab);
   GET(t->d_mstats, (size_t)cap2 * 6 * 4, int, mstats);
   int* mfirst = mstats + (size_t)cap2 * 5;
-  launch_ccl(comp, 1, pm.H, pm.W, 0, 8, mlab, n_dev, mstats, cap2, ws, st, 0, mfirst, 1);
+  T_TRY(launch_ccl(comp, 1, pm.H, pm.W, 0, 8, mlab, n_dev, mstats, cap2, ws, ws_bytes, st, mfirst, 1));
   launch_label_counters_zero(counters2, n_dev, cap2, st);
   if (fused) launch_tw_holes_all(dw, n, mlab, mstats, mfirst, cap2, count255, merged_b, pm.W, counters2, st);
   else launch_tw_holes(dw, n, max_pix, mlab, mstats, mfirst, cap2, count255, top2, merged_b, pm.W, counters2, st);
@@ -668,17 +671,21 @@ int undetected_pass(ctd_tail* t, const std::vector<std::vector<int32_t>>& blk_xy
            t->poff[b] == t->poff[b - 1] + max_px;
   const int nb = same ? B : 1;
   GET(t->d_lab_f, (size_t)nb * max_px * 4, int, lab);
-  GET(t->d_ccl_ws, same ? ccl_workspace_bytes(B, t->pages[0].im_h, t->pages[0].im_w) : ccl_workspace_bytes(1, 1, (int)max_px), uint8_t, ws);
+  // the workspace is laid out for a shape, not a pixel count: page by page it is the largest any page's own shape needs
+  size_t ws_bytes = 0;
+  if (same) ws_bytes = ccl_workspace_bytes(B, t->pages[0].im_h, t->pages[0].im_w);
+  else for (int b = 0; b < B; ++b) ws_bytes = std::max(ws_bytes, ccl_workspace_bytes(1, t->pages[b].im_h, t->pages[b].im_w));
+  GET(t->d_ccl_ws, ws_bytes, uint8_t, ws);
   GET(t->d_ccl_small, (size_t)B * 4 + (size_t)B * cap * 5 * 4, int, nst);
   int* n_dev = nst;
   int* st_dev = nst + B;
   GET(t->h_small, (size_t)B * 4, int, n_host);
   if (same) {
-    launch_ccl(pmask + t->poff[0], B, t->pages[0].im_h, t->pages[0].im_w, 30, 4, lab, n_dev, st_dev, cap, ws, st, 0, nullptr, 1);
+    T_TRY(launch_ccl(pmask + t->poff[0], B, t->pages[0].im_h, t->pages[0].im_w, 30, 4, lab, n_dev, st_dev, cap, ws, ws_bytes, st, nullptr, 1));
   } else {
     for (int b = 0; b < B; ++b)
-      launch_ccl(pmask + t->poff[b], 1, t->pages[b].im_h, t->pages[b].im_w, 30, 4, lab, n_dev + b,
-                 st_dev + (size_t)b * cap * 5, cap, ws, st, 0, nullptr, 1);   // only the statistics are used
+      T_TRY(launch_ccl(pmask + t->poff[b], 1, t->pages[b].im_h, t->pages[b].im_w, 30, 4, lab, n_dev + b,
+                       st_dev + (size_t)b * cap * 5, cap, ws, ws_bytes, st, nullptr, 1));   // only the statistics are used
   }
   T_TRY(hipMemcpyAsync(n_host, n_dev, (size_t)B * 4, hipMemcpyDeviceToHost, st));
   T_TRY(hipStreamSynchronize(st));
@@ -699,7 +706,7 @@ int undetected_pass(ctd_tail* t, const std::vector<std::vector<int32_t>>& blk_xy
       const int n = n_host[b];
       whole.resize(B);
       GET(t->d_ccl_small, 16 + (size_t)n * 20, int, again);                 // [n (1) | pad | stats (n,5)]
-      launch_ccl(pmask + t->poff[b], 1, t->pages[b].im_h, t->pages[b].im_w, 30, 4, lab, again, again + 4, n, ws, st, 0, nullptr, 1);
+      T_TRY(launch_ccl(pmask + t->poff[b], 1, t->pages[b].im_h, t->pages[b].im_w, 30, 4, lab, again, again + 4, n, ws, ws_bytes, st, nullptr, 1));
       T_TRY(hipGetLastError());
       whole[b].resize((size_t)n * 5);
       T_TRY(hipMemcpyAsync(whole[b].data(), again + 4, (size_t)n * 20, hipMemcpyDeviceToHost, st));
@@ -816,7 +823,8 @@ int db_enqueue(ctd_tail* t, DbStage& d, int B, int Hn, int Wn, const float* prob
   const int cap = kCompCap, rcap = kRowCap;
   d.B = B, d.Hn = Hn, d.Wn = Wn, d.prob = prob_dev, d.prob_stride = prob_stride;
   GET(t->d_lab_f, (size_t)B * hw * 4, int, lab);
-  GET(t->d_ccl_ws, ccl_workspace_bytes(B, Hn, Wn), uint8_t, ccl_ws);
+  const size_t ccl_ws_bytes = ccl_workspace_bytes(B, Hn, Wn);
+  GET(t->d_ccl_ws, ccl_ws_bytes, uint8_t, ccl_ws);
   // int tables: n_f, n_b (B each) | st_f, st_b (B,cap,5) | first, par, off x2 (B,cap) | hdr (B,4) | ring_cnt (B,cap) |
   // hole_rows (B) | seg_live (B, ceil(hw / 64)) bytes
   const size_t bc = (size_t)B * cap, nseg = (hw + 63) / 64;
@@ -844,8 +852,8 @@ int db_enqueue(ctd_tail* t, DbStage& d, int B, int Hn, int Wn, const float* prob
   pre.fill(td, 0, 3 * bc * 8);
   pre.fill(d.ring_cnt, 0, bc * 4);
   pre.flush();
-  launch_ccl_dual(bitmap_dev, B, Hn, Wn, 0, lab, d.n_f, d.n_b, d.st_f, d.st_b, d.first_f, d.first_b, cap, ccl_ws, st,
-                  d.seg_live);
+  T_TRY(launch_ccl_dual(bitmap_dev, B, Hn, Wn, 0, lab, d.n_f, d.n_b, d.st_f, d.st_b, d.first_f, d.first_b, cap, ccl_ws, ccl_ws_bytes,
+                        st, d.seg_live));
   DbcTables dt;
   dt.B = B, dt.H = Hn, dt.W = Wn, dt.cap = cap, dt.rcap = rcap;
   dt.prob = prob_dev, dt.prob_stride = prob_stride;

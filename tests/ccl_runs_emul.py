@@ -1,13 +1,14 @@
-"""TEST INFRASTRUCTURE of tests/test_ccl_runs_emul.py and tests/test_gpu_ccl_runs.py: the dual labelling on row runs
-(`launch_ccl_dual`, csrc/kernels_post.hip) in numpy and plain Python, kernel by kernel, and the pages both
-tests label.
+"""TEST INFRASTRUCTURE of tests/test_ccl_runs_emul.py and tests/test_gpu_ccl_runs.py: the labelling on row runs
+(`launch_ccl_dual` and its single-class front `launch_ccl`, csrc/kernels_post.hip) in numpy and plain
+Python, kernel by kernel, and the pages both tests label.
 
-    pack()         ccl2_pack          bits / starts words
+    pack()         ccl2_pack          bits / starts words; the class flip of the 4-connected single-class labelling
     scan()         ccl2_run_scan      base words, the run count R
     word_unions()  ccl2_word_unions   one word against the row above: groups of set bits, halo bits for the foreground
     label_runs()   ccl2_band (a table in "LDS" per band, global when the band has more than RB_CAP runs),
                    ccl2_band_border, ccl2_flatten_count / ccl2_scan_chunks / ccl2_rank / ccl2_spread
-    paint()        ccl2_label         the plane, statistics, first pixels, segment flags
+    paint()        ccl2_label         the plane, statistics, first pixels, segment flags; keep = its single-class form
+    label_single() launch_ccl         conn 8: the foreground class; conn 4: the background class of the flipped page
 
 What can go wrong in the kernels and shows here first: a run id off by one at a word's first or last bit, a halo bit taken
 from the wrong word or at the page's edge, the background joined diagonally, a union skipped because "the word to the left
@@ -31,8 +32,9 @@ def ffs(v):
     return (v & -v).bit_length()
 
 
-def pack(fg):
-    """(H, W) bool -> bits, starts: lists of H * wp Python ints."""
+def pack(fg, flip=False):
+    """(H, W) bool (pixel > thresh) -> bits, starts: lists of H * wp Python ints.  A bit is set where fg != flip."""
+    fg = fg != flip
     H, W = fg.shape
     wp = (W + 31) // 32
     bits, starts = [], []
@@ -116,12 +118,12 @@ def union(parent, a, b):
         parent[max(a, b)] = min(a, b)
 
 
-def label_runs(fg, cap=RB_CAP):
+def label_runs(fg, cap=RB_CAP, flip=False):
     """The run tables of one page: bits, starts, base, R, rcls, rparent (flat), rlabel, n_f, n_b, and `over` = the bands
     that did not fit a table of `cap` runs."""
     H, W = fg.shape
     wp = (W + 31) // 32
-    bits, starts = pack(fg)
+    bits, starts = pack(fg, flip)
     base, R = scan(starts)
     rparent, rcls, over = [None] * R, [None] * R, []
     nbands = (H + RB_ROWS - 1) // RB_ROWS
@@ -172,9 +174,11 @@ def label_runs(fg, cap=RB_CAP):
                 n_b=n_b, over=over)
 
 
-def paint(t, max_labels):
+def paint(t, max_labels, keep=0, other=0):
     """The plane from base / starts / rlabel; statistics [x, y, w, h, area] and first pixels of labels 1..max_labels of
-    either class (rows beyond the count stay -1 here; the device leaves them unwritten); the 64-pixel segment flags."""
+    either class (rows beyond the count stay -1 here; the device leaves them unwritten); the 64-pixel segment flags.
+    keep = +1 / -1 (ccl2_label<KEEP>): that class alone -- its pixels get |id| and its tables are st[1] / first[1], a
+    pixel of the other class gets `other` and takes no part in the tables; no segment flags."""
     H, W, wp = t["H"], t["W"], t["wp"]
     plane = np.zeros((H, W), np.int32)
     st = {1: np.full((max_labels, 5), -1, np.int64), -1: np.full((max_labels, 5), -1, np.int64)}
@@ -185,6 +189,11 @@ def paint(t, max_labels):
             w, bit = y * wp + (x >> 5), x & 31
             run = t["base"][w] + popc(t["starts"][w] & low_mask(bit)) - 1
             lab, root = t["rlabel"][run] >> 1, t["rlabel"][run] & 1
+            if keep:
+                lab = abs(lab) if (lab > 0) == (keep > 0) else 0
+                if not lab:
+                    plane[y, x] = other
+                    continue
             plane[y, x] = lab
             mag, sign = abs(lab), (1 if lab > 0 else -1)
             if mag > max_labels:
@@ -195,9 +204,20 @@ def paint(t, max_labels):
             b[0], b[1], b[2], b[3], b[4] = min(b[0], x), min(b[1], y), max(b[2], x), max(b[3], y), b[4] + 1
     for lab, b in box.items():
         st[1 if lab > 0 else -1][abs(lab) - 1] = [b[0], b[1], b[2] - b[0] + 1, b[3] - b[1] + 1, b[4]]
-    other = plane.ravel() != -1
-    seg = np.r_[other, np.zeros((-other.size) % 64, bool)].reshape(-1, 64).any(axis=1)
+    if keep:
+        return plane, st, first, None
+    live = plane.ravel() != -1
+    seg = np.r_[live, np.zeros((-live.size) % 64, bool)].reshape(-1, 64).any(axis=1)
     return plane, st, first, seg
+
+
+def label_single(fg, conn, max_labels, other=0, cap=RB_CAP):
+    """launch_ccl on (pixel > thresh) = fg: (run tables, n, plane, stats, first).  conn 8 is the foreground half of the dual
+    labelling; conn 4 is the background half of the dual labelling of the flipped page."""
+    keep = 1 if conn == 8 else -1
+    t = label_runs(fg, cap, flip=(conn == 4))
+    plane, st, first, _ = paint(t, max_labels, keep, other)
+    return t, (t["n_f"] if keep > 0 else t["n_b"]), plane, st[1], first[1]
 
 
 # ---------------------------------------------------------------------------------------------------------------------------

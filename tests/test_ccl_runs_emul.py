@@ -1,7 +1,9 @@
 """The dual labelling on row runs as tests/ccl_runs_emul.py spells it out (the kernels of `launch_ccl_dual` in numpy) against
 the oracle's `connected_components_with_stats`, 8-connected for the foreground and 4-connected for the background: label
 plane, counts, statistics and first pixels, exactly.  Widths 1..131 put a page in one word, in whole words and in a partial
-last word; heights 1..65 put a band boundary nowhere, after the last row and inside the page.  No GPU is needed."""
+last word; heights 1..65 put a band boundary nowhere, after the last row and inside the page.  The single-class form
+(`launch_ccl`: conn 8 keeps the foreground class, conn 4 the background class of the flipped page) on the same pages against
+`connected_components_with_stats(img, conn)`.  No GPU is needed."""
 import os
 import re
 
@@ -86,3 +88,54 @@ def test_max_labels_below_the_component_count_drops_the_rows_beyond():
     t = E.label_runs(fg)
     assert min(t["n_f"], t["n_b"]) > 7
     check_page("noise, max_labels 7", fg, max_labels=7)
+
+
+# ---------------------------------------------------------------------------------------------------------------------------
+# launch_ccl: one class of the same engine
+# ---------------------------------------------------------------------------------------------------------------------------
+def check_single(name, fg, conn, cap=E.RB_CAP, max_labels=None, other=0):
+    from oracle import postproc_ref as R
+    nref, lref, sref = R.connected_components_with_stats(fg.astype(np.uint8) * 255, conn)
+    nref, sref = nref - 1, sref[1:]
+    cap_l = max_labels if max_labels is not None else max(1, nref)
+    t, n, plane, st, first = E.label_single(fg, conn, cap_l, other, cap)
+    name = f"{name}, conn {conn}"
+    assert n == nref, f"{name}: {n} components, the oracle has {nref}"
+    np.testing.assert_array_equal(plane, np.where(lref > 0, lref, other), err_msg=name)
+    k = min(n, cap_l)
+    np.testing.assert_array_equal(st[:k], sref[:k], err_msg=name)
+    flat = lref.ravel()
+    for l in range(k):
+        assert first[l] == int(np.argmax(flat == l + 1)), f"{name}: first pixel of {l + 1}"
+    assert (st[k:] == -1).all() and (first[k:] == -1).all(), f"{name}: rows beyond the labels that exist"
+    return t
+
+
+@pytest.mark.parametrize("conn", (4, 8))
+@pytest.mark.parametrize("H", E.HEIGHTS)
+def test_one_class_of_every_kind_of_page_at_every_width(H, conn):
+    for (h, W), pages in E.small_calls():
+        if h != H:
+            continue
+        for i, (name, fg) in enumerate(pages):
+            check_single(f"{name}, {H} x {W}", fg, conn, other=-(i % 2))     # both background values of the plane
+
+
+@pytest.mark.parametrize("conn", (4, 8))
+def test_one_class_with_small_tables_and_with_a_band_over_the_capacity(conn):
+    n_over = 0
+    for H, W in ((65, 131), (33, 65), (65, 33)):
+        for name, fg in E.pages_for(H, W):
+            n_over += len(check_single(f"{name}, {H} x {W}, table of 64", fg, conn, cap=64)["over"])
+    assert n_over > 50
+    t = check_single("alternating band between sparse bands", E.over_capacity_page(W=1024), conn, other=-1)
+    assert t["over"] == [1]
+
+
+@pytest.mark.parametrize("conn", (4, 8))
+@pytest.mark.parametrize("other", (0, -1))
+def test_one_class_with_max_labels_below_the_component_count(conn, other):
+    fg = E.noise(33, 65, 0.3, 9)
+    t, n, *_ = E.label_single(fg, conn, 7)
+    assert n > 7
+    check_single("noise, max_labels 7", fg, conn, max_labels=7, other=other)
