@@ -3,7 +3,7 @@
 // component that lowers the xor distance to the eroded prediction, next candidate; dilate; fill holes; OR the window into
 // the page's refined mask.
 //
-// Why: as separate passes over packed canvases (kernels_tail.hip `tw_render / tw_accept_all / tw_dilate / tw_holes_all /
+// Why: as separate passes over packed canvases (kernels_tail.hip `tw_render / tw_accept_* / tw_dilate / tw_holes /
 // tw_commit` around two launches of the page-scale labelling, kernels_post.hip) this stage wrote and re-read int32 label
 // planes of every candidate of every window: 4.6 of the tail's 8.7 ms of kernel time and 2.3 of its 3.9 GB per 32 pages
 // (DESIGN 4.12).  Nothing in it needs a label PLANE.  What a merge round needs is, per component, one number:

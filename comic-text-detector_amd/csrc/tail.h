@@ -64,12 +64,8 @@ void launch_tw_render(const TWin* wins, const TBand* bands, int nbands, int max_
 void launch_tw_accept(const TWin* wins, const TBand* bands, int nbands, int max_pix, int round, const int* labels,
                       int canvas_w, const int* stats, int max_labels, int min_box, uint8_t* merged, int merged_w,
                       unsigned* counters, hipStream_t st);
-// ALL merge rounds of every window in one launch: a block owns a window and walks its bands in merge order (count,
-// decide, apply, next band) -- the rounds of a window depend on each other, windows do not
 // zeroes the per-label counter pairs of the labels a labelling launch produced (their count is on the device)
 void launch_label_counters_zero(unsigned* counters, const int* n_labels, int cap, hipStream_t st);
-void launch_tw_accept_all(const TWin* wins, const TBand* bands, int n, const int* labels, int canvas_w, const int* stats,
-                          int max_labels, int min_box, uint8_t* merged, int merged_w, unsigned* counters, hipStream_t st);
 void launch_tw_dilate(const TWin* wins, int n, int max_pix, const uint8_t* in, uint8_t* out, uint8_t* comp, int merged_w,
                       unsigned* count255, int dilate, hipStream_t st);
 // hole filling (reference utils/textmask.py:113-131) on the labelled complement canvas: per-window
@@ -78,9 +74,6 @@ void launch_tw_dilate(const TWin* wins, int n, int max_pix, const uint8_t* in, u
 void launch_tw_holes(const TWin* wins, int n, int max_pix, const int* labels2, const int* stats2, const int* first2,
                      int max_labels, const unsigned* count255, int* top2, uint8_t* merged, int merged_w,
                      unsigned* counters2, hipStream_t st);
-// the four passes of the hole filling as one launch, a block per window
-void launch_tw_holes_all(const TWin* wins, int n, const int* labels2, const int* stats2, const int* first2, int max_labels,
-                         const unsigned* count255, uint8_t* merged, int merged_w, unsigned* counters2, hipStream_t st);
 void launch_tw_commit(const TWin* wins, int n, int max_pix, const uint8_t* merged, int merged_w, hipStream_t st);
 // ---- the merge stage of a window (render -> merge rounds -> dilation -> hole filling -> commit) as ONE block on bit planes
 // in LDS (kernels_twlds.hip): windows order[0 .. n) of `wins`, planes of at most `max_words` 32-pixel words, `rcap` runs per

@@ -30,7 +30,7 @@
 #include "tail.h"
 
 int ctd_fail_msg(int code, const std::string& msg);   // engine.hip: sets the thread-local error text
-// the tail's knobs ("tail_*": stream priority, CU mask, event chain, fused rounds, the LDS path's limits): tuning.def
+// the tail's knobs ("tail_*": stream priority, CU mask, event chain, the LDS path's limits): tuning.def
 
 #define T_TRY(expr)                                                                                  \
   do {                                                                                               \
@@ -414,23 +414,16 @@ int refine_canvas(ctd_tail* t, const TWin* hw, const std::vector<TBand>& bands, 
   bt.fill(top2, 0xFF, (size_t)n * 12);
   bt.fill(canvas, 0, cpx);
   bt.flush();
-  // One block per window for all merge rounds / hole passes (`tw_accept_all`, `tw_holes_all`) suits windows of a few 10 K
-  // pixels; since round 6 those are merged in LDS and what arrives here is mostly LARGE (page-sized windows of
-  // refine_undetected_mask's left-over components: one block walked 1 M pixels six times, 5-7 ms per launch next to a
-  // 10-ms forward) -- those take the per-round grid kernels, many blocks per window.  Same results either way
-  // (test_fused_merge_rounds_equal_the_per_round_launches).
-  const bool fused = g_tail_fused_rounds && max_pix < g_tail_fused_max_pix;
+  // What arrives here is a window beyond the LDS (mostly the page-sized windows of refine_undetected_mask's left-over
+  // components) or one whose run table overflowed: every kernel below has many blocks per window; a merge round is a
+  // count and an apply launch, a hole pass one launch.
   GpuChain chain(st, t->device, g_tail_chain >= 2);
   T_TRY(chain.begin());
   launch_tw_render(dw, db, nbands, max_pix, canvas, pc.W, st);
   T_TRY(launch_ccl(canvas, 1, pc.H, pc.W, 0, 8, clab, n_dev, cstats, cap1, ws, ws_bytes, st, nullptr, 1));   // the window kernels test `label > 0`
   launch_label_counters_zero(counters, n_dev, cap1, st);
-  if (fused) {
-    launch_tw_accept_all(dw, db, n, clab, pc.W, cstats, cap1, 3, merged_a, pm.W, counters, st);
-  } else {
-    for (int r = 0; r < rounds; ++r)
-      launch_tw_accept(dw, db, nbands, max_pix, r, clab, pc.W, cstats, cap1, 3, merged_a, pm.W, counters, st);
-  }
+  for (int r = 0; r < rounds; ++r)
+    launch_tw_accept(dw, db, nbands, max_pix, r, clab, pc.W, cstats, cap1, 3, merged_a, pm.W, counters, st);
   launch_tw_dilate(dw, n, max_pix, merged_a, merged_b, comp, pm.W, count255, refine_mode == 0 ? 1 : 0, st);
   // ---- hole filling on the complement, then the OR into the pages
   GET(t->d_mlab, mpx * 4, int, mlab);
@@ -438,8 +431,7 @@ int refine_canvas(ctd_tail* t, const TWin* hw, const std::vector<TBand>& bands, 
   int* mfirst = mstats + (size_t)cap2 * 5;
   T_TRY(launch_ccl(comp, 1, pm.H, pm.W, 0, 8, mlab, n_dev, mstats, cap2, ws, ws_bytes, st, mfirst, 1));
   launch_label_counters_zero(counters2, n_dev, cap2, st);
-  if (fused) launch_tw_holes_all(dw, n, mlab, mstats, mfirst, cap2, count255, merged_b, pm.W, counters2, st);
-  else launch_tw_holes(dw, n, max_pix, mlab, mstats, mfirst, cap2, count255, top2, merged_b, pm.W, counters2, st);
+  launch_tw_holes(dw, n, max_pix, mlab, mstats, mfirst, cap2, count255, top2, merged_b, pm.W, counters2, st);
   launch_tw_commit(dw, n, max_pix, merged_b, pm.W, st);
   T_TRY(chain.end());
   T_TRY(hipGetLastError());
@@ -551,10 +543,17 @@ int refine_windows(ctd_tail* t, const std::vector<WinReq>& reqs, int refine_mode
   const long long lds_max = std::min(g_tail_lds_max_bytes, t->lds_per_block - 2048);
   std::vector<int> lds_win, canvas_win;
   std::vector<int> words(n);
+  struct LdsNeed {
+    int rcap;          // the run capacity a launch whose largest window has `wd` words asks for
+    long long bytes;   // the LDS such a launch gets (tw_lds_bytes lays out at least half a run per word)
+  };
+  auto lds_need = [](int wd) {
+    const int rc = g_tail_lds_rcap > 0 ? g_tail_lds_rcap : tw_lds_rcap(wd);
+    return LdsNeed{rc, (long long)tw_lds_bytes(wd, rc)};
+  };
   for (int i = 0; i < n; ++i) {
     words[i] = ((ww[i] + 31) >> 5) * wh[i];
-    const int rc = g_tail_lds_rcap > 0 ? g_tail_lds_rcap : tw_lds_rcap(words[i]);
-    if (g_tail_lds && (long long)tw_lds_bytes(words[i], std::max(rc, (words[i] + 1) / 2)) <= lds_max) lds_win.push_back(i);
+    if (g_tail_lds && lds_need(words[i]).bytes <= lds_max) lds_win.push_back(i);
     else canvas_win.push_back(i);
   }
   int nl = (int)lds_win.size();
@@ -579,17 +578,12 @@ int refine_windows(ctd_tail* t, const std::vector<WinReq>& reqs, int refine_mode
     int k0 = 0;
     for (int c = 0; c < 3 && k0 < nl; ++c) {
       int k1 = k0;
-      auto need = [&](int k) {
-        const int wd = words[lds_win[k]];
-        const int rc = g_tail_lds_rcap > 0 ? g_tail_lds_rcap : tw_lds_rcap(wd);
-        return (long long)tw_lds_bytes(wd, std::max(rc, (wd + 1) / 2));
-      };
-      while (k1 < nl && (c == 2 || need(k1) <= cls[c])) ++k1;
+      while (k1 < nl && (c == 2 || lds_need(words[lds_win[k1]]).bytes <= cls[c])) ++k1;
       if (k1 > k0) {
         const int mw = words[lds_win[k1 - 1]];
         TwLdsLaunch used{};
-        if (!launch_tw_lds(dw, db, dl + k0, k1 - k0, mw, g_tail_lds_rcap > 0 ? g_tail_lds_rcap : tw_lds_rcap(mw),
-                           refine_mode == 0 ? 1 : 0, dl + n, st, t->trace ? &used : nullptr))
+        if (!launch_tw_lds(dw, db, dl + k0, k1 - k0, mw, lds_need(mw).rcap, refine_mode == 0 ? 1 : 0, dl + n, st,
+                           t->trace ? &used : nullptr))
           for (int k = k0; k < k1; ++k) refused.push_back(lds_win[k]);
         if (t->trace) t->tr_lds.push_back(used);
       }

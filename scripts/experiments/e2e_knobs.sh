@@ -8,5 +8,4 @@ run tail_chain=1 "--tail-split 2"
 run tail_chain=1 "--tail-split 6"
 run tail_chain=1 "--tail-split 1 --depth 6"
 run halo3=0
-run tail_fused_rounds=0
 run tail_chain=1

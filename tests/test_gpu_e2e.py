@@ -496,33 +496,23 @@ def _speckle_page(H, W, seed):
     return page, mask
 
 
-def test_fused_merge_rounds_equal_the_per_round_launches():
-    """`tw_accept_all_kernel` / `tw_holes_all_kernel` (one block per window for every merge round / every hole pass,
-    `tail_fused_rounds` = 1, the default) against the per-round launches they replaced (`tail_fused_rounds` = 0) on pages
-    built to overflow the fused kernels' LDS tables: page-sized windows over a speckle of 7x7 squares give every candidate
-    mask thousands of components (> 2048 keys per band, probe failures), i.e. the global-memory fallback inside the kernels
-    -- a branch the text-like pages of the other tests never reach.  Byte-identical refined masks, and equal to
-    the oracle on the smaller page."""
+def test_canvas_path_equals_the_oracle_on_speckle_pages():
+    """The canvas path (`tail_lds` = 0: every window through `tw_accept_count_kernel` / `tw_accept_apply_kernel` /
+    `tw_holes_kernel`, many blocks per window) on pages built to overflow the count kernel's per-block LDS table:
+    page-sized windows over a speckle of 7x7 squares give every candidate mask thousands of components (more keys per block
+    than its 1024 slots, probe failures), i.e. the global-atomic spill inside the kernel -- a branch the text-like pages of
+    the other tests never reach.  Both refine modes, byte-identical to the oracle's refine_mask on both pages."""
     p = pkg()
-    L = p._lib
-    for (H, W), check_oracle in (((320, 448), True), ((960, 1024), False)):
+    for H, W in ((320, 448), (960, 1024)):
         page, mask = _speckle_page(H, W, 5)
         boxes = [[2, 2, W - 2, H - 2], [0, 0, W // 2, H // 2], [W // 3, H // 4, W - 5, H - 9], [5, H // 2, W // 2, H - 1]]
         blks = [p.textblock.TextBlock(b) for b in boxes]
-        out = {}
-        # round 6: the canvas path for every window (`tail_lds` = 0), and the block-per-window kernels also for these
-        # LARGE windows (by default sets with a window of `tail_fused_max_pix` pixels or more take the per-round launches)
-        with L.tuning(tail_lds=0, tail_fused_max_pix=1 << 40):
-            for fused in (1, 0):
-                with L.tuning(tail_fused_rounds=fused):
-                    out[fused] = [p.textmask.refine_mask(page, mask, blks, mode, "cuda") for mode in (0, 1)]
-        for a, b in zip(out[1], out[0]):
-            np.testing.assert_array_equal(a, b)
-        assert (out[1][0] > 0).mean() > 0.2
-        if check_oracle:
-            rblks = [R.TextBlock(b) for b in boxes]
-            for mode in (0, 1):
-                np.testing.assert_array_equal(out[1][mode], R.refine_mask(page, mask, rblks, mode))
+        got, paths = _refine_under(p, {"tail_lds": 0}, page, mask, blks)
+        assert paths["lds"] == 0 and paths["canvas"] == len(boxes), paths
+        assert (got[0] > 0).mean() > 0.2
+        rblks = [R.TextBlock(b) for b in boxes]
+        for mode in (0, 1):
+            np.testing.assert_array_equal(got[mode], R.refine_mask(page, mask, rblks, mode))
 
 
 def _refine_under(p, key_values, page, mask, blks, dev="cuda"):

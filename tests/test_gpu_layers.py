@@ -522,7 +522,6 @@ NOT_DISPATCH_KEYS = {
     "no_reuse": "arena layout only: every activation stays readable (what the float64 checks run under)",
     "tail_max_blocks": "tail: grid cap",
     "tail_chain": "tests/test_gpu_e2e.py::test_detect_stream_equals_detect_batch_under_every_tail_chain (0, 1, 2; with and without tail_lds)",
-    "tail_fused_rounds": "tail: launches per round", "tail_fused_max_pix": "tail: threshold of tail_fused_rounds",
     "tail_lds": "tail: LDS variant of the window kernels (tests/test_gpu_sweeps.py)", "tail_lds_rcap": "tail: LDS run capacity",
     "tail_lds_max_bytes": "tail: LDS threshold",
     "tail_lds_runs_x10": "tests/test_gpu_tail_trace.py::test_run_capacity (1, 25, 160, 1000: logged rcap, routing, overflows)",

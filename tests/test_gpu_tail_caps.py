@@ -18,9 +18,9 @@ DB scores (atol 1e-6, as everywhere in the suite).
     (one per page), each page against its single-page call; `Tail.run` on u_over with no detections against `R.detector_tail`.
   * canvas bound: a call of nothing but windows whose every candidate holds exactly ((w + 1) / 2) * ((h + 1) / 2) components
     (1, 4, 272, 2 145; two bands each: the labelling of the canvas returns 4 844 = cap1 - 1 labels, asserted on the CPU)
-    through the canvases with fused rounds, with per-round launches, and at the defaults; all equal the oracle and each
-    other.  The masks are all zero either way (the test's docstring says what that can and cannot see); a text-like window
-    runs the same three paths in a call of its own.
+    through the canvases (`tail_lds` = 0) and at the defaults; both equal the oracle and each other.  The masks are all zero
+    either way (the test's docstring says what that can and cannot see); a text-like window runs the same two paths in a
+    call of its own.
   * history, on a tail of its own: u_at, u_grow (90 113 components: the relabelling's table outgrows the buffer and is
     allocated again), the largest batch, u_at again -- the same bytes both times.
 
@@ -224,11 +224,10 @@ def test_whole_tail_on_u_over_without_detections(mode):
 
 # ---------------------------------------------------------------------------------------------------------- canvas bound
 
-CANVAS_RUNS = [(" [tail_lds = 0, fused rounds]", {"tail_lds": 0, "tail_fused_rounds": 1, "tail_fused_max_pix": 1 << 20}),
-               (" [tail_lds = 0, per-round launches]", {"tail_lds": 0, "tail_fused_rounds": 0}), (" [defaults]", {})]
+CANVAS_RUNS = [(" [tail_lds = 0]", {"tail_lds": 0}), (" [defaults]", {})]
 
 
-def on_the_three_merge_paths(case, n_windows):
+def on_the_two_merge_paths(case, n_windows):
     """A case under `CANVAS_RUNS`: every run against the oracle (records, path counts, masks) and the runs against each other."""
     total, bad, before, masks = 0, [], [], []
     for what, tune in CANVAS_RUNS:
@@ -241,8 +240,8 @@ def on_the_three_merge_paths(case, n_windows):
         total, bad = total + n, bad + b
         before.append(T.before_merge(got[0]))
         masks.append([m.tobytes() for m in got[2] + got[3]])
-    assert before[0] == before[1] == before[2], "the records before the merge stage differ between the merge paths"
-    assert masks[0] == masks[1] == masks[2], "the masks differ between the merge paths"
+    assert before[0] == before[1], "the records before the merge stage differ between the merge paths"
+    assert masks[0] == masks[1], "the masks differ between the merge paths"
     return total, bad
 
 
@@ -251,21 +250,21 @@ def test_canvas_tables_at_their_bound(mode):
     """The dot-grid pages, and nothing else in the call: every candidate of the 1 x 1, 3 x 3, 33 x 31 and 65 x 129 windows
     holds exactly one component per 2 x 2 cell, so the canvas labelling returns `cap1` - 1 = 4 844 labels and the last row of
     `cstats` and of the counter table is used (summed on the CPU in tests/test_tail_cap_cases.py; the device does not report
-    the count).  Every window through the canvases with fused rounds, the same with per-round launches, and at the defaults.
+    the count).  Every window through the canvases (`tail_lds` = 0), and at the defaults.
 
     What this can see: a fault, or a non-zero mask, if a table a few rows short lets the labelling's statistics or the
     counters run into what lies behind them.  What it cannot: the dots are single pixels, all refused by the `w * h >= 3`
     rule, and `ccl_label_body` writes no statistics for an id above `max_labels`; so a bound that is short, with a
     `max_labels` that is short with it, still gives the all-zero masks of the oracle."""
-    total, bad = on_the_three_merge_paths(in_mode(K.canvas_case(), mode), 4)
+    total, bad = on_the_two_merge_paths(in_mode(K.canvas_case(), mode), 4)
     report(f"canvas bound, refine mode {mode}", total, bad)
 
 
 @pytest.mark.parametrize("mode", (0, 1))
 def test_canvas_path_on_the_text_window_alone(mode):
-    """The text-like window of the second dot page in a call of its own on the same three paths: a result that is not all
-    zero (2 672 pixels in mode 0) from the canvases with fused rounds and with per-round launches."""
-    total, bad = on_the_three_merge_paths(in_mode(K.canvas_text_case(), mode), 1)
+    """The text-like window of the second dot page in a call of its own on the same two paths: a result that is not all
+    zero (2 672 pixels in mode 0) from the canvases."""
+    total, bad = on_the_two_merge_paths(in_mode(K.canvas_text_case(), mode), 1)
     report(f"canvas path, text window, refine mode {mode}", total, bad)
 
 

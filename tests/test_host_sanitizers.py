@@ -311,7 +311,6 @@ TUNING_PIN = {
     "split_stem": ("int", 1, None, True), "split_planes": ("int", 1, None, True), "split_halo": ("int", 1, None, True),
     "split_halo_min_patches": ("long long", 512, None, True),
     "tail_max_blocks": ("int", 1024, 1, False), "tail_chain": ("int", 1, None, False),
-    "tail_fused_rounds": ("int", 1, None, False), "tail_fused_max_pix": ("long long", 100000, None, False),
     "tail_lds": ("int", 1, None, False), "tail_lds_rcap": ("int", 0, None, False),
     "tail_lds_max_bytes": ("long long", 150 << 10, None, False), "tail_lds_runs_x10": ("int", 25, 1, False),
     "tail_lds_threads": ("int", 512, None, False), "tail_lds_cls0": ("long long", 40 << 10, None, False),
@@ -333,11 +332,11 @@ def test_tuning_table_holds_the_pinned_defaults_with_and_without_the_sanitizers(
     for fl, r in runs.items():
         assert r.returncode == 0 and r.stderr == "", (fl, r.returncode, r.stdout[-1000:], r.stderr[-3000:])
     assert runs["plain"].stdout == runs["asan"].stdout
-    assert len(TUNING_PIN) == 35
+    assert len(TUNING_PIN) == 33
     assert all(replan == (not key.startswith("tail_")) for key, (_, _, _, replan) in TUNING_PIN.items())
     want = sorted(f"{key} {typ} {default} {int(replan)} {-7 if low is None else low} {0 if typ == 'int' else 1 << 40}"
                   for key, (typ, default, low, replan) in TUNING_PIN.items())
     *rows, unknown, restored = runs["plain"].stdout.splitlines()
     assert sorted(rows) == want and len(rows) == len(set(rows))
     assert unknown == "unknown key: set -1 get -1, null key: set -1 get -1, null value: get -1, untouched 12345 0"
-    assert restored == "restored 35 keys"
+    assert restored == "restored 33 keys"
