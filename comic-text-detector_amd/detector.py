@@ -369,6 +369,8 @@ class TextDetector:
                       tune: bool = True, line_batches: Optional[dict] = None, font_colors: bool = False) -> Iterator[list]:
         """Yields `detect_batch(batch)` for every batch, in order, with up to `depth` batches in flight:
         the forward of the next batches is launched while `workers` threads run the tails of earlier ones.
+        `depth` = 1 is the unpipelined order (every batch's tail is awaited before the next forward is launched); less than 1
+        is a ValueError, raised before any work.
         Host (numpy) pages are staged to the GPU by `loaders` threads up to `depth` batches ahead (`_stage`).
         `engines` > 1 alternates the batches over that many engine copies on their own streams (`_lane`).
         `tail_split` cuts every batch's tail into that many page ranges, each a work item of its own for the workers
@@ -397,6 +399,8 @@ class TextDetector:
         HIP stream and ~250 MB of device tables at 32 pages per batch."""
         if font_colors and lazy:
             raise ValueError("font_colors=True fills TextBlock objects: not with lazy=True (use font_colors(..., apply=False))")
+        if int(depth) < 1:
+            raise ValueError("depth must be at least 1: the batch whose tail is awaited is in flight itself")
         if int(workers) <= 0:
             tb = thread_budget()
             workers = tb["tail_workers"]
