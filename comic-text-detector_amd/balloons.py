@@ -19,7 +19,6 @@ pixels.  There is no per-block Python and no CPU fallback: without a GPU it rais
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from typing import Optional, Sequence
 
@@ -28,17 +27,13 @@ import torch
 
 from . import _lib as L
 from . import erase as E
-from .regions import Page, _check_pages, _device_pages
+from .pagecall import Page, PageCall, blk_lists_of, check_pages, check_pitch, table_dtype
 
 __all__ = ["balloon_regions", "BalloonRegions", "balloon_tables", "check_params", "JOB_DTYPE", "ROW_DTYPE"]
 
-# numpy views of `ctd_balloon_job` / `ctd_balloon_row` (include/ctd_hip.h; _lib.CtdBalloonJob / CtdBalloonRow); the page table
-# is `erase.PAGE_DTYPE`
-JOB_DTYPE = np.dtype([("page", "<i4"), ("xyxy", "<i4", (4,)), ("erase_row", "<i4"), ("word0", "<i8")])
-ROW_DTYPE = np.dtype([("status", "<i4"), ("area", "<i4"), ("bbox", "<i4", (4,)), ("flags", "<i4"), ("n_seed", "<i4"),
-                      ("sum_x", "<i8"), ("sum_y", "<i8")])
-assert JOB_DTYPE.itemsize == C.sizeof(L.CtdBalloonJob) == 32
-assert ROW_DTYPE.itemsize == C.sizeof(L.CtdBalloonRow) == 48
+# numpy views of `ctd_balloon_job` / `ctd_balloon_row` (include/ctd_hip.h); the page table is `erase.PAGE_DTYPE`
+JOB_DTYPE = table_dtype(L.CtdBalloonJob)
+ROW_DTYPE = table_dtype(L.CtdBalloonRow)
 
 
 def check_params(grow, tol, reach, reach_min) -> L.CtdBalloonParams:
@@ -135,9 +130,8 @@ def balloon_regions(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Seq
     prm = check_params(grow, tol, reach, reach_min)
     if len(pages) != len(blk_lists) or len(masks) != len(pages):
         raise ValueError("one mask and one blk_list per page")
-    _check_pages(pages, masks, "BGR ")
-    lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in blk_lists]
-    boxes = [E._page_boxes(b) for b in lists]
+    check_pages(pages, masks, "BGR ")
+    boxes = [E._page_boxes(b) for b in blk_lists_of(blk_lists)]
     shapes = [tuple(p.shape[:2]) for p in pages]
     ejobs, block0, counts, _, _ = E.erase_tables(boxes, shapes)
     n, n_pages = len(ejobs), len(pages)
@@ -151,51 +145,30 @@ def balloon_regions(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Seq
     if n_pages == 0:
         return BalloonRegions(index, np.zeros((0,), ROW_DTYPE), win, nw, word0, too_large, torch.zeros((0,), dtype=torch.uint64),
                               np.zeros((0,), E.ROW_DTYPE))
-    if not torch.cuda.is_available():
-        raise L.CtdError("balloon regions run on the GPU and there is none (no CPU fallback)")
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        pages, _, device = _device_pages(pages, device)
-        masks = _device_pages(masks, device)[0]
-        with torch.cuda.device(device):
-            st = torch.cuda.current_stream(device)
-            W = np.array([p.shape[1] for p in pages], np.int64)
-            pitch = np.array([p.stride(0) for p in pages], np.int64)
-            mpitch = np.array([m.stride(0) for m in masks], np.int64)
-            if max(pitch.max(), mpitch.max(), (3 * W).max()) >= 2 ** 31:
-                raise ValueError("row pitch beyond int32")
-            # one upload: erase jobs, balloon jobs, pages, and the erase rows where the caller has them
-            js, ps, rs = E.JOB_DTYPE.itemsize, E.PAGE_DTYPE.itemsize, E.ROW_DTYPE.itemsize
-            o_jobs, o_pages, o_rows = n * js, n * (js + JOB_DTYPE.itemsize), n * (js + JOB_DTYPE.itemsize) + n_pages * ps
-            table = np.zeros((o_rows + (n * rs if erased is not None else 0),), np.uint8)
-            table[:o_jobs] = ejobs.view(np.uint8)
-            jt = table[o_jobs:o_pages].view(JOB_DTYPE)
-            jt["page"], jt["xyxy"], jt["erase_row"], jt["word0"] = ejobs["page"], ejobs["xyxy"], np.arange(n), word0
-            pt = table[o_pages:o_rows].view(E.PAGE_DTYPE)
-            pt["page_dev"] = [p.data_ptr() for p in pages]
-            pt["mask_dev"] = [m.data_ptr() for m in masks]
-            pt["H"], pt["W"], pt["pitch"], pt["mask_pitch"] = [s[0] for s in shapes], W, pitch, mpitch
-            pt["block0"], pt["n_blocks"] = block0, counts
-            if erased is not None:
-                table[o_rows:] = np.ascontiguousarray(erased.rows).view(np.uint8)
-            tab = torch.from_numpy(table).to(device)
-            # one buffer behind both row tables: balloon rows, then erase rows
-            res = torch.empty((max(n, 1) * (ROW_DTYPE.itemsize + rs),), dtype=torch.uint8, device=device)
-            bits = torch.empty((max(total, 1),), dtype=torch.int64, device=device)[:total].view(torch.uint64)
-            if n:
-                lib = L.lib()
-                erows_ptr = tab.data_ptr() + o_rows
-                if erased is None:
-                    eprm = E.check_params(grow, 4, tol, 16)             # n_tiles = 0: the stats launch alone
-                    erows_ptr = res.data_ptr() + n * ROW_DTYPE.itemsize
-                    L.check(lib.ctd_erase_text(tab.data_ptr(), n, tab.data_ptr() + o_pages, n_pages, C.byref(eprm), erows_ptr,
-                                               st.cuda_stream), "ctd_erase_text")
-                owned = (nw * (win[:, 3] - win[:, 1]))[~too_large]
-                prm.max_words = int(owned.max()) if len(owned) else 0
-                L.check(lib.ctd_balloon_regions(tab.data_ptr() + o_jobs, n, tab.data_ptr() + o_pages, n_pages, erows_ptr,
-                                                C.byref(prm), res.data_ptr(), bits.data_ptr() if total else None, st.cuda_stream),
-                        "ctd_balloon_regions")
-            host = res.cpu().numpy()                                    # stream-ordered: behind the launches
-            st.synchronize()
+    rs = E.ROW_DTYPE.itemsize
+    with PageCall("balloon regions run", pages, stream, device) as pc:
+        P, M = pc.pages(pages), pc.pages(masks)
+        check_pitch(3 * P.W)
+        jt = np.zeros((n,), JOB_DTYPE)
+        jt["page"], jt["xyxy"], jt["erase_row"], jt["word0"] = ejobs["page"], ejobs["xyxy"], np.arange(n), word0
+        erows_up = np.ascontiguousarray(erased.rows) if erased is not None else np.zeros((0,), E.ROW_DTYPE)
+        # one upload: erase jobs, balloon jobs, pages, and the erase rows where the caller has them
+        _, (ejobs_ptr, jobs_ptr, pages_ptr, erows_ptr) = pc.upload([ejobs, jt, E.page_table(P, M, block0, counts), erows_up])
+        # one buffer behind both row tables: balloon rows, then erase rows
+        res = torch.empty((max(n, 1) * (ROW_DTYPE.itemsize + rs),), dtype=torch.uint8, device=pc.device)
+        bits = torch.empty((max(total, 1),), dtype=torch.int64, device=pc.device)[:total].view(torch.uint64)
+        if n:
+            lib = L.lib()
+            if erased is None:
+                eprm = E.check_params(grow, 4, tol, 16)             # n_tiles = 0: the stats launch alone
+                erows_ptr = res.data_ptr() + n * ROW_DTYPE.itemsize
+                L.check(lib.ctd_erase_text(ejobs_ptr, n, pages_ptr, n_pages, C.byref(eprm), erows_ptr, pc.st.cuda_stream),
+                        "ctd_erase_text")
+            owned = (nw * (win[:, 3] - win[:, 1]))[~too_large]
+            prm.max_words = int(owned.max()) if len(owned) else 0
+            L.check(lib.ctd_balloon_regions(jobs_ptr, n, pages_ptr, n_pages, erows_ptr, C.byref(prm), res.data_ptr(),
+                                            bits.data_ptr() if total else None, pc.st.cuda_stream), "ctd_balloon_regions")
+        host = pc.rows(res, np.uint8, n * (ROW_DTYPE.itemsize + rs))
     rows = host[: n * ROW_DTYPE.itemsize].view(ROW_DTYPE)
     erows = erased.rows if erased is not None else host[n * ROW_DTYPE.itemsize: n * (ROW_DTYPE.itemsize + rs)].view(E.ROW_DTYPE)
     if erased is not None and not np.array_equal(rows["n_seed"][rows["status"] == L.BALLOON_OK],

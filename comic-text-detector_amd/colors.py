@@ -16,8 +16,6 @@ fallback: without a GPU it raises `CtdError` like the rest of the package.
 """
 from __future__ import annotations
 
-import contextlib
-import ctypes as C
 from collections import namedtuple
 from typing import Optional, Sequence
 
@@ -25,18 +23,14 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .regions import Page, _batch_lines, _check_pages, _device_pages
+from .pagecall import Page, PageCall, blk_lists_of, check_pages, table_dtype
+from .regions import batch_lines
 
 __all__ = ["line_colors", "LineColors", "BlockColors", "color_rows", "JOB_DTYPE", "OUT_DTYPE"]
 
-# numpy views of `ctd_color_job` / `ctd_line_color` (include/ctd_hip.h; _lib.CtdColorJob / _lib.CtdLineColor)
-JOB_DTYPE = np.dtype([("page_dev", "<u8"), ("mask_dev", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i4"), ("mask_pitch", "<i4"),
-                      ("quad", "<i4", (8,))])
-OUT_DTYPE = np.dtype([("n_fg", "<i8"), ("s_fg", "<i8", (3,)), ("n_bg", "<i8"), ("s_bg", "<i8", (3,)), ("g_on", "<i8"),
-                      ("g_off", "<i8"), ("n_on", "<i4"), ("n_off", "<i4"), ("status", "<i4"), ("fg", "u1", (3,)), ("bg", "u1", (3,)),
-                      ("pad_", "u1", (6,))])
-assert JOB_DTYPE.itemsize == C.sizeof(L.CtdColorJob) == 64
-assert OUT_DTYPE.itemsize == C.sizeof(L.CtdLineColor) == 104
+# numpy views of `ctd_color_job` / `ctd_line_color` (include/ctd_hip.h)
+JOB_DTYPE = table_dtype(L.CtdColorJob)
+OUT_DTYPE = table_dtype(L.CtdLineColor)
 
 BlockColors = namedtuple("BlockColors", "index valid fg bg")
 BlockColors.__doc__ = """`LineColors.blocks()`: `index` (m,2) i32 = (page, block) of every block that has lines, in order; `valid[j]`
@@ -46,7 +40,7 @@ False where none of the block's lines has status OK / NO_CONTRAST (fg / bg are 0
 def color_rows(pages: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], page_of, quads,
                stream: Optional[torch.cuda.Stream] = None) -> np.ndarray:
     """`ctd_line_colors`: row i = the rule of include/ctd_hip.h on (pages[page_of[i]], masks[page_of[i]], quads[i]).  `pages`
-    (H,W,3) / `masks` (H,W): dense uint8 device tensors as `regions._device_pages` returns them (any row pitch); quads (n,8)
+    (H,W,3) / `masks` (H,W): dense uint8 device tensors as `pagecall.device_pages` returns them (any row pitch); quads (n,8)
     i32.  One upload, ONE launch, one download; returns the rows on the host as an `OUT_DTYPE` array (synchronises `stream`,
     default the current stream of the pages' device)."""
     quads = np.ascontiguousarray(np.asarray(quads, np.int32).reshape(-1, 8))
@@ -56,23 +50,15 @@ def color_rows(pages: Sequence[torch.Tensor], masks: Sequence[torch.Tensor], pag
     if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in list(pages) + list(masks)):
         raise L.CtdError("the kernel reads its pages and masks in device memory (no CPU fallback)")
     page_of = np.asarray(page_of, np.int64).reshape(n)
-    dev = pages[0].device
-    pitch = np.array([p.stride(0) for p in pages], np.int64)
-    mpitch = np.array([m.stride(0) for m in masks], np.int64)
-    if pitch.max() >= 2 ** 31 or mpitch.max() >= 2 ** 31:
-        raise ValueError("row pitch beyond int32")
-    jobs = np.zeros((n,), JOB_DTYPE)
-    jobs["page_dev"] = np.array([p.data_ptr() for p in pages], np.uint64)[page_of]
-    jobs["mask_dev"] = np.array([m.data_ptr() for m in masks], np.uint64)[page_of]
-    jobs["H"] = np.array([p.shape[0] for p in pages], np.int32)[page_of]
-    jobs["W"] = np.array([p.shape[1] for p in pages], np.int32)[page_of]
-    jobs["pitch"], jobs["mask_pitch"], jobs["quad"] = pitch[page_of], mpitch[page_of], quads
-    with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev)
-        tab = torch.from_numpy(jobs.view(np.uint8)).to(dev)
-        out = torch.empty((n * OUT_DTYPE.itemsize,), dtype=torch.uint8, device=dev)
-        L.check(L.lib().ctd_line_colors(tab.data_ptr(), n, out.data_ptr(), st.cuda_stream), "ctd_line_colors")
-        rows = out.cpu().numpy().view(OUT_DTYPE)             # stream-ordered: behind the launch
+    with PageCall("font colours run", pages, stream) as pc:
+        P, M = pc.pages(pages, dense=True), pc.pages(masks, dense=True)
+        jobs = np.zeros((n,), JOB_DTYPE)
+        jobs["page_dev"], jobs["mask_dev"], jobs["H"], jobs["W"] = P.ptr[page_of], M.ptr[page_of], P.H[page_of], P.W[page_of]
+        jobs["pitch"], jobs["mask_pitch"], jobs["quad"] = P.pitch[page_of], M.pitch[page_of], quads
+        tab = pc.upload([jobs])[0]
+        out = torch.empty((n * OUT_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+        L.check(L.lib().ctd_line_colors(tab.data_ptr(), n, out.data_ptr(), pc.st.cuda_stream), "ctd_line_colors")
+        rows = pc.rows(out, OUT_DTYPE, n)
     return rows
 
 
@@ -107,7 +93,7 @@ class LineColors:
             return BlockColors(np.zeros((0, 2), np.int32), np.zeros((0,), bool), z, z.copy())
         key = self.index[:, :2]
         first = np.ones((n,), bool)
-        first[1:] = (key[1:] != key[:-1]).any(axis=1)        # lines come block by block (`regions._batch_lines`)
+        first[1:] = (key[1:] != key[:-1]).any(axis=1)        # lines come block by block (`regions.batch_lines`)
         starts = np.nonzero(first)[0]
         use = ((self.status == L.COLOR_OK) | (self.status == L.COLOR_NO_CONTRAST)).astype(np.int64)
         pool = lambda col: np.add.reduceat(col * (use if col.ndim == 1 else use[:, None]), starts, axis=0)   # noqa: E731
@@ -124,7 +110,7 @@ class LineColors:
         `TextBlock`s, a `BlockList` or a result triple): `blk.get_font_colors()` then returns exactly the pooled colours.
         Blocks without a valid line are left untouched.  Returns `blocks()`."""
         bc = self.blocks()
-        lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in blk_lists]
+        lists = blk_lists_of(blk_lists)
         for (pg, b), ok, fg, bg in zip(bc.index.tolist(), bc.valid.tolist(), bc.fg.tolist(), bc.bg.tolist()):
             if ok:
                 lists[pg][b].set_font_colors(fg, bg, accumulate=True)
@@ -148,14 +134,10 @@ def line_colors(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequenc
     `COLOR_NO_CONTRAST`, the second as the mean of whatever falls on each side of the grey split."""
     if len(pages) != len(blk_lists) or len(masks) != len(pages):
         raise ValueError("one mask and one blk_list per page")
-    _check_pages(pages, masks, "BGR ", nonempty=False)
-    index, quads = _batch_lines(blk_lists)[:2]
+    check_pages(pages, masks, "BGR ", nonempty=False)
+    index, quads = batch_lines(blk_lists)[:2]
     if len(index) == 0:
         return LineColors(index, np.zeros((0,), OUT_DTYPE))
-    if not torch.cuda.is_available():
-        raise L.CtdError("font colours run on the GPU and there is none (no CPU fallback)")
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        pages, _, device = _device_pages(pages, device)
-        masks = _device_pages(masks, device)[0]
-        rows = color_rows(pages, masks, index[:, 0], quads, None)
+    with PageCall("font colours run", pages, stream, device) as pc:
+        rows = color_rows(pc.pages(pages).t, pc.pages(masks).t, index[:, 0], quads)
     return LineColors(index, rows)

@@ -33,6 +33,7 @@ import torch
 from . import _lib as L
 from . import backend as BK
 from . import postproc as PP
+from .pagecall import blk_lists_of
 from .tail import bind_thread, thread_tail
 from .textblock import TextBlock
 from .textmask import (REFINEMASK_ANNOTATION, REFINEMASK_INPAINT, refine_mask, refine_mask_batch,   # noqa: F401
@@ -515,6 +516,16 @@ class TextDetector:
         return thread_tail(dev).run(gpu, metas, blks, mask_u8, prob, bitmap, self.conf_thresh, self.nms_thresh, 0.6, True,
                                     refine_mode, keep_undetected_mask, None, want_extras)
 
+    def _on_device(self, pages: Sequence[Page]):
+        """`pages` for a page call on the detector's device: host (H,W,3) pages go up through the pinned staging ring
+        (`_stage`) and the current stream waits for the copy; device pages, and pages the ring does not take (grey ones: the
+        call uploads or refuses them itself), pass through."""
+        if not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
+                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
+            pages, ev = self._stage(pages)
+            torch.cuda.current_stream(self.net.device).wait_event(ev)
+        return pages
+
     def line_regions(self, pages: Sequence[Page], results, textheight: int = 48):
         """The OCR stage's input for a detected batch: the `TextBlock.get_transformed_region` crop of every text line of
         every page, in one kernel launch on the detector's device (`regions.line_regions`; returns its `LineRegions`).
@@ -522,26 +533,14 @@ class TextDetector:
         just the blk_lists (lists of `TextBlock`s or `BlockList`s).  Host pages are uploaded through the pinned staging
         ring (`_stage`); pages already on the device are read where they are."""
         from . import regions
-        blk_lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in results]
-        dev = self.net.device
-        if not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
-                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
-            pages, ev = self._stage(pages)
-            torch.cuda.current_stream(dev).wait_event(ev)
-        return regions.line_regions(pages, blk_lists, textheight, device=dev)
+        return regions.line_regions(self._on_device(pages), blk_lists_of(results), textheight, device=self.net.device)
 
     def line_batches(self, pages: Sequence[Page], results, **kw):
         """`line_regions`' lines as the input tensors of an OCR network -- width-bucketed, normalised, padded per bucket -- in
         one kernel launch on the detector's device (`regions.line_batches` and its keywords; returns its `LineBatches`).
         `pages` / `results` as for `line_regions`."""
         from . import regions
-        blk_lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in results]
-        dev = self.net.device
-        if not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
-                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
-            pages, ev = self._stage(pages)
-            torch.cuda.current_stream(dev).wait_event(ev)
-        return regions.line_batches(pages, blk_lists, device=dev, **kw)
+        return regions.line_batches(self._on_device(pages), blk_lists_of(results), device=self.net.device, **kw)
 
     def font_colors(self, pages: Sequence[Page], results, apply: bool = True):
         """Fill and surround colour of every text line of a detected batch in one kernel launch on the detector's device
@@ -552,12 +551,7 @@ class TextDetector:
         from . import colors
         masks = [r[1] for r in results]
         blk_lists = [r[2] for r in results]
-        dev = self.net.device
-        if not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
-                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
-            pages, ev = self._stage(pages)
-            torch.cuda.current_stream(dev).wait_event(ev)
-        lc = colors.line_colors(pages, masks, blk_lists, device=dev)
+        lc = colors.line_colors(self._on_device(pages), masks, blk_lists, device=self.net.device)
         if apply:
             lc.apply(blk_lists)
         return lc
@@ -572,12 +566,8 @@ class TextDetector:
         masks = [r[1] for r in results]
         blk_lists = [r[2] for r in results]
         erase.check_params(*(kw.get(k, d) for k, d in (("grow", 2), ("ring", 4), ("tol", 12), ("min_ring", 16))))
-        dev = self.net.device
-        if len(pages) and not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
-                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
-            pages, ev = self._stage(pages)
-            torch.cuda.current_stream(dev).wait_event(ev)
-        return erase.erase_text(pages, masks, blk_lists, device=dev, **kw)
+        pages = self._on_device(pages)                        # no page: nothing is staged
+        return erase.erase_text(pages, masks, blk_lists, device=self.net.device, **kw)
 
     def balloons(self, pages: Sequence[Page], results, erased=None, **kw):
         """The balloon region of every block of a detected batch -- the free area around the text of each block that stands
@@ -591,12 +581,8 @@ class TextDetector:
         masks = [r[1] for r in results]
         blk_lists = [r[2] for r in results]
         balloons.check_params(*(kw.get(k, d) for k, d in (("grow", 2), ("tol", 12), ("reach", 8), ("reach_min", 32))))
-        dev = self.net.device
-        if len(pages) and not all(isinstance(p, torch.Tensor) and p.is_cuda for p in pages) and \
-                all(getattr(p, "ndim", 0) == 3 and p.shape[2] == 3 for p in pages):
-            pages, ev = self._stage(pages)
-            torch.cuda.current_stream(dev).wait_event(ev)
-        return balloons.balloon_regions(pages, masks, blk_lists, erased=erased, device=dev, **kw)
+        pages = self._on_device(pages)                        # no page: nothing is staged
+        return balloons.balloon_regions(pages, masks, blk_lists, erased=erased, device=self.net.device, **kw)
 
     def layout_boxes(self, pages: Sequence[Page], results, erased=None, regions=None, inset: int = 2, **balloon_kw):
         """The box a typesetter lays the translated text into, for every block of a detected batch: the largest axis-aligned

@@ -17,7 +17,6 @@ median.  There is no per-block Python and no CPU fallback: without a GPU it rais
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from typing import List, Optional, Sequence
 
@@ -25,21 +24,15 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .regions import Page, _check_pages, _device_pages, _views
+from .pagecall import Page, PageCall, blk_lists_of, check_pages, check_pitch, table_dtype
 from .textblock import BlockList
 
 __all__ = ["erase_text", "ErasedPages", "erase_tables", "JOB_DTYPE", "PAGE_DTYPE", "ROW_DTYPE"]
 
-# numpy views of `ctd_erase_job` / `ctd_erase_page` / `ctd_erase_row` (include/ctd_hip.h; _lib.CtdEraseJob / ...)
-JOB_DTYPE = np.dtype([("page", "<i4"), ("xyxy", "<i4", (4,)), ("pad_", "<i4", (3,))])
-PAGE_DTYPE = np.dtype([("page_dev", "<u8"), ("mask_dev", "<u8"), ("out_dev", "<u8"), ("rest_dev", "<u8"), ("H", "<i4"), ("W", "<i4"),
-                       ("pitch", "<i4"), ("mask_pitch", "<i4"), ("out_pitch", "<i4"), ("rest_pitch", "<i4"), ("block0", "<i4"),
-                       ("n_blocks", "<i4"), ("tile0", "<i4"), ("pad_", "<i4")])
-ROW_DTYPE = np.dtype([("status", "<i4"), ("n_fill", "<i4"), ("n_ring", "<i4"), ("cnt", "<i4", (3,)), ("med", "u1", (3,)),
-                      ("pad_", "u1", (5,))])
-assert JOB_DTYPE.itemsize == C.sizeof(L.CtdEraseJob) == 32
-assert PAGE_DTYPE.itemsize == C.sizeof(L.CtdErasePage) == 72
-assert ROW_DTYPE.itemsize == C.sizeof(L.CtdEraseRow) == 32
+# numpy views of `ctd_erase_job` / `ctd_erase_page` / `ctd_erase_row` (include/ctd_hip.h)
+JOB_DTYPE = table_dtype(L.CtdEraseJob)
+PAGE_DTYPE = table_dtype(L.CtdErasePage)
+ROW_DTYPE = table_dtype(L.CtdEraseRow)
 
 
 def check_params(grow, ring, tol, min_ring) -> L.CtdEraseParams:
@@ -78,6 +71,14 @@ def erase_tables(boxes: Sequence[np.ndarray], shapes: Sequence) -> tuple:
     if n_tiles >= 2 ** 31 or n >= 2 ** 31:
         raise ValueError("too many pixels or blocks for one call")
     return jobs, np.cumsum(counts) - counts, counts, np.cumsum(tiles) - tiles, n_tiles
+
+
+def page_table(P, M, block0, counts) -> np.ndarray:
+    """The input columns of the `PAGE_DTYPE` table, which `balloons` reads too; P, M: `PageCall.pages` of pages and masks."""
+    pt = np.zeros((len(P.t),), PAGE_DTYPE)
+    pt["page_dev"], pt["mask_dev"], pt["H"], pt["W"], pt["pitch"], pt["mask_pitch"] = P.ptr, M.ptr, P.H, P.W, P.pitch, M.pitch
+    pt["block0"], pt["n_blocks"] = block0, counts
+    return pt
 
 
 class ErasedPages:
@@ -123,45 +124,28 @@ def erase_text(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequence
     prm = check_params(grow, ring, tol, min_ring)
     if len(pages) != len(blk_lists) or len(masks) != len(pages):
         raise ValueError("one mask and one blk_list per page")
-    _check_pages(pages, masks, "BGR ")
-    lists = [r[2] if isinstance(r, tuple) and len(r) == 3 else r for r in blk_lists]
-    boxes = [_page_boxes(b) for b in lists]
+    check_pages(pages, masks, "BGR ")
+    boxes = [_page_boxes(b) for b in blk_lists_of(blk_lists)]
     jobs, block0, counts, tile0, n_tiles = erase_tables(boxes, [tuple(p.shape[:2]) for p in pages])
     n, n_pages = len(jobs), len(pages)
     index = np.stack([jobs["page"], np.arange(n) - np.repeat(block0, counts)], axis=1).astype(np.int32) if n else \
         np.zeros((0, 2), np.int32)
     if n_pages == 0:
         return ErasedPages([], [], index, np.zeros((0,), ROW_DTYPE))
-    if not torch.cuda.is_available():
-        raise L.CtdError("erasing text runs on the GPU and there is none (no CPU fallback)")
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        pages, _, device = _device_pages(pages, device)
-        masks = _device_pages(masks, device)[0]
-        with torch.cuda.device(device):
-            st = torch.cuda.current_stream(device)
-            H = np.array([p.shape[0] for p in pages], np.int64)
-            W = np.array([p.shape[1] for p in pages], np.int64)
-            pitch = np.array([p.stride(0) for p in pages], np.int64)
-            mpitch = np.array([m.stride(0) for m in masks], np.int64)
-            if max(pitch.max(), mpitch.max(), (3 * W).max()) >= 2 ** 31:
-                raise ValueError("row pitch beyond int32")
-            # one buffer behind all the outputs: the pages, then the rest masks, each on a 256-byte boundary
-            views = _views([(int(h), int(w), 3) for h, w in zip(H, W)] + [(int(h), int(w)) for h, w in zip(H, W)], device)[1]
-            out, rest = views[:n_pages], views[n_pages:]
-            table = np.zeros((n * JOB_DTYPE.itemsize + n_pages * PAGE_DTYPE.itemsize,), np.uint8)   # jobs, then pages: one upload
-            table[: n * JOB_DTYPE.itemsize] = jobs.view(np.uint8)
-            pt = table[n * JOB_DTYPE.itemsize:].view(PAGE_DTYPE)
-            pt["page_dev"] = [p.data_ptr() for p in pages]
-            pt["mask_dev"] = [m.data_ptr() for m in masks]
-            pt["out_dev"] = [o.data_ptr() for o in out]
-            pt["rest_dev"] = [r.data_ptr() for r in rest]
-            pt["H"], pt["W"], pt["pitch"], pt["mask_pitch"], pt["out_pitch"], pt["rest_pitch"] = H, W, pitch, mpitch, 3 * W, W
-            pt["block0"], pt["n_blocks"], pt["tile0"] = block0, counts, tile0
-            prm.n_tiles = n_tiles
-            tab = torch.from_numpy(table).to(device)
-            rows_dev = torch.empty((max(n, 1) * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=device)
-            L.check(L.lib().ctd_erase_text(tab.data_ptr(), n, tab.data_ptr() + n * JOB_DTYPE.itemsize, n_pages, C.byref(prm),
-                                           rows_dev.data_ptr(), st.cuda_stream), "ctd_erase_text")
-            rows = rows_dev.cpu().numpy().view(ROW_DTYPE)[:n] if n else np.zeros((0,), ROW_DTYPE)   # stream-ordered: behind the launches
-            st.synchronize()
+    with PageCall("erasing text runs", pages, stream, device) as pc:
+        P, M = pc.pages(pages), pc.pages(masks)
+        check_pitch(3 * P.W)
+        # one buffer behind all the outputs: the pages, then the rest masks, each on a 256-byte boundary
+        views = pc.outputs([(int(h), int(w), 3) for h, w in zip(P.H, P.W)] + [(int(h), int(w)) for h, w in zip(P.H, P.W)])
+        out, rest = views[:n_pages], views[n_pages:]
+        pt = page_table(P, M, block0, counts)
+        pt["out_dev"] = [o.data_ptr() for o in out]
+        pt["rest_dev"] = [r.data_ptr() for r in rest]
+        pt["out_pitch"], pt["rest_pitch"], pt["tile0"] = 3 * P.W, P.W, tile0
+        prm.n_tiles = n_tiles
+        _, (jobs_ptr, pages_ptr) = pc.upload([jobs, pt])                    # jobs, then pages: one upload
+        rows_dev = torch.empty((max(n, 1) * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+        L.check(L.lib().ctd_erase_text(jobs_ptr, n, pages_ptr, n_pages, C.byref(prm), rows_dev.data_ptr(), pc.st.cuda_stream),
+                "ctd_erase_text")
+        rows = pc.rows(rows_dev, ROW_DTYPE, n) if n else np.zeros((0,), ROW_DTYPE)
     return ErasedPages(out, rest, index, rows)

@@ -17,7 +17,6 @@ There is no per-page Python and no CPU fallback: without a GPU it raises `CtdErr
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from typing import List, Optional, Sequence
 
@@ -25,17 +24,13 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .regions import Page, _check_pages, _device_pages, _views
+from .pagecall import Page, PageCall, check_pages, table_dtype
 
 __all__ = ["fill_rest", "FilledPages", "fill_tables", "level_shapes", "PAGE_DTYPE", "ROW_DTYPE"]
 
-# numpy views of `ctd_fill_page` / `ctd_fill_row` (include/ctd_hip.h; _lib.CtdFillPage / CtdFillRow)
-PAGE_DTYPE = np.dtype([("page_dev", "<u8"), ("hole_dev", "<u8"), ("out_dev", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i4"),
-                       ("hole_pitch", "<i4"), ("out_pitch", "<i4"), ("tile0", "<i4"), ("lvl0", "<i8")])
-ROW_DTYPE = np.dtype([("status", "<i4"), ("n_hole", "<i4"), ("levels", "<i4"), ("top", "u1", (3,)), ("pad_", "u1", (17,))])
-assert PAGE_DTYPE.itemsize == C.sizeof(L.CtdFillPage) == 56
-assert ROW_DTYPE.itemsize == C.sizeof(L.CtdFillRow) == 32
-assert C.sizeof(L.CtdFillParams) == 32
+# numpy views of `ctd_fill_page` / `ctd_fill_row` (include/ctd_hip.h)
+PAGE_DTYPE = table_dtype(L.CtdFillPage)
+ROW_DTYPE = table_dtype(L.CtdFillRow)
 
 STORED_LEVELS = 6          # levels 1 .. 6 pass through the scratch buffer; the coarser ones never leave the chip
 
@@ -108,38 +103,24 @@ def fill_rest(pages: Sequence[Page], holes: Sequence[Page], stream: Optional[tor
     the pages' device) and waits for the result; see `FilledPages`."""
     if len(holes) != len(pages):
         raise ValueError("one hole mask per page")
-    _check_pages(pages, holes, mask="hole mask")
+    check_pages(pages, holes, mask="hole mask")
     tile0, n_tiles, lvl0, scratch_dwords, _ = fill_tables([tuple(p.shape[:2]) for p in pages])
     n_pages = len(pages)
     if n_pages == 0:
         return FilledPages([], np.zeros((0,), ROW_DTYPE))
-    if not torch.cuda.is_available():
-        raise L.CtdError("filling holes runs on the GPU and there is none (no CPU fallback)")
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        pages, _, device = _device_pages(pages, device)
-        holes = _device_pages(holes, device)[0]
-        with torch.cuda.device(device):
-            st = torch.cuda.current_stream(device)
-            H = np.array([p.shape[0] for p in pages], np.int64)
-            W = np.array([p.shape[1] for p in pages], np.int64)
-            pitch = np.array([p.stride(0) for p in pages], np.int64)
-            hpitch = np.array([m.stride(0) for m in holes], np.int64)
-            if max(pitch.max(), hpitch.max()) >= 2 ** 31:
-                raise ValueError("row pitch beyond int32")
-            # one buffer behind all the outputs, each on a 256-byte boundary
-            out = _views([(int(h), int(w), 3) for h, w in zip(H, W)], device)[1]
-            pt = np.zeros((n_pages,), PAGE_DTYPE)
-            pt["page_dev"] = [p.data_ptr() for p in pages]
-            pt["hole_dev"] = [m.data_ptr() for m in holes]
-            pt["out_dev"] = [o.data_ptr() for o in out]
-            pt["H"], pt["W"], pt["pitch"], pt["hole_pitch"], pt["out_pitch"] = H, W, pitch, hpitch, 3 * W
-            pt["tile0"], pt["lvl0"] = tile0, lvl0
-            tab = torch.from_numpy(pt.view(np.uint8)).to(device)
-            scratch = torch.empty((scratch_dwords,), dtype=torch.int32, device=device)
-            rows_dev = torch.empty((n_pages * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=device)
-            prm = L.CtdFillParams(n_tiles)
-            L.check(L.lib().ctd_fill_rest(tab.data_ptr(), n_pages, C.byref(prm), scratch.data_ptr(), rows_dev.data_ptr(),
-                                          st.cuda_stream), "ctd_fill_rest")
-            rows = rows_dev.cpu().numpy().view(ROW_DTYPE)           # stream-ordered: behind the launches
-            st.synchronize()
+    with PageCall("filling holes runs", pages, stream, device) as pc:
+        P, M = pc.pages(pages), pc.pages(holes)
+        # one buffer behind all the outputs, each on a 256-byte boundary
+        out = pc.outputs([(int(h), int(w), 3) for h, w in zip(P.H, P.W)])
+        pt = np.zeros((n_pages,), PAGE_DTYPE)
+        pt["page_dev"], pt["hole_dev"], pt["out_dev"] = P.ptr, M.ptr, [o.data_ptr() for o in out]
+        pt["H"], pt["W"], pt["pitch"], pt["hole_pitch"], pt["out_pitch"] = P.H, P.W, P.pitch, M.pitch, 3 * P.W
+        pt["tile0"], pt["lvl0"] = tile0, lvl0
+        tab = pc.upload([pt])[0]
+        scratch = torch.empty((scratch_dwords,), dtype=torch.int32, device=pc.device)
+        rows_dev = torch.empty((n_pages * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+        prm = L.CtdFillParams(n_tiles)
+        L.check(L.lib().ctd_fill_rest(tab.data_ptr(), n_pages, C.byref(prm), scratch.data_ptr(), rows_dev.data_ptr(),
+                                      pc.st.cuda_stream), "ctd_fill_rest")
+        rows = pc.rows(rows_dev, ROW_DTYPE, n_pages)
     return FilledPages(out, rows)

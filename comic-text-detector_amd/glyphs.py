@@ -30,7 +30,6 @@ layer of its own.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from typing import Optional, Sequence
 
@@ -38,26 +37,17 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .regions import Page
-from .typeset import (MAX_COORD, ROW_DTYPE, TILE_DTYPE, TypesetPages, _bin_tiles, _ints, _layer_args, _layers, _open_pages, _pack,
-                      _rects)
+from .pagecall import Page, PageCall, need_gpu, table_dtype
+from .typeset import MAX_COORD, ROW_DTYPE, TILE_DTYPE, TypesetPages, _bin_tiles, _ints, _layer_args, _layers, _open_pages, _rects
 
 __all__ = ["GlyphAtlas", "glyph_tables", "typeset_glyphs", "flow", "LAYER_DTYPE", "PLACE_DTYPE", "RECORD_DTYPE", "OutlineFont",
            "segments_from_ops", "outline_boxes", "flow_outlines", "fit", "RASTER_JOB_DTYPE"]
 
-# numpy views of `ctd_glyph_layer` / `_place` / `_record` (include/ctd_hip.h; the _lib.CtdGlyph* mirrors)
-LAYER_DTYPE = np.dtype([("page", "<i4"), ("clip", "<i4", (4,)), ("fill", "u1", (3,)), ("stroke", "u1", (3,)), ("radius", "u1"),
-                        ("pad_", "u1"), ("pad2_", "<i4")])
-PLACE_DTYPE = np.dtype([("layer", "<i4"), ("glyph", "<i4"), ("x", "<i4"), ("y", "<i4")])
-RECORD_DTYPE = np.dtype([("off", "<i8"), ("w", "<i4"), ("h", "<i4")])
-assert LAYER_DTYPE.itemsize == C.sizeof(L.CtdGlyphLayer) == 32
-assert PLACE_DTYPE.itemsize == C.sizeof(L.CtdGlyphPlace) == 16
-assert RECORD_DTYPE.itemsize == C.sizeof(L.CtdGlyphRecord) == 16
-assert C.sizeof(L.CtdGlyphParams) == 32
-# `ctd_raster_job` (the _lib.CtdRasterJob mirror)
-RASTER_JOB_DTYPE = np.dtype([("off", "<i8"), ("w", "<i4"), ("h", "<i4"), ("bx", "<i4"), ("by", "<i4"), ("seg_first", "<i4"),
-                             ("seg_count", "<i4"), ("scale", "<i4"), ("pad_", "<i4")])
-assert RASTER_JOB_DTYPE.itemsize == C.sizeof(L.CtdRasterJob) == 40
+# numpy views of `ctd_glyph_layer` / `_place` / `_record` and `ctd_raster_job` (include/ctd_hip.h)
+LAYER_DTYPE = table_dtype(L.CtdGlyphLayer)
+PLACE_DTYPE = table_dtype(L.CtdGlyphPlace)
+RECORD_DTYPE = table_dtype(L.CtdGlyphRecord)
+RASTER_JOB_DTYPE = table_dtype(L.CtdRasterJob)
 
 
 class GlyphAtlas:
@@ -70,8 +60,7 @@ class GlyphAtlas:
     `rasterise(font, gids, size)` appends instances of an `OutlineFont`'s glyphs without any coverage crossing the bus."""
 
     def __init__(self, device=None):
-        if not torch.cuda.is_available():
-            raise L.CtdError("the glyph atlas lives on the GPU and there is none (no CPU fallback)")
+        need_gpu("the glyph atlas lives")
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.sizes = np.zeros((0, 2), np.int64)
         self.offsets = np.zeros((0,), np.int64)
@@ -118,7 +107,7 @@ class GlyphAtlas:
             raise ValueError("too many glyphs")
         rec = np.zeros((k,), RECORD_DTYPE)
         rec["off"], rec["h"], rec["w"] = off, sizes[:, 0], sizes[:, 1]
-        with torch.cuda.device(self.device):
+        with PageCall("the glyph atlas lives", (), None, self.device):       # waits: a later call may run on any stream
             self._cov = self._grown(self._cov, self.nbytes, self.nbytes + total)
             self._rec = self._grown(self._rec, n0 * RECORD_DTYPE.itemsize, (n0 + k) * RECORD_DTYPE.itemsize)
             if total:
@@ -129,7 +118,6 @@ class GlyphAtlas:
         self.sizes, self.offsets = np.concatenate([self.sizes, sizes]), np.concatenate([self.offsets, off])
         self.advance, self.bearing = np.concatenate([self.advance, advance]), np.concatenate([self.bearing, bearing])
         self.nbytes += total
-        torch.cuda.current_stream(self.device).synchronize()                # a later call may run on any stream
         return np.arange(n0, n0 + k, dtype=np.int32)
 
     def rasterise(self, font: "OutlineFont", gids, size) -> np.ndarray:
@@ -179,19 +167,17 @@ class GlyphAtlas:
             if font.device != self.device:
                 raise ValueError("the font's outlines live on another device")
             want = np.where((area == 0) | (font.seg_count[new_g] == 0), L.RASTER_EMPTY, L.RASTER_OK)
-            with torch.cuda.device(self.device):
-                st = torch.cuda.current_stream(self.device)
+            with PageCall("the glyph atlas lives", (), None, self.device) as pc:
                 cov = self._grown(self._cov, self.nbytes, self.nbytes + total)
                 recs = self._grown(self._rec, n0 * RECORD_DTYPE.itemsize, (n0 + k) * RECORD_DTYPE.itemsize)
-                blob, at = _pack([jobs, rec])               # one upload: the job table and the new records
-                tab = torch.from_numpy(blob).to(self.device)
+                tab, (jobs_ptr, rec_ptr) = pc.upload([jobs, rec])       # one upload: the job table and the new records
                 status_dev = torch.empty((k,), dtype=torch.int32, device=self.device)
-                L.check(L.lib().ctd_rasterise_glyphs(segs_dev.data_ptr(), font.n_segs, tab.data_ptr() + int(at[0]), k, cov.data_ptr(),
-                                                     self.nbytes + total, status_dev.data_ptr(), st.cuda_stream),
+                L.check(L.lib().ctd_rasterise_glyphs(segs_dev.data_ptr(), font.n_segs, jobs_ptr, k, cov.data_ptr(),
+                                                     self.nbytes + total, status_dev.data_ptr(), pc.st.cuda_stream),
                         "ctd_rasterise_glyphs")
-                recs[n0 * RECORD_DTYPE.itemsize: (n0 + k) * RECORD_DTYPE.itemsize].copy_(tab[int(at[1]): int(at[1]) + rec.nbytes])
-                status = status_dev.cpu().numpy()           # stream-ordered: behind the launch
-                st.synchronize()
+                at = rec_ptr - tab.data_ptr()
+                recs[n0 * RECORD_DTYPE.itemsize: (n0 + k) * RECORD_DTYPE.itemsize].copy_(tab[at: at + rec.nbytes])
+                status = pc.rows(status_dev, np.int32, k)
             if not np.array_equal(status, want):
                 raise L.CtdError(f"ctd_rasterise_glyphs: status {status.tolist()} where {want.tolist()} was expected")
             self._cov, self._rec = cov, recs
@@ -332,26 +318,21 @@ def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, 
     device = atlas.device if device is None else torch.device(device)
     if device != atlas.device:
         raise ValueError("the atlas lives on another device")
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        with torch.cuda.device(device):
-            st = torch.cuda.current_stream(device)
-            out, pt, clip4 = _open_pages(pages, shapes, page_of, clip, inplace, device)
-            rows = np.zeros((nl,), ROW_DTYPE)
-            if n_tiles:
-                lt = np.zeros((nl,), LAYER_DTYPE)
-                lt["page"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = page_of, clip4, fill, stroke, r
-                qt = np.zeros((n,), PLACE_DTYPE)
-                qt["layer"], qt["glyph"], qt["x"], qt["y"] = layer_of, glyph, xy[:, 0], xy[:, 1]
-                blob, at = _pack([pt, lt, qt, tiles, entries])     # one upload: the tables and the placements
-                tab = torch.from_numpy(blob).to(device)
-                rows_dev = torch.empty((nl * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=device)
-                prm = L.CtdGlyphParams(nl, n_pages, n_tiles, len(entries), n, len(atlas), atlas.nbytes)
-                ptr = [tab.data_ptr() + int(a) for a in at]
-                L.check(L.lib().ctd_typeset_glyphs(ptr[0], ptr[1], ptr[2], atlas._rec.data_ptr(), ptr[3], ptr[4],
-                                                   atlas._cov.data_ptr(), C.byref(prm), rows_dev.data_ptr(), st.cuda_stream),
-                        "ctd_typeset_glyphs")
-                rows = rows_dev.cpu().numpy().view(ROW_DTYPE)           # stream-ordered: behind the launch
-            st.synchronize()
+    with PageCall("typesetting runs", pages, stream, device) as pc:
+        out, pt, clip4 = _open_pages(pc, pages, shapes, page_of, clip, inplace)
+        rows = np.zeros((nl,), ROW_DTYPE)
+        if n_tiles:
+            lt = np.zeros((nl,), LAYER_DTYPE)
+            lt["page"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = page_of, clip4, fill, stroke, r
+            qt = np.zeros((n,), PLACE_DTYPE)
+            qt["layer"], qt["glyph"], qt["x"], qt["y"] = layer_of, glyph, xy[:, 0], xy[:, 1]
+            _, ptr = pc.upload([pt, lt, qt, tiles, entries])       # one upload: the tables and the placements
+            rows_dev = torch.empty((nl * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+            prm = L.CtdGlyphParams(nl, n_pages, n_tiles, len(entries), n, len(atlas), atlas.nbytes)
+            L.check(L.lib().ctd_typeset_glyphs(ptr[0], ptr[1], ptr[2], atlas._rec.data_ptr(), ptr[3], ptr[4],
+                                               atlas._cov.data_ptr(), C.byref(prm), rows_dev.data_ptr(), pc.st.cuda_stream),
+                    "ctd_typeset_glyphs")
+            rows = pc.rows(rows_dev, ROW_DTYPE, nl)
     tp = TypesetPages(out, rows, status, np.zeros((nl, 2), np.int64))
     tp.xy, tp.place_layer, tp.place_glyph = xy, layer_of, glyph             # per placement here, not per layer
     return tp

@@ -17,7 +17,6 @@ raises `CtdError` like the rest of the package.
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from typing import Optional
 
@@ -27,15 +26,13 @@ import torch
 from . import _lib as L
 from .balloons import ROW_DTYPE as BALLOON_ROW_DTYPE
 from .balloons import BalloonRegions
+from .pagecall import PageCall, table_dtype
 
 __all__ = ["layout_boxes", "LayoutBoxes", "box_anchors", "check_params", "JOB_DTYPE", "ROW_DTYPE"]
 
-# numpy views of `ctd_layout_job` / `ctd_layout_row` (include/ctd_hip.h; _lib.CtdLayoutJob / CtdLayoutRow)
-JOB_DTYPE = np.dtype([("win", "<i4", (4,)), ("ax", "<i4"), ("ay", "<i4"), ("word0", "<i8")])
-ROW_DTYPE = np.dtype([("status", "<i4"), ("n_inner", "<i4"), ("area", "<i4"), ("rect", "<i4", (4,)), ("a_area", "<i4"),
-                      ("a_rect", "<i4", (4,))])
-assert JOB_DTYPE.itemsize == C.sizeof(L.CtdLayoutJob) == 32
-assert ROW_DTYPE.itemsize == C.sizeof(L.CtdLayoutRow) == 48
+# numpy views of `ctd_layout_job` / `ctd_layout_row` (include/ctd_hip.h)
+JOB_DTYPE = table_dtype(L.CtdLayoutJob)
+ROW_DTYPE = table_dtype(L.CtdLayoutRow)
 
 
 def check_params(inset) -> L.CtdLayoutParams:
@@ -103,24 +100,18 @@ def layout_boxes(br: BalloonRegions, anchors=None, inset: int = 2, stream: Optio
         return LayoutBoxes(br.index, np.zeros((0,), ROW_DTYPE), anchors, inset)
     if not torch.cuda.is_available() or not br.bits.is_cuda:
         raise L.CtdError("layout boxes run on the GPU and there is none (no CPU fallback)")
-    device = br.bits.device
     jobs = np.zeros((n,), JOB_DTYPE)
     jobs["win"], jobs["ax"], jobs["ay"], jobs["word0"] = br.windows, anchors[:, 0], anchors[:, 1], br.word0
     owned = (br.nw * (br.windows[:, 3] - br.windows[:, 1]))[~br.too_large]
     prm.max_words, prm.n_rows = int(owned.max()) if len(owned) else 0, n
-    # one upload: the jobs, then the balloon rows as the balloon call returned them
     brows = np.ascontiguousarray(br.rows)
     if brows.dtype != BALLOON_ROW_DTYPE:
         raise ValueError("`br.rows` are not balloon rows")
-    table = np.concatenate([jobs.view(np.uint8), brows.view(np.uint8)])
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        with torch.cuda.device(device):
-            st = torch.cuda.current_stream(device)
-            tab = torch.from_numpy(table).to(device)
-            res = torch.empty((n * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=device)
-            L.check(L.lib().ctd_layout_boxes(tab.data_ptr(), n, tab.data_ptr() + n * JOB_DTYPE.itemsize,
-                                             br.bits.data_ptr() if prm.max_words else None, C.byref(prm), res.data_ptr(),
-                                             st.cuda_stream), "ctd_layout_boxes")
-            host = res.cpu().numpy()                                    # stream-ordered: behind the launch
-            st.synchronize()
-    return LayoutBoxes(br.index, host.view(ROW_DTYPE), anchors, inset)
+    with PageCall("layout boxes run", (), stream, br.bits.device) as pc:
+        # one upload: the jobs, then the balloon rows as the balloon call returned them
+        _, (jobs_ptr, brows_ptr) = pc.upload([jobs, brows])
+        res = torch.empty((n * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+        L.check(L.lib().ctd_layout_boxes(jobs_ptr, n, brows_ptr, br.bits.data_ptr() if prm.max_words else None, C.byref(prm),
+                                         res.data_ptr(), pc.st.cuda_stream), "ctd_layout_boxes")
+        rows = pc.rows(res, ROW_DTYPE, n)
+    return LayoutBoxes(br.index, rows, anchors, inset)

@@ -22,29 +22,24 @@ What is restated from cv2 here (four-point homography, the fixed-point linear wa
 """
 from __future__ import annotations
 
-import ctypes as C
-import math
 from collections import namedtuple
-from typing import List, Optional, Sequence, Union
+from typing import List, Optional, Sequence
 
 import numpy as np
 import torch
 
 from . import _lib as L
+from .pagecall import Page, PageCall, table_dtype
+from .pagecall import align as _align, check_pages as _check_pages, device_pages as _device_pages, views as _views  # noqa: F401
+# (the underscore names: plain aliases, kept for the tests that import them)
 from .textblock import LANGCLS2IDX, BlockList, TextBlock
 
 __all__ = ["line_regions", "LineRegions", "transforms", "warp", "JOB_DTYPE", "line_batches", "LineBatches", "batch_plan",
            "BatchPlan", "value_tables", "warp_batches", "BATCH_JOB_DTYPE"]
 
-# numpy view of `ctd_region_job` (include/ctd_hip.h; _lib.CtdRegionJob)
-JOB_DTYPE = np.dtype([("page_dev", "<u8"), ("H", "<i4"), ("W", "<i4"), ("C", "<i4"), ("pitch", "<i4"), ("Minv", "<f8", (9,)),
-                      ("w", "<i4"), ("h", "<i4"), ("rotate", "<i4"), ("pad_", "<i4"), ("out_off", "<i8")])
-assert JOB_DTYPE.itemsize == C.sizeof(L.CtdRegionJob)
-# numpy view of `ctd_region_batch_job` (_lib.CtdRegionBatchJob)
-BATCH_JOB_DTYPE = np.dtype([("warp", JOB_DTYPE), ("slot", "<i4"), ("rows", "<i4"), ("Wk", "<i4"), ("cut", "<i4")])
-assert BATCH_JOB_DTYPE.itemsize == C.sizeof(L.CtdRegionBatchJob) == 136
-
-Page = Union[np.ndarray, torch.Tensor]
+# numpy views of `ctd_region_job` / `ctd_region_batch_job` (include/ctd_hip.h)
+JOB_DTYPE = table_dtype(L.CtdRegionJob)
+BATCH_JOB_DTYPE = table_dtype(L.CtdRegionBatchJob)
 
 
 def transforms(quads, language, vertical, font_size, im_w, im_h, textheight=48):
@@ -123,72 +118,6 @@ class LineRegions:
                 f"{self.packed.numel()} bytes)")
 
 
-def _shape_of(a):
-    return tuple(a.shape), (a.dtype == torch.uint8 if isinstance(a, torch.Tensor) else np.asarray(a).dtype == np.uint8)
-
-
-def _check_pages(pages: Sequence[Page], masks: Optional[Sequence[Page]] = None, order: str = "", mask: str = "mask",
-                 nonempty: bool = True) -> None:
-    """The page arguments of the tail calls, on the host or on the device: ValueError unless every page is uint8 (H,W,3),
-    its mask (where masks are given, one a page) uint8 (H,W) of the page's size and, with `nonempty`, no side is 0.  `order`
-    ("BGR ") and `mask` ("hole mask") only word the message."""
-    for i, p in enumerate(pages):
-        ps, pu8 = _shape_of(p)
-        if not pu8 or len(ps) != 3 or ps[2] != 3:
-            raise ValueError(f"pages must be uint8 {order}(H,W,3)")
-        if masks is not None:
-            ms, mu8 = _shape_of(masks[i])
-            if not mu8 or ms != ps[:2]:
-                raise ValueError(f"a {mask} must be uint8 and have the shape of its page")
-        if nonempty and (ps[0] < 1 or ps[1] < 1):
-            raise ValueError("empty page")
-
-
-def _align(n: int, a: int = 256) -> int:
-    return (n + a - 1) // a * a
-
-
-def _views(shapes: Sequence[tuple], device) -> tuple:
-    """Uninitialised uint8 device tensors of `shapes`: views of ONE new allocation, in the order given, each on a 256-byte
-    boundary.  Returns (store, views)."""
-    sizes = [math.prod(s) for s in shapes]
-    offs = np.cumsum([0] + [_align(n) for n in sizes]).tolist()
-    store = torch.empty((offs[-1],), dtype=torch.uint8, device=device)
-    return store, [store[o: o + n].view(s) for o, n, s in zip(offs, sizes, shapes)]
-
-
-def _device_pages(pages: Sequence[Page], device=None):
-    """Pages as uint8 device tensors (H,W) / (H,W,C) whose rows are dense (any row pitch): host pages are uploaded, tensors
-    on the device pass through.  Returns (tensors, C, device)."""
-    if not torch.cuda.is_available():
-        raise L.CtdError("line crops run on the GPU and there is none (no CPU fallback)")
-    if device is None:
-        device = next((p.device for p in pages if isinstance(p, torch.Tensor) and p.is_cuda), torch.device("cuda", 0))
-    device = torch.device(device)
-    out, ch = [], None
-    for p in pages:
-        if isinstance(p, torch.Tensor):
-            t = p.to(device)
-        else:
-            a = np.asarray(p)
-            if a.dtype != np.uint8:
-                raise ValueError("pages must be uint8")
-            t = torch.from_numpy(np.ascontiguousarray(a)).to(device)
-        if t.dtype != torch.uint8 or t.dim() not in (2, 3) or (t.dim() == 3 and t.shape[2] not in (1, 3)):
-            raise ValueError("pages must be uint8 (H,W) or (H,W,3)")
-        c = 1 if t.dim() == 2 else int(t.shape[2])
-        dense = t.stride(1) == c and (t.dim() == 2 or t.stride(2) == 1) and t.stride(0) >= t.shape[1] * c
-        if t.shape[0] < 1 or t.shape[1] < 1:
-            raise ValueError("empty page")
-        if not dense:
-            t = t.contiguous()
-        if ch is not None and c != ch:
-            raise ValueError("the pages of one call must have the same number of channels")
-        ch = c
-        out.append(t)
-    return out, (ch or 3), device
-
-
 def warp(pages: Sequence[torch.Tensor], page_of: np.ndarray, wh: np.ndarray, Minv: np.ndarray, rotate: np.ndarray,
          channels: int, stream: Optional[torch.cuda.Stream] = None):
     """`ctd_warp_regions`: crop i = cv2.warpPerspective(pages[page_of[i]], inverse of Minv[i], wh[i]) (INTER_LINEAR, constant
@@ -205,33 +134,33 @@ def warp(pages: Sequence[torch.Tensor], page_of: np.ndarray, wh: np.ndarray, Min
     offsets = np.cumsum(nbytes) - nbytes
     total = int(nbytes.sum())
     sizes = np.where(rotate[:, None], wh, wh[:, ::-1])
-    dev = pages[0].device if pages else torch.device("cuda", 0)
     tiles = (pix + L.REGION_TILE - 1) // L.REGION_TILE
     n_tiles = int(tiles.sum())
     if n_tiles >= 2 ** 31:
         raise ValueError("too many pixels for one launch")
-    with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev)
-        packed = torch.empty((total,), dtype=torch.uint8, device=dev)
+    with PageCall("line crops run", pages, stream, sync=False) as pc:
+        packed = torch.empty((total,), dtype=torch.uint8, device=pc.device)
         if n_tiles == 0:
             return packed, offsets, sizes
-        page_of = np.asarray(page_of, np.int64).reshape(n)
-        ptr = np.array([p.data_ptr() for p in pages], np.uint64)
-        H = np.array([p.shape[0] for p in pages], np.int32)
-        W = np.array([p.shape[1] for p in pages], np.int32)
-        pitch = np.array([p.stride(0) for p in pages], np.int64)
-        if pitch.max() >= 2 ** 31:
-            raise ValueError("row pitch beyond int32")
-        table = np.zeros((n * JOB_DTYPE.itemsize + (n + 1) * 4,), np.uint8)          # jobs, then the tile prefix: one upload
-        jobs = table[: n * JOB_DTYPE.itemsize].view(JOB_DTYPE)
-        jobs["page_dev"], jobs["H"], jobs["W"], jobs["C"], jobs["pitch"] = ptr[page_of], H[page_of], W[page_of], channels, pitch[page_of]
-        jobs["Minv"] = np.asarray(Minv, np.float64).reshape(n, 9)
-        jobs["w"], jobs["h"], jobs["rotate"], jobs["out_off"] = wh[:, 0], wh[:, 1], rotate, offsets
-        table[n * JOB_DTYPE.itemsize:].view(np.int32)[:] = np.concatenate(([0], np.cumsum(tiles)))
-        tab = torch.from_numpy(table).to(dev)
-        L.check(L.lib().ctd_warp_regions(tab.data_ptr(), n, tab.data_ptr() + n * JOB_DTYPE.itemsize, n_tiles, packed.data_ptr(),
-                                         st.cuda_stream), "ctd_warp_regions")
+        jobs = np.zeros((n,), JOB_DTYPE)
+        _fill_jobs(jobs, pc.pages(pages, dense=True), page_of, channels, Minv, wh, rotate)
+        jobs["out_off"] = offsets
+        _, (jobs_ptr, prefix_ptr) = pc.upload([jobs, _tile_prefix(tiles)])           # jobs, then the tile prefix: one upload
+        L.check(L.lib().ctd_warp_regions(jobs_ptr, n, prefix_ptr, n_tiles, packed.data_ptr(), pc.st.cuda_stream),
+                "ctd_warp_regions")
     return packed, offsets, sizes
+
+
+def _fill_jobs(jobs, P, page_of, channels, Minv, wh, rotate) -> None:
+    """The page and warp columns of `JOB_DTYPE` rows, which both warp calls fill alike; P: `PageCall.pages` of the pages."""
+    page_of = np.asarray(page_of, np.int64).reshape(len(jobs))
+    jobs["page_dev"], jobs["H"], jobs["W"], jobs["pitch"], jobs["C"] = P.ptr[page_of], P.H[page_of], P.W[page_of], P.pitch[page_of], channels
+    jobs["Minv"] = np.asarray(Minv, np.float64).reshape(len(jobs), 9)
+    jobs["w"], jobs["h"], jobs["rotate"] = wh[:, 0], wh[:, 1], rotate
+
+
+def _tile_prefix(tiles) -> np.ndarray:
+    return np.concatenate(([0], np.cumsum(tiles))).astype(np.int32)
 
 
 def _page_lines(blk_list):
@@ -263,7 +192,7 @@ def _page_lines(blk_list):
     return (quads, np.asarray(lang, np.int32)[blk], np.asarray(vert, bool)[blk], np.asarray(fs, np.float64)[blk], blk, within)
 
 
-def _batch_lines(blk_lists):
+def batch_lines(blk_lists):
     """The lines of every page of a batch as columns: index (n,3) i32 = (page, block, line), quads, language, vertical,
     font_size."""
     cols = [_page_lines(b) for b in blk_lists]
@@ -275,15 +204,14 @@ def _batch_lines(blk_lists):
     return index, quads, cat(1, np.int32), cat(2, np.int32), cat(3, np.float64)
 
 
-def _regions(pages, ch, index, quads, lang, vert, fs, textheight, stream) -> LineRegions:
-    H = np.array([p.shape[0] for p in pages], np.int32)
-    W = np.array([p.shape[1] for p in pages], np.int32)
+def _regions(P, index, quads, lang, vert, fs, textheight) -> LineRegions:
+    """Inside the caller's `PageCall`, on its stream; P: its `pages`."""
     pg = index[:, 0]
-    wh, _, Minv, status = transforms(quads, lang, vert, fs, W[pg] if len(pg) else 0, H[pg] if len(pg) else 0, textheight)
+    wh, _, Minv, status = transforms(quads, lang, vert, fs, P.W[pg] if len(pg) else 0, P.H[pg] if len(pg) else 0, textheight)
     vert = np.asarray(vert).astype(bool)
-    packed, offsets, sizes = warp(pages, pg, wh, Minv, vert, ch, stream)
-    return LineRegions(packed, index, sizes[:, 1].astype(np.int64), offsets, status == L.REGION_OK, int(textheight), ch,
-                       keep=pages)
+    packed, offsets, sizes = warp(P.t, pg, wh, Minv, vert, P.C)
+    return LineRegions(packed, index, sizes[:, 1].astype(np.int64), offsets, status == L.REGION_OK, int(textheight), P.C,
+                       keep=P.t)
 
 
 def line_regions(pages: Sequence[Page], blk_lists: Sequence, textheight: int = 48,
@@ -296,9 +224,8 @@ def line_regions(pages: Sequence[Page], blk_lists: Sequence, textheight: int = 4
         raise ValueError("one blk_list per page")
     if textheight < 1 or int(textheight) > L.REGION_MAX_SIDE:
         raise ValueError("textheight out of range")
-    pages, ch, device = _device_pages(pages, device)
-    index, quads, lang, vert, fs = _batch_lines(blk_lists)
-    return _regions(pages, ch, index, quads, lang, vert, fs, textheight, stream)
+    with PageCall("line crops run", pages, stream, device, sync=False) as pc:
+        return _regions(pc.pages(pages), *batch_lines(blk_lists), textheight)
 
 
 def transformed_region(blk: TextBlock, img: Page, idx: int, textheight):
@@ -307,17 +234,18 @@ def transformed_region(blk: TextBlock, img: Page, idx: int, textheight):
     host = not isinstance(img, torch.Tensor)
     if not host and not img.is_cuda:
         raise L.CtdError("get_transformed_region takes a numpy image or a CUDA tensor (there is no CPU path)")
-    pages, ch, _ = _device_pages([img])
-    q = np.asarray(blk.lines[idx], np.float64).reshape(1, 8)
-    if not np.array_equal(q, np.trunc(q)):
-        raise ValueError("text lines must have integer coordinates (the detector's quads)")
-    regs = _regions(pages, ch, np.zeros((1, 3), np.int32), q.astype(np.int32), [LANGCLS2IDX.get(blk.language, 1)],
-                    [bool(blk.vertical)], [float(blk.font_size)], textheight, None)
-    if not regs.valid[0]:
-        raise ValueError(f"degenerate text line {blk.lines[idx]}: no region of height {textheight} (zero size, non-finite "
-                         "aspect ratio or singular homography)")
-    out = regs[0] if pages[0].dim() == 3 else regs[0][:, :, 0]
-    return out.cpu().numpy() if host else out
+    with PageCall("line crops run", [img], sync=False) as pc:
+        P = pc.pages([img])
+        q = np.asarray(blk.lines[idx], np.float64).reshape(1, 8)
+        if not np.array_equal(q, np.trunc(q)):
+            raise ValueError("text lines must have integer coordinates (the detector's quads)")
+        regs = _regions(P, np.zeros((1, 3), np.int32), q.astype(np.int32), [LANGCLS2IDX.get(blk.language, 1)],
+                        [bool(blk.vertical)], [float(blk.font_size)], textheight)
+        if not regs.valid[0]:
+            raise ValueError(f"degenerate text line {blk.lines[idx]}: no region of height {textheight} (zero size, non-finite "
+                             "aspect ratio or singular homography)")
+        out = regs[0] if P.t[0].dim() == 3 else regs[0][:, :, 0]
+        return out.cpu().numpy() if host else out
 
 
 # ---- OCR input batches ------------------------------------------------------------------------------------------------------
@@ -423,53 +351,36 @@ def warp_batches(pages: Sequence[torch.Tensor], page_of, wh, Minv, rotate, chann
     for k in range(K):                                   # per BATCH: every batch starts on a 16-byte boundary
         offsets[k] = (total + align - 1) // align * align
         total = int(offsets[k] + elems[k])
-    dev = pages[0].device if pages else torch.device("cuda", 0)
     tiles = np.zeros((n,), np.int64)
     tiles[used] = (th[bk] * batch_width[bk] + L.REGION_TILE - 1) // L.REGION_TILE
     n_tiles = int(tiles.sum())
     if n_tiles >= 2 ** 31:
         raise ValueError("too many pixels for one launch")
-    with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(dev):
-        st = torch.cuda.current_stream(dev)
-        storage = torch.empty((total,), dtype=dtype, device=dev)
+    with PageCall("line crops run", pages, stream, sync=False) as pc:
+        storage = torch.empty((total,), dtype=dtype, device=pc.device)
         if n_tiles == 0:
             return storage, offsets
-        page_of = np.asarray(page_of, np.int64).reshape(n)
-        ptr = np.array([p.data_ptr() for p in pages], np.uint64)
-        H = np.array([p.shape[0] for p in pages], np.int32)
-        W = np.array([p.shape[1] for p in pages], np.int32)
-        pitch = np.array([p.stride(0) for p in pages], np.int64)
-        if pitch.max() >= 2 ** 31:
-            raise ValueError("row pitch beyond int32")
-        tab_bytes = b""
-        if dtype != torch.uint8:
+        P = pc.pages(pages, dense=True)
+        if dtype == torch.uint8:
+            tables = np.zeros((0,), np.uint8)
+        else:
             if tables is None:
                 tables = value_tables(dtype, channels)
             tables = np.ascontiguousarray(tables, _NP_DTYPE[dtype])
             if tables.shape != (channels, 256):
                 raise ValueError("tables: (channels, 256)")
-            tab_bytes = tables.tobytes()
-        o_pre = n * BATCH_JOB_DTYPE.itemsize             # jobs, the tile prefix, the value tables: one upload
-        o_tab = o_pre + (n + 1) * 4
-        table = np.zeros((o_tab + len(tab_bytes),), np.uint8)
-        rows = table[:o_pre].view(BATCH_JOB_DTYPE)
-        jobs = rows["warp"]
-        jobs["page_dev"], jobs["H"], jobs["W"], jobs["C"], jobs["pitch"] = ptr[page_of], H[page_of], W[page_of], channels, pitch[page_of]
-        jobs["Minv"] = np.asarray(Minv, np.float64).reshape(n, 9)
-        jobs["w"], jobs["h"], jobs["rotate"] = wh[:, 0], wh[:, 1], rotate
+        rows = np.zeros((n,), BATCH_JOB_DTYPE)
+        _fill_jobs(rows["warp"], P, page_of, channels, Minv, wh, rotate)
         safe = np.where(used, batch_of, 0)
-        jobs["out_off"] = np.where(used, offsets[safe] if K else 0, 0)
+        rows["warp"]["out_off"] = np.where(used, offsets[safe] if K else 0, 0)
         rows["slot"] = np.where(used, slot, 0)
         rows["rows"] = np.where(used, th[safe] if K else 0, 0)
         rows["Wk"] = np.where(used, batch_width[safe] if K else 0, 0)
         rows["cut"] = np.where(used, cut, 0)
-        table[o_pre:o_tab].view(np.int32)[:] = np.concatenate(([0], np.cumsum(tiles)))
-        table[o_tab:] = np.frombuffer(tab_bytes, np.uint8)
-        tab = torch.from_numpy(table).to(dev)
-        L.check(L.lib().ctd_warp_region_batches(tab.data_ptr(), n, tab.data_ptr() + o_pre, n_tiles,
-                                                (tab.data_ptr() + o_tab) if tab_bytes else None, storage.data_ptr(),
-                                                _ABI_DTYPE[dtype], _LAYOUT[layout], int(bool(rgb)), int(pad), st.cuda_stream),
-                "ctd_warp_region_batches")
+        _, ptr = pc.upload([rows, _tile_prefix(tiles), tables])       # jobs, the tile prefix, the value tables: one upload
+        L.check(L.lib().ctd_warp_region_batches(ptr[0], n, ptr[1], n_tiles, ptr[2] if tables.size else None, storage.data_ptr(),
+                                                _ABI_DTYPE[dtype], _LAYOUT[layout], int(bool(rgb)), int(pad),
+                                                pc.st.cuda_stream), "ctd_warp_region_batches")
     return storage, offsets
 
 
@@ -536,26 +447,24 @@ def line_batches(pages: Sequence[Page], blk_lists: Sequence, textheight: int = 4
         raise ValueError("dtype: torch.uint8 / float16 / float32; layout: 'nchw' / 'nhwc'")
     if any(isinstance(p, torch.Tensor) and not p.is_cuda for p in pages):
         raise L.CtdError("line_batches takes numpy pages or CUDA tensors (there is no CPU path for CPU tensors)")
-    pages, ch, device = _device_pages(pages, device)
-    tables = value_tables(dtype, ch, mean, std)
-    index, quads, lang, vert, fs = _batch_lines(blk_lists)
-    H = np.array([p.shape[0] for p in pages], np.int32)
-    W = np.array([p.shape[1] for p in pages], np.int32)
-    pg = index[:, 0]
-    wh, _, Minv, status = transforms(quads, lang, vert, fs, W[pg] if len(pg) else 0, H[pg] if len(pg) else 0, textheight)
-    vert = np.asarray(vert).astype(bool)
-    valid = status == L.REGION_OK
-    widths = np.where(vert, wh[:, 1], wh[:, 0]).astype(np.int64)          # columns of the stored crops
-    plan = batch_plan(widths, valid, max_batch, width_multiple, max_width)
-    n, m = len(widths), len(plan.order)
-    batch_of, slot, cut = np.full((n,), -1, np.int64), np.zeros((n,), np.int64), np.zeros((n,), np.int64)
-    counts = np.diff(plan.bounds)
-    batch_of[plan.order] = np.repeat(np.arange(len(counts)), counts)
-    slot[plan.order] = np.arange(m) - np.repeat(plan.bounds[:-1], counts)
-    cut[plan.order] = plan.cut
-    with torch.cuda.stream(stream) if stream is not None else torch.cuda.device(device):
-        storage, offsets = warp_batches(pages, pg, wh, Minv, vert, ch, batch_of, slot, cut, counts, plan.batch_width,
-                                        int(textheight), dtype, layout, tables, rgb, pad, None)
+    with PageCall("line crops run", pages, stream, device, sync=False) as pc:
+        P = pc.pages(pages)
+        tables = value_tables(dtype, P.C, mean, std)
+        index, quads, lang, vert, fs = batch_lines(blk_lists)
+        pg = index[:, 0]
+        wh, _, Minv, status = transforms(quads, lang, vert, fs, P.W[pg] if len(pg) else 0, P.H[pg] if len(pg) else 0, textheight)
+        vert = np.asarray(vert).astype(bool)
+        valid = status == L.REGION_OK
+        widths = np.where(vert, wh[:, 1], wh[:, 0]).astype(np.int64)          # columns of the stored crops
+        plan = batch_plan(widths, valid, max_batch, width_multiple, max_width)
+        n, m = len(widths), len(plan.order)
+        batch_of, slot, cut = np.full((n,), -1, np.int64), np.zeros((n,), np.int64), np.zeros((n,), np.int64)
+        counts = np.diff(plan.bounds)
+        batch_of[plan.order] = np.repeat(np.arange(len(counts)), counts)
+        slot[plan.order] = np.arange(m) - np.repeat(plan.bounds[:-1], counts)
+        cut[plan.order] = plan.cut
+        storage, offsets = warp_batches(P.t, pg, wh, Minv, vert, P.C, batch_of, slot, cut, counts, plan.batch_width,
+                                        int(textheight), dtype, layout, tables, rgb, pad)
         ready = torch.cuda.Event()
-        ready.record(torch.cuda.current_stream(device))
-    return LineBatches(storage, offsets, index, valid, widths, plan, int(textheight), ch, layout, ready, keep=pages)
+        ready.record(pc.st)
+    return LineBatches(storage, offsets, index, valid, widths, plan, int(textheight), P.C, layout, ready, keep=P.t)

@@ -244,11 +244,7 @@ def _fast_block(xyxy, lines, language, vertical, font_size, distance, angle, vec
 
 
 # numpy view of `ctd_blk` (include/ctd_hip.h; _lib.CtdBlk): the records of a page become columns in one call
-BLK_DTYPE = _BLK_DT = np.dtype([("xyxy", "<i4", (4,)), ("language", "<i4"), ("vertical", "<i4"), ("angle", "<i4"),
-                    ("font_is_float", "<i4"), ("font_size", "<f8"), ("vec", "<f8", (2,)), ("norm", "<f8"),
-                    ("weight", "<f8"), ("merged", "<i4"), ("line_off", "<i4"), ("n_lines", "<i4"), ("dist_off", "<i4"),
-                    ("n_dist", "<i4"), ("pad_", "<i4")])
-assert _BLK_DT.itemsize == C.sizeof(L.CtdBlk)
+BLK_DTYPE = _BLK_DT = np.dtype(L.CtdBlk)
 
 
 def blocks_from_records(recs, lines: np.ndarray, dist: np.ndarray, n: Optional[int] = None, native: bool = True) -> List[TextBlock]:

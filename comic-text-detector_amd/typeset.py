@@ -17,7 +17,6 @@ and no CPU fallback: without a GPU it raises `CtdError` like the rest of the pac
 """
 from __future__ import annotations
 
-import contextlib
 import ctypes as C
 from typing import List, Optional, Sequence
 
@@ -25,22 +24,15 @@ import numpy as np
 import torch
 
 from . import _lib as L
-from .regions import Page, _align, _check_pages, _device_pages, _views
+from .pagecall import Page, PageCall, check_pages, device_pages, table_dtype, views
 
 __all__ = ["typeset_pages", "TypesetPages", "typeset_tables", "place", "PAGE_DTYPE", "LAYER_DTYPE", "TILE_DTYPE", "ROW_DTYPE"]
 
-# numpy views of `ctd_typeset_page` / `_layer` / `_tile` / `_row` (include/ctd_hip.h; the _lib.CtdTypeset* mirrors)
-PAGE_DTYPE = np.dtype([("page_dev", "<u8"), ("H", "<i4"), ("W", "<i4"), ("pitch", "<i8")])
-LAYER_DTYPE = np.dtype([("cov0", "<i8"), ("page", "<i4"), ("x0", "<i4"), ("y0", "<i4"), ("w", "<i4"), ("h", "<i4"),
-                        ("cov_pitch", "<i4"), ("clip", "<i4", (4,)), ("fill", "u1", (3,)), ("stroke", "u1", (3,)),
-                        ("radius", "u1"), ("pad_", "u1")])
-TILE_DTYPE = np.dtype([("page", "<i4"), ("tx", "<i4"), ("ty", "<i4"), ("first", "<i4")])
-ROW_DTYPE = np.dtype([("n_fill", "<i4"), ("n_stroke", "<i4")])
-assert PAGE_DTYPE.itemsize == C.sizeof(L.CtdTypesetPage) == 24
-assert LAYER_DTYPE.itemsize == C.sizeof(L.CtdTypesetLayer) == 56
-assert TILE_DTYPE.itemsize == C.sizeof(L.CtdTypesetTile) == 16
-assert ROW_DTYPE.itemsize == C.sizeof(L.CtdTypesetRow) == 8
-assert C.sizeof(L.CtdTypesetParams) == 32
+# numpy views of `ctd_typeset_page` / `_layer` / `_tile` / `_row` (include/ctd_hip.h)
+PAGE_DTYPE = table_dtype(L.CtdTypesetPage)
+LAYER_DTYPE = table_dtype(L.CtdTypesetLayer)
+TILE_DTYPE = table_dtype(L.CtdTypesetTile)
+ROW_DTYPE = table_dtype(L.CtdTypesetRow)
 
 MAX_COORD = 1 << 29
 
@@ -196,7 +188,7 @@ def _dense(t) -> bool:
 def _copies(pages, device):
     """The pages copied into views of ONE new allocation, each on a 256-byte boundary: one device copy where they already lie
     like that in one buffer (as `FilledPages.pages` do), else one copy (or upload) a page."""
-    store, out = _views([(int(p.shape[0]), int(p.shape[1]), 3) for p in pages], device)
+    store, out = views([(int(p.shape[0]), int(p.shape[1]), 3) for p in pages], device)
     dev = [p for p in pages if isinstance(p, torch.Tensor) and p.device == device and p.is_contiguous()]
     if len(dev) == len(pages) and all(p.untyped_storage().data_ptr() == dev[0].untyped_storage().data_ptr() and
                                       p.data_ptr() - dev[0].data_ptr() == o.data_ptr() - out[0].data_ptr() for p, o in zip(dev, out)):
@@ -212,7 +204,7 @@ def _copies(pages, device):
 def _layer_args(pages, page_of, fill, stroke, radius, inplace: bool) -> tuple:
     """What `typeset_pages` and `glyphs.typeset_glyphs` check first, ValueError where it is wrong: the pages, the per-layer
     columns -> (shapes, page_of, fill (n, 3) BGR, stroke (n, 3) BGR, r)."""
-    _check_pages(pages, nonempty=False)                    # an empty page is the tables' "page sides" error
+    check_pages(pages, nonempty=False)                    # an empty page is the tables' "page sides" error
     if inplace and not all(isinstance(p, torch.Tensor) and p.is_cuda and _dense(p) for p in pages):
         raise ValueError("inplace=True needs device pages with dense rows")
     shapes = [tuple(int(v) for v in p.shape[:2]) for p in pages]
@@ -227,8 +219,8 @@ def _layer_args(pages, page_of, fill, stroke, radius, inplace: bool) -> tuple:
     return shapes, page_of, colours[0], colours[1], _per_layer(radius, n, 1, "radius")[:, 0]
 
 
-def _open_pages(pages, shapes, page_of, clip, inplace: bool, device) -> tuple:
-    """Behind the tables, which have checked `page_of` and `clip`, and on the call's device and stream: (out, pt, clip4).
+def _open_pages(pc: PageCall, pages, shapes, page_of, clip, inplace: bool) -> tuple:
+    """Behind the tables, which have checked `page_of` and `clip`, inside the call's `PageCall`: (out, pt, clip4).
     out: the pages the kernel writes, the caller's own where `inplace`, else copies (views of one new allocation); pt:
     their `ctd_typeset_page` table; clip4: the clip of every layer, (n, 4), the page where none was given."""
     n = len(page_of)
@@ -237,25 +229,15 @@ def _open_pages(pages, shapes, page_of, clip, inplace: bool, device) -> tuple:
     if not pages:
         out = []
     elif inplace:
-        out = _device_pages(pages, device)[0]
+        out = device_pages(pages, pc.device, pc.what)[0]       # the caller's own tensors (checked below): nothing to keep
         if any(o.data_ptr() != p.data_ptr() for o, p in zip(out, pages)):
             raise ValueError("inplace=True needs pages on the device the call runs on")
     else:
-        out = _copies(pages, device)
+        out = _copies(pages, pc.device)
     pt = np.zeros((len(out),), PAGE_DTYPE)
     pt["page_dev"] = [o.data_ptr() for o in out]
     pt["H"], pt["W"], pt["pitch"] = [s[0] for s in shapes], [s[1] for s in shapes], [o.stride(0) for o in out]
     return out, pt, clip4
-
-
-def _pack(parts) -> tuple:
-    """The tables of a call as ONE byte array for one upload, each part on an 8-byte boundary: (blob, offsets)."""
-    parts = [x.view(np.uint8) for x in parts]
-    at = np.cumsum([0] + [_align(len(x), 8) for x in parts])
-    blob = np.zeros((int(at[-1]),), np.uint8)
-    for a, x in zip(at, parts):
-        blob[int(a): int(a) + len(x)] = x
-    return blob, at
 
 
 def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray], xy, fill=(0, 0, 0), stroke=(255, 255, 255),
@@ -280,31 +262,21 @@ def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray],
     sizes = np.array([b.shape for b in bitmaps], np.int64).reshape(n, 2)
     xy = _ints(xy, (n, 2), "xy")
     tiles, entries, status = typeset_tables(shapes, page_of, sizes, xy, r, clip)
-    if not torch.cuda.is_available():
-        raise L.CtdError("typesetting runs on the GPU and there is none (no CPU fallback)")
     area = sizes[:, 0] * sizes[:, 1]
     cov0 = np.cumsum(area) - area
     cov = np.concatenate([b.ravel() for b in bitmaps]) if n else np.zeros((0,), np.uint8)
     n_pages, n_tiles = len(pages), len(tiles) - 1
-    with torch.cuda.stream(stream) if stream is not None else contextlib.nullcontext():
-        if device is None:
-            device = next((p.device for p in pages if isinstance(p, torch.Tensor) and p.is_cuda), torch.device("cuda", 0))
-        device = torch.device(device)
-        with torch.cuda.device(device):
-            st = torch.cuda.current_stream(device)
-            out, pt, clip4 = _open_pages(pages, shapes, page_of, clip, inplace, device)
-            rows = np.zeros((n,), ROW_DTYPE)
-            if n and n_pages:
-                lt = np.zeros((n,), LAYER_DTYPE)
-                lt["cov0"], lt["page"], lt["x0"], lt["y0"], lt["h"], lt["w"] = cov0, page_of, xy[:, 0], xy[:, 1], sizes[:, 0], sizes[:, 1]
-                lt["cov_pitch"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = sizes[:, 1], clip4, fill, stroke, r
-                blob, at = _pack([pt, lt, tiles, entries, cov])    # one upload: the four tables and the coverage
-                tab = torch.from_numpy(blob).to(device)
-                rows_dev = torch.empty((n * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=device)
-                prm = L.CtdTypesetParams(n, n_pages, n_tiles, len(entries), len(cov), 0)
-                ptr = [tab.data_ptr() + int(a) for a in at]
-                L.check(L.lib().ctd_typeset(ptr[0], ptr[1], ptr[2], ptr[3] if len(entries) else None, ptr[4] if len(cov) else None,
-                                            C.byref(prm), rows_dev.data_ptr(), st.cuda_stream), "ctd_typeset")
-                rows = rows_dev.cpu().numpy().view(ROW_DTYPE)           # stream-ordered: behind the launch
-            st.synchronize()
+    with PageCall("typesetting runs", pages, stream, device) as pc:
+        out, pt, clip4 = _open_pages(pc, pages, shapes, page_of, clip, inplace)
+        rows = np.zeros((n,), ROW_DTYPE)
+        if n and n_pages:
+            lt = np.zeros((n,), LAYER_DTYPE)
+            lt["cov0"], lt["page"], lt["x0"], lt["y0"], lt["h"], lt["w"] = cov0, page_of, xy[:, 0], xy[:, 1], sizes[:, 0], sizes[:, 1]
+            lt["cov_pitch"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = sizes[:, 1], clip4, fill, stroke, r
+            _, ptr = pc.upload([pt, lt, tiles, entries, cov])   # one upload: the four tables and the coverage
+            rows_dev = torch.empty((n * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+            prm = L.CtdTypesetParams(n, n_pages, n_tiles, len(entries), len(cov), 0)
+            L.check(L.lib().ctd_typeset(ptr[0], ptr[1], ptr[2], ptr[3] if len(entries) else None, ptr[4] if len(cov) else None,
+                                        C.byref(prm), rows_dev.data_ptr(), pc.st.cuda_stream), "ctd_typeset")
+            rows = pc.rows(rows_dev, ROW_DTYPE, n)
     return TypesetPages(out, rows, status, xy)

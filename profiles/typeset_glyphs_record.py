@@ -64,7 +64,7 @@ def host(fn):
 
 
 def blob(parts, dev):
-    b, at = T._pack(parts)
+    b, at = pkg.pagecall.pack(parts)
     tab = torch.from_numpy(b).to(dev)
     return tab, [tab.data_ptr() + int(a) for a in at], len(b)
 

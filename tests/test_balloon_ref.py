@@ -3,16 +3,14 @@ out by hand, 4-connectivity, a closed outline against one with a gap -- the host
 the restatement's windows, argument checks of `balloons.balloon_regions`, and the layout of the ABI structs against the
 header.  The kernel itself is compared with the restatement in tests/test_gpu_balloons.py."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import balloon_ref as BR
 import erase_ref as ER
-from conftest import ROOT, pkg
+from c_layout import compiled_flat
+from conftest import pkg
 
 
 def _plain(med, n_fill=0):
@@ -187,16 +185,7 @@ def test_balloon_structs_have_the_c_layout():
     consts = ("CTD_BALLOON_OK", "CTD_BALLOON_NOT_PLAIN", "CTD_BALLOON_TOO_LARGE", "CTD_BALLOON_MAX_WORDS", "CTD_BALLOON_MAX_REACH",
               "CTD_BALLOON_MIN_REACH_MIN", "CTD_BALLOON_MAX_REACH_MIN", "CTD_BALLOON_CUT_LEFT", "CTD_BALLOON_CUT_TOP",
               "CTD_BALLOON_CUT_RIGHT", "CTD_BALLOON_CUT_BOTTOM", "CTD_ABI_VERSION")
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "ctd_hip.h"\nint main(void){\n'
-    for s, fs in fields.items():
-        prog += f'printf("%zu ", sizeof({s}));\n' + "".join(f'printf("%zu ", offsetof({s}, {f}));\n' for f in fs)
-    prog += "".join(f'printf("%d ", {c});\n' for c in consts) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    vals = compiled_flat(fields, consts)
     mirrors = {"ctd_balloon_job": (L.CtdBalloonJob, B.JOB_DTYPE, 32), "ctd_balloon_params": (L.CtdBalloonParams, None, 32),
                "ctd_balloon_row": (L.CtdBalloonRow, B.ROW_DTYPE, 48)}
     k = 0

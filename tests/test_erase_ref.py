@@ -2,15 +2,13 @@
 pages, both sides of every boundary of the decision -- argument checks of `erase.erase_text`, and the layout of the ABI
 structs against the header.  The kernels themselves are compared with the restatement in tests/test_gpu_erase.py."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import erase_ref as R
-from conftest import ROOT, pkg
+from c_layout import compiled_flat
+from conftest import pkg
 
 
 # ---- the rule ----------------------------------------------------------------------------------------------------------
@@ -204,16 +202,7 @@ def test_erase_structs_have_the_c_layout():
     consts = ("CTD_ERASE_PLAIN", "CTD_ERASE_TEXTURED", "CTD_ERASE_NO_RING", "CTD_ERASE_NO_MASK", "CTD_ERASE_EMPTY",
               "CTD_ERASE_TOO_LARGE", "CTD_ERASE_MAX_PIXELS", "CTD_ERASE_MAX_COORD", "CTD_ERASE_MAX_GROW", "CTD_ERASE_MAX_RING",
               "CTD_ERASE_TILE_W", "CTD_ERASE_TILE_H", "CTD_ABI_VERSION")
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "ctd_hip.h"\nint main(void){\n'
-    for s, fs in fields.items():
-        prog += f'printf("%zu ", sizeof({s}));\n' + "".join(f'printf("%zu ", offsetof({s}, {f}));\n' for f in fs)
-    prog += "".join(f'printf("%d ", {c});\n' for c in consts) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    vals = compiled_flat(fields, consts)
     mirrors = {"ctd_erase_job": (L.CtdEraseJob, E.JOB_DTYPE, 32), "ctd_erase_page": (L.CtdErasePage, E.PAGE_DTYPE, 72),
                "ctd_erase_params": (L.CtdEraseParams, None, 32), "ctd_erase_row": (L.CtdEraseRow, E.ROW_DTYPE, 32)}
     k = 0

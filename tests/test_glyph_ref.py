@@ -3,9 +3,6 @@
 restatement; the ABI structs and constants against the header; the entry point's refusals.  The kernel itself is compared
 with the restatement, and with `typeset_pages` on the same bitmaps, in tests/test_gpu_glyphs.py."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 import types
 
 import numpy as np
@@ -13,7 +10,8 @@ import pytest
 
 import glyph_ref as GR
 import typeset_ref as TR
-from conftest import ROOT, pkg
+from c_layout import compiled_flat
+from conftest import pkg
 
 
 def _columns(layers, places, atlas):
@@ -261,16 +259,7 @@ def test_glyph_structs_have_the_c_layout():
               "ctd_glyph_record": ("off", "w", "h"),
               "ctd_glyph_params": ("n_layers", "n_pages", "n_tiles", "n_entries", "n_places", "n_glyphs", "atlas_bytes")}
     consts = ("CTD_TYPESET_MAX_SIDE", "CTD_TYPESET_MAX_RADIUS", "CTD_TYPESET_TILE_W", "CTD_TYPESET_TILE_H", "CTD_ABI_VERSION")
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "ctd_hip.h"\nint main(void){\n'
-    for s, fs in fields.items():
-        prog += f'printf("%zu ", sizeof({s}));\n' + "".join(f'printf("%zu ", offsetof({s}, {f}));\n' for f in fs)
-    prog += "".join(f'printf("%d ", {c});\n' for c in consts) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    vals = compiled_flat(fields, consts)
     mirrors = {"ctd_glyph_layer": (L.CtdGlyphLayer, G.LAYER_DTYPE, 32), "ctd_glyph_place": (L.CtdGlyphPlace, G.PLACE_DTYPE, 16),
                "ctd_glyph_record": (L.CtdGlyphRecord, G.RECORD_DTYPE, 16), "ctd_glyph_params": (L.CtdGlyphParams, None, 32)}
     k = 0

@@ -2,16 +2,14 @@
 answers written out by hand, what the named material promises, argument checks of `layout.layout_boxes`, and the layout of
 the ABI structs against the header.  The kernel itself is compared with the restatement in tests/test_gpu_layout.py."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import balloon_ref as BR
 import layout_ref as LR
-from conftest import ROOT, pkg
+from c_layout import compiled_flat
+from conftest import pkg
 
 
 # ---- the rule ----------------------------------------------------------------------------------------------------------
@@ -166,16 +164,7 @@ def test_layout_structs_have_the_c_layout():
               "ctd_layout_params": ("inset", "max_words", "n_rows", "pad_"),
               "ctd_layout_row": ("status", "n_inner", "area", "rect", "a_area", "a_rect")}
     consts = ("CTD_LAYOUT_OK", "CTD_LAYOUT_NO_REGION", "CTD_LAYOUT_EMPTY", "CTD_LAYOUT_MAX_INSET", "CTD_ABI_VERSION")
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "ctd_hip.h"\nint main(void){\n'
-    for s, fs in fields.items():
-        prog += f'printf("%zu ", sizeof({s}));\n' + "".join(f'printf("%zu ", offsetof({s}, {f}));\n' for f in fs)
-    prog += "".join(f'printf("%d ", {c});\n' for c in consts) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    vals = compiled_flat(fields, consts)
     mirrors = {"ctd_layout_job": (L.CtdLayoutJob, Y.JOB_DTYPE, 32), "ctd_layout_params": (L.CtdLayoutParams, None, 16),
                "ctd_layout_row": (L.CtdLayoutRow, Y.ROW_DTYPE, 48)}
     k = 0

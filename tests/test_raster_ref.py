@@ -6,14 +6,13 @@ import ctypes as C
 import glob
 import os
 import re
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import raster_ref as RR
-from conftest import ROOT, pkg
+from c_layout import compiled_flat
+from conftest import pkg
 
 ONE = 65536                                                # a pixel a font unit
 
@@ -282,15 +281,7 @@ def test_the_raster_job_has_the_c_layout_and_the_entry_point_refuses():
     L, G = p._lib, p.glyphs
     fs = ("off", "w", "h", "bx", "by", "seg_first", "seg_count", "scale", "pad_")
     consts = ("CTD_RASTER_MAX_SIDE", "CTD_RASTER_MAX_SCALE", "CTD_RASTER_OK", "CTD_RASTER_EMPTY", "CTD_RASTER_REFUSED", "CTD_ABI_VERSION")
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "ctd_hip.h"\nint main(void){\n'
-    prog += 'printf("%zu ", sizeof(ctd_raster_job));\n' + "".join(f'printf("%zu ", offsetof(ctd_raster_job, {f}));\n' for f in fs)
-    prog += "".join(f'printf("%d ", {c});\n' for c in consts) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    vals = compiled_flat({"ctd_raster_job": fs}, consts)
     assert vals[0] == C.sizeof(L.CtdRasterJob) == G.RASTER_JOB_DTYPE.itemsize == 40
     assert vals[1:10] == [getattr(L.CtdRasterJob, f).offset for f in fs] == [G.RASTER_JOB_DTYPE.fields[f][1] for f in fs]
     assert [f for f, _ in L.CtdRasterJob._fields_] == list(fs) and G.RASTER_JOB_DTYPE.names == fs

@@ -401,20 +401,11 @@ def test_overflow_is_decided_by_the_emulation_alone():
 def test_trace_window_record_has_the_c_layout():
     """`tail.TRACE_WIN_DTYPE` / `_lib.CtdTraceWin` against `ctd_trace_win` of the header, compiled: size and every offset."""
     import ctypes as C
-    import os
-    import subprocess
-    import tempfile
-    from conftest import ROOT, pkg
+    from c_layout import compiled_flat
+    from conftest import pkg
     p = pkg()
     names = ["page", "x1", "y1", "w", "h", "pass", "path", "n_cand", "hist", "rules", "cand_rule", "cand_invert", "sums", "cand_dist"]
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "ctd_hip.h"\nint main(void){ printf("%zu", sizeof(ctd_trace_win));\n'
-    prog += "".join(f'printf(" %zu", offsetof(ctd_trace_win, {n}));\n' for n in names) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    vals = compiled_flat({"ctd_trace_win": names})
     dt, W = p.tail.TRACE_WIN_DTYPE, p._lib.CtdTraceWin
     py = ["pass_" if n == "pass" else n for n in names]
     assert vals == [dt.itemsize] + [dt.fields[n][1] for n in py] == [C.sizeof(W)] + [getattr(W, n).offset for n in py]

@@ -3,15 +3,13 @@
 `typeset.typeset_pages`; the ABI structs and constants against the header; the entry point's refusals.  The kernel itself is
 compared with the restatement in tests/test_gpu_typeset.py."""
 import ctypes as C
-import os
-import subprocess
-import tempfile
 
 import numpy as np
 import pytest
 
 import typeset_ref as TR
-from conftest import ROOT, pkg
+from c_layout import compiled_flat
+from conftest import pkg
 
 
 # ---- the rule ----------------------------------------------------------------------------------------------------------
@@ -194,16 +192,7 @@ def test_typeset_structs_have_the_c_layout():
               "ctd_typeset_params": ("n_layers", "n_pages", "n_tiles", "n_entries", "cov_bytes", "pad_"),
               "ctd_typeset_row": ("n_fill", "n_stroke")}
     consts = ("CTD_TYPESET_MAX_SIDE", "CTD_TYPESET_MAX_RADIUS", "CTD_TYPESET_TILE_W", "CTD_TYPESET_TILE_H", "CTD_ABI_VERSION")
-    prog = '#include <stdio.h>\n#include <stddef.h>\n#include "ctd_hip.h"\nint main(void){\n'
-    for s, fs in fields.items():
-        prog += f'printf("%zu ", sizeof({s}));\n' + "".join(f'printf("%zu ", offsetof({s}, {f}));\n' for f in fs)
-    prog += "".join(f'printf("%d ", {c});\n' for c in consts) + "return 0; }\n"
-    with tempfile.TemporaryDirectory() as d:
-        c = os.path.join(d, "t.c")
-        open(c, "w").write(prog)
-        exe = os.path.join(d, "t")
-        subprocess.check_call(["gcc", "-I", os.path.join(ROOT, "include"), c, "-o", exe])
-        vals = [int(v) for v in subprocess.check_output([exe]).split()]
+    vals = compiled_flat(fields, consts)
     mirrors = {"ctd_typeset_page": (L.CtdTypesetPage, T.PAGE_DTYPE, 24), "ctd_typeset_layer": (L.CtdTypesetLayer, T.LAYER_DTYPE, 56),
                "ctd_typeset_tile": (L.CtdTypesetTile, T.TILE_DTYPE, 16), "ctd_typeset_params": (L.CtdTypesetParams, None, 32),
                "ctd_typeset_row": (L.CtdTypesetRow, T.ROW_DTYPE, 8)}
