@@ -36,6 +36,8 @@ BALLOON_MAX_WORDS, BALLOON_MAX_REACH, BALLOON_MIN_REACH_MIN, BALLOON_MAX_REACH_M
 BALLOON_CUT_LEFT, BALLOON_CUT_TOP, BALLOON_CUT_RIGHT, BALLOON_CUT_BOTTOM = 1, 2, 4, 8
 FILL_OK, FILL_NO_HOLE, FILL_NO_KNOWN = range(3)
 FILL_MAX_SIDE, FILL_TILE = 8192, 64
+TEXTURE_OK, TEXTURE_NO_HOLE, TEXTURE_NO_SOURCE = range(3)
+TEXTURE_PATCH, TEXTURE_MAX_RADIUS, TEXTURE_MAX_SIDE, TEXTURE_TILE = 7, 127, 8192, 64
 LAYOUT_OK, LAYOUT_NO_REGION, LAYOUT_EMPTY = range(3)
 LAYOUT_MAX_INSET = 16
 TYPESET_MAX_SIDE, TYPESET_MAX_RADIUS, TYPESET_TILE_W, TYPESET_TILE_H = 8192, 12, 64, 32
@@ -221,6 +223,22 @@ class CtdFillRow(C.Structure):
                 ("pad_", C.c_uint8 * 17)]
 
 
+class CtdTexturePage(C.Structure):
+    _fields_ = [("page_dev", C.c_void_p), ("hole_dev", C.c_void_p), ("init_dev", C.c_void_p), ("out_dev", C.c_void_p),
+                ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int32), ("hole_pitch", C.c_int32), ("init_pitch", C.c_int32),
+                ("out_pitch", C.c_int32), ("tile0", C.c_int32), ("pad_", C.c_int32), ("fld0", C.c_int64), ("cls0", C.c_int64)]
+
+
+class CtdTextureParams(C.Structure):
+    _fields_ = [("n_tiles", C.c_int32), ("radius", C.c_int32), ("n_em", C.c_int32), ("n_sweep", C.c_int32), ("n_init", C.c_int32),
+                ("seed", C.c_uint32), ("scratch_bytes", C.c_int64)]
+
+
+class CtdTextureRow(C.Structure):
+    _fields_ = [("status", C.c_int32), ("n_hole", C.c_int32), ("n_target", C.c_int32), ("n_source", C.c_int32),
+                ("n_unmatched", C.c_int32), ("pad_", C.c_int32 * 3)]
+
+
 # every symbol include/ctd_hip.h declares: (restype, argtypes)
 _vp, _i32, _i64, _f = C.c_void_p, C.c_int32, C.c_int64, C.c_float
 SYMBOLS = {
@@ -257,6 +275,7 @@ SYMBOLS = {
     "ctd_typeset_glyphs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdGlyphParams), _vp, _vp]),
     "ctd_rasterise_glyphs": (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
     "ctd_fill_rest": (_i32, [_vp, _i32, C.POINTER(CtdFillParams), _vp, _vp, _vp]),
+    "ctd_texture_fill": (_i32, [_vp, _i32, C.POINTER(CtdTextureParams), _vp, _vp, _vp]),
     "ctd_db_boxes": (_i32, [_vp, _vp, _vp, _i32, _vp, _vp, _i32, _i32, _i32, _i32, C.c_double, _vp, _vp, C.POINTER(_i32)]),
     "ctd_tail_create": (_i32, [C.POINTER(_vp), _i32]),
     "ctd_tail_destroy": (None, [_vp]),

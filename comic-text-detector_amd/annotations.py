@@ -146,6 +146,12 @@ def filled_files(save_dir: str, imgname: str, filled: np.ndarray) -> dict:
     return {osp.join(save_dir, "filled-" + imname + ".png"): png_bytes(filled)}
 
 
+def textured_files(save_dir: str, imgname: str, textured: np.ndarray) -> dict:
+    """File name -> PNG bytes of one page's `texture=True` output: `textured-<name>.png`."""
+    imname = imgname.replace(Path(imgname).suffix, "")
+    return {osp.join(save_dir, "textured-" + imname + ".png"): png_bytes(textured)}
+
+
 def write_files(files: dict) -> None:
     for path, content in files.items():
         if isinstance(content, bytes):
@@ -162,13 +168,17 @@ def write_page_annotations(save_dir, imgname, img, mask_refined, blk_list, save_
 
 def model2annotations(model_path: Union[str, dict], img_dir_list, save_dir: str, save_json: bool = False,
                       batch_size: int = 8, device: str = "cuda", detector=None, io_threads: int = 4,
-                      font_colors: bool = False, erase: bool = False, fill: bool = False) -> int:
+                      font_colors: bool = False, erase: bool = False, fill: bool = False,
+                      texture: bool = False) -> int:
     """reference inference.py:19-70, batched.  Returns the number of pages written.  `font_colors=True`: the blocks' colour
     fields in the JSON records are filled (`TextDetector.detect_batch(font_colors=True)`); the default writes the zeros the
     reference's detector writes.  `erase=True`: also writes `clean-<name>.png`, the page with the text on plain backgrounds
     erased, and `rest-<name>.png`, the mask an inpainter still needs (`TextDetector.erase_text` on the batch's
     `mask_refined`); the default writes exactly the reference's files.  `fill=True` implies `erase` and also writes
-    `filled-<name>.png`, the clean page with the rest mask filled smoothly (`TextDetector.fill_rest`)."""
+    `filled-<name>.png`, the clean page with the rest mask filled smoothly (`TextDetector.fill_rest`).  `texture=True`
+    implies `fill` and also writes `textured-<name>.png`, that page with the screentone put back by patch matching
+    (`TextDetector.texture_fill`)."""
+    fill = fill or texture
     from .detector import TextDetector
     if isinstance(img_dir_list, str):
         img_dir_list = [img_dir_list]
@@ -195,8 +205,12 @@ def model2annotations(model_path: Union[str, dict], img_dir_list, save_dir: str,
                 for path, clean, rest in zip(paths, *er.to_host()):
                     pending_writes.append(pool.submit(write_files, erased_files(save_dir, osp.basename(path), clean, rest)))
                 if fill:
-                    for path, filled in zip(paths, det.fill_rest(imgs, results, erased=er).to_host()):
+                    fp = det.fill_rest(imgs, results, erased=er)
+                    for path, filled in zip(paths, fp.to_host()):
                         pending_writes.append(pool.submit(write_files, filled_files(save_dir, osp.basename(path), filled)))
+                    if texture:
+                        for path, tex in zip(paths, det.texture_fill(imgs, results, erased=er, filled=fp).to_host()):
+                            pending_writes.append(pool.submit(write_files, textured_files(save_dir, osp.basename(path), tex)))
         for f in pending_writes:
             f.result()
     return len(imglist)

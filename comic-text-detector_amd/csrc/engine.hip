@@ -27,6 +27,13 @@ int fail(int code, const std::string& msg) {
   return code;
 }
 
+}  // namespace
+
+// `fail` for the entry points that live next to their kernels (kernels_texture.hip)
+int api_fail(int code, const std::string& msg) { return fail(code, msg); }
+
+namespace {
+
 #define HIP_TRY(expr)                                                                              \
   do {                                                                                             \
     hipError_t _e = (expr);                                                                        \

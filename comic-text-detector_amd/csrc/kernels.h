@@ -1,5 +1,6 @@
 // Host-side launchers of every device kernel (definitions in the .hip files).
 #pragma once
+#include <string>
 #include <vector>
 
 #include "ctd_common.h"
@@ -232,6 +233,11 @@ hipError_t launch_rasterise_glyphs(const int32_t* segs, int64_t n_segs, const ct
 // says right after the first launch that failed
 hipError_t launch_fill_rest(const ctd_fill_page* pages, int n_pages, int n_tiles, void* scratch, ctd_fill_row* rows,
                             hipStream_t st);
+
+// ---- kernels_texture.hip --------------------------------------------------------
+// ctd_texture_fill is defined there, next to its kernels; this is how it sets the message ctd_last_error returns (engine.hip):
+// returns `code`
+int api_fail(int code, const std::string& msg);
 
 // ---- mfma layout probe (selftest) -------------------------------------------
 void launch_mfma_probe(const half_t* a, const half_t* b, float* out, hipStream_t st);

@@ -717,5 +717,18 @@ class TextDetector:
             erased = self.erase_text(pages, results, **erase_kw)
         return fill.fill_rest(erased.pages, erased.rest, device=self.net.device)
 
+    def texture_fill(self, pages: Sequence[Page], results, erased=None, filled=None, **kw):
+        """`fill_rest` and then the texture back in what it filled, on the detector's device: `texture.texture_fill` on the
+        erased pages and their rest masks, started from the pull-push pages (returns its `TexturedPages`).  `erased`,
+        `filled`: the `ErasedPages` of `erase_text(pages, results)` and the `FilledPages` of `fill_rest(pages, results,
+        erased=erased)` where the caller has them; otherwise they run first, with their defaults.  `kw`: `radius`,
+        `iterations`, `sweeps`, `n_init`, `seed` of `texture.texture_fill`.  Builds no `TextBlock` of a `BlockList`."""
+        from . import texture
+        if erased is None:
+            erased = self.erase_text(pages, results)
+        if filled is None:
+            filled = self.fill_rest(pages, results, erased=erased)
+        return texture.texture_fill(erased.pages, erased.rest, init=filled.pages, device=self.net.device, **kw)
+
     def __call__(self, img: np.ndarray, refine_mode=REFINEMASK_INPAINT, keep_undetected_mask=False):
         return self.detect_batch([img], refine_mode, keep_undetected_mask)[0]

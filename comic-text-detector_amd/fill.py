@@ -12,7 +12,8 @@ the 64 x 64 tiles of all pages, one workgroup per page for the coarse levels, a 
 between them) and downloads one small table.  The rule is integers only and stated in include/ctd_hip.h (restated in numpy in
 tests/fill_ref.py; DESIGN.md section 4.19 has its limits): pull builds an image pyramid of the known pixels -- a level pixel is
 the rounded mean of its known children --, push fills the unknown pixels from coarse to fine by bilinear upsampling with the
-weights 9, 3, 3, 1.  A gradient comes back as the gradient, art as its blurred surroundings; texture does not come back.
+weights 9, 3, 3, 1.  A gradient comes back as the gradient, art as its blurred surroundings; texture does not come back
+(`texture.texture_fill` starts from this result and puts screentone back by patch matching).
 There is no per-page Python and no CPU fallback: without a GPU it raises `CtdError` like the rest of the package.
 """
 from __future__ import annotations

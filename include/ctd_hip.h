@@ -694,6 +694,116 @@ typedef struct ctd_fill_row {
 int ctd_fill_rest(const ctd_fill_page* pages_dev, int32_t n_pages, const ctd_fill_params* params, void* scratch_dev,
                   ctd_fill_row* rows_dev, void* stream);
 
+/* ---- texture fill: screentone in the hole by patch matching (added within ABI v10) ----------------------------------- */
+
+/* An addition to ABI v10 like those above: one entry point, three structs, nothing existing changes.
+ * ctd_fill_rest gives a hole its smooth surroundings; screentone comes back as its local mean.  This is the step that
+ * starts from that result: an exemplar-based fill, a nearest-neighbour field of 7 x 7 patches found by propagation and
+ * random search (PatchMatch) with patch voting, this library's own rule, integers only, so the result is a function of
+ * (page, hole mask, init, parameters) to the byte, whatever the page's position in the batch and whatever the launch order.
+ * Restated in numpy in tests/texture_ref.py.
+ *
+ * Inputs, per page (any pitches): P (H x W x 3 u8), a hole mask M (H x W u8; a pixel is a HOLE where M != 0) and `init`
+ *   (H x W x 3 u8), normally ctd_fill_rest's output for the same P and M.
+ * Parameters: the patch radius is 3 (CTD_TEXTURE_PATCH 7); R, the search radius, 1 .. CTD_TEXTURE_MAX_RADIUS (default 32);
+ *   n_em 1 .. 16 (5); n_sweep 1 .. 8 (2); n_init 1 .. 16 (8); seed, a u32.
+ * Sets: the working image C is `init` on hole pixels and P elsewhere.  A pixel s is a VALID source centre, V(s), where its
+ *   whole 7 x 7 patch lies inside the page and holds no hole pixel.  A pixel t is a TARGET where its patch holds a hole
+ *   pixel; patch coordinates are clamped to the page for targets.  Each target carries an offset (dy, dx) and a flag ok;
+ *   initially ok = 0 and the offset is (0, 0).
+ * Cost: D(t, off) = the sum over the 49 patch offsets o and the 3 channels of (C[clamp(t + o)] - C[t + off + o])^2, at most
+ *   49 * 3 * 255^2: a u32.  A candidate `off` is ADMISSIBLE where |dy|, |dx| <= R, t + off lies inside the page and
+ *   V(t + off) holds.  (A source patch holds no hole pixel, so C is P there.)
+ * Hash (mod 2^32): h = x * 0x9E3779B1 + y * 0x85EBCA77 + s * 0xC2B2AE3D + k * 0x27D4EB2F + seed;
+ *   h ^= h >> 16; h *= 0x7FEB352D; h ^= h >> 15; h *= 0x846CA68B; h ^= h >> 16
+ *   with (x, y) the target, s the sweep index counted from 0 over the whole call, k the draw index inside the sweep.  A draw
+ *   of radius rho is (h mod (2 rho + 1)) - rho; draw 2j gives dy and draw 2j + 1 gives dx.
+ * Sweeps are Jacobi: a sweep reads the field of the sweep before it and writes a new one.  There are n_em rounds of n_sweep
+ *   sweeps and one vote each; round 0 has one extra sweep in front, the INITIAL sweep.  In every sweep a target takes as its
+ *   best its own entry of the old field, its cost computed anew (C has changed); where ok = 0 the best is "none".  It then
+ *   tries candidates in a fixed order; an admissible candidate replaces the best where its cost is STRICTLY lower (or the
+ *   best is none).
+ *     initial sweep:   n_init candidates, candidate j = (draw 2j, draw 2j + 1) of radius R.
+ *     other sweeps:    propagation: for d in 1, 2, 4, 8 and for each d the neighbours t + (0, -d), (0, +d), (-d, 0), (+d, 0)
+ *                      as (dy, dx): a neighbour that lies inside the page, is a target and has ok = 1 in the OLD field gives
+ *                      its old offset as the candidate.  Then random search: for rho = R, R >> 1, .., 1 (the j-th of them
+ *                      uses draws 2j and 2j + 1) the candidate is the best so far in this sweep, or (0, 0) where it is
+ *                      none, plus the draw pair of radius rho.
+ * Vote, in place on C (it reads C at source pixels only, which are known, and writes hole pixels only): for a hole pixel p
+ *   and every patch offset o let t = p - o; where t lies inside the page and has ok = 1, add C[t + off(t) + o] to S and 1
+ *   to n.  n > 0: C[p] = (2 S + n) / (2 n) per channel; n = 0: C[p] keeps its value.
+ * Output: `out` is the last C: P on known pixels, bytes untouched.
+ * Row per page (ctd_texture_row, 32 bytes, padding 0): status; n_hole; n_target; n_source, the number of valid centres;
+ * n_unmatched, the targets with ok = 0 at the end.  status:
+ *   CTD_TEXTURE_NO_HOLE    n_hole = 0: `out` is a copy of P
+ *   CTD_TEXTURE_NO_SOURCE  n_hole > 0 and n_source = 0: `out` is P with `init` on the holes
+ *   CTD_TEXTURE_OK         otherwise: the last C
+ * (no status is a special case of the rule: without a hole there is no target, without a source no candidate is admissible).
+ * Properties: known pixels are unchanged; every filled value lies within the per-channel [min, max] of P's known pixels and
+ * `init`'s hole pixels; where those are all one colour, `out` is that colour.
+ * What the rule cannot do: it works at a single scale, so structure wider than a patch -- panel borders, long lines -- is
+ * not continued; a target further than R from every valid centre stays unmatched and keeps the smooth fill; a page smaller
+ * than 7 x 7 has no source; the defaults come from a measurement of the rule on synthetic screentone (DESIGN.md section
+ * 4.30) and have not been tuned on real pages.
+ *
+ * Scratch: scratch_dev, 16-byte aligned, scratch_bytes long.  With tiles(page) = ceil(H / 64) * ceil(W / 64) and
+ * px(page) = H * W:
+ *   bytes 0 .. 16 n_tiles - 1        four int32 a 64 x 64 tile (tile tile0 + ty * ceil(W / 64) + tx): its hole pixels, targets,
+ *                                    valid centres and, after every sweep, unmatched targets
+ *   bytes fld0 .. fld0 + 8 px - 1    the page's two field planes, one after the other, a dword a pixel:
+ *                                    (dy & 255) | (dx & 255) << 8 | ok << 16; sweep s reads plane s & 1 and writes the other
+ *   bytes cls0 .. cls0 + px - 1      the page's class plane, a byte a pixel: 1 hole, 2 target, 4 valid centre
+ * where fld0 = 16 n_tiles + 8 * (px of the pages before) and cls0 = 16 n_tiles + 8 * (px of all pages) + (px of the pages
+ * before): 16 bytes a tile and 9 bytes a pixel.  The contents after the call are not part of the interface. */
+#define CTD_TEXTURE_OK 0
+#define CTD_TEXTURE_NO_HOLE 1
+#define CTD_TEXTURE_NO_SOURCE 2
+#define CTD_TEXTURE_PATCH 7
+#define CTD_TEXTURE_MAX_RADIUS 127
+#define CTD_TEXTURE_MAX_SIDE 8192
+#define CTD_TEXTURE_TILE 64
+
+/* One page of a ctd_texture_fill call (a row of the device page table). */
+typedef struct ctd_texture_page {
+  const uint8_t* page_dev; /* 3 x u8 a pixel, rows `pitch` bytes apart                                      */
+  const uint8_t* hole_dev; /* u8, rows `hole_pitch` bytes apart                                             */
+  const uint8_t* init_dev; /* 3 x u8 a pixel, rows `init_pitch` bytes apart                                 */
+  uint8_t* out_dev;        /* H x W x 3, rows `out_pitch` bytes apart; overlaps no input of any page; read back
+                              as the aligned dwords that hold its bytes                                     */
+  int32_t H, W;            /* 1 .. CTD_TEXTURE_MAX_SIDE                                                     */
+  int32_t pitch, hole_pitch, init_pitch, out_pitch; /* >= 3 W, W, 3 W, 3 W                                  */
+  int32_t tile0;           /* tiles of the pages before this one                                            */
+  int32_t pad_;
+  int64_t fld0, cls0;      /* the page's field planes and class plane in scratch_dev, byte offsets          */
+} ctd_texture_page;
+
+typedef struct ctd_texture_params {
+  int32_t n_tiles; /* tiles of all pages (tile0 of a page after the last) */
+  int32_t radius, n_em, n_sweep, n_init;
+  uint32_t seed;
+  int64_t scratch_bytes; /* >= 16 n_tiles + 9 * (px of all pages) */
+} ctd_texture_params;
+
+/* One row of the result. */
+typedef struct ctd_texture_row {
+  int32_t status; /* CTD_TEXTURE_* */
+  int32_t n_hole, n_target, n_source, n_unmatched;
+  int32_t pad_[3];
+} ctd_texture_row;
+
+/* The rule above for all pages of a batch in 1 + (n_em * n_sweep + 1) + n_em + 1 launches on `stream`, a number the
+ * parameters fix, with no host wait between them: a prepare launch (one workgroup per tile: classes, C into `out`, the
+ * tile's counts), the sweeps and votes (one workgroup per tile; a tile without a target, or without a hole, returns after
+ * reading its count) and a rows launch (one workgroup per page: rows_dev[i] for page i).  All counts are sums of integers.
+ * The page table and `params` are read on the host during the call (the table is fetched from the device behind whatever
+ * `stream` holds, before the first launch).  n_pages = 0 launches nothing and returns CTD_OK.  A null table, params, row or
+ * scratch pointer with n_pages > 0, a negative count, a null page, hole, init or out pointer, a side < 1 or
+ * > CTD_TEXTURE_MAX_SIDE, a pitch below the row size, tile0 / n_tiles / fld0 / cls0 that are not the sums above, a
+ * scratch_bytes below the layout's size, a parameter outside its range, or an `out` that overlaps an input of any page is
+ * an error rc and launches nothing. */
+int ctd_texture_fill(const ctd_texture_page* pages_dev, int32_t n_pages, const ctd_texture_params* params, void* scratch_dev,
+                     ctd_texture_row* rows_dev, void* stream);
+
 /* ---- layout boxes: the largest free rectangle in every balloon (added within ABI v10) ------------------------------- */
 
 /* An addition to ABI v10 like the four above: one entry point, three structs, nothing existing changes.
