@@ -40,6 +40,8 @@ TEXTURE_OK, TEXTURE_NO_HOLE, TEXTURE_NO_SOURCE = range(3)
 TEXTURE_PATCH, TEXTURE_MAX_RADIUS, TEXTURE_MAX_SIDE, TEXTURE_TILE = 7, 127, 8192, 64
 LAYOUT_OK, LAYOUT_NO_REGION, LAYOUT_EMPTY = range(3)
 LAYOUT_MAX_INSET = 16
+FIT_OK, FIT_NO_REGION, FIT_NO_TEXT, FIT_NO_ANCHOR, FIT_NO_FIT = range(5)
+FIT_MAX_CANDS, FIT_MAX_LINES, FIT_MAX_GLYPHS = 16, 32, 4096
 TYPESET_MAX_SIDE, TYPESET_MAX_RADIUS, TYPESET_TILE_W, TYPESET_TILE_H = 8192, 12, 64, 32
 TYPESET_OK, TYPESET_EMPTY, TYPESET_OUTSIDE = range(3)          # typeset.typeset_tables' status column (not part of the ABI)
 RASTER_MAX_SIDE, RASTER_MAX_SCALE = 1024, 1 << 22
@@ -162,6 +164,28 @@ class CtdLayoutRow(C.Structure):
                 ("a_area", C.c_int32), ("a_rect", C.c_int32 * 4)]
 
 
+class CtdFitJob(C.Structure):
+    _fields_ = [("n_glyphs", C.c_int32), ("n_cands", C.c_int32), ("cand0", C.c_int32), ("pad_", C.c_int32), ("break0", C.c_int64)]
+
+
+class CtdFitCand(C.Structure):
+    _fields_ = [("line", C.c_int32), ("gap", C.c_int32), ("cum0", C.c_int64)]
+
+
+class CtdFitParams(C.Structure):
+    _fields_ = [("inset", C.c_int32), ("max_words", C.c_int32), ("n_rows", C.c_int32), ("n_cands", C.c_int32),
+                ("n_cum", C.c_int64), ("n_breaks", C.c_int64)]
+
+
+class CtdFitLine(C.Structure):
+    _fields_ = [("start", C.c_int32), ("x1", C.c_int32), ("y", C.c_int32), ("width", C.c_int32), ("length", C.c_int32)]
+
+
+class CtdFitRow(C.Structure):
+    _fields_ = [("status", C.c_int32), ("cand", C.c_int32), ("n_lines", C.c_int32), ("n_inner", C.c_int32),
+                ("lines", CtdFitLine * 32)]
+
+
 class CtdTypesetPage(C.Structure):
     _fields_ = [("page_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int64)]
 
@@ -271,6 +295,7 @@ SYMBOLS = {
     "ctd_erase_text": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(CtdEraseParams), _vp, _vp]),
     "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
     "ctd_layout_boxes": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdLayoutParams), _vp, _vp]),
+    "ctd_layout_fit": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdFitParams), _vp, _vp]),
     "ctd_typeset": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(CtdTypesetParams), _vp, _vp]),
     "ctd_typeset_glyphs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdGlyphParams), _vp, _vp]),
     "ctd_rasterise_glyphs": (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),

@@ -1438,6 +1438,46 @@ int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloo
   return CTD_OK;
 }
 
+int ctd_layout_fit(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_dev, int32_t n,
+                   const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev, const ctd_fit_cand* cands_dev,
+                   const int32_t* cum_dev, const uint8_t* breaks_dev, const ctd_fit_params* params, ctd_fit_row* rows_dev,
+                   void* stream) {
+  if (n < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
+  const ctd_fit_params prm = *params;
+  if (prm.inset < 0 || prm.inset > CTD_LAYOUT_MAX_INSET || prm.max_words < 0 || prm.max_words > CTD_BALLOON_MAX_WORDS ||
+      prm.n_rows < 0 || prm.n_cands < 0 || prm.n_cum < 0 || prm.n_breaks < 0)
+    return fail(CTD_ERR_INVALID, "fit: inset 0..16, max_words 0..8192, n_rows, n_cands, n_cum, n_breaks >= 0");
+  if (n == 0) return CTD_OK;
+  if (!jobs_dev || !fit_jobs_dev || !balloon_rows_dev || !rows_dev || (prm.max_words > 0 && !bits_dev) ||
+      (prm.n_cands > 0 && !cands_dev) || (prm.n_cum > 0 && !cum_dev) || (prm.n_breaks > 0 && !breaks_dev))
+    return fail(CTD_ERR_INVALID, "null pointer");
+  // the two small tables decide what the kernel reads: fetched and checked here, before anything launches
+  std::vector<ctd_fit_job> fj((size_t)n);
+  std::vector<ctd_fit_cand> cd((size_t)prm.n_cands);
+  HIP_TRY(hipMemcpyAsync(fj.data(), fit_jobs_dev, fj.size() * sizeof(ctd_fit_job), hipMemcpyDefault, (hipStream_t)stream));
+  if (prm.n_cands > 0)
+    HIP_TRY(hipMemcpyAsync(cd.data(), cands_dev, cd.size() * sizeof(ctd_fit_cand), hipMemcpyDefault, (hipStream_t)stream));
+  HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+  for (int32_t i = 0; i < n; ++i) {
+    const ctd_fit_job& j = fj[(size_t)i];
+    if (j.n_glyphs < 0 || j.n_glyphs > CTD_FIT_MAX_GLYPHS || j.n_cands < 0 || j.n_cands > CTD_FIT_MAX_CANDS || j.cand0 < 0 ||
+        (int64_t)j.cand0 + j.n_cands > prm.n_cands)
+      return fail(CTD_ERR_INVALID, "fit: a job's n_glyphs 0..4096, n_cands 0..16, candidate rows inside n_cands");
+    if (j.break0 != -1 && (j.break0 < 0 || j.break0 > prm.n_breaks - j.n_glyphs))
+      return fail(CTD_ERR_INVALID, "fit: a job's break0 is -1 or leaves n_glyphs bytes inside n_breaks");
+    for (int32_t c = 0; c < j.n_cands; ++c) {
+      const ctd_fit_cand& k = cd[(size_t)(j.cand0 + c)];
+      if (k.line < 1 || k.gap < 0) return fail(CTD_ERR_INVALID, "fit: a candidate's line >= 1, gap >= 0");
+      if (k.cum0 < 0 || k.cum0 > prm.n_cum - j.n_glyphs - 1)
+        return fail(CTD_ERR_INVALID, "fit: a candidate's cum0 leaves n_glyphs + 1 int32 inside n_cum");
+    }
+  }
+  HIP_TRY(launch_layout_fit(jobs_dev, fit_jobs_dev, n, balloon_rows_dev, bits_dev, cands_dev, cum_dev, breaks_dev, prm, rows_dev,
+                            (hipStream_t)stream));
+  return CTD_OK;
+}
+
 int ctd_typeset(const ctd_typeset_page* pages_dev, const ctd_typeset_layer* layers_dev, const ctd_typeset_tile* tiles_dev,
                 const int32_t* entries_dev, const uint8_t* cov_dev, const ctd_typeset_params* params,
                 ctd_typeset_row* rows_dev, void* stream) {

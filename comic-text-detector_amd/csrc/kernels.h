@@ -204,6 +204,13 @@ hipError_t launch_balloon_regions(const ctd_balloon_job* jobs, int n, const ctd_
 hipError_t launch_layout_boxes(const ctd_layout_job* jobs, int n, const ctd_balloon_row* balloon_rows,
                                const uint64_t* bits, const ctd_layout_params& prm, ctd_layout_row* rows, hipStream_t st);
 
+// ---- kernels_fit.hip ------------------------------------------------------------
+// ctd_layout_fit's one launch (one workgroup per block; n >= 1, prm and every offset of the two small tables checked by the
+// caller): the dynamic-LDS limit as above
+hipError_t launch_layout_fit(const ctd_layout_job* jobs, const ctd_fit_job* fit_jobs, int n, const ctd_balloon_row* balloon_rows,
+                             const uint64_t* bits, const ctd_fit_cand* cands, const int32_t* cum, const uint8_t* breaks,
+                             const ctd_fit_params& prm, ctd_fit_row* rows, hipStream_t st);
+
 // ---- kernels_typeset.hip --------------------------------------------------------
 // ctd_typeset's one launch (one workgroup per row of the tile table; n_tiles >= 1, n_layers >= 1, the counts and pointers
 // checked and the rows cleared by the caller): returns what hipGetLastError says right after the launch

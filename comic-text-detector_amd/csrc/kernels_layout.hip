@@ -5,7 +5,8 @@
 //
 // layout_kernel, ONE launch, one workgroup per block, two bit planes of the window in dynamic LDS (nw = ceil(ww / 64)
 // 64-bit words a row, at most CTD_BALLOON_MAX_WORDS words each; the launch is sized by params.max_words):
-//   load    B_b from bits_dev into plane A (read only; the last word of a row is masked to the window).
+//   load    B_b from bits_dev into plane A (read only; the last word of a row is masked to the window).  This step and the
+//           next are layout_bits.h's `load_eroded`, shared with kernels_fit.hip.
 //   erode   by shifted ANDs: rows A -> Q (shifts cross the word boundaries of a row, zeros come in at the window's sides),
 //           columns Q -> A = E_b (rows beyond the window count as zero); |E_b| by popcount on the way.
 //   search  one thread a top row y, no barrier: for k = 1, 2, ... the row P_k[y] = E[y] & ... & E[y + k - 1] is kept in
@@ -22,20 +23,18 @@
 // step is one AND and one comparison because no row ever changes after its first step.
 #include <mutex>
 
-#include "kernels.h"
+#include "layout_bits.h"
 
 namespace {
 
-constexpr int LY_THREADS = 512, LY_WAVES = LY_THREADS / 64;
+using namespace lybits;                                    // u64, LY_THREADS, hero3 / load_eroded, run_at
+
 constexpr int LY_MAX_DEVICES = 64;
 static_assert(sizeof(ctd_layout_job) == 32 && sizeof(ctd_layout_params) == 16 && sizeof(ctd_layout_row) == 48,
               "layout ABI sizes (layout.py dtypes)");
 static_assert(offsetof(ctd_layout_job, ax) == 16 && offsetof(ctd_layout_job, word0) == 24 && offsetof(ctd_layout_row, rect) == 12 &&
               offsetof(ctd_layout_row, a_area) == 28 && offsetof(ctd_layout_row, a_rect) == 32 && alignof(ctd_layout_row) == 4,
               "layout ABI offsets");
-static_assert(CTD_LAYOUT_MAX_INSET < 64, "an erosion shift stays inside the neighbouring word");
-
-typedef unsigned long long u64;
 
 // a rectangle of the search, in window coordinates; area 0: none yet
 struct Rect {
@@ -52,13 +51,6 @@ __device__ __forceinline__ bool better(const Rect& a, const Rect& b) {
 __device__ __forceinline__ void offer(Rect& best, int w, int y, int x, int k) {
   const Rect c = {w * k, y, x, y + k};
   if (better(c, best)) best = c;
-}
-
-// the middle word of three eroded by m pixels either way (m < 64): bit x stays iff bits x - m .. x + m are all set
-__device__ __forceinline__ u64 hero3(u64 l, u64 mid, u64 r, int m) {
-  u64 v = mid;
-  for (int s = 1; s <= m; ++s) v &= ((mid << s) | (l >> (64 - s))) & ((mid >> s) | (r << (64 - s)));
-  return v;
 }
 
 // the leftmost longest run of ones of a word that is neither 0 nor all ones: s2, s4, ... mark the starts of runs of at
@@ -106,41 +98,6 @@ __device__ __forceinline__ void row_run(const u64* __restrict__ p, int nw, int& 
   width = bw, x = bx;
 }
 
-// the run of ones of a row that contains column c (0 <= c < 64 nw): [x1, x2), or false where the bit is not set
-__device__ __forceinline__ bool run_at(const u64* __restrict__ p, int nw, int c, int& x1, int& x2) {
-  const int jc = c >> 6, b = c & 63;
-  const u64 w = p[jc];
-  if (!((w >> b) & 1ull)) return false;
-  const u64 lo = ~w & ((1ull << b) - 1ull), hi = ~w & ~((2ull << b) - 1ull);
-  int l = 64 * jc, r = 64 * jc + 64;
-  if (lo) {
-    l += 64 - __builtin_clzll(lo);
-  } else {
-    for (int j = jc - 1; j >= 0; --j) {
-      const u64 v = p[j];
-      if (v != ~0ull) {
-        l -= __builtin_clzll(~v);
-        break;
-      }
-      l -= 64;
-    }
-  }
-  if (hi) {
-    r = 64 * jc + __builtin_ctzll(hi);
-  } else {
-    for (int j = jc + 1; j < nw; ++j) {
-      const u64 v = p[j];
-      if (v != ~0ull) {
-        r += __builtin_ctzll(~v);
-        break;
-      }
-      r += 64;
-    }
-  }
-  x1 = l, x2 = r;
-  return true;
-}
-
 __device__ __forceinline__ Rect shfl_down(const Rect& r, int d) {
   return {__shfl_down(r.area, d, 64), __shfl_down(r.y1, d, 64), __shfl_down(r.x1, d, 64), __shfl_down(r.y2, d, 64)};
 }
@@ -167,39 +124,12 @@ __global__ __launch_bounds__(LY_THREADS) void layout_kernel(const ctd_layout_job
     }
     return;
   }
-  const int ww = (int)ww_ll, wh = (int)wh_ll, nw = (int)nw_ll, words = (int)words_ll, m = prm.inset;
+  const int ww = (int)ww_ll, wh = (int)wh_ll, nw = (int)nw_ll, m = prm.inset;
   u64* __restrict__ A = planes;
   u64* __restrict__ Q = planes + prm.max_words;
-  const u64 last_valid = (ww & 63) ? ((1ull << (ww & 63)) - 1ull) : ~0ull;   // the window's bits of a row's last word
 
-  // ---- load B_b
-  {
-    const u64* __restrict__ src = bits + J.word0;
-    for (int i = t; i < words; i += LY_THREADS) {
-      const int j = i % nw;
-      A[i] = j == nw - 1 ? src[i] & last_valid : src[i];
-    }
-  }
-  __syncthreads();
-  // ---- erode: rows A -> Q ...
-  for (int i = t; i < words; i += LY_THREADS) {
-    const int j = i % nw;
-    Q[i] = hero3(j > 0 ? A[i - 1] : 0ull, A[i], j + 1 < nw ? A[i + 1] : 0ull, m);
-  }
-  __syncthreads();
-  // ... and columns Q -> A = E_b
-  int n_inner = 0;
-  for (int i = t; i < words; i += LY_THREADS) {
-    const int y = i / nw;
-    u64 v = 0ull;
-    if (y >= m && y + m < wh) {
-      v = Q[i];
-      for (int d = 1; d <= m; ++d) v &= Q[i - d * nw] & Q[i + d * nw];
-    }
-    A[i] = v;
-    n_inner += __popcll(v);
-  }
-  __syncthreads();
+  // ---- load B_b and erode it: plane A = E_b, |E_b| by popcount on the way
+  int n_inner = load_eroded(A, Q, bits + J.word0, ww, wh, nw, m, t);
 
   // ---- search: one thread a top row; plane Q holds P_k[y] of every row, each touched by its own thread alone
   const bool anchored = J.ax >= wx1 && J.ax < J.win[2] && J.ay >= wy1 && J.ay < J.win[3];

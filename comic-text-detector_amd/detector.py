@@ -670,7 +670,7 @@ class TextDetector:
         return out
 
     def typeset_text(self, pages: Sequence[Page], boxes, font, atlas, runs, sizes, fill=(0, 0, 0), stroke=(255, 255, 255),
-                     radius=3, prefer: str = "a_rect", inplace: bool = False, **flow_kw):
+                     radius=3, prefer: str = "a_rect", inplace: bool = False, shaped=None, **flow_kw):
         """`typeset_glyphs` from outlines, at the size that fits: per block of `boxes` that is `ok` and has a run,
         `glyphs.fit` picks the largest of the ascending `sizes` (pixels an em) at which the run flows into the block's
         rectangle (the one `typeset_glyphs` uses); ONE `atlas.rasterise` launch then makes every (glyph, size) instance
@@ -678,7 +678,15 @@ class TextDetector:
         composites all of them in one launch (returns its `TypesetPages`).  `font`: a `glyphs.OutlineFont`; `runs[j]`:
         block j's gids OF THE FONT, or None to skip the block.  The result's `layer_of[j]` is block j's layer, -1 where it was skipped; `size[i]` the size chosen for layer
         i and `fits[i]` whether its lines stay inside its rectangle at that size (False: not even `sizes[0]` fits, which is
-        then used)."""
+        then used).
+        shaped: the `BalloonRegions` that `boxes` was made from.  The lines then follow each balloon's outline instead of
+        filling its rectangle: the metrics are taken per size over the batch's unique gids (a loop over `sizes`, at most
+        16 of them, not over blocks), ONE `layout.shaped_fit` call with `boxes.anchors` and the inset `boxes.inset` plus the
+        largest stroke radius (16 at the most) gives every block its largest size and its line slots, and
+        `glyphs.place_lines` places all runs at once.  Horizontal text only; `flow_kw` may hold `line` (one height for all
+        sizes), `gap`, `align` and `breaks` (one list entry per block of `boxes`).  A block whose fit is not OK takes the
+        rectangle path above.  The result gains `shaped[i]` (bool: layer i follows the outline), `n_lines[i]` (its lines; 0
+        on the rectangle path) and `fit`, the `ShapedFit` of all blocks of `boxes`."""
         from . import glyphs as gl, typeset as ts
         if prefer not in ("a_rect", "rect"):
             raise ValueError('prefer: "a_rect" or "rect"')
@@ -694,6 +702,9 @@ class TextDetector:
         anchored = (np.asarray(boxes.a_area) > 0) if prefer == "a_rect" else np.zeros((nb,), bool)
         rects = np.where(anchored[:, None], boxes.a_rect, boxes.rect).reshape(nb, 4)[idx]
         run_of = [ts._ints(runs[j], (-1,), "runs") for j in idx]
+        if shaped is not None:
+            return self._typeset_shaped(pages, boxes, shaped, font, atlas, idx, layer_of, run_of, rects, sizes, fill, stroke,
+                                        radius, inplace, dict(flow_kw))
         chosen = [gl.fit(run, font, rects[i], sizes, **flow_kw) for i, run in enumerate(run_of)]
         count = [len(a) for a in run_of]
         ids = atlas.rasterise(font, np.concatenate(run_of) if run_of else np.zeros((0,), np.int64),
@@ -704,6 +715,71 @@ class TextDetector:
                                 stroke=stroke, radius=radius, inplace=inplace, device=self.net.device)
         out.layer_of, out.fits = layer_of, np.array([c[1] for c in chosen], bool)
         out.size = np.array([c[0] for c in chosen])
+        return out
+
+    def _typeset_shaped(self, pages, boxes, shaped, font, atlas, idx, layer_of, run_of, rects, sizes, fill, stroke, radius,
+                        inplace, kw):
+        """`typeset_text` with `shaped=`: layers `idx` of `boxes` with the runs `run_of`; see there."""
+        from . import _lib as L, glyphs as gl, layout
+        sizes = list(sizes)
+        if not sizes or len(sizes) > L.FIT_MAX_CANDS or any(b <= a for a, b in zip(sizes, sizes[1:])):
+            raise ValueError(f"sizes: ascending, 1 .. {L.FIT_MAX_CANDS} of them")
+        if kw.get("vertical"):
+            raise ValueError("shaped: horizontal lines only")
+        nb, nl = len(boxes), len(idx)
+        if len(shaped) != nb or not np.array_equal(shaped.index, boxes.index):
+            raise ValueError("`shaped` is not the BalloonRegions that `boxes` was made from")
+        align, gap, line, breaks = kw.pop("align", "center"), int(kw.pop("gap", 0)), kw.pop("line", None), kw.pop("breaks", None)
+        kw.pop("vertical", None)
+        if kw:
+            raise ValueError(f"shaped: unknown keywords {sorted(kw)}")
+        if breaks is not None and len(breaks) != nb:
+            raise ValueError("shaped: breaks holds one entry (or None) per block of `boxes`")
+        count = np.array([len(a) for a in run_of], np.int64).reshape(nl)
+        flat = np.concatenate(run_of) if run_of else np.zeros((0,), np.int64)
+        uniq, pos = np.unique(flat, return_inverse=True)
+        metrics = [font.metrics(uniq, s) for s in sizes]                     # per SIZE, over the batch's unique gids
+        adv = np.stack([m.advance[pos.reshape(-1), 0] for m in metrics]).reshape(len(sizes), len(flat))
+        first = np.cumsum(count) - count
+        # per size the cumulative advances of every run, a 0 in front of each: (sizes, glyphs + layers), cut per layer
+        cum = np.zeros((len(sizes), len(flat) + nl), np.int64)
+        at = np.arange(len(flat)) + np.repeat(np.arange(nl), count) + 1
+        csum = np.cumsum(adv, axis=1)
+        base = np.concatenate([np.zeros((len(sizes), 1), np.int64), csum], axis=1)[:, first]      # the sum in front of a run
+        cum[:, at] = csum - np.repeat(base, count, axis=1)
+        cums = [None] * nb
+        for j, c in zip(idx, np.split(cum, (first + np.arange(nl))[1:], axis=1)):
+            cums[j] = c
+        lines = np.array([m.line if line is None else int(line) for m in metrics], np.int64)
+        inset = min(boxes.inset + (int(radius.max()) if nl else 0), L.LAYOUT_MAX_INSET)
+        fit = layout.shaped_fit(shaped, cums, lines, gap, breaks=breaks, anchors=boxes.anchors, inset=inset)
+        ok = fit.ok[idx]
+        cand = np.where(ok, fit.cand[idx], 0)
+        # the rest takes the rectangle path: `glyphs.fit` and `flow_outlines` per block, as without `shaped`
+        rect_kw = dict(gap=gap, align=align, line=line)
+        rest = np.flatnonzero(~ok)
+        chosen = {i: gl.fit(run_of[i], font, rects[i], sizes, breaks=None if breaks is None else breaks[idx[i]], **rect_kw)
+                  for i in rest}
+        size = np.array(sizes)[cand]
+        for i, c in chosen.items():
+            size[i] = c[0]
+        ids = atlas.rasterise(font, flat, np.repeat(size.astype(np.float64), count))
+        xy = np.zeros((len(flat), 2), np.int64)
+        of_layer = np.repeat(np.arange(nl), count)
+        sel = ok[of_layer]
+        if sel.any():
+            per = np.repeat(cand, count)[sel]
+            bearing = np.stack([m.bearing for m in metrics])[per, pos.reshape(-1)[sel]]
+            xy[sel] = gl.place_lines(fit, count[ok], adv[per, np.flatnonzero(sel)], bearing, align=align, blocks=idx[ok])
+        for i in rest:
+            xy[first[i]: first[i] + count[i]] = gl.flow_outlines(run_of[i], font, rects[i], chosen[i][0], breaks=None if breaks is None
+                                                                 else breaks[idx[i]], **rect_kw)[0]
+        out = gl.typeset_glyphs(pages, atlas, boxes.index[idx, 0], of_layer, ids, xy, fill=fill, stroke=stroke, radius=radius,
+                                inplace=inplace, device=self.net.device)
+        out.layer_of, out.size, out.shaped = layer_of, size, ok.copy()
+        out.fits = np.array([True if ok[i] else chosen[i][1] for i in range(nl)], bool)
+        out.n_lines = np.where(ok, fit.n_lines[idx], 0).astype(np.int64)
+        out.fit = fit
         return out
 
     def fill_rest(self, pages: Sequence[Page], results, erased=None, **erase_kw):

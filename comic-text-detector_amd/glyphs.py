@@ -40,7 +40,7 @@ from . import _lib as L
 from .pagecall import Page, PageCall, need_gpu, table_dtype
 from .typeset import MAX_COORD, ROW_DTYPE, TILE_DTYPE, TypesetPages, _bin_tiles, _ints, _layer_args, _layers, _open_pages, _rects
 
-__all__ = ["GlyphAtlas", "glyph_tables", "typeset_glyphs", "flow", "LAYER_DTYPE", "PLACE_DTYPE", "RECORD_DTYPE", "OutlineFont",
+__all__ = ["GlyphAtlas", "glyph_tables", "typeset_glyphs", "flow", "place_lines", "LAYER_DTYPE", "PLACE_DTYPE", "RECORD_DTYPE", "OutlineFont",
            "segments_from_ops", "outline_boxes", "flow_outlines", "fit", "RASTER_JOB_DTYPE"]
 
 # numpy views of `ctd_glyph_layer` / `_place` / `_record` and `ctd_raster_job` (include/ctd_hip.h)
@@ -291,6 +291,44 @@ def flow(ids, atlas, rect, line: Optional[int] = None, gap: int = 0, vertical: b
         xy = np.stack([x1 + pen + bear[:, 0], y1 + lead + of * (line + gap) + bear[:, 1]], axis=1)
     fits = bool((length <= along).all() and total <= across)
     return xy.astype(np.int64).reshape(n, 2), fits
+
+
+def place_lines(fit, count, adv, bearing, align: str = "center", blocks=None) -> np.ndarray:
+    """The glyph positions of the blocks of a `layout.ShapedFit`, all blocks at once in numpy: xy (sum(count), 2), the
+    top-left pixel of every glyph.  blocks: the blocks of `fit` to place, all of them `ok` (default: every ok block, in
+    order); count[i]: the glyphs of blocks[i]'s run; adv and bearing: per glyph, runs one behind the other, the horizontal
+    advance and the bearing (x, y) at the size of the block's chosen candidate.  A line's pen starts at its slot's x1 plus
+    the shift `flow` gives a line in its box -- "left" 0, "center" slack >> 1, "right" the slack, the slack the slot's width
+    less the line's advances -- and a glyph goes to (pen + bearing_x, line top + bearing_y).  ValueError where the runs are
+    not the ones the fit was made with (a line record's length is not the sum of its glyphs' advances)."""
+    if align not in ("left", "center", "right"):
+        raise ValueError('align: "left", "center" or "right"')
+    blocks = np.flatnonzero(fit.ok) if blocks is None else _ints(blocks, (-1,), "blocks")
+    nb = len(blocks)
+    if nb and (blocks.min() < 0 or blocks.max() >= len(fit) or not fit.ok[blocks].all()):
+        raise ValueError("blocks: blocks of the fit that are ok")
+    count = _ints(count, (nb,), "count")
+    total = int(count.sum())
+    adv, bearing = _ints(adv, (total,), "adv"), _ints(bearing, (total, 2), "bearing")
+    if total == 0:
+        return np.zeros((0, 2), np.int64)
+    n_lines = fit.n_lines[blocks].astype(np.int64)
+    first = np.cumsum(count) - count                       # a block's first glyph
+    of_block = np.repeat(np.arange(nb), n_lines)           # per line of all blocks
+    k = np.arange(len(of_block)) - np.repeat(np.cumsum(n_lines) - n_lines, n_lines)
+    rec = fit.lines[blocks[of_block], k].astype(np.int64)  # start, x1, y, width, length
+    start = first[of_block] + rec[:, 0]
+    end = np.concatenate([start[1:], [total]])
+    end[np.cumsum(n_lines) - 1] = first + count            # a block's last line ends with its run
+    before = np.cumsum(adv) - adv                          # the advances in front of a glyph, over all runs
+    cum = np.concatenate([before, [before[-1] + adv[-1]]])
+    if (end <= start).any() or not np.array_equal(cum[end] - cum[start], rec[:, 4]):
+        raise ValueError("the runs are not the ones the fit was made with")
+    slack = rec[:, 3] - rec[:, 4]
+    shift = {"left": np.zeros_like(slack), "center": slack >> 1, "right": slack}[align]
+    of = np.repeat(np.arange(len(start)), end - start)     # the glyph's line
+    pen = rec[of, 1] + shift[of] + before - before[start][of]
+    return np.stack([pen + bearing[:, 0], rec[of, 2] + bearing[:, 1]], axis=1)
 
 
 def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, glyph, xy, fill=(0, 0, 0),

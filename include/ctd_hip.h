@@ -870,6 +870,117 @@ typedef struct ctd_layout_row {
 int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloon_row* balloon_rows_dev,
                      const uint64_t* bits_dev, const ctd_layout_params* params, ctd_layout_row* rows_dev, void* stream);
 
+/* ---- shaped fit: text lines that follow each balloon's outline (added within ABI v10) -------------------------------- */
+
+/* An addition to ABI v10 like the ones above: one entry point, five structs, nothing existing changes.
+ * The layout section's rectangle holds about 64 % of an elliptic balloon.  A typesetter sets short-long-short lines that
+ * follow the outline instead.  This is that step for every block of a batch and every candidate size of its run, this
+ * library's own rule, integers only.  Restated in numpy in tests/fit_ref.py.  It builds on the layout section's job (window,
+ * word0, anchor (ax, ay) in page coordinates) and its E_b: B_b eroded by a (2m + 1)-square and clipped at the window, inset
+ * m in 0 .. CTD_LAYOUT_MAX_INSET.  The caller adds the stroke radius of the text to the inset.
+ * Inputs, per block b: the layout job; a run of G_b glyphs (0 .. CTD_FIT_MAX_GLYPHS); C_b candidates (0 ..
+ *   CTD_FIT_MAX_CANDS) in ascending order of size, consecutive rows of the candidate table; optionally a break byte per
+ *   glyph (non-zero: a line may end after this glyph); without a break table a line may end after every glyph.
+ * Inputs, per candidate c: a line height h >= 1, a gap g >= 0 and the run's cumulative advances at that size, G_b + 1
+ *   non-decreasing int32 of which the first is 0 (the host makes the prefix sums).
+ *   axis run   of window row y: where pixel (ax, y) is in E_b, [l(y), r(y)), the maximal run of ones of that row of E_b that
+ *           contains column ax; otherwise the row has none.  (The run that contains ax of an AND of rows is the
+ *           intersection of the rows' own axis runs.)
+ *   slot    of top row t at height h: it exists where rows t .. t + h - 1 all lie in the window and all have an axis run.
+ *           L = max l and R = min r over those rows, half = min(ax - L, R - ax); the slot is [ax - half, ax + half): 2 half
+ *           wide and symmetric about the axis.
+ *   stack   of n lines for (h, g): total = n h + (n - 1) g, top = ay - (total >> 1), line k has the top row
+ *           top + k (h + g).  The stack is admissible where every line has a slot.
+ *   break   glyphs.flow's horizontal greedy breaker with the slot's width for the box's: line k starts at glyph s_k
+ *           (s_0 = 0) and ends before the first glyph whose advance summed from s_k would pass the slot's width; where that
+ *           is not the run's end and there is a break table, it ends after the last allowed break in s_k .. end - 1 where
+ *           there is one, and stays where it is otherwise (a hard break).  A line whose first glyph does not fit its slot
+ *           makes the stack FAIL (flow lets that glyph stand alone; here the text would leave the balloon).
+ *   fit     stack n fits where it is admissible and the breaker places all G_b glyphs in exactly n lines, none of them
+ *           empty.  A candidate's n is the smallest n in 1 .. CTD_FIT_MAX_LINES that fits; the block's answer is the
+ *           candidate of the largest index that has one.  Every (candidate, n) is evaluated: nothing is assumed monotone.
+ * status, the first that applies:
+ *   CTD_FIT_NO_REGION  as CTD_LAYOUT_NO_REGION (no balloon row, a balloon row that is not OK, more than max_words words)
+ *   CTD_FIT_NO_TEXT    G_b = 0 or C_b = 0
+ *   CTD_FIT_NO_ANCHOR  (ax, ay) is no pixel of E_b (or lies outside the window)
+ *   CTD_FIT_NO_FIT     no candidate has a stack that fits
+ *   CTD_FIT_OK
+ * In every status but OK all other fields of the row are 0.
+ * Row per block, 656 bytes of int32, no padding: status; cand, the candidate's index among the block's; n_lines; n_inner =
+ * |E_b|; CTD_FIT_MAX_LINES line records of five int32 (the start glyph, the slot's x1 and the line's top row in page
+ * coordinates, the slot's width, the length of the line's advances <= width); the records beyond n_lines are 0.
+ * PRECONDITION: a candidate's cumulative advances do not decrease.  The entry point sees no device array of that size; where
+ * they do decrease the lines are some function of the table, and nothing outside the tables is read.
+ * Limits: the order of the glyphs is kept and no word is moved down to balance the lines, so a last line may be short;
+ * horizontal lines only; a region whose anchor column leaves the region is cut there (a comb's teeth, the far side of a
+ * ring); one axis per block, so an L-shaped balloon still gets the arm of its anchor. */
+#define CTD_FIT_OK 0
+#define CTD_FIT_NO_REGION 1
+#define CTD_FIT_NO_TEXT 2
+#define CTD_FIT_NO_ANCHOR 3
+#define CTD_FIT_NO_FIT 4
+#define CTD_FIT_MAX_CANDS 16
+#define CTD_FIT_MAX_LINES 32
+#define CTD_FIT_MAX_GLYPHS 4096
+
+/* One block's text (a row of the device fit job table, beside row i of the layout job table), 24 bytes. */
+typedef struct ctd_fit_job {
+  int32_t n_glyphs; /* G_b                                                                                  */
+  int32_t n_cands;  /* C_b                                                                                  */
+  int32_t cand0;    /* the block's first row of the candidate table                                         */
+  int32_t pad_;
+  int64_t break0;   /* the run's first byte of breaks_dev (n_glyphs bytes), or -1: a break after every glyph */
+} ctd_fit_job;
+
+/* One candidate size of one block (a row of the device candidate table), 16 bytes. */
+typedef struct ctd_fit_cand {
+  int32_t line; /* h, the line height                                                      */
+  int32_t gap;  /* g, the rows between two lines                                           */
+  int64_t cum0; /* the first of the run's n_glyphs + 1 cumulative advances in cum_dev      */
+} ctd_fit_cand;
+
+typedef struct ctd_fit_params {
+  int32_t inset;
+  int32_t max_words; /* as ctd_layout_params                                               */
+  int32_t n_rows;    /* as ctd_layout_params                                               */
+  int32_t n_cands;   /* the rows of cands_dev                                              */
+  int64_t n_cum;     /* the int32 of cum_dev                                               */
+  int64_t n_breaks;  /* the bytes of breaks_dev                                            */
+} ctd_fit_params;
+
+/* One line of a fitted stack. */
+typedef struct ctd_fit_line {
+  int32_t start;  /* the line's first glyph                                                */
+  int32_t x1;     /* the slot's left column, page coordinates                              */
+  int32_t y;      /* the line's top row, page coordinates                                  */
+  int32_t width;  /* the slot's width                                                      */
+  int32_t length; /* the sum of the line's advances                                        */
+} ctd_fit_line;
+
+/* One row of the result. */
+typedef struct ctd_fit_row {
+  int32_t status; /* CTD_FIT_* */
+  int32_t cand;
+  int32_t n_lines;
+  int32_t n_inner;
+  ctd_fit_line lines[CTD_FIT_MAX_LINES];
+} ctd_fit_row;
+
+/* The rule above for n blocks in ONE launch on `stream`, one workgroup per block: rows_dev[i] is the row of jobs_dev[i] and
+ * fit_jobs_dev[i].  jobs_dev, balloon_rows_dev and bits_dev are ctd_layout_boxes' (bits_dev is read only; rows_dev needs
+ * 4-byte alignment, cum_dev too).  `params` is read on the host during the call, and so are fit_jobs_dev and cands_dev: the two
+ * small tables are fetched from the device behind whatever `stream` holds, before the launch, so that every offset is checked
+ * before a kernel uses it.  n = 0 launches nothing.  An error rc, and no launch, for: a negative n, n_rows, n_cands, n_cum or
+ * n_breaks; inset outside 0 .. 16; max_words outside 0 .. 8192; a missing table with n > 0 (bits_dev may be NULL where
+ * max_words is 0, cands_dev, cum_dev and breaks_dev where their counts are 0); a job with n_glyphs outside 0 ..
+ * CTD_FIT_MAX_GLYPHS, n_cands outside 0 .. CTD_FIT_MAX_CANDS, candidate rows beyond n_cands, or a break0 that is neither -1
+ * nor leaves n_glyphs bytes inside n_breaks; a candidate of a job with line < 1, gap < 0, or a cum0 that does not leave
+ * n_glyphs + 1 int32 inside n_cum. */
+int ctd_layout_fit(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_dev, int32_t n,
+                   const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev, const ctd_fit_cand* cands_dev,
+                   const int32_t* cum_dev, const uint8_t* breaks_dev, const ctd_fit_params* params, ctd_fit_row* rows_dev,
+                   void* stream);
+
 /* ---- typeset: text layers with outlines composited into pages (added within ABI v10) ---------------------------------- */
 
 /* An addition to ABI v10 like the five above: one entry point, six structs, nothing existing changes.
