@@ -186,6 +186,10 @@ class CtdFitRow(C.Structure):
                 ("lines", CtdFitLine * 32)]
 
 
+class CtdFitBalance(C.Structure):
+    _fields_ = [("balanced", C.c_int32), ("pad_", C.c_int32), ("cost", C.c_int64)]
+
+
 class CtdTypesetPage(C.Structure):
     _fields_ = [("page_dev", C.c_void_p), ("H", C.c_int32), ("W", C.c_int32), ("pitch", C.c_int64)]
 
@@ -296,6 +300,9 @@ SYMBOLS = {
     "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
     "ctd_layout_boxes": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdLayoutParams), _vp, _vp]),
     "ctd_layout_fit": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdFitParams), _vp, _vp]),
+    "ctd_layout_fit_work_bytes": (C.c_int64, [_vp, _i32]),
+    "ctd_layout_fit_balanced": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdFitParams), _vp, _vp, _vp, C.c_int64,
+                                       _vp]),
     "ctd_typeset": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(CtdTypesetParams), _vp, _vp]),
     "ctd_typeset_glyphs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdGlyphParams), _vp, _vp]),
     "ctd_rasterise_glyphs": (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),

@@ -1438,10 +1438,12 @@ int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloo
   return CTD_OK;
 }
 
-int ctd_layout_fit(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_dev, int32_t n,
-                   const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev, const ctd_fit_cand* cands_dev,
-                   const int32_t* cum_dev, const uint8_t* breaks_dev, const ctd_fit_params* params, ctd_fit_row* rows_dev,
-                   void* stream) {
+// ctd_layout_fit's checks, ctd_layout_fit_balanced's too: CTD_OK with `fj` the host copy of the job table (n > 0), or the
+// error rc.  The two small tables decide what the kernel reads: fetched and checked here, before anything launches.
+static int fit_checks(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_dev, int32_t n,
+                      const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev, const ctd_fit_cand* cands_dev,
+                      const int32_t* cum_dev, const uint8_t* breaks_dev, const ctd_fit_params* params, ctd_fit_row* rows_dev,
+                      void* stream, std::vector<ctd_fit_job>& fj) {
   if (n < 0) return fail(CTD_ERR_INVALID, "bad sizes");
   if (!params) return fail(CTD_ERR_INVALID, "null pointer");
   const ctd_fit_params prm = *params;
@@ -1452,8 +1454,7 @@ int ctd_layout_fit(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_d
   if (!jobs_dev || !fit_jobs_dev || !balloon_rows_dev || !rows_dev || (prm.max_words > 0 && !bits_dev) ||
       (prm.n_cands > 0 && !cands_dev) || (prm.n_cum > 0 && !cum_dev) || (prm.n_breaks > 0 && !breaks_dev))
     return fail(CTD_ERR_INVALID, "null pointer");
-  // the two small tables decide what the kernel reads: fetched and checked here, before anything launches
-  std::vector<ctd_fit_job> fj((size_t)n);
+  fj.resize((size_t)n);
   std::vector<ctd_fit_cand> cd((size_t)prm.n_cands);
   HIP_TRY(hipMemcpyAsync(fj.data(), fit_jobs_dev, fj.size() * sizeof(ctd_fit_job), hipMemcpyDefault, (hipStream_t)stream));
   if (prm.n_cands > 0)
@@ -1473,8 +1474,43 @@ int ctd_layout_fit(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_d
         return fail(CTD_ERR_INVALID, "fit: a candidate's cum0 leaves n_glyphs + 1 int32 inside n_cum");
     }
   }
-  HIP_TRY(launch_layout_fit(jobs_dev, fit_jobs_dev, n, balloon_rows_dev, bits_dev, cands_dev, cum_dev, breaks_dev, prm, rows_dev,
+  return CTD_OK;
+}
+
+int ctd_layout_fit(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_dev, int32_t n,
+                   const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev, const ctd_fit_cand* cands_dev,
+                   const int32_t* cum_dev, const uint8_t* breaks_dev, const ctd_fit_params* params, ctd_fit_row* rows_dev,
+                   void* stream) {
+  std::vector<ctd_fit_job> fj;
+  const int rc = fit_checks(jobs_dev, fit_jobs_dev, n, balloon_rows_dev, bits_dev, cands_dev, cum_dev, breaks_dev, params, rows_dev,
+                            stream, fj);
+  if (rc != CTD_OK || n == 0) return rc;
+  HIP_TRY(launch_layout_fit(jobs_dev, fit_jobs_dev, n, balloon_rows_dev, bits_dev, cands_dev, cum_dev, breaks_dev, *params, rows_dev,
                             (hipStream_t)stream));
+  return CTD_OK;
+}
+
+int64_t ctd_layout_fit_work_bytes(const ctd_fit_job* fit_jobs_host, int32_t n) {
+  if (n < 0 || (n > 0 && !fit_jobs_host)) return -1;
+  return fit_work_bytes(fit_jobs_host, n);
+}
+
+int ctd_layout_fit_balanced(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_dev, int32_t n,
+                            const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev, const ctd_fit_cand* cands_dev,
+                            const int32_t* cum_dev, const uint8_t* breaks_dev, const ctd_fit_params* params,
+                            ctd_fit_row* rows_dev, ctd_fit_balance* bal_dev, void* work_dev, int64_t work_bytes, void* stream) {
+  if (work_bytes < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  std::vector<ctd_fit_job> fj;
+  const int rc = fit_checks(jobs_dev, fit_jobs_dev, n, balloon_rows_dev, bits_dev, cands_dev, cum_dev, breaks_dev, params, rows_dev,
+                            stream, fj);
+  if (rc != CTD_OK || n == 0) return rc;
+  if (!bal_dev) return fail(CTD_ERR_INVALID, "null pointer");
+  const long long need = fit_work_bytes(fj.data(), n);
+  if (work_bytes < need) return fail(CTD_ERR_INVALID, "workspace too small");
+  if (need > 0 && (!work_dev || ((uintptr_t)work_dev & 7))) return fail(CTD_ERR_INVALID, "fit: work_dev is 8-byte aligned");
+  HIP_TRY(launch_layout_fit_balanced(jobs_dev, fit_jobs_dev, n, balloon_rows_dev, bits_dev, cands_dev, cum_dev, breaks_dev, *params,
+                                     rows_dev, bal_dev, need > 0 ? work_dev : nullptr, need > 0 ? work_bytes : 0,
+                                     (hipStream_t)stream));
   return CTD_OK;
 }
 

@@ -210,6 +210,18 @@ hipError_t launch_layout_boxes(const ctd_layout_job* jobs, int n, const ctd_ball
 hipError_t launch_layout_fit(const ctd_layout_job* jobs, const ctd_fit_job* fit_jobs, int n, const ctd_balloon_row* balloon_rows,
                              const uint64_t* bits, const ctd_fit_cand* cands, const int32_t* cum, const uint8_t* breaks,
                              const ctd_fit_params& prm, ctd_fit_row* rows, hipStream_t st);
+// ctd_layout_fit_balanced's one launch: the same kernel with the balanced breaker behind the winner.  A block's table of
+// states lies in LDS where it fits and in its part of `work` otherwise: fit_work_block_bytes(G_j) bytes a block, one behind
+// the other in job order, which is where fit_work_bytes ends.  The caller has checked work_bytes against fit_work_bytes;
+// a `work` that is not 8-byte aligned is hipErrorInvalidValue and launches nothing.
+constexpr long long fit_work_block_bytes(int n_glyphs) {
+  return n_glyphs > 0 && n_glyphs <= CTD_FIT_MAX_GLYPHS ? 8ll * CTD_FIT_MAX_LINES * (n_glyphs + 1) : 0ll;
+}
+long long fit_work_bytes(const ctd_fit_job* fit_jobs_host, int n);
+hipError_t launch_layout_fit_balanced(const ctd_layout_job* jobs, const ctd_fit_job* fit_jobs, int n,
+                                      const ctd_balloon_row* balloon_rows, const uint64_t* bits, const ctd_fit_cand* cands,
+                                      const int32_t* cum, const uint8_t* breaks, const ctd_fit_params& prm, ctd_fit_row* rows,
+                                      ctd_fit_balance* bals, void* work, long long work_bytes, hipStream_t st);
 
 // ---- kernels_typeset.hip --------------------------------------------------------
 // ctd_typeset's one launch (one workgroup per row of the tile table; n_tiles >= 1, n_layers >= 1, the counts and pointers

@@ -670,7 +670,7 @@ class TextDetector:
         return out
 
     def typeset_text(self, pages: Sequence[Page], boxes, font, atlas, runs, sizes, fill=(0, 0, 0), stroke=(255, 255, 255),
-                     radius=3, prefer: str = "a_rect", inplace: bool = False, shaped=None, **flow_kw):
+                     radius=3, prefer: str = "a_rect", inplace: bool = False, shaped=None, balance: bool = False, **flow_kw):
         """`typeset_glyphs` from outlines, at the size that fits: per block of `boxes` that is `ok` and has a run,
         `glyphs.fit` picks the largest of the ascending `sizes` (pixels an em) at which the run flows into the block's
         rectangle (the one `typeset_glyphs` uses); ONE `atlas.rasterise` launch then makes every (glyph, size) instance
@@ -686,10 +686,15 @@ class TextDetector:
         `glyphs.place_lines` places all runs at once.  Horizontal text only; `flow_kw` may hold `line` (one height for all
         sizes), `gap`, `align` and `breaks` (one list entry per block of `boxes`).  A block whose fit is not OK takes the
         rectangle path above.  The result gains `shaped[i]` (bool: layer i follows the outline), `n_lines[i]` (its lines; 0
-        on the rectangle path) and `fit`, the `ShapedFit` of all blocks of `boxes`."""
+        on the rectangle path) and `fit`, the `ShapedFit` of all blocks of `boxes`.
+        balance: with `shaped`, the same launch spreads each block's slack evenly over its lines
+        (`layout.shaped_fit(balance=True)`: same sizes, line counts and slots, no short last line where the breaks allow
+        it); the result gains `balanced[i]` (bool: layer i's lines are the balanced ones).  ValueError without `shaped`."""
         from . import glyphs as gl, typeset as ts
         if prefer not in ("a_rect", "rect"):
             raise ValueError('prefer: "a_rect" or "rect"')
+        if not isinstance(balance, (bool, np.bool_)) or (balance and shaped is None):
+            raise ValueError("balance: a bool, and True only with `shaped`")
         nb = len(boxes)
         if len(runs) != nb:
             raise ValueError("one run (or None) per block of `boxes`")
@@ -704,7 +709,7 @@ class TextDetector:
         run_of = [ts._ints(runs[j], (-1,), "runs") for j in idx]
         if shaped is not None:
             return self._typeset_shaped(pages, boxes, shaped, font, atlas, idx, layer_of, run_of, rects, sizes, fill, stroke,
-                                        radius, inplace, dict(flow_kw))
+                                        radius, inplace, dict(flow_kw), bool(balance))
         chosen = [gl.fit(run, font, rects[i], sizes, **flow_kw) for i, run in enumerate(run_of)]
         count = [len(a) for a in run_of]
         ids = atlas.rasterise(font, np.concatenate(run_of) if run_of else np.zeros((0,), np.int64),
@@ -718,7 +723,7 @@ class TextDetector:
         return out
 
     def _typeset_shaped(self, pages, boxes, shaped, font, atlas, idx, layer_of, run_of, rects, sizes, fill, stroke, radius,
-                        inplace, kw):
+                        inplace, kw, balance=False):
         """`typeset_text` with `shaped=`: layers `idx` of `boxes` with the runs `run_of`; see there."""
         from . import _lib as L, glyphs as gl, layout
         sizes = list(sizes)
@@ -752,7 +757,8 @@ class TextDetector:
             cums[j] = c
         lines = np.array([m.line if line is None else int(line) for m in metrics], np.int64)
         inset = min(boxes.inset + (int(radius.max()) if nl else 0), L.LAYOUT_MAX_INSET)
-        fit = layout.shaped_fit(shaped, cums, lines, gap, breaks=breaks, anchors=boxes.anchors, inset=inset)
+        fit = layout.shaped_fit(shaped, cums, lines, gap, breaks=breaks, anchors=boxes.anchors, inset=inset,
+                                balance=balance)
         ok = fit.ok[idx]
         cand = np.where(ok, fit.cand[idx], 0)
         # the rest takes the rectangle path: `glyphs.fit` and `flow_outlines` per block, as without `shaped`
@@ -780,6 +786,8 @@ class TextDetector:
         out.fits = np.array([True if ok[i] else chosen[i][1] for i in range(nl)], bool)
         out.n_lines = np.where(ok, fit.n_lines[idx], 0).astype(np.int64)
         out.fit = fit
+        if balance:
+            out.balanced = fit.balanced[idx].copy()
         return out
 
     def fill_rest(self, pages: Sequence[Page], results, erased=None, **erase_kw):

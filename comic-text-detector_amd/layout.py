@@ -17,7 +17,9 @@ raises `CtdError` like the rest of the package.
 
 `shaped_fit(br, cum, line, gap)` is the step beyond the box: per block the largest candidate size at which its glyph run sets
 in line slots that follow the balloon region, ONE `ctd_layout_fit` launch (csrc/kernels_fit.hip) on the same planes; the rule
-is stated in include/ctd_hip.h ("shaped fit"), restated in tests/fit_ref.py, DESIGN.md section 4.31 has its limits.
+is stated in include/ctd_hip.h ("shaped fit"), restated in tests/fit_ref.py, DESIGN.md section 4.31 has its limits.  With
+`balance=True` the same launch (`ctd_layout_fit_balanced`) also spreads the slack evenly over the lines by a dynamic program in
+the block: the header's "balanced lines", restated in tests/balance_ref.py, DESIGN.md section 4.32.
 """
 from __future__ import annotations
 
@@ -33,7 +35,7 @@ from .balloons import BalloonRegions
 from .pagecall import PageCall, table_dtype
 
 __all__ = ["layout_boxes", "LayoutBoxes", "shaped_fit", "ShapedFit", "box_anchors", "check_params", "JOB_DTYPE", "ROW_DTYPE",
-           "FIT_JOB_DTYPE", "FIT_CAND_DTYPE", "FIT_ROW_DTYPE"]
+           "FIT_JOB_DTYPE", "FIT_CAND_DTYPE", "FIT_ROW_DTYPE", "FIT_BALANCE_DTYPE"]
 
 # numpy views of `ctd_layout_job` / `ctd_layout_row` (include/ctd_hip.h)
 JOB_DTYPE = table_dtype(L.CtdLayoutJob)
@@ -42,6 +44,7 @@ ROW_DTYPE = table_dtype(L.CtdLayoutRow)
 FIT_JOB_DTYPE = table_dtype(L.CtdFitJob)
 FIT_CAND_DTYPE = table_dtype(L.CtdFitCand)
 FIT_ROW_DTYPE = table_dtype(L.CtdFitRow)
+FIT_BALANCE_DTYPE = table_dtype(L.CtdFitBalance)
 
 
 def check_params(inset) -> L.CtdLayoutParams:
@@ -135,13 +138,17 @@ class ShapedFit:
     candidate sets in 32 lines), `ok[j]` bool, `cand[j]` the index of the largest candidate that fits, `n_lines[j]` its
     lines, `n_inner[j]` the pixels of the eroded region, and `lines[j]` (32, 5) int32: per line the start glyph, the slot's
     x1 and the line's top row in page coordinates, the slot's width and the length of the line's advances; 0 beyond
-    `n_lines[j]`.  All 0 where the block is not `ok`."""
+    `n_lines[j]`.  All 0 where the block is not `ok`.  `balanced[j]` bool: the block's lines are the balanced ones
+    (`shaped_fit(balance=True)` and an admissible vector exists), `cost[j]` int64 the sum of the squared slacks of the lines
+    written; all False and 0 from a call without `balance`, where `bal_rows` (`FIT_BALANCE_DTYPE`) is None."""
 
-    def __init__(self, index, rows, anchors, inset):
+    def __init__(self, index, rows, anchors, inset, bal_rows=None):
         self.index = np.asarray(index, np.int32).reshape(-1, 2)
-        self.rows, self.anchors, self.inset = rows, anchors, int(inset)
-        if len(self.index) != len(rows) or len(anchors) != len(rows):
+        self.rows, self.anchors, self.inset, self.bal_rows = rows, anchors, int(inset), bal_rows
+        if len(self.index) != len(rows) or len(anchors) != len(rows) or (bal_rows is not None and len(bal_rows) != len(rows)):
             raise ValueError("one index row and one anchor per block")
+        self.balanced = np.zeros((len(rows),), bool) if bal_rows is None else bal_rows["balanced"] != 0
+        self.cost = np.zeros((len(rows),), np.int64) if bal_rows is None else bal_rows["cost"].astype(np.int64)
         self.status = rows["status"]
         self.ok = self.status == L.FIT_OK
         self.cand, self.n_lines, self.n_inner = rows["cand"], rows["n_lines"], rows["n_inner"]
@@ -217,13 +224,18 @@ def fit_tables(cum, line, gap, breaks=None) -> tuple:
 
 
 def shaped_fit(br: BalloonRegions, cum, line, gap, breaks=None, anchors=None, inset: int = 2,
-               stream: Optional[torch.cuda.Stream] = None) -> ShapedFit:
+               stream: Optional[torch.cuda.Stream] = None, balance: bool = False) -> ShapedFit:
     """The shaped fit of EVERY block of a `BalloonRegions`: per block the largest candidate size at which its glyph run sets
     in line slots that follow the balloon region, symmetric about the anchor's column -- one table upload, one
     `ctd_layout_fit` launch on `br.bits` where they lie, one small download.  cum, line, gap, breaks: one entry per block
     of `br`, see `fit_tables`.  anchors and inset as `layout_boxes`; add the text's stroke radius to `inset`.  Runs on `stream`
-    (default: the current stream of the bits' device) and waits for the result; see `ShapedFit`."""
+    (default: the current stream of the bits' device) and waits for the result; see `ShapedFit`.  balance=True: the launch
+    is `ctd_layout_fit_balanced`'s, which keeps every block's size, line count and slots and moves the line ends to the
+    admissible breaks of least summed squared slack (the greedy lines stand where there are none); its scratch is one
+    allocation of `ctd_layout_fit_work_bytes` on the call's stream."""
     check_params(inset)
+    if not isinstance(balance, (bool, np.bool_)):
+        raise ValueError("balance is a bool")
     n = len(br)
     if len(cum) != n:
         raise ValueError("cum: one entry per block")
@@ -235,7 +247,8 @@ def shaped_fit(br: BalloonRegions, cum, line, gap, breaks=None, anchors=None, in
         raise ValueError("anchor beyond int32")
     fjobs, cands, flat, brk = fit_tables(cum, line, gap, breaks)
     if n == 0:
-        return ShapedFit(br.index, np.zeros((0,), FIT_ROW_DTYPE), anchors, inset)
+        return ShapedFit(br.index, np.zeros((0,), FIT_ROW_DTYPE), anchors, inset,
+                         np.zeros((0,), FIT_BALANCE_DTYPE) if balance else None)
     if not torch.cuda.is_available() or not br.bits.is_cuda:
         raise L.CtdError("the shaped fit runs on the GPU and there is none (no CPU fallback)")
     jobs = np.zeros((n,), JOB_DTYPE)
@@ -248,10 +261,21 @@ def shaped_fit(br: BalloonRegions, cum, line, gap, breaks=None, anchors=None, in
     with PageCall("the shaped fit runs", (), stream, br.bits.device) as pc:
         # one upload: the two job tables, the balloon rows as the balloon call returned them, candidates, advances, breaks
         _, ptr = pc.upload([jobs, fjobs, brows, cands, flat, brk])
-        res = torch.empty((n * FIT_ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
-        L.check(L.lib().ctd_layout_fit(ptr[0], ptr[1], n, ptr[2], br.bits.data_ptr() if prm.max_words else None,
-                                       ptr[3] if len(cands) else None, ptr[4] if len(flat) else None,
-                                       ptr[5] if len(brk) else None, C.byref(prm), res.data_ptr(), pc.st.cuda_stream),
-                "ctd_layout_fit")
-        rows = pc.rows(res, FIT_ROW_DTYPE, n)
-    return ShapedFit(br.index, rows, anchors, inset)
+        args = (ptr[0], ptr[1], n, ptr[2], br.bits.data_ptr() if prm.max_words else None, ptr[3] if len(cands) else None,
+                ptr[4] if len(flat) else None, ptr[5] if len(brk) else None, C.byref(prm))
+        if not balance:
+            res = torch.empty((n * FIT_ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+            L.check(L.lib().ctd_layout_fit(*args, res.data_ptr(), pc.st.cuda_stream), "ctd_layout_fit")
+            rows, bal_rows = pc.rows(res, FIT_ROW_DTYPE, n), None
+        else:
+            need = int(L.lib().ctd_layout_fit_work_bytes(fjobs.ctypes.data, n))
+            if need < 0:
+                raise L.CtdError("ctd_layout_fit_work_bytes refused the job table")
+            # one allocation: the rows, the balance rows right behind them (656 n is a multiple of 8), the scratch
+            at = n * FIT_ROW_DTYPE.itemsize
+            res, work = pc.outputs([(at + n * FIT_BALANCE_DTYPE.itemsize,), (need,)])
+            L.check(L.lib().ctd_layout_fit_balanced(*args, res.data_ptr(), res.data_ptr() + at, work.data_ptr() if need else None,
+                                                    need, pc.st.cuda_stream), "ctd_layout_fit_balanced")
+            both = pc.rows(res, np.uint8, len(res))         # one download for both tables
+            rows, bal_rows = both[:at].view(FIT_ROW_DTYPE), both[at:].view(FIT_BALANCE_DTYPE)
+    return ShapedFit(br.index, rows, anchors, inset, bal_rows)

@@ -911,8 +911,8 @@ int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloo
  * coordinates, the slot's width, the length of the line's advances <= width); the records beyond n_lines are 0.
  * PRECONDITION: a candidate's cumulative advances do not decrease.  The entry point sees no device array of that size; where
  * they do decrease the lines are some function of the table, and nothing outside the tables is read.
- * Limits: the order of the glyphs is kept and no word is moved down to balance the lines, so a last line may be short;
- * horizontal lines only; a region whose anchor column leaves the region is cut there (a comb's teeth, the far side of a
+ * Limits: the order of the glyphs is kept; this entry point moves no word down to balance the lines, so a last line may be
+ * short (ctd_layout_fit_balanced below does); horizontal lines only; a region whose anchor column leaves the region is cut there (a comb's teeth, the far side of a
  * ring); one axis per block, so an L-shaped balloon still gets the arm of its anchor. */
 #define CTD_FIT_OK 0
 #define CTD_FIT_NO_REGION 1
@@ -980,6 +980,54 @@ int ctd_layout_fit(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_d
                    const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev, const ctd_fit_cand* cands_dev,
                    const int32_t* cum_dev, const uint8_t* breaks_dev, const ctd_fit_params* params, ctd_fit_row* rows_dev,
                    void* stream);
+
+/* ---- shaped fit, balanced lines (added within ABI v10) ------------------------------------------------------------------ */
+
+/* An addition to ABI v10: two entry points, one struct; ctd_layout_fit, its structs and its results do not change.
+ * The greedy breaker above fills every line and leaves what remains to the last one, which may then stand far off the
+ * outline.  This is the same fit with the slack spread evenly over the lines.  Integers only.  Restated in numpy in
+ * tests/balance_ref.py.
+ *   start     everything up to the block's answer is the shaped-fit rule unchanged: the status, the candidate c*, its n*
+ *             lines, and the slots of that stack with their widths w_0 .. w_(n* - 1).  The balanced breaker changes neither
+ *             the size nor the line count: for a fixed stack, filling each line to the furthest allowed break is optimal for
+ *             feasibility.  cum is c*'s cumulative advances, G the run's glyphs.
+ *   boundary  a line may end in front of glyph e, 1 <= e <= G, where e = G, or there is no break table, or the break byte of
+ *             glyph e - 1 is non-zero.
+ *   vector    0 = s_0 < s_1 < ... < s_n* = G is admissible where every s_1 .. s_(n* - 1) is a boundary and
+ *             cum[s_(k+1)] - cum[s_k] <= w_k for every k.  Lines are non-empty by glyph count; advances of 0 are legal.
+ *   cost      the sum over k of (w_k - (cum[s_(k+1)] - cum[s_k]))^2 in int64: at most 32 x 32766^2 < 2^35.  The sum of the
+ *             slacks is fixed by c* and n*, so the cost measures only how evenly the slack is spread.
+ *   answer    the admissible vector of least cost; among equals the lexicographically largest (s_1, .., s_(n* - 1)): what a
+ *             backward table g(k, s) gives when a forward pass takes the largest end that attains it.
+ *   fallback  where no admissible vector exists the greedy lines stand: the greedy stack needed a hard break and no other
+ *             vector avoids one.
+ * The row is ctd_fit_row as above; against ctd_layout_fit's row only `start` and `length` of the line records may differ.
+ * A second row per block, ctd_fit_balance, 16 bytes: balanced, 1 where the answer was written and 0 where the greedy lines
+ * stand; cost, the cost of the lines written.  Every field is 0 in any status but OK.
+ * Limits: squares of the slack in pixels, so a narrow slot at the top and a wide one in the middle are drawn to the same
+ * slack, not to the same share of their width; the last line is treated like every other (no allowance for a short last
+ * line); horizontal lines only, and the limits of the shaped fit above other than its first. */
+typedef struct ctd_fit_balance {
+  int32_t balanced; /* 1: the balanced lines were written, 0: the greedy lines stand      */
+  int32_t pad_;
+  int64_t cost;     /* the sum of the squared slacks of the lines written                 */
+} ctd_fit_balance;
+
+/* The bytes of work_dev that ctd_layout_fit_balanced needs for the n jobs of the HOST copy of a fit job table: a function
+ * of the table alone, 8 x 32 x (n_glyphs + 1) bytes for every job with n_glyphs in 1 .. CTD_FIT_MAX_GLYPHS (a block's table
+ * of states where it does not fit the block's LDS), 0 for any other job.  -1 for a negative n or a missing table with n > 0. */
+int64_t ctd_layout_fit_work_bytes(const ctd_fit_job* fit_jobs_host, int32_t n);
+
+/* ctd_layout_fit with the balanced breaker, ONE launch, one workgroup per block: the block that has found the winning stack
+ * runs the dynamic program and writes rows_dev[i] and bal_dev[i] (4-byte alignment each; every int32 of both written once).
+ * All of ctd_layout_fit's arguments, reads and refusals apply.  work_dev: work_bytes bytes of scratch, 8-byte aligned, its
+ * contents do not matter before and mean nothing after; nothing behind work_bytes is written.  An error rc, and no launch and
+ * no row written, too for: a NULL bal_dev with n > 0; a negative work_bytes; a work_bytes below
+ * ctd_layout_fit_work_bytes of the job table; a work_dev that is NULL or not 8-byte aligned where that is more than 0. */
+int ctd_layout_fit_balanced(const ctd_layout_job* jobs_dev, const ctd_fit_job* fit_jobs_dev, int32_t n,
+                            const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev, const ctd_fit_cand* cands_dev,
+                            const int32_t* cum_dev, const uint8_t* breaks_dev, const ctd_fit_params* params,
+                            ctd_fit_row* rows_dev, ctd_fit_balance* bal_dev, void* work_dev, int64_t work_bytes, void* stream);
 
 /* ---- typeset: text layers with outlines composited into pages (added within ABI v10) ---------------------------------- */
 
