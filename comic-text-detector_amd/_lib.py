@@ -34,6 +34,7 @@ ERASE_TILE_W, ERASE_TILE_H = 64, 32
 BALLOON_OK, BALLOON_NOT_PLAIN, BALLOON_TOO_LARGE = range(3)
 BALLOON_MAX_WORDS, BALLOON_MAX_REACH, BALLOON_MIN_REACH_MIN, BALLOON_MAX_REACH_MIN = 8192, 32, 8, 1024
 BALLOON_CUT_LEFT, BALLOON_CUT_TOP, BALLOON_CUT_RIGHT, BALLOON_CUT_BOTTOM = 1, 2, 4, 8
+BALLOON_FOOTPRINT, FOOTPRINT_MAX_PAD, FOOTPRINT_DEFAULT_PAD = 256, 16, 4
 FILL_OK, FILL_NO_HOLE, FILL_NO_KNOWN = range(3)
 FILL_MAX_SIDE, FILL_TILE = 8192, 64
 TEXTURE_OK, TEXTURE_NO_HOLE, TEXTURE_NO_SOURCE = range(3)
@@ -149,6 +150,11 @@ class CtdBalloonParams(C.Structure):
 class CtdBalloonRow(C.Structure):
     _fields_ = [("status", C.c_int32), ("area", C.c_int32), ("bbox", C.c_int32 * 4), ("flags", C.c_int32), ("n_seed", C.c_int32),
                 ("sum_x", C.c_int64), ("sum_y", C.c_int64)]
+
+
+class CtdFootprintParams(C.Structure):
+    _fields_ = [("grow", C.c_int32), ("pad", C.c_int32), ("reach", C.c_int32), ("reach_min", C.c_int32), ("max_words", C.c_int32),
+                ("pad_", C.c_int32 * 3)]
 
 
 class CtdLayoutJob(C.Structure):
@@ -298,6 +304,7 @@ SYMBOLS = {
     "ctd_line_colors": (_i32, [_vp, _i32, _vp, _vp]),
     "ctd_erase_text": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(CtdEraseParams), _vp, _vp]),
     "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
+    "ctd_balloon_footprints": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdFootprintParams), _vp, _vp, _vp]),
     "ctd_layout_boxes": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdLayoutParams), _vp, _vp]),
     "ctd_layout_fit": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdFitParams), _vp, _vp]),
     "ctd_layout_fit_work_bytes": (C.c_int64, [_vp, _i32]),

@@ -16,6 +16,14 @@ rule is integers only and stated in include/ctd_hip.h (restated in numpy with a 
 DESIGN.md section 4.18 has its limits): in a window around the block's box, the pixels within `tol` of the erase row's median
 in every channel, plus the block's own filled glyphs, are open; the region is what is 4-connected to the glyphs through open
 pixels.  There is no per-block Python and no CPU fallback: without a GPU it raises `CtdError` like the rest of the package.
+
+A block that does not stand on a plain background -- a caption on screentone, narration over artwork, a sound effect -- has no
+balloon: it comes back `BALLOON_NOT_PLAIN`, and layout and typeset skip it although the fill calls removed its text.  With
+`footprint=True` a second launch (`ctd_balloon_footprints`, csrc/kernels_footprint.hip) follows the balloon launch on the same
+stream, with the same uploaded tables, and gives every such block (erase row TEXTURED or NO_RING) the place where its old text
+stood as its region: the orthogonally convex closure of its filled glyphs, grown by `pad`, minus other blocks' text -- written
+into the same rows and the same bit buffer as an OK row with `_lib.BALLOON_FOOTPRINT` in its flags, so `layout_boxes`,
+`shaped_fit` and the typeset calls run on it unchanged (`BalloonRegions.footprint[j]`).
 """
 from __future__ import annotations
 
@@ -29,7 +37,7 @@ from . import _lib as L
 from . import erase as E
 from .pagecall import Page, PageCall, blk_lists_of, check_pages, check_pitch, table_dtype
 
-__all__ = ["balloon_regions", "BalloonRegions", "balloon_tables", "check_params", "JOB_DTYPE", "ROW_DTYPE"]
+__all__ = ["balloon_regions", "BalloonRegions", "balloon_tables", "check_params", "check_footprint", "JOB_DTYPE", "ROW_DTYPE"]
 
 # numpy views of `ctd_balloon_job` / `ctd_balloon_row` (include/ctd_hip.h); the page table is `erase.PAGE_DTYPE`
 JOB_DTYPE = table_dtype(L.CtdBalloonJob)
@@ -44,6 +52,14 @@ def check_params(grow, tol, reach, reach_min) -> L.CtdBalloonParams:
             and L.BALLOON_MIN_REACH_MIN <= reach_min <= L.BALLOON_MAX_REACH_MIN):
         raise ValueError("grow in 0..8, tol in 0..255, reach in 0..32, reach_min in 8..1024")
     return L.CtdBalloonParams(int(grow), int(tol), int(reach), int(reach_min), 0)
+
+
+def check_footprint(footprint, pad) -> None:
+    """`footprint` is a bool and `pad` an integer in 0 .. `FOOTPRINT_MAX_PAD`, whether or not footprints are asked for."""
+    if not isinstance(footprint, (bool, np.bool_)):
+        raise ValueError("footprint is a bool")
+    if not isinstance(pad, (int, np.integer)) or isinstance(pad, (bool, np.bool_)) or not 0 <= pad <= L.FOOTPRINT_MAX_PAD:
+        raise ValueError("pad is an integer in 0..16")
 
 
 def balloon_tables(boxes: Sequence[np.ndarray], shapes: Sequence, reach: int = 8, reach_min: int = 32) -> tuple:
@@ -80,7 +96,10 @@ class BalloonRegions:
     `bbox[j]` x1, y1, x2, y2 in page coordinates (exclusive), `center[j]` = (sum_x // area, sum_y // area) where `ok`, else
     -1, `flags[j]`: bits 0..3 (`_lib.BALLOON_CUT_LEFT / TOP / RIGHT / BOTTOM`) the region reaches that side of its window --
     it was cut by the window, or it leaked through a gap in the balloon's outline -- bits 4..7 the same where that side is
-    the page's edge.  `windows[j]` x1, y1, x2, y2 of the block's window, `nw[j]`, `word0[j]`: its words in `bits`, the device
+    the page's edge; bit 8 (`_lib.BALLOON_FOOTPRINT`) the region is the block's footprint, not a balloon: `footprint[j]` bool
+    (`balloon_regions(..., footprint=True)`: where the old text stood, for a block off a plain background; `erase_rows[j]` says
+    TEXTURED or NO_RING there).  `windows[j]` x1, y1, x2, y2 of the block's window, `nw[j]`, `word0[j]`: its words in
+    `bits`, the device
     u64 buffer of all regions (window row y, columns 64 k .. 64 k + 63 in word `word0 + y * nw + k`, least significant bit
     first); `mask(j)` unpacks one.  `erase_rows`: the blocks' `erase.ROW_DTYPE` rows that decided plain / not plain."""
 
@@ -93,6 +112,7 @@ class BalloonRegions:
         self.status = rows["status"]
         self.ok = self.status == L.BALLOON_OK
         self.area, self.bbox, self.flags = rows["area"], rows["bbox"], rows["flags"]
+        self.footprint = (self.flags & L.BALLOON_FOOTPRINT) != 0
         den = np.where(self.ok, np.maximum(rows["area"], 1), 1).astype(np.int64)
         self.center = np.where(self.ok[:, None], np.stack([rows["sum_x"] // den, rows["sum_y"] // den], axis=1), -1)
 
@@ -119,15 +139,20 @@ class BalloonRegions:
 
 def balloon_regions(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Sequence, erased: Optional[E.ErasedPages] = None,
                     grow: int = 2, tol: int = 12, reach: int = 8, reach_min: int = 32,
-                    stream: Optional[torch.cuda.Stream] = None, device=None) -> BalloonRegions:
+                    stream: Optional[torch.cuda.Stream] = None, device=None, footprint: bool = False,
+                    pad: int = L.FOOTPRINT_DEFAULT_PAD) -> BalloonRegions:
     """The balloon region of EVERY block of EVERY page of a batch: one table upload, one `ctd_balloon_regions` launch, one
     small download.  pages, masks, blk_lists as for `erase.erase_text`.  erased: the `ErasedPages` of an `erase_text` call
     on the same pages, masks and blocks with the same `grow` (its rows are uploaded); without it the erase rule's stats launch
     runs first on the same stream, with `grow`, `tol` and the erase defaults, and its rows never leave the device in between.
     grow: as in `erase_text`; tol: how far from the block's background colour an open pixel may lie, per channel; reach: the
-    window is the box grown by reach / 8 of its side, but at least by reach_min pixels.  Runs on `stream` (default: the
-    current stream of the pages' device) and waits for the result; see `BalloonRegions`."""
+    window is the box grown by reach / 8 of its side, but at least by reach_min pixels.  footprint: a second launch,
+    `ctd_balloon_footprints`, follows on the same stream with the same tables and gives every block whose erase row is
+    TEXTURED or NO_RING the place where its old text stood as its region (OK, `BALLOON_FOOTPRINT` in its flags), grown by
+    `pad` pixels (0 .. 16); off, the call launches and returns what it always did.  Runs on `stream` (default: the current
+    stream of the pages' device) and waits for the result; see `BalloonRegions`."""
     prm = check_params(grow, tol, reach, reach_min)
+    check_footprint(footprint, pad)
     if len(pages) != len(blk_lists) or len(masks) != len(pages):
         raise ValueError("one mask and one blk_list per page")
     check_pages(pages, masks, "BGR ")
@@ -168,6 +193,11 @@ def balloon_regions(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Seq
             prm.max_words = int(owned.max()) if len(owned) else 0
             L.check(lib.ctd_balloon_regions(jobs_ptr, n, pages_ptr, n_pages, erows_ptr, C.byref(prm), res.data_ptr(),
                                             bits.data_ptr() if total else None, pc.st.cuda_stream), "ctd_balloon_regions")
+            if footprint:                                           # the same tables, rows and bits, no host step between
+                fprm = L.CtdFootprintParams(prm.grow, int(pad), prm.reach, prm.reach_min, prm.max_words)
+                L.check(lib.ctd_balloon_footprints(jobs_ptr, n, pages_ptr, n_pages, erows_ptr, C.byref(fprm), res.data_ptr(),
+                                                   bits.data_ptr() if total else None, pc.st.cuda_stream),
+                        "ctd_balloon_footprints")
         host = pc.rows(res, np.uint8, n * (ROW_DTYPE.itemsize + rs))
     rows = host[: n * ROW_DTYPE.itemsize].view(ROW_DTYPE)
     erows = erased.rows if erased is not None else host[n * ROW_DTYPE.itemsize: n * (ROW_DTYPE.itemsize + rs)].view(E.ROW_DTYPE)

@@ -1424,6 +1424,24 @@ int ctd_balloon_regions(const ctd_balloon_job* jobs_dev, int32_t n, const ctd_er
   return CTD_OK;
 }
 
+int ctd_balloon_footprints(const ctd_balloon_job* jobs_dev, int32_t n, const ctd_erase_page* pages_dev, int32_t n_pages,
+                           const ctd_erase_row* erase_rows_dev, const ctd_footprint_params* params, ctd_balloon_row* rows_dev,
+                           uint64_t* bits_dev, void* stream) {
+  if (n < 0 || n_pages < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
+  const ctd_footprint_params prm = *params;
+  if (prm.grow < 0 || prm.grow > CTD_ERASE_MAX_GROW || prm.pad < 0 || prm.pad > CTD_FOOTPRINT_MAX_PAD || prm.reach < 0 ||
+      prm.reach > CTD_BALLOON_MAX_REACH || prm.reach_min < CTD_BALLOON_MIN_REACH_MIN || prm.reach_min > CTD_BALLOON_MAX_REACH_MIN ||
+      prm.max_words < 0 || prm.max_words > CTD_BALLOON_MAX_WORDS)
+    return fail(CTD_ERR_INVALID, "footprints: grow 0..8, pad 0..16, reach 0..32, reach_min 8..1024, max_words 0..8192");
+  if (n > 0 && n_pages == 0) return fail(CTD_ERR_INVALID, "blocks without pages");
+  if (n == 0) return CTD_OK;
+  if (!jobs_dev || !pages_dev || !erase_rows_dev || !rows_dev || (prm.max_words > 0 && !bits_dev))
+    return fail(CTD_ERR_INVALID, "null pointer");
+  HIP_TRY(launch_balloon_footprints(jobs_dev, n, pages_dev, n_pages, erase_rows_dev, prm, rows_dev, bits_dev, (hipStream_t)stream));
+  return CTD_OK;
+}
+
 int ctd_layout_boxes(const ctd_layout_job* jobs_dev, int32_t n, const ctd_balloon_row* balloon_rows_dev,
                      const uint64_t* bits_dev, const ctd_layout_params* params, ctd_layout_row* rows_dev, void* stream) {
   if (n < 0) return fail(CTD_ERR_INVALID, "bad sizes");

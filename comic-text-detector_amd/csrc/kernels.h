@@ -198,6 +198,13 @@ hipError_t launch_balloon_regions(const ctd_balloon_job* jobs, int n, const ctd_
                                   const ctd_erase_row* erase_rows, const ctd_balloon_params& prm, ctd_balloon_row* rows,
                                   uint64_t* bits, hipStream_t st);
 
+// ---- kernels_footprint.hip ------------------------------------------------------
+// ctd_balloon_footprints' one launch behind the balloon launch (one workgroup per block; n >= 1, prm checked by the caller):
+// the dynamic-LDS limit under a once-flag of its own, and what hipGetLastError says right after the launch
+hipError_t launch_balloon_footprints(const ctd_balloon_job* jobs, int n, const ctd_erase_page* pages, int n_pages,
+                                     const ctd_erase_row* erase_rows, const ctd_footprint_params& prm, ctd_balloon_row* rows,
+                                     uint64_t* bits, hipStream_t st);
+
 // ---- kernels_layout.hip ---------------------------------------------------------
 // ctd_layout_boxes' one launch (one workgroup per block; n >= 1, prm checked by the caller): raises the kernel's dynamic
 // LDS limit once per device, launches, and returns what hipGetLastError says right after the launch

@@ -8,6 +8,7 @@
 // 64-bit words a row, at most CTD_BALLOON_MAX_WORDS words each; the launch is sized to the call's largest window):
 //   seed    T_b = M & X_b by one __ballot per 64 mask bytes into plane R, D_g of it by word shifts and ORs: rows R -> O,
 //           columns O -> R.  X_b lies g or more inside the window except at a page edge, where D_g is clipped anyway: no halo.
+//           (The window, this pass and the reduce are balloon_bits.h's, shared with kernels_footprint.hip.)
 //   open    one __ballot per 64 page pixels (three byte loads a lane: rows and pixels have any alignment; a wave loads four
 //           consecutive words' pixels before the first compare) of "every channel within tol of the erase row's median",
 //           ORed with the seed, into plane O.
@@ -22,21 +23,18 @@
 //           the plane goes out as aligned 8-byte stores, thread 0 writes the row with ordinary stores.
 #include <mutex>
 
-#include "kernels.h"
+#include "balloon_bits.h"
 
 namespace {
 
-constexpr int BL_THREADS = 512, BL_WAVES = BL_THREADS / 64;
-constexpr int BL_MAX_DEVICES = 64;
+using namespace blbits;
+
 constexpr int BL_COL = 8;                                    // rows a column sweep loads ahead
 constexpr int BL_UNROLL = 4;                                 // words a wave stages per step of the open plane
 static_assert(sizeof(ctd_balloon_job) == 32 && sizeof(ctd_balloon_params) == 32 && sizeof(ctd_balloon_row) == 48,
               "balloon ABI sizes (balloons.py dtypes)");
 static_assert(offsetof(ctd_balloon_job, erase_row) == 20 && offsetof(ctd_balloon_job, word0) == 24 &&
               offsetof(ctd_balloon_row, flags) == 24 && offsetof(ctd_balloon_row, sum_x) == 32, "balloon ABI offsets");
-static_assert(CTD_BALLOON_MIN_REACH_MIN >= CTD_ERASE_MAX_GROW, "F_b lies inside the window");
-
-typedef unsigned long long u64;
 
 // the bits of `open` in runs of `open` that hold a bit of seed (seed is a subset of open).  Adding the seed to the word
 // carries through every run from its lowest seed upwards and flips exactly those bits (and the 0 above the run, which
@@ -44,19 +42,6 @@ typedef unsigned long long u64;
 __device__ __forceinline__ u64 fill_up(u64 seed, u64 open) { return (((open + seed) ^ open) & open) | seed; }
 __device__ __forceinline__ u64 runfill(u64 seed, u64 open) {
   return fill_up(seed, open) | __brevll(fill_up(__brevll(seed), __brevll(open)));
-}
-
-// the middle word of three dilated by k pixels either way (k < 64)
-__device__ __forceinline__ u64 hdil3(u64 l, u64 m, u64 r, int k) {
-  u64 v = m;
-  for (int s = 1; s <= k; ++s) v |= (m << s) | (l >> (64 - s)) | (m >> s) | (r << (64 - s));
-  return v;
-}
-
-// the sum of the indices of the set bits of a word
-__device__ __forceinline__ int bit_index_sum(u64 w) {
-  return __popcll(w & 0xAAAAAAAAAAAAAAAAull) + 2 * __popcll(w & 0xCCCCCCCCCCCCCCCCull) + 4 * __popcll(w & 0xF0F0F0F0F0F0F0F0ull) +
-         8 * __popcll(w & 0xFF00FF00FF00FF00ull) + 16 * __popcll(w & 0xFFFF0000FFFF0000ull) + 32 * __popcll(w & 0xFFFFFFFF00000000ull);
 }
 
 __device__ __forceinline__ void zero_row(ctd_balloon_row* row, int status) {
@@ -80,17 +65,12 @@ __global__ __launch_bounds__(BL_THREADS) void balloon_kernel(const ctd_balloon_j
   // ---- the window, from the box and the page alone (block-uniform, before any pixel is read)
   const bool has_page = J.page >= 0 && J.page < n_pages;
   ctd_erase_page P;
-  int wx1 = 0, wy1 = 0, ww = 0, wh = 0, bx1 = 0, by1 = 0, bx2 = 0, by2 = 0;
+  window w = {0, 0, 0, 0, 0, 0, 0, 0};
   if (has_page) {
     P = pages[J.page];
-    bx1 = max(J.xyxy[0], 0), by1 = max(J.xyxy[1], 0), bx2 = min(J.xyxy[2], P.W), by2 = min(J.xyxy[3], P.H);
-    if (bx1 < bx2 && by1 < by2) {
-      const long long ex = max((long long)prm.reach_min, ((long long)(bx2 - bx1) * prm.reach) >> 3);
-      const long long ey = max((long long)prm.reach_min, ((long long)(by2 - by1) * prm.reach) >> 3);
-      wx1 = (int)max((long long)bx1 - ex, 0ll), wy1 = (int)max((long long)by1 - ey, 0ll);
-      ww = (int)min((long long)bx2 + ex, (long long)P.W) - wx1, wh = (int)min((long long)by2 + ey, (long long)P.H) - wy1;
-    }
+    w = window_of(J.xyxy, P.W, P.H, prm.reach, prm.reach_min);
   }
+  const int wx1 = w.wx1, wy1 = w.wy1, ww = w.ww, wh = w.wh;
   const int nw = (ww + 63) >> 6;
   const long long words_ll = (long long)nw * wh;
   const bool owns = words_ll <= (long long)min(prm.max_words, CTD_BALLOON_MAX_WORDS);   // what fits this launch's planes
@@ -107,36 +87,9 @@ __global__ __launch_bounds__(BL_THREADS) void balloon_kernel(const ctd_balloon_j
   u64* __restrict__ O = planes;
   u64* __restrict__ R = planes + prm.max_words;
   const int g = prm.grow;
-  const u64 last_valid = (ww & 63) ? ((1ull << (ww & 63)) - 1ull) : ~0ull;   // the window's bits of a row's last word
 
-  // ---- seed: T_b into R ...
-  for (int task = wave; task < words; task += BL_WAVES) {
-    const int y = task / nw, j = task - y * nw;
-    const int px = wx1 + 64 * j + lane, py = wy1 + y;
-    bool bit = false;
-    if (py >= by1 && py < by2 && px >= bx1 && px < bx2) bit = P.mask_dev[(long long)py * P.mask_pitch + px] != 0;
-    const u64 word = __ballot(bit);
-    if (lane == 0) R[task] = word;
-  }
-  __syncthreads();
-  // ... its rows dilated into O ...
-  for (int i = t; i < words; i += BL_THREADS) {
-    const int y = i / nw, j = i - y * nw;
-    u64 v = hdil3(j > 0 ? R[i - 1] : 0ull, R[i], j + 1 < nw ? R[i + 1] : 0ull, g);
-    if (j == nw - 1) v &= last_valid;
-    O[i] = v;
-  }
-  __syncthreads();
-  // ... and the columns of that into R = F_b
-  int n_seed = 0;
-  for (int i = t; i < words; i += BL_THREADS) {
-    const int y = i / nw;
-    u64 v = 0ull;
-    for (int yy = max(y - g, 0); yy <= min(y + g, wh - 1); ++yy) v |= O[i + (yy - y) * nw];
-    R[i] = v;
-    n_seed += __popcll(v);
-  }
-  __syncthreads();
+  // ---- seed: F_b into R
+  int n_seed = load_seed(O, R, P, w, nw, words, g, t);
   // ---- open: near the median in every channel, or seed
   {
     const int lo0 = (int)E.med[0] - prm.tol, hi0 = (int)E.med[0] + prm.tol, lo1 = (int)E.med[1] - prm.tol,
@@ -218,54 +171,13 @@ __global__ __launch_bounds__(BL_THREADS) void balloon_kernel(const ctd_balloon_j
   }
 
   // ---- the plane goes out; area, box, sums, contact
-  int area = 0, minx = 0x7fffffff, miny = 0x7fffffff, maxx = -1, maxy = -1, flags = 0;
-  long long sx = 0, sy = 0;
+  tally a = tally_none();
   for (int i = t; i < words; i += BL_THREADS) {
     const u64 rw = R[i];
     out[i] = rw;
-    if (!rw) continue;
-    const int y = i / nw, j = i - y * nw;
-    const int n = __popcll(rw), x0 = wx1 + 64 * j;
-    area += n;
-    minx = min(minx, x0 + __ffsll((long long)rw) - 1), maxx = max(maxx, x0 + 63 - __clzll((long long)rw));
-    miny = min(miny, wy1 + y), maxy = max(maxy, wy1 + y);
-    sx += (long long)n * x0 + bit_index_sum(rw), sy += (long long)n * (wy1 + y);
-    if (j == 0 && (rw & 1ull)) flags |= CTD_BALLOON_CUT_LEFT;
-    if (y == 0) flags |= CTD_BALLOON_CUT_TOP;
-    if (j == nw - 1 && ((rw >> ((ww - 1) & 63)) & 1ull)) flags |= CTD_BALLOON_CUT_RIGHT;
-    if (y == wh - 1) flags |= CTD_BALLOON_CUT_BOTTOM;
+    tally_word(a, rw, i, nw, w);
   }
-#pragma unroll
-  for (int d = 32; d >= 1; d >>= 1) {
-    area += __shfl_down(area, d, 64), n_seed += __shfl_down(n_seed, d, 64);
-    minx = min(minx, __shfl_down(minx, d, 64)), miny = min(miny, __shfl_down(miny, d, 64));
-    maxx = max(maxx, __shfl_down(maxx, d, 64)), maxy = max(maxy, __shfl_down(maxy, d, 64));
-    flags |= __shfl_down(flags, d, 64);
-    sx += __shfl_down(sx, d, 64), sy += __shfl_down(sy, d, 64);
-  }
-  if (lane == 0) {
-    red_i[wave][0] = area, red_i[wave][1] = n_seed, red_i[wave][2] = minx, red_i[wave][3] = miny, red_i[wave][4] = maxx,
-    red_i[wave][5] = maxy, red_i[wave][6] = flags;
-    red_l[wave][0] = sx, red_l[wave][1] = sy;
-  }
-  __syncthreads();
-  if (t == 0) {
-    for (int w = 1; w < BL_WAVES; ++w) {
-      area += red_i[w][0], n_seed += red_i[w][1];
-      minx = min(minx, red_i[w][2]), miny = min(miny, red_i[w][3]), maxx = max(maxx, red_i[w][4]), maxy = max(maxy, red_i[w][5]);
-      flags |= red_i[w][6];
-      sx += red_l[w][0], sy += red_l[w][1];
-    }
-    // a side that is the page's edge reports in bits 4 .. 7
-    int f = 0;
-    f |= (flags & CTD_BALLOON_CUT_LEFT) << (wx1 == 0 ? 4 : 0);
-    f |= (flags & CTD_BALLOON_CUT_TOP) << (wy1 == 0 ? 4 : 0);
-    f |= (flags & CTD_BALLOON_CUT_RIGHT) << (wx1 + ww == P.W ? 4 : 0);
-    f |= (flags & CTD_BALLOON_CUT_BOTTOM) << (wy1 + wh == P.H ? 4 : 0);
-    row->status = CTD_BALLOON_OK, row->area = area;
-    row->bbox[0] = area ? minx : 0, row->bbox[1] = area ? miny : 0, row->bbox[2] = area ? maxx + 1 : 0, row->bbox[3] = area ? maxy + 1 : 0;
-    row->flags = f, row->n_seed = n_seed, row->sum_x = sx, row->sum_y = sy;
-  }
+  write_row(a, n_seed, red_i, red_l, row, w, P.W, P.H, 0, t);
 }
 
 std::once_flag g_lds_once[BL_MAX_DEVICES];

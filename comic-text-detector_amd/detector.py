@@ -573,14 +573,17 @@ class TextDetector:
         """The balloon region of every block of a detected batch -- the free area around the text of each block that stands
         on a plain background: area, bounding box, centre, cut flags and the region as a bit plane -- in one launch on the
         detector's device (`balloons.balloon_regions` and its keywords `grow`, `tol`, `reach`, `reach_min`; returns its
-        `BalloonRegions`).  `results`: what `detect_batch` / `detect_stream` returned for `pages`; the masks are their
-        `mask_refined`.  `erased`: the `ErasedPages` of `erase_text(pages, results)` with the same `grow`, where the caller
-        has it; otherwise the erase rule's stats launch runs first.  Builds no `TextBlock` of a `BlockList`.  Host pages are
+        `BalloonRegions`).  `footprint=True` (with `pad`, 0 .. 16, default 4) adds a second launch that gives every block off
+        a plain background the place where its old text stood as its region, so layout and typeset no longer skip it.
+        `results`: what `detect_batch` / `detect_stream` returned for `pages`; the masks are their `mask_refined`.  `erased`:
+        the `ErasedPages` of `erase_text(pages, results)` with the same `grow`, where the caller has it; otherwise the erase
+        rule's stats launch runs first.  Builds no `TextBlock` of a `BlockList`.  Host pages are
         uploaded through the pinned staging ring (`_stage`)."""
         from . import balloons
         masks = [r[1] for r in results]
         blk_lists = [r[2] for r in results]
         balloons.check_params(*(kw.get(k, d) for k, d in (("grow", 2), ("tol", 12), ("reach", 8), ("reach_min", 32))))
+        balloons.check_footprint(kw.get("footprint", False), kw.get("pad", 4))
         pages = self._on_device(pages)                        # no page: nothing is staged
         return balloons.balloon_regions(pages, masks, blk_lists, erased=erased, device=self.net.device, **kw)
 
@@ -590,9 +593,12 @@ class TextDetector:
         centre of the block's box, ((x1 + x2) >> 1, (y1 + y2) >> 1) of the box clipped to the page -- one launch behind the
         balloon launch (`layout.layout_boxes`; returns its `LayoutBoxes`).  `results`: what `detect_batch` / `detect_stream`
         returned for `pages`.  `regions`: the `BalloonRegions` of `balloons(pages, results)` where the caller has them;
-        otherwise that runs first, with `erased` and `balloon_kw`.  Builds no `TextBlock` of a `BlockList`."""
-        from . import erase, layout
+        otherwise that runs first, with `erased` and `balloon_kw` -- `footprint=True` and `pad` among them: a block off a
+        plain background then gets a box inside the place where its old text stood instead of NO_REGION.  Builds no
+        `TextBlock` of a `BlockList`."""
+        from . import balloons, erase, layout
         layout.check_params(inset)
+        balloons.check_footprint(balloon_kw.get("footprint", False), balloon_kw.get("pad", 4))
         if regions is None:
             regions = self.balloons(pages, results, erased=erased, **balloon_kw)
         boxes = [erase._page_boxes(r[2]) for r in results]

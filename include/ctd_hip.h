@@ -605,6 +605,58 @@ int ctd_balloon_regions(const ctd_balloon_job* jobs_dev, int32_t n, const ctd_er
                         const ctd_erase_row* erase_rows_dev, const ctd_balloon_params* params, ctd_balloon_row* rows_dev,
                         uint64_t* bits_dev, void* stream);
 
+/* ---- footprint regions (added within ABI v10) ------------------------------------------------------------------------ */
+
+/* An addition to ABI v10 like the three above: one entry point, one struct, three constants, nothing existing changes.
+ * The balloon rule gives a region only to a block whose erase row is PLAIN.  A caption on screentone, narration over artwork,
+ * a sound effect, a balloon with a gradient: each comes back NOT_PLAIN with an all-zero plane, the layout and fit calls answer
+ * NO_REGION, and the text that the fill calls removed is never put back.  The only honest notion of "where the text may go"
+ * there is where the old text stood: the block's footprint.  This call writes it into the SAME rows and the SAME bit buffer as
+ * an OK row, so that everything downstream runs unchanged on all blocks.  Integers only.  Restated in numpy, with per-row and
+ * per-column spans, in tests/footprint_ref.py.  It reuses M, D_k, X_b, T_b, F_b = D_g(T_b) and Win_b (wx1, wy1, ww, wh, nw)
+ * exactly as the erase and balloon sections define them.
+ * Parameters (ctd_footprint_params): grow g (0 .. 8; the value the erase rows were made with), pad (0 .. CTD_FOOTPRINT_MAX_PAD,
+ * default 4), reach and reach_min (as the balloon call's: they only reproduce the window), max_words (as the balloon call's).
+ * Block b is ELIGIBLE iff its job's page is a row of the page table, its erase_row is a row of the erase table, that row's
+ * status is CTD_ERASE_TEXTURED or CTD_ERASE_NO_RING (so T_b is not empty), and nw * wh <= min(CTD_BALLOON_MAX_WORDS,
+ * params.max_words).  For a block that is not eligible nothing is read beyond that decision and nothing is written: its balloon
+ * row and its words keep what the balloon call left there.  For an eligible block:
+ *   C_b     the orthogonally convex closure of F_b inside the window: the smallest set Q of window pixels that contains F_b
+ *           such that whenever two pixels of Q lie in one row every pixel between them is in Q, and likewise for columns.
+ *           Such sets are closed under intersection, so the smallest exists and is unique, whatever order it is found in.
+ *           C_b lies inside the bounding box of F_b.  This is what closes the gaps between lines and between words, which a
+ *           union of line quads would leave open as stripes.
+ *   P_b     = D_pad(C_b), clipped to the window (and so to the page).
+ *   N_b     = (M \ X_b) & Win_b, other text: the mask pixels of the page outside the block's own box.  A hole, as in the
+ *           balloon rule.
+ *   B_b     = P_b \ N_b.
+ * Row (ctd_balloon_row, overwritten): status = CTD_BALLOON_OK; area = |B_b| (where it is 0 the bbox is 0); bbox, sum_x, sum_y
+ * over B_b; n_seed = |F_b| (= the erase row's n_fill); flags = the balloon rule's eight cut bits computed on B_b, plus bit 8,
+ * CTD_BALLOON_FOOTPRINT.
+ * Bits: every owned word of an eligible block is written exactly once, bits beyond ww are 0; no other word of the buffer is
+ * touched.
+ * Limits: the closure of two pieces that share no row and no column stays two pieces; pad is a square dilation; where
+ * g + pad > reach_min the window cuts the region, and bits 0 .. 3 of the flags say so; boxes that overlap share mask pixels, as
+ * in the erase rule; a block whose window holds more than 8192 words gets no region. */
+#define CTD_BALLOON_FOOTPRINT 256 /* flags, bit 8: the row and the plane are the block's footprint */
+#define CTD_FOOTPRINT_MAX_PAD 16
+#define CTD_FOOTPRINT_DEFAULT_PAD 4
+
+typedef struct ctd_footprint_params {
+  int32_t grow, pad, reach, reach_min;
+  int32_t max_words; /* as ctd_balloon_params': sizes the launch's LDS */
+  int32_t pad_[3];
+} ctd_footprint_params;
+
+/* The rule above for n blocks in ONE launch on `stream`, one workgroup per block.  jobs_dev, pages_dev, erase_rows_dev,
+ * rows_dev and bits_dev are those of the ctd_balloon_regions call it follows on the same stream (no host step between the
+ * two): rows_dev[i] and the owned words of bits_dev are overwritten for the eligible blocks only.  `params` is read on the
+ * host during the call.  n = 0 launches nothing.  A parameter outside its bounds, a negative count, blocks without pages or a
+ * missing table is an error rc and launches nothing (bits_dev may be NULL where no block owns a word). */
+int ctd_balloon_footprints(const ctd_balloon_job* jobs_dev, int32_t n, const ctd_erase_page* pages_dev, int32_t n_pages,
+                           const ctd_erase_row* erase_rows_dev, const ctd_footprint_params* params, ctd_balloon_row* rows_dev,
+                           uint64_t* bits_dev, void* stream);
+
 /* ---- fill what erase leaves: smooth pull-push fill of a hole mask (added within ABI v10) --------------------------- */
 
 /* An addition to ABI v10 like the three above: one entry point, three structs, nothing existing changes.
