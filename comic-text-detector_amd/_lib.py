@@ -35,6 +35,7 @@ BALLOON_OK, BALLOON_NOT_PLAIN, BALLOON_TOO_LARGE = range(3)
 BALLOON_MAX_WORDS, BALLOON_MAX_REACH, BALLOON_MIN_REACH_MIN, BALLOON_MAX_REACH_MIN = 8192, 32, 8, 1024
 BALLOON_CUT_LEFT, BALLOON_CUT_TOP, BALLOON_CUT_RIGHT, BALLOON_CUT_BOTTOM = 1, 2, 4, 8
 BALLOON_FOOTPRINT, FOOTPRINT_MAX_PAD, FOOTPRINT_DEFAULT_PAD = 256, 16, 4
+BALLOON_TILTED = 512
 FILL_OK, FILL_NO_HOLE, FILL_NO_KNOWN = range(3)
 FILL_MAX_SIDE, FILL_TILE = 8192, 64
 TEXTURE_OK, TEXTURE_NO_HOLE, TEXTURE_NO_SOURCE = range(3)
@@ -157,6 +158,15 @@ class CtdFootprintParams(C.Structure):
                 ("pad_", C.c_int32 * 3)]
 
 
+class CtdTiltJob(C.Structure):
+    _fields_ = [("win", C.c_int32 * 4), ("ax", C.c_int32), ("ay", C.c_int32), ("c", C.c_int32), ("s", C.c_int32),
+                ("W", C.c_int32), ("H", C.c_int32), ("word0", C.c_int64)]
+
+
+class CtdTiltParams(C.Structure):
+    _fields_ = [("max_words", C.c_int32), ("pad_", C.c_int32 * 3)]
+
+
 class CtdLayoutJob(C.Structure):
     _fields_ = [("win", C.c_int32 * 4), ("ax", C.c_int32), ("ay", C.c_int32), ("word0", C.c_int64)]
 
@@ -222,6 +232,12 @@ class CtdTypesetRow(C.Structure):
 class CtdGlyphLayer(C.Structure):
     _fields_ = [("page", C.c_int32), ("clip", C.c_int32 * 4), ("fill", C.c_uint8 * 3), ("stroke", C.c_uint8 * 3),
                 ("radius", C.c_uint8), ("pad_", C.c_uint8), ("pad2_", C.c_int32)]
+
+
+class CtdTiltLayer(C.Structure):
+    _fields_ = [("page", C.c_int32), ("clip", C.c_int32 * 4), ("fill", C.c_uint8 * 3), ("stroke", C.c_uint8 * 3),
+                ("radius", C.c_uint8), ("pad_", C.c_uint8), ("ax", C.c_int32), ("ay", C.c_int32), ("c", C.c_int32),
+                ("s", C.c_int32), ("pad2_", C.c_int32)]
 
 
 class CtdGlyphPlace(C.Structure):
@@ -305,6 +321,7 @@ SYMBOLS = {
     "ctd_erase_text": (_i32, [_vp, _i32, _vp, _i32, C.POINTER(CtdEraseParams), _vp, _vp]),
     "ctd_balloon_regions": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdBalloonParams), _vp, _vp, _vp]),
     "ctd_balloon_footprints": (_i32, [_vp, _i32, _vp, _i32, _vp, C.POINTER(CtdFootprintParams), _vp, _vp, _vp]),
+    "ctd_balloon_tilt": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdTiltParams), _vp, _vp, _vp]),
     "ctd_layout_boxes": (_i32, [_vp, _i32, _vp, _vp, C.POINTER(CtdLayoutParams), _vp, _vp]),
     "ctd_layout_fit": (_i32, [_vp, _vp, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdFitParams), _vp, _vp]),
     "ctd_layout_fit_work_bytes": (C.c_int64, [_vp, _i32]),
@@ -312,6 +329,7 @@ SYMBOLS = {
                                        _vp]),
     "ctd_typeset": (_i32, [_vp, _vp, _vp, _vp, _vp, C.POINTER(CtdTypesetParams), _vp, _vp]),
     "ctd_typeset_glyphs": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdGlyphParams), _vp, _vp]),
+    "ctd_typeset_tilted": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp, C.POINTER(CtdGlyphParams), _vp, _vp]),
     "ctd_rasterise_glyphs": (_i32, [_vp, _i64, _vp, _i32, _vp, _i64, _vp, _vp]),
     "ctd_fill_rest": (_i32, [_vp, _i32, C.POINTER(CtdFillParams), _vp, _vp, _vp]),
     "ctd_texture_fill": (_i32, [_vp, _i32, C.POINTER(CtdTextureParams), _vp, _vp, _vp]),

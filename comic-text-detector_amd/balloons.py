@@ -24,6 +24,11 @@ stream, with the same uploaded tables, and gives every such block (erase row TEX
 stood as its region: the orthogonally convex closure of its filled glyphs, grown by `pad`, minus other blocks' text -- written
 into the same rows and the same bit buffer as an OK row with `_lib.BALLOON_FOOTPRINT` in its flags, so `layout_boxes`,
 `shaped_fit` and the typeset calls run on it unchanged (`BalloonRegions.footprint[j]`).
+
+A block set at an angle wants its box in its own frame, not the small upright one inside a slanted balloon:
+`tilt_regions(br, angles)` turns every region into its block's frame in ONE `ctd_balloon_tilt` launch (csrc/kernels_tilt.hip)
+-- the same windows and word layout in a second bit buffer, an ordinary `BalloonRegions` that the layout calls take as it
+stands -- and the typeset calls turn the text back (`TextDetector.layout_boxes(tilt=True)`).
 """
 from __future__ import annotations
 
@@ -37,11 +42,13 @@ from . import _lib as L
 from . import erase as E
 from .pagecall import Page, PageCall, blk_lists_of, check_pages, check_pitch, table_dtype
 
-__all__ = ["balloon_regions", "BalloonRegions", "balloon_tables", "check_params", "check_footprint", "JOB_DTYPE", "ROW_DTYPE"]
+__all__ = ["balloon_regions", "BalloonRegions", "balloon_tables", "check_params", "check_footprint", "JOB_DTYPE", "ROW_DTYPE",
+           "tilt_regions", "cs_of", "check_angles", "TILT_JOB_DTYPE"]
 
 # numpy views of `ctd_balloon_job` / `ctd_balloon_row` (include/ctd_hip.h); the page table is `erase.PAGE_DTYPE`
 JOB_DTYPE = table_dtype(L.CtdBalloonJob)
 ROW_DTYPE = table_dtype(L.CtdBalloonRow)
+TILT_JOB_DTYPE = table_dtype(L.CtdTiltJob)
 
 
 def check_params(grow, tol, reach, reach_min) -> L.CtdBalloonParams:
@@ -113,6 +120,8 @@ class BalloonRegions:
         self.ok = self.status == L.BALLOON_OK
         self.area, self.bbox, self.flags = rows["area"], rows["bbox"], rows["flags"]
         self.footprint = (self.flags & L.BALLOON_FOOTPRINT) != 0
+        self.shapes = None                                     # (H, W) per page, where `balloon_regions` made the regions
+        self.angle = self.pivot = self.cs = None               # set by `tilt_regions`: the regions are in the blocks' frames
         den = np.where(self.ok, np.maximum(rows["area"], 1), 1).astype(np.int64)
         self.center = np.where(self.ok[:, None], np.stack([rows["sum_x"] // den, rows["sum_y"] // den], axis=1), -1)
 
@@ -204,4 +213,84 @@ def balloon_regions(pages: Sequence[Page], masks: Sequence[Page], blk_lists: Seq
     if erased is not None and not np.array_equal(rows["n_seed"][rows["status"] == L.BALLOON_OK],
                                                  erows["n_fill"][rows["status"] == L.BALLOON_OK]):
         raise ValueError("`erased` was made with another `grow`, or from other pages, masks or blocks")
-    return BalloonRegions(index, rows, win, nw, word0, too_large, bits, erows)
+    out = BalloonRegions(index, rows, win, nw, word0, too_large, bits, erows)
+    out.shapes = shapes
+    return out
+
+
+# ---- tilted regions (include/ctd_hip.h, "tilted text") ------------------------------------------------------
+
+def check_angles(angles, n: int, what: str = "angles") -> np.ndarray:
+    """`angles` as (n,) int64: one whole number of degrees in -180 .. 180 per item; ValueError otherwise."""
+    a = np.asarray(angles)
+    if a.dtype.kind not in "iu" or a.dtype == bool or a.shape != (n,):
+        raise ValueError(f"{what}: one integer per block")
+    a = a.astype(np.int64)
+    if n and (a.min() < -180 or a.max() > 180):
+        raise ValueError(f"{what}: -180 .. 180 degrees")
+    return a
+
+
+def cs_of(angles) -> np.ndarray:
+    """(n, 2) int64: c = rint(cos 65536), s = rint(sin 65536) of whole degrees.  No product lies nearer than 0.004 to a
+    rounding tie, so the table does not depend on the libm (tests/test_tilt_ref.py pins it)."""
+    t = np.deg2rad(np.asarray(angles, np.float64))
+    return np.stack([np.rint(np.cos(t) * 65536), np.rint(np.sin(t) * 65536)], axis=-1).astype(np.int64).reshape(-1, 2)
+
+
+def tilt_regions(br: BalloonRegions, angles, pivots=None, stream: Optional[torch.cuda.Stream] = None) -> BalloonRegions:
+    """The regions of a `BalloonRegions` turned into their blocks' own frames: one table upload, one `ctd_balloon_tilt`
+    launch (csrc/kernels_tilt.hip) on `br.bits` where they lie, one small download.  angles: one integer per block, degrees,
+    -180 .. 180 (a detected block's `angle`); pivots: (n, 2) integers, x and y in page coordinates, about which each block
+    turns (default: the centre of its window).  `br.shapes[p]` = (H, W) of page p, as `balloon_regions` leaves it, decides
+    whether a cut flag names a window side or the page's edge (None: the right and bottom sides are never one).  The result is an ordinary
+    `BalloonRegions` in FRAME coordinates -- the same index, windows, nw, word0, too_large and erase_rows, new rows and a new
+    bit buffer, `_lib.BALLOON_TILTED` in the flags of every ok row -- so `layout.layout_boxes` and `layout.shaped_fit` take
+    it as it stands; it also carries `angle`, `pivot` and `cs` (the 16.16 pairs), which the typeset calls need to turn the
+    text back.  Frame pixel q of a window is set iff the page pixel nearest to frame -> page (q) is in the window and in the
+    region.  Bad arguments raise ValueError before anything is uploaded."""
+    n = len(br)
+    angles = check_angles(angles, n)
+    if pivots is None:
+        pivots = np.stack([(br.windows[:, 0] + br.windows[:, 2]) >> 1, (br.windows[:, 1] + br.windows[:, 3]) >> 1], axis=1)
+    pivots = np.asarray(pivots)
+    if pivots.dtype.kind not in "iu" or pivots.shape != (n, 2):
+        raise ValueError("pivots: an (n, 2) integer array, x and y per block")
+    pivots = pivots.astype(np.int64)
+    if n and np.abs(pivots).max() > 1 << 29:
+        raise ValueError("pivot beyond 2^29")
+    WH = np.full((n, 2), -1, np.int64)                           # no window side is a page's right or bottom edge
+    shapes = getattr(br, "shapes", None)
+    if shapes is not None:
+        hw = np.asarray([tuple(s[:2]) for s in shapes], np.int64).reshape(-1, 2)
+        if n and (br.index[:, 0].min() < 0 or br.index[:, 0].max() >= len(hw)):
+            raise ValueError("shapes: one (H, W) per page of the regions")
+        WH = hw[br.index[:, 0]][:, ::-1] if n else WH
+    brows = np.ascontiguousarray(br.rows)
+    if brows.dtype != ROW_DTYPE:
+        raise ValueError("`br.rows` are not balloon rows")
+    cs = cs_of(angles)
+
+    def result(rows, bits):
+        out = BalloonRegions(br.index, rows, br.windows, br.nw, br.word0, br.too_large, bits, br.erase_rows)
+        out.angle, out.pivot, out.cs, out.shapes = angles, pivots, cs, shapes
+        return out
+
+    if n == 0:
+        return result(np.zeros((0,), ROW_DTYPE), br.bits)
+    if not torch.cuda.is_available() or not br.bits.is_cuda:
+        raise L.CtdError("tilted regions run on the GPU and there is none (no CPU fallback)")
+    jobs = np.zeros((n,), TILT_JOB_DTYPE)
+    jobs["win"], jobs["ax"], jobs["ay"], jobs["c"], jobs["s"] = br.windows, pivots[:, 0], pivots[:, 1], cs[:, 0], cs[:, 1]
+    jobs["W"], jobs["H"], jobs["word0"] = WH[:, 0], WH[:, 1], br.word0
+    owned = (br.nw * (br.windows[:, 3] - br.windows[:, 1]))[~br.too_large]
+    prm = L.CtdTiltParams(int(owned.max()) if len(owned) else 0)
+    with PageCall("tilted regions run", (), stream, br.bits.device) as pc:
+        _, (jobs_ptr, brows_ptr) = pc.upload([jobs, brows])     # one upload: the jobs, then the balloon rows
+        res = torch.empty((n * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+        bits = torch.empty((max(br.bits.numel(), 1),), dtype=torch.int64, device=pc.device)[: br.bits.numel()].view(torch.uint64)
+        L.check(L.lib().ctd_balloon_tilt(jobs_ptr, n, brows_ptr, br.bits.data_ptr() if prm.max_words else None, C.byref(prm),
+                                         res.data_ptr(), bits.data_ptr() if prm.max_words else None, pc.st.cuda_stream),
+                "ctd_balloon_tilt")
+        rows = pc.rows(res, ROW_DTYPE, n)
+    return result(rows, bits)

@@ -1568,6 +1568,38 @@ int ctd_typeset_glyphs(const ctd_typeset_page* pages_dev, const ctd_glyph_layer*
   return CTD_OK;
 }
 
+int ctd_balloon_tilt(const ctd_tilt_job* jobs_dev, int32_t n, const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev,
+                     const ctd_tilt_params* params, ctd_balloon_row* rows_out_dev, uint64_t* bits_out_dev, void* stream) {
+  if (n < 0) return fail(CTD_ERR_INVALID, "bad sizes");
+  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
+  const ctd_tilt_params prm = *params;
+  if (prm.max_words < 0 || prm.max_words > CTD_BALLOON_MAX_WORDS) return fail(CTD_ERR_INVALID, "tilt: max_words 0..8192");
+  if (n == 0) return CTD_OK;
+  if (!jobs_dev || !balloon_rows_dev || !rows_out_dev || (prm.max_words > 0 && (!bits_dev || !bits_out_dev)))
+    return fail(CTD_ERR_INVALID, "null pointer");
+  HIP_TRY(launch_balloon_tilt(jobs_dev, n, balloon_rows_dev, bits_dev, prm, rows_out_dev, bits_out_dev, (hipStream_t)stream));
+  return CTD_OK;
+}
+
+int ctd_typeset_tilted(const ctd_typeset_page* pages_dev, const ctd_tilt_layer* layers_dev, const ctd_glyph_place* places_dev,
+                       const ctd_glyph_record* glyphs_dev, const ctd_typeset_tile* tiles_dev, const int32_t* entries_dev,
+                       const uint8_t* atlas_dev, const ctd_glyph_params* params, ctd_typeset_row* rows_dev, void* stream) {
+  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
+  const ctd_glyph_params prm = *params;
+  if (prm.n_layers < 0 || prm.n_pages < 0 || prm.n_tiles < 0 || prm.n_entries < 0 || prm.n_places < 0 || prm.n_glyphs < 0 ||
+      prm.atlas_bytes < 0)
+    return fail(CTD_ERR_INVALID, "bad sizes");
+  if ((prm.n_pages > 0 && !pages_dev) || (prm.n_layers > 0 && (!layers_dev || !rows_dev)) || (prm.n_places > 0 && !places_dev) ||
+      (prm.n_glyphs > 0 && !glyphs_dev) || (prm.n_tiles > 0 && !tiles_dev) || (prm.n_entries > 0 && !entries_dev) ||
+      (prm.atlas_bytes > 0 && !atlas_dev))
+    return fail(CTD_ERR_INVALID, "null pointer");
+  if (prm.n_tiles == 0 || prm.n_layers == 0) return CTD_OK;
+  HIP_TRY(hipMemsetAsync(rows_dev, 0, (size_t)prm.n_layers * sizeof(ctd_typeset_row), (hipStream_t)stream));
+  HIP_TRY(launch_typeset_tilted(pages_dev, layers_dev, places_dev, glyphs_dev, tiles_dev, entries_dev, atlas_dev, prm, rows_dev,
+                                (hipStream_t)stream));
+  return CTD_OK;
+}
+
 int ctd_rasterise_glyphs(const int32_t* segs_dev, int64_t n_segs, const ctd_raster_job* jobs_dev, int32_t n_jobs,
                          uint8_t* atlas_dev, int64_t atlas_bytes, int32_t* status_dev, void* stream) {
   if (n_segs < 0 || n_jobs < 0 || atlas_bytes < 0) return fail(CTD_ERR_INVALID, "bad sizes");

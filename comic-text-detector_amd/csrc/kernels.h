@@ -244,6 +244,19 @@ hipError_t launch_typeset_glyphs(const ctd_typeset_page* pages, const ctd_glyph_
                                  const ctd_glyph_record* glyphs, const ctd_typeset_tile* tiles, const int32_t* entries,
                                  const uint8_t* atlas, const ctd_glyph_params& prm, ctd_typeset_row* rows, hipStream_t st);
 
+// ---- kernels_tilt.hip -----------------------------------------------------------
+// ctd_balloon_tilt's one launch (one workgroup per block; n >= 1, prm checked by the caller): the dynamic-LDS limit under a
+// once-flag of its own, and what hipGetLastError says right after the launch
+hipError_t launch_balloon_tilt(const ctd_tilt_job* jobs, int n, const ctd_balloon_row* balloon_rows, const uint64_t* bits,
+                               const ctd_tilt_params& prm, ctd_balloon_row* rows_out, uint64_t* bits_out, hipStream_t st);
+
+// ---- kernels_tilted.hip ---------------------------------------------------------
+// ctd_typeset_tilted's one launch (as launch_typeset_glyphs: n_tiles >= 1, n_layers >= 1, the counts and pointers checked
+// and the rows cleared by the caller): returns what hipGetLastError says right after the launch
+hipError_t launch_typeset_tilted(const ctd_typeset_page* pages, const ctd_tilt_layer* layers, const ctd_glyph_place* places,
+                                 const ctd_glyph_record* glyphs, const ctd_typeset_tile* tiles, const int32_t* entries,
+                                 const uint8_t* atlas, const ctd_glyph_params& prm, ctd_typeset_row* rows, hipStream_t st);
+
 // ---- kernels_raster.hip ---------------------------------------------------------
 // the shape of ctd_rasterise_glyphs' launch (mirrored in _lib.py for the tests, which probe every boundary; no result
 // depends on any of them): pixel rows a band, pixel columns a chunk, segments a staging pass, workgroups a job

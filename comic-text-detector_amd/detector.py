@@ -587,7 +587,8 @@ class TextDetector:
         pages = self._on_device(pages)                        # no page: nothing is staged
         return balloons.balloon_regions(pages, masks, blk_lists, erased=erased, device=self.net.device, **kw)
 
-    def layout_boxes(self, pages: Sequence[Page], results, erased=None, regions=None, inset: int = 2, **balloon_kw):
+    def layout_boxes(self, pages: Sequence[Page], results, erased=None, regions=None, inset: int = 2, tilt: bool = False,
+                     angles=None, **balloon_kw):
         """The box a typesetter lays the translated text into, for every block of a detected batch: the largest axis-aligned
         rectangle inside the block's balloon region, `inset` pixels off its outline, and the largest one that contains the
         centre of the block's box, ((x1 + x2) >> 1, (y1 + y2) >> 1) of the box clipped to the page -- one launch behind the
@@ -595,17 +596,55 @@ class TextDetector:
         returned for `pages`.  `regions`: the `BalloonRegions` of `balloons(pages, results)` where the caller has them;
         otherwise that runs first, with `erased` and `balloon_kw` -- `footprint=True` and `pad` among them: a block off a
         plain background then gets a box inside the place where its old text stood instead of NO_REGION.  Builds no
-        `TextBlock` of a `BlockList`."""
+        `TextBlock` of a `BlockList`.
+        tilt=True: the boxes are taken in every block's OWN frame -- the page turned by the block's `angle` (the detector's,
+        read from the blocks; or `angles`, one integer of -180 .. 180 degrees per block) about the block's anchor -- so a
+        slanted balloon gets the large rectangle along its slant instead of the small upright one inside it.  One more
+        launch, `balloons.tilt_regions`, runs behind the balloon launch and the layout launch runs on its planes; the
+        result's `rect` and `a_rect` are then FRAME coordinates, and it carries `angle`, `pivot` (= `anchors`) and `frame`
+        (the tilted `BalloonRegions`, what `typeset_text(shaped=...)` takes), which `typeset`, `typeset_glyphs` and
+        `typeset_text` read to turn the text back into the page.  Off, the call launches and returns what it always did."""
         from . import balloons, erase, layout
         layout.check_params(inset)
         balloons.check_footprint(balloon_kw.get("footprint", False), balloon_kw.get("pad", 4))
+        if not isinstance(tilt, (bool, np.bool_)) or (angles is not None and not tilt):
+            raise ValueError("tilt: a bool; angles only with tilt=True")
+        if tilt:
+            if angles is None:
+                angles = np.concatenate([self._block_angles(r[2]) for r in results]) if len(results) else np.zeros((0,), np.int64)
+            angles = balloons.check_angles(angles, sum(len(r[2]) for r in results))
         if regions is None:
             regions = self.balloons(pages, results, erased=erased, **balloon_kw)
         boxes = [erase._page_boxes(r[2]) for r in results]
         anchors = layout.box_anchors(boxes, [tuple(p.shape[:2]) for p in pages])
         if len(anchors) != len(regions):
             raise ValueError("`regions` is not the result of balloons on these pages and blocks")
-        return layout.layout_boxes(regions, anchors, inset=inset)
+        if not tilt:
+            return layout.layout_boxes(regions, anchors, inset=inset)
+        if regions.angle is not None:
+            raise ValueError("`regions` are tilted already: pass the upright ones")
+        frame = balloons.tilt_regions(regions, angles, pivots=anchors)
+        lb = layout.layout_boxes(frame, anchors, inset=inset)
+        lb.angle, lb.pivot, lb.frame = frame.angle, frame.pivot, frame
+        return lb
+
+    @staticmethod
+    def _block_angles(blk_list) -> np.ndarray:
+        """The blocks' `angle` in order, int64; a `BlockList` is read from its records (no `TextBlock` is built)."""
+        from .textblock import BlockList
+        if isinstance(blk_list, BlockList):
+            return np.asarray(blk_list.records["angle"], np.int64).reshape(-1)
+        a = np.asarray([b.angle for b in blk_list], np.float64).reshape(-1)
+        if not np.array_equal(a, np.trunc(a)):
+            raise ValueError("block angles must be whole degrees (the detector's angle)")
+        return a.astype(np.int64)
+
+    @staticmethod
+    def _tilt_kw(boxes, idx) -> dict:
+        """The `angle` / `pivot` keywords of a typeset call for the layers `idx` of `boxes`: none for upright boxes."""
+        if getattr(boxes, "angle", None) is None:
+            return {}
+        return dict(angle=np.asarray(boxes.angle, np.int64)[idx], pivot=np.asarray(boxes.pivot, np.int64).reshape(-1, 2)[idx])
 
     def typeset(self, pages: Sequence[Page], boxes, bitmaps, fill=(0, 0, 0), stroke=(255, 255, 255), radius=0,
                 prefer: str = "a_rect", inplace: bool = False):
@@ -636,7 +675,7 @@ class TextDetector:
         rects = np.where(anchored[:, None], boxes.a_rect, boxes.rect).reshape(nb, 4)[idx]
         xy, fits = ts.place(rects, np.array([b.shape for b in maps], np.int64).reshape(len(idx), 2), radius)
         out = ts.typeset_pages(pages, boxes.index[idx, 0], maps, xy, fill=fill, stroke=stroke, radius=radius, inplace=inplace,
-                               device=self.net.device)
+                               device=self.net.device, **self._tilt_kw(boxes, idx))
         out.layer_of, out.fits = layer_of, fits
         return out
 
@@ -671,7 +710,7 @@ class TextDetector:
         ids = np.concatenate(ids) if ids else np.zeros((0,), np.int64)
         xy = np.concatenate(xy) if xy else np.zeros((0, 2), np.int64)
         out = gl.typeset_glyphs(pages, atlas, boxes.index[idx, 0], np.repeat(np.arange(len(idx)), count), ids, xy, fill=fill,
-                                stroke=stroke, radius=radius, inplace=inplace, device=self.net.device)
+                                stroke=stroke, radius=radius, inplace=inplace, device=self.net.device, **self._tilt_kw(boxes, idx))
         out.layer_of, out.fits = layer_of, np.array(fits, bool)
         return out
 
@@ -689,7 +728,9 @@ class TextDetector:
         filling its rectangle: the metrics are taken per size over the batch's unique gids (a loop over `sizes`, at most
         16 of them, not over blocks), ONE `layout.shaped_fit` call with `boxes.anchors` and the inset `boxes.inset` plus the
         largest stroke radius (16 at the most) gives every block its largest size and its line slots, and
-        `glyphs.place_lines` places all runs at once.  Horizontal text only; `flow_kw` may hold `line` (one height for all
+        `glyphs.place_lines` places all runs at once.  For the boxes of `layout_boxes(tilt=True)` it is `boxes.frame`, the
+        tilted regions (anything else is a ValueError): the lines then follow the outline in the block's frame and are
+        turned back with the text.  Horizontal text only; `flow_kw` may hold `line` (one height for all
         sizes), `gap`, `align` and `breaks` (one list entry per block of `boxes`).  A block whose fit is not OK takes the
         rectangle path above.  The result gains `shaped[i]` (bool: layer i follows the outline), `n_lines[i]` (its lines; 0
         on the rectangle path) and `fit`, the `ShapedFit` of all blocks of `boxes`.
@@ -723,7 +764,7 @@ class TextDetector:
         xy = [gl.flow_outlines(run, font, rects[i], chosen[i][0], **flow_kw)[0] for i, run in enumerate(run_of)]
         xy = np.concatenate(xy) if xy else np.zeros((0, 2), np.int64)
         out = gl.typeset_glyphs(pages, atlas, boxes.index[idx, 0], np.repeat(np.arange(len(idx)), count), ids, xy, fill=fill,
-                                stroke=stroke, radius=radius, inplace=inplace, device=self.net.device)
+                                stroke=stroke, radius=radius, inplace=inplace, device=self.net.device, **self._tilt_kw(boxes, idx))
         out.layer_of, out.fits = layer_of, np.array([c[1] for c in chosen], bool)
         out.size = np.array([c[0] for c in chosen])
         return out
@@ -740,6 +781,9 @@ class TextDetector:
         nb, nl = len(boxes), len(idx)
         if len(shaped) != nb or not np.array_equal(shaped.index, boxes.index):
             raise ValueError("`shaped` is not the BalloonRegions that `boxes` was made from")
+        if (getattr(boxes, "frame", None) is not None and shaped is not boxes.frame) or \
+                (getattr(boxes, "frame", None) is None and getattr(shaped, "angle", None) is not None):
+            raise ValueError("`shaped` and `boxes` are not in one frame: tilted boxes take `shaped=boxes.frame`")
         align, gap, line, breaks = kw.pop("align", "center"), int(kw.pop("gap", 0)), kw.pop("line", None), kw.pop("breaks", None)
         kw.pop("vertical", None)
         if kw:
@@ -787,7 +831,7 @@ class TextDetector:
             xy[first[i]: first[i] + count[i]] = gl.flow_outlines(run_of[i], font, rects[i], chosen[i][0], breaks=None if breaks is None
                                                                  else breaks[idx[i]], **rect_kw)[0]
         out = gl.typeset_glyphs(pages, atlas, boxes.index[idx, 0], of_layer, ids, xy, fill=fill, stroke=stroke, radius=radius,
-                                inplace=inplace, device=self.net.device)
+                                inplace=inplace, device=self.net.device, **self._tilt_kw(boxes, idx))
         out.layer_of, out.size, out.shaped = layer_of, size, ok.copy()
         out.fits = np.array([True if ok[i] else chosen[i][1] for i in range(nl)], bool)
         out.n_lines = np.where(ok, fit.n_lines[idx], 0).astype(np.int64)

@@ -38,7 +38,8 @@ import torch
 
 from . import _lib as L
 from .pagecall import Page, PageCall, need_gpu, table_dtype
-from .typeset import MAX_COORD, ROW_DTYPE, TILE_DTYPE, TypesetPages, _bin_tiles, _ints, _layer_args, _layers, _open_pages, _rects
+from .typeset import (MAX_COORD, ROW_DTYPE, TILE_DTYPE, TypesetPages, _bin_tiles, _ints, _layer_args, _layers, _open_pages, _rects,
+                      _tilt_args, _tilt_layer_table, tilt_tables)
 
 __all__ = ["GlyphAtlas", "glyph_tables", "typeset_glyphs", "flow", "place_lines", "LAYER_DTYPE", "PLACE_DTYPE", "RECORD_DTYPE", "OutlineFont",
            "segments_from_ops", "outline_boxes", "flow_outlines", "fit", "RASTER_JOB_DTYPE"]
@@ -333,7 +334,7 @@ def place_lines(fit, count, adv, bearing, align: str = "center", blocks=None) ->
 
 def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, glyph, xy, fill=(0, 0, 0),
                    stroke=(255, 255, 255), radius=0, clip=None, inplace: bool = False,
-                   stream: Optional[torch.cuda.Stream] = None, device=None) -> TypesetPages:
+                   stream: Optional[torch.cuda.Stream] = None, device=None, angle=None, pivot=None) -> TypesetPages:
     """Composite glyph layers into the pages of a batch: one upload of tables and placements, one `ctd_typeset_glyphs`
     launch, one small download.  pages: as `typeset.typeset_pages`.  Per LAYER: page_of[l]; fill / stroke (RGB, one triple for
     all or one per layer); radius 0 .. 12 and clip (x1, y1, x2, y2) exclusive (one for all or one per layer; default the
@@ -341,9 +342,15 @@ def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, 
     pixel in page coordinates.  A layer's coverage is the max over its placements; layers are applied in order.  `inplace`
     as in `typeset_pages`.  Bad arguments raise ValueError before anything is uploaded.  Runs on `stream` (default: the
     current stream of the atlas's device) and waits for the result: a `TypesetPages` with one row and one status per
-    LAYER, whose `xy` is per PLACEMENT and which also carries `place_layer` (= layer_of) and `place_glyph`."""
+    LAYER, whose `xy` is per PLACEMENT and which also carries `place_layer` (= layer_of) and `place_glyph`.
+    angle, pivot: per LAYER (one for all or one per layer) the whole degrees, -180 .. 180, and the page pixel (x, y; default
+    (0, 0)) of the layer's frame; xy is then in FRAME coordinates and the layer is turned about its pivot into the page
+    (include/ctd_hip.h, "tilted text"; `typeset.tilt_tables` bins each placement by a conservative page box), in ONE
+    `ctd_typeset_tilted` launch (csrc/kernels_tilted.hip) for all layers, tilted or not.  Where no layer has a non-zero
+    angle the call is the one above, exactly."""
     shapes, page_of, fill, stroke, r = _layer_args(pages, page_of, fill, stroke, radius, inplace)
     nl = len(page_of)
+    tilt = _tilt_args(angle, pivot, nl)
     layer_of = _ints(layer_of, (-1,), "layer_of")
     n = len(layer_of)
     glyph, xy = _ints(glyph, (n,), "glyph"), _ints(xy, (n, 2), "xy")
@@ -351,7 +358,10 @@ def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, 
         raise ValueError("atlas: an open GlyphAtlas")
     if n and (glyph.min() < 0 or glyph.max() >= len(atlas)):
         raise ValueError("glyph: an id of the atlas")
-    tiles, entries, status = glyph_tables(shapes, page_of, layer_of, atlas.sizes[glyph], xy, r, clip)
+    if tilt is None:
+        tiles, entries, status = glyph_tables(shapes, page_of, layer_of, atlas.sizes[glyph], xy, r, clip)
+    else:
+        tiles, entries, status = tilt_tables(shapes, page_of, layer_of, atlas.sizes[glyph], xy, r, clip, tilt[1], tilt[2])
     n_pages, n_tiles = len(pages), len(tiles) - 1
     device = atlas.device if device is None else torch.device(device)
     if device != atlas.device:
@@ -360,16 +370,19 @@ def typeset_glyphs(pages: Sequence[Page], atlas: GlyphAtlas, page_of, layer_of, 
         out, pt, clip4 = _open_pages(pc, pages, shapes, page_of, clip, inplace)
         rows = np.zeros((nl,), ROW_DTYPE)
         if n_tiles:
-            lt = np.zeros((nl,), LAYER_DTYPE)
-            lt["page"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = page_of, clip4, fill, stroke, r
+            if tilt is None:
+                lt = np.zeros((nl,), LAYER_DTYPE)
+                lt["page"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = page_of, clip4, fill, stroke, r
+            else:
+                lt = _tilt_layer_table(page_of, clip4, fill, stroke, r, tilt[1], tilt[2])
+            entry = L.lib().ctd_typeset_glyphs if tilt is None else L.lib().ctd_typeset_tilted
             qt = np.zeros((n,), PLACE_DTYPE)
             qt["layer"], qt["glyph"], qt["x"], qt["y"] = layer_of, glyph, xy[:, 0], xy[:, 1]
             _, ptr = pc.upload([pt, lt, qt, tiles, entries])       # one upload: the tables and the placements
             rows_dev = torch.empty((nl * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
             prm = L.CtdGlyphParams(nl, n_pages, n_tiles, len(entries), n, len(atlas), atlas.nbytes)
-            L.check(L.lib().ctd_typeset_glyphs(ptr[0], ptr[1], ptr[2], atlas._rec.data_ptr(), ptr[3], ptr[4],
-                                               atlas._cov.data_ptr(), C.byref(prm), rows_dev.data_ptr(), pc.st.cuda_stream),
-                    "ctd_typeset_glyphs")
+            L.check(entry(ptr[0], ptr[1], ptr[2], atlas._rec.data_ptr(), ptr[3], ptr[4], atlas._cov.data_ptr(), C.byref(prm),
+                          rows_dev.data_ptr(), pc.st.cuda_stream), "ctd_typeset_glyphs" if tilt is None else "ctd_typeset_tilted")
             rows = pc.rows(rows_dev, ROW_DTYPE, nl)
     tp = TypesetPages(out, rows, status, np.zeros((nl, 2), np.int64))
     tp.xy, tp.place_layer, tp.place_glyph = xy, layer_of, glyph             # per placement here, not per layer

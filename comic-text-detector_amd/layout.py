@@ -86,6 +86,9 @@ class LayoutBoxes:
         self.ok = self.status == L.LAYOUT_OK
         self.n_inner, self.area, self.rect = rows["n_inner"], rows["area"], rows["rect"]
         self.a_area, self.a_rect = rows["a_area"], rows["a_rect"]
+        # set by `TextDetector.layout_boxes(tilt=True)`: per block the frame's angle and pivot, and the tilted regions; `rect`
+        # and `a_rect` are then frame coordinates
+        self.angle = self.pivot = self.frame = None
 
     def __len__(self) -> int:
         return len(self.index)

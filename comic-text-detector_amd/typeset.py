@@ -26,7 +26,8 @@ import torch
 from . import _lib as L
 from .pagecall import Page, PageCall, check_pages, device_pages, table_dtype, views
 
-__all__ = ["typeset_pages", "TypesetPages", "typeset_tables", "place", "PAGE_DTYPE", "LAYER_DTYPE", "TILE_DTYPE", "ROW_DTYPE"]
+__all__ = ["typeset_pages", "TypesetPages", "typeset_tables", "place", "PAGE_DTYPE", "LAYER_DTYPE", "TILE_DTYPE", "ROW_DTYPE",
+           "tilt_tables", "TILT_LAYER_DTYPE"]
 
 # numpy views of `ctd_typeset_page` / `_layer` / `_tile` / `_row` (include/ctd_hip.h)
 PAGE_DTYPE = table_dtype(L.CtdTypesetPage)
@@ -126,6 +127,92 @@ def _bin_tiles(H, W, page_of_item, x1, y1, x2, y2, items) -> tuple:
     tiles["page"][:-1], tiles["tx"][:-1], tiles["ty"][:-1], tiles["first"][:-1] = pg[at], tx[at], ty[at], first
     tiles["first"][-1] = total
     return tiles, item[order].astype(np.int32)
+
+
+# ---- tilted layers (include/ctd_hip.h, "tilted text") -------------------------------------------------------
+
+TILT_LAYER_DTYPE = table_dtype(L.CtdTiltLayer)
+TILT_MAX_COORD = 1 << 27                                   # |xy| and |pivot| of a tilted layer: the binner's products fit int64
+
+
+def _tilt_args(angle, pivot, n: int):
+    """The `angle` / `pivot` keywords of the typeset calls, checked: None where no layer is tilted (the call then runs as it
+    always did), else (angle (n,) int64 degrees, pivot (n, 2) int64, cs (n, 2) int64 16.16 cosine and sine)."""
+    if angle is None:
+        if pivot is not None:
+            raise ValueError("pivot: only with angle")
+        return None
+    angle = _per_layer(angle, n, 1, "angle")[:, 0]
+    if n and (angle.min() < -180 or angle.max() > 180):
+        raise ValueError("angle: -180 .. 180 degrees")
+    pivot = _per_layer((0, 0) if pivot is None else pivot, n, 2, "pivot")
+    if n and np.abs(pivot).max() > TILT_MAX_COORD:
+        raise ValueError("pivot beyond 2^27")
+    if not angle.any():
+        return None
+    from .balloons import cs_of                            # the one table of both calls (balloons imports nothing of this module)
+    return angle, pivot, cs_of(angle)
+
+
+def _tilt_rects(n: int, sizes, xy, r, clip, pw, ph, pivot, cs, what: str) -> tuple:
+    """`_rects` for bitmaps in a frame: sizes[i] = (h, w) at FRAME position xy[i], frame pivot[i] and cs[i] = (c, s).  The
+    page pixels whose four taps can touch the bitmap are those p with page -> frame (p) inside the bitmap's rectangle grown
+    by one pixel to the left and up; d = p - pivot is the exact inverse image 65536 (c a - s b, s a + c b) / (c^2 + s^2) of
+    (a, b) = frame point - pivot, linear, so its extremes lie at the rectangle's corners: floor of the least and ceiling of
+    the greatest, in integers, then grown by r + 1, cut to clip[i] and the page."""
+    sizes, xy = _ints(sizes, (n, 2), "sizes"), _ints(xy, (n, 2), "xy")
+    if n and (sizes.min() < 0 or sizes.max() > L.TYPESET_MAX_SIDE):
+        raise ValueError(f"{what} sides must be 0 .. {L.TYPESET_MAX_SIDE}")
+    if n and np.abs(xy).max() > TILT_MAX_COORD:
+        raise ValueError("xy of a tilted call beyond 2^27")
+    c, s = cs[:, 0:1], cs[:, 1:2]
+    N = (c * c + s * s)[:, 0]
+    a = np.stack([xy[:, 0] - 1, xy[:, 0] + sizes[:, 1]], axis=1) - pivot[:, 0:1]
+    b = np.stack([xy[:, 1] - 1, xy[:, 1] + sizes[:, 0]], axis=1) - pivot[:, 1:2]
+    A, B = a[:, [0, 1, 0, 1]], b[:, [0, 0, 1, 1]]                             # the four corners
+    numx, numy = 65536 * (c * A - s * B), 65536 * (s * A + c * B)
+    lox, hix = numx.min(axis=1) // N, -((-numx.max(axis=1)) // N)
+    loy, hiy = numy.min(axis=1) // N, -((-numy.max(axis=1)) // N)
+    x1 = np.maximum(np.maximum(pivot[:, 0] + lox - r - 1, clip[:, 0]), 0)
+    y1 = np.maximum(np.maximum(pivot[:, 1] + loy - r - 1, clip[:, 1]), 0)
+    x2 = np.minimum(np.minimum(pivot[:, 0] + hix + r + 2, clip[:, 2]), pw)
+    y2 = np.minimum(np.minimum(pivot[:, 1] + hiy + r + 2, clip[:, 3]), ph)
+    return sizes, xy, x1, y1, x2, y2
+
+
+def tilt_tables(shapes: Sequence, page_of, layer_of, sizes, xy, radius, clip, pivot, cs) -> tuple:
+    """`glyphs.glyph_tables` for tilted layers: (tiles, entries, status).  pivot (n_layers, 2) and cs (n_layers, 2) give
+    every layer's frame; xy[i] is placement i's FRAME position.  A placement is entered in every tile that the conservative
+    page box of `_tilt_rects` meets; OUTSIDE means that box is empty.  For a bitmap call layer_of is arange(n).  Numpy only."""
+    H, W, page_of, r, clip = _layers(shapes, page_of, radius, clip)
+    nl = len(page_of)
+    layer_of = _ints(layer_of, (-1,), "layer_of")
+    n = len(layer_of)
+    if n and (layer_of.min() < 0 or layer_of.max() >= nl):
+        raise ValueError("layer_of: an index of the layers")
+    if n and (np.diff(layer_of) < 0).any():
+        raise ValueError("layer_of must be non-decreasing: the placements of a layer are consecutive")
+    pg = page_of[layer_of]
+    sizes, xy, x1, y1, x2, y2 = _tilt_rects(n, sizes, xy, r[layer_of], clip[layer_of], W[pg], H[pg], pivot[layer_of], cs[layer_of],
+                                            "glyph")
+    inked = (sizes[:, 0] > 0) & (sizes[:, 1] > 0)
+    drawn = inked & (x1 < x2) & (y1 < y2)
+    n_inked, n_drawn = np.bincount(layer_of[inked], minlength=nl), np.bincount(layer_of[drawn], minlength=nl)
+    status = np.where(n_inked == 0, L.TYPESET_EMPTY, np.where(n_drawn == 0, L.TYPESET_OUTSIDE, L.TYPESET_OK)).astype(np.int32)
+    return _bin_tiles(H, W, pg, x1, y1, x2, y2, np.flatnonzero(drawn)) + (status,)
+
+
+def _tilt_layer_table(page_of, clip4, fill, stroke, r, pivot, cs) -> np.ndarray:
+    lt = np.zeros((len(page_of),), TILT_LAYER_DTYPE)
+    lt["page"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = page_of, clip4, fill, stroke, r
+    lt["ax"], lt["ay"], lt["c"], lt["s"] = pivot[:, 0], pivot[:, 1], cs[:, 0], cs[:, 1]
+    return lt
+
+
+def _place_table(layer_of, glyph, xy) -> np.ndarray:
+    qt = np.zeros((len(layer_of),), table_dtype(L.CtdGlyphPlace))
+    qt["layer"], qt["glyph"], qt["x"], qt["y"] = layer_of, glyph, xy[:, 0], xy[:, 1]
+    return qt
 
 
 def typeset_tables(shapes: Sequence, page_of, sizes, xy, radius=0, clip=None) -> tuple:
@@ -242,7 +329,7 @@ def _open_pages(pc: PageCall, pages, shapes, page_of, clip, inplace: bool) -> tu
 
 def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray], xy, fill=(0, 0, 0), stroke=(255, 255, 255),
                   radius=0, clip=None, inplace: bool = False, stream: Optional[torch.cuda.Stream] = None,
-                  device=None) -> TypesetPages:
+                  device=None, angle=None, pivot=None) -> TypesetPages:
     """Composite layers into the pages of a batch by the typeset rule: one upload of coverage and tables, one `ctd_typeset`
     launch, one small download.  pages: uint8 (H,W,3) pages of any mix of sizes, on the device or on the host; per layer
     page_of[i], bitmaps[i] a (h, w) uint8 numpy array of coverage, xy[i] = (x0, y0) of its top-left pixel in page
@@ -251,9 +338,15 @@ def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray],
     default the page.  Layers are applied in the order given.  inplace=False composites into a copy, views of one new
     allocation; inplace=True writes the given pages, which must then be device tensors with dense rows (any row pitch).
     Bad arguments raise ValueError before anything is uploaded.  Runs on `stream` (default: the current stream of the pages'
-    device) and waits for the result; see `TypesetPages`."""
+    device) and waits for the result; see `TypesetPages`.
+    angle, pivot: per layer (one for all or one per layer) the whole degrees, -180 .. 180, and the page pixel (x, y; default
+    (0, 0)) of the layer's frame; xy[i] is then the bitmap's position in that FRAME, and the bitmap is turned about the pivot
+    into the page (include/ctd_hip.h, "tilted text": resampled by four taps, the outline a page-space disk).  The launch is
+    then `ctd_typeset_tilted`'s: each bitmap is the one glyph of its layer, the packed coverage is the atlas and the record
+    table is built here.  Where no layer has a non-zero angle the call is the one above, exactly."""
     shapes, page_of, fill, stroke, r = _layer_args(pages, page_of, fill, stroke, radius, inplace)
     n = len(page_of)
+    tilt = _tilt_args(angle, pivot, n)
     if len(bitmaps) != n:
         raise ValueError("one bitmap per layer")
     for b in bitmaps:
@@ -261,7 +354,10 @@ def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray],
             raise ValueError("a bitmap is a (h, w) uint8 numpy array")
     sizes = np.array([b.shape for b in bitmaps], np.int64).reshape(n, 2)
     xy = _ints(xy, (n, 2), "xy")
-    tiles, entries, status = typeset_tables(shapes, page_of, sizes, xy, r, clip)
+    if tilt is None:
+        tiles, entries, status = typeset_tables(shapes, page_of, sizes, xy, r, clip)
+    else:
+        tiles, entries, status = tilt_tables(shapes, page_of, np.arange(n), sizes, xy, r, clip, tilt[1], tilt[2])
     area = sizes[:, 0] * sizes[:, 1]
     cov0 = np.cumsum(area) - area
     cov = np.concatenate([b.ravel() for b in bitmaps]) if n else np.zeros((0,), np.uint8)
@@ -269,7 +365,18 @@ def typeset_pages(pages: Sequence[Page], page_of, bitmaps: Sequence[np.ndarray],
     with PageCall("typesetting runs", pages, stream, device) as pc:
         out, pt, clip4 = _open_pages(pc, pages, shapes, page_of, clip, inplace)
         rows = np.zeros((n,), ROW_DTYPE)
-        if n and n_pages:
+        if tilt is not None and n_tiles:
+            rec = np.zeros((n,), table_dtype(L.CtdGlyphRecord))
+            rec["off"], rec["w"], rec["h"] = cov0, sizes[:, 1], sizes[:, 0]
+            lt = _tilt_layer_table(page_of, clip4, fill, stroke, r, tilt[1], tilt[2])
+            # one upload: the tables, the records made here, and the coverage as the atlas
+            _, ptr = pc.upload([pt, lt, _place_table(np.arange(n), np.arange(n), xy), rec, tiles, entries, cov])
+            rows_dev = torch.empty((n * ROW_DTYPE.itemsize,), dtype=torch.uint8, device=pc.device)
+            prm = L.CtdGlyphParams(n, n_pages, n_tiles, len(entries), n, n, len(cov))
+            L.check(L.lib().ctd_typeset_tilted(ptr[0], ptr[1], ptr[2], ptr[3], ptr[4], ptr[5], ptr[6] if len(cov) else None,
+                                               C.byref(prm), rows_dev.data_ptr(), pc.st.cuda_stream), "ctd_typeset_tilted")
+            rows = pc.rows(rows_dev, ROW_DTYPE, n)
+        elif tilt is None and n and n_pages:
             lt = np.zeros((n,), LAYER_DTYPE)
             lt["cov0"], lt["page"], lt["x0"], lt["y0"], lt["h"], lt["w"] = cov0, page_of, xy[:, 0], xy[:, 1], sizes[:, 0], sizes[:, 1]
             lt["cov_pitch"], lt["clip"], lt["fill"], lt["stroke"], lt["radius"] = sizes[:, 1], clip4, fill, stroke, r

@@ -883,7 +883,8 @@ int ctd_texture_fill(const ctd_texture_page* pages_dev, int32_t n_pages, const c
  *   CTD_LAYOUT_OK
  * Row per block, 48 bytes, twelve int32, no padding: status; n_inner = |E_b|; area and rect; a_area and a_rect.  Rectangles
  * are in page coordinates.  Areas fit int32: a window has at most 8192 x 64 pixels.
- * Limits: an L-shaped balloon gets its larger arm; rotated text gets an axis-aligned box; a region that leaked through a gap
+ * Limits: an L-shaped balloon gets its larger arm; rotated text gets an axis-aligned box (unless the plane is first turned
+ * into the block's frame: the "tilted text" section below); a region that leaked through a gap
  * in the outline gives a box cut at the window, and the balloon row's flags say so. */
 #define CTD_LAYOUT_OK 0
 #define CTD_LAYOUT_NO_REGION 1
@@ -1310,6 +1311,94 @@ typedef struct ctd_raster_job {
  * n_segs > 0 or atlas_dev NULL with atlas_bytes > 0 is an error rc (plus ctd_last_error) and launches nothing. */
 int ctd_rasterise_glyphs(const int32_t* segs_dev, int64_t n_segs, const ctd_raster_job* jobs_dev, int32_t n_jobs,
                          uint8_t* atlas_dev, int64_t atlas_bytes, int32_t* status_dev, void* stream);
+
+/* ---- tilted text: regions and typeset in a block's own frame (added within ABI v10) ------------------------------------------ */
+
+/* An addition to ABI v10 like the ones above: two entry points, three structs, one flag, nothing existing changes.
+ * The detector gives every block an integer angle in degrees; the layout section's limit "rotated text gets an axis-aligned
+ * box" is lifted here WITHOUT a new layout or fit kernel.  ctd_layout_boxes, ctd_layout_fit and ctd_layout_fit_balanced read
+ * a window, a bit plane, an anchor and a balloon row: given the region plane turned into the block's frame they run as they
+ * stand, and the compositor turns the frame back into the page.  Integers only, every product in 64 bits; image coordinates
+ * are x right, y down.  Restated in numpy in tests/tilt_ref.py.
+ *   frame   a pivot (ax, ay), an integer page pixel, and a pair (c, s) of 16.16 integers.  The HOST makes them from an
+ *           integer angle t in -180 .. 180 degrees: c = rint(cos(t) 65536), s = rint(sin(t) 65536); the device sees no
+ *           trigonometry.  (65536, 0) is the identity.
+ *   frame -> page   for frame pixel q with d = q - pivot: PX = (ax << 16) + c dx - s dy, PY = (ay << 16) + s dx + c dy.
+ *   page -> frame   for page pixel p with d = p - pivot:  u = (ax << 16) + c dx + s dy,  v = (ay << 16) - s dx + c dy.
+ *           With t the block's angle, page -> frame turns the block's text lines axis-parallel.
+ * Tilted region (ctd_balloon_tilt).  Job i belongs to row i of the source balloon rows; it names the block's window (wx1,
+ * wy1, ww, wh, nw and word0 exactly as the balloon section lays them out), the frame, and the page's W and H.  T_b lives in
+ * the SAME window and the same word layout, in a second bit buffer of the same size:
+ *   T_b     frame pixel q of the window is set iff page pixel ((PX + 32768) >> 16, (PY + 32768) >> 16) lies in the window
+ *           and in B_b.  The pivot need not lie in the window or in the region.
+ *   row     status is the source row's.  A source row that is not CTD_BALLOON_OK is copied as it stands and the block's
+ *           owned words are written 0; a window of more than min(params.max_words, CTD_BALLOON_MAX_WORDS) words (or one
+ *           with x2 <= x1 or y2 <= y1) owns no words and an OK source row there comes back TOO_LARGE, all else 0; a job
+ *           with |c| or |s| above 65537 or |ax| or |ay| above 2^29 has no frame: NOT_PLAIN, all else 0, words 0.  For an
+ *           OK row: area, bbox, sum_x and sum_y are taken over T_b (frame coordinates), n_seed is the source row's, and
+ *           flags = the eight cut bits computed on T_b, bit 8 copied from the source, bit 9 CTD_BALLOON_TILTED set.
+ *           (c, s) = (65536, 0) gives the source plane and the source row plus bit 9.
+ * Tilted coverage (ctd_typeset_tilted).  A layer is ctd_glyph_layer plus its frame; its placements' (x, y) are FRAME
+ * coordinates.
+ *   U(q)    the glyph section's F over frame pixels: the max over the layer's placements, 0 outside every glyph.
+ *   F(p)    for page pixel p: x0 = u >> 16, fx = (u >> 8) & 255, y0 = v >> 16, fy = (v >> 8) & 255, Uij = U(x0 + i, y0 + j):
+ *           F = ((U00 (256 - fx) + U10 fx) (256 - fy) + (U01 (256 - fx) + U11 fx) fy + 32768) >> 16.
+ *   S, blend, layers, clip, row   the typeset rule, unchanged, in PAGE space: S is the disk max of F, r <= 12, the pixel is
+ *           blend(blend(P, stroke, S), fill, F), layers apply in table order, clips are page rectangles, n_fill and n_stroke
+ *           count the pixels written with F > 0 and S > 0.  With (65536, 0), F = U and the result is ctd_typeset_glyphs' to
+ *           the byte.
+ *   invalid as the glyph section, and: a layer whose frame maps the tile's coverage patch (CTD_TYPESET_TILE_W + 24 by
+ *           CTD_TYPESET_TILE_H + 24 pixels) onto more than 106 frame columns or rows draws nothing.  c^2 + s^2 <=
+ *           65537^2 never does: the patch's diagonal is under 103 pixels.
+ * The tile table is ctd_typeset_glyphs': the caller lists, per touched tile, every placement whose rectangle, grown by one
+ * pixel, turned into the page and grown by r, cut to page and clip, can meet it (glyphs.tilt_tables is the producer and
+ * computes that box conservatively in integers).
+ * Limits: nearest-neighbour turning is no bijection of the pixel grid, so T_b is contained in the turned B_b only up to a
+ * pixel (add a pixel of inset); the window is kept, so a large angle cuts the corners of a long window, and the cut flags
+ * say so; the outline is a page-space disk; glyphs are resampled, not re-rasterised, so tilted text is slightly softer. */
+#define CTD_BALLOON_TILTED 512 /* flags, bit 9: the row and the plane are in the block's frame */
+
+/* One block of a ctd_balloon_tilt call (a row of the device job table), 48 bytes. */
+typedef struct ctd_tilt_job {
+  int32_t win[4]; /* the block's window x1, y1, x2, y2 in page coordinates, as the balloon call's caller laid it out */
+  int32_t ax, ay; /* the pivot, page coordinates                                                                       */
+  int32_t c, s;   /* 16.16 cosine and sine                                                                             */
+  int32_t W, H;   /* the page's size: which window sides are page edges                                                */
+  int64_t word0;  /* the block's first word of bits_dev and of bits_out_dev                                            */
+} ctd_tilt_job;
+
+typedef struct ctd_tilt_params {
+  int32_t max_words; /* the largest nw * wh <= CTD_BALLOON_MAX_WORDS among the call's blocks: sizes the launch's LDS */
+  int32_t pad_[3];
+} ctd_tilt_params;
+
+/* The tilted-region rule for n blocks in ONE launch on `stream`, one workgroup per block: rows_out_dev[i] and the owned
+ * words of bits_out_dev are job i's.  balloon_rows_dev and bits_dev may be the results of a balloon call earlier on the same
+ * stream; both are read only, and the outputs must not overlap them.  `params` is read on the host during the call.
+ * n = 0 launches nothing.  A negative n, max_words outside 0 .. 8192 or a missing table with n > 0 is an error rc and
+ * launches nothing (bits_dev and bits_out_dev may be NULL where max_words is 0). */
+int ctd_balloon_tilt(const ctd_tilt_job* jobs_dev, int32_t n, const ctd_balloon_row* balloon_rows_dev, const uint64_t* bits_dev,
+                     const ctd_tilt_params* params, ctd_balloon_row* rows_out_dev, uint64_t* bits_out_dev, void* stream);
+
+/* One tilted glyph layer (a row of the device layer table), 48 bytes: ctd_glyph_layer's fields, then the frame. */
+typedef struct ctd_tilt_layer {
+  int32_t page;
+  int32_t clip[4];   /* x1, y1, x2, y2, exclusive, page coordinates                */
+  uint8_t fill[3];   /* page channel order                                         */
+  uint8_t stroke[3];
+  uint8_t radius;
+  uint8_t pad_;
+  int32_t ax, ay;    /* the pivot, page coordinates, |ax|, |ay| <= 2^29            */
+  int32_t c, s;      /* 16.16 cosine and sine                                      */
+  int32_t pad2_;
+} ctd_tilt_layer;
+
+/* ctd_typeset_glyphs with tilted layers: the same page, placement, record, tile, entry and atlas tables, the same params and
+ * rows, the same launch shape (one workgroup of 256 threads per row of the tile table, no cap on the placements of a tile or
+ * a layer) and the same refusals. */
+int ctd_typeset_tilted(const ctd_typeset_page* pages_dev, const ctd_tilt_layer* layers_dev, const ctd_glyph_place* places_dev,
+                       const ctd_glyph_record* glyphs_dev, const ctd_typeset_tile* tiles_dev, const int32_t* entries_dev,
+                       const uint8_t* atlas_dev, const ctd_glyph_params* params, ctd_typeset_row* rows_dev, void* stream);
 
 /* ---- the detector tail ------------------------------------------------------ */
 
