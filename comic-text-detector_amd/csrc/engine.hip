@@ -1549,9 +1549,12 @@ int ctd_typeset(const ctd_typeset_page* pages_dev, const ctd_typeset_layer* laye
   return CTD_OK;
 }
 
-int ctd_typeset_glyphs(const ctd_typeset_page* pages_dev, const ctd_glyph_layer* layers_dev, const ctd_glyph_place* places_dev,
-                       const ctd_glyph_record* glyphs_dev, const ctd_typeset_tile* tiles_dev, const int32_t* entries_dev,
-                       const uint8_t* atlas_dev, const ctd_glyph_params* params, ctd_typeset_row* rows_dev, void* stream) {
+// ctd_typeset_glyphs' checks, ctd_typeset_tilted's too (`layers_dev` is either's layer table): CTD_OK with `launch` set where
+// there is something to launch, the rows then zeroed on the stream, or the error rc.
+static int glyph_checks(const void* pages_dev, const void* layers_dev, const void* places_dev, const void* glyphs_dev,
+                        const void* tiles_dev, const void* entries_dev, const void* atlas_dev, const ctd_glyph_params* params,
+                        ctd_typeset_row* rows_dev, void* stream, bool& launch) {
+  launch = false;
   if (!params) return fail(CTD_ERR_INVALID, "null pointer");
   const ctd_glyph_params prm = *params;
   if (prm.n_layers < 0 || prm.n_pages < 0 || prm.n_tiles < 0 || prm.n_entries < 0 || prm.n_places < 0 || prm.n_glyphs < 0 ||
@@ -1563,7 +1566,18 @@ int ctd_typeset_glyphs(const ctd_typeset_page* pages_dev, const ctd_glyph_layer*
     return fail(CTD_ERR_INVALID, "null pointer");
   if (prm.n_tiles == 0 || prm.n_layers == 0) return CTD_OK;
   HIP_TRY(hipMemsetAsync(rows_dev, 0, (size_t)prm.n_layers * sizeof(ctd_typeset_row), (hipStream_t)stream));
-  HIP_TRY(launch_typeset_glyphs(pages_dev, layers_dev, places_dev, glyphs_dev, tiles_dev, entries_dev, atlas_dev, prm, rows_dev,
+  launch = true;
+  return CTD_OK;
+}
+
+int ctd_typeset_glyphs(const ctd_typeset_page* pages_dev, const ctd_glyph_layer* layers_dev, const ctd_glyph_place* places_dev,
+                       const ctd_glyph_record* glyphs_dev, const ctd_typeset_tile* tiles_dev, const int32_t* entries_dev,
+                       const uint8_t* atlas_dev, const ctd_glyph_params* params, ctd_typeset_row* rows_dev, void* stream) {
+  bool launch;
+  const int rc = glyph_checks(pages_dev, layers_dev, places_dev, glyphs_dev, tiles_dev, entries_dev, atlas_dev, params, rows_dev, stream,
+                              launch);
+  if (!launch) return rc;
+  HIP_TRY(launch_typeset_glyphs(pages_dev, layers_dev, places_dev, glyphs_dev, tiles_dev, entries_dev, atlas_dev, *params, rows_dev,
                                 (hipStream_t)stream));
   return CTD_OK;
 }
@@ -1584,18 +1598,11 @@ int ctd_balloon_tilt(const ctd_tilt_job* jobs_dev, int32_t n, const ctd_balloon_
 int ctd_typeset_tilted(const ctd_typeset_page* pages_dev, const ctd_tilt_layer* layers_dev, const ctd_glyph_place* places_dev,
                        const ctd_glyph_record* glyphs_dev, const ctd_typeset_tile* tiles_dev, const int32_t* entries_dev,
                        const uint8_t* atlas_dev, const ctd_glyph_params* params, ctd_typeset_row* rows_dev, void* stream) {
-  if (!params) return fail(CTD_ERR_INVALID, "null pointer");
-  const ctd_glyph_params prm = *params;
-  if (prm.n_layers < 0 || prm.n_pages < 0 || prm.n_tiles < 0 || prm.n_entries < 0 || prm.n_places < 0 || prm.n_glyphs < 0 ||
-      prm.atlas_bytes < 0)
-    return fail(CTD_ERR_INVALID, "bad sizes");
-  if ((prm.n_pages > 0 && !pages_dev) || (prm.n_layers > 0 && (!layers_dev || !rows_dev)) || (prm.n_places > 0 && !places_dev) ||
-      (prm.n_glyphs > 0 && !glyphs_dev) || (prm.n_tiles > 0 && !tiles_dev) || (prm.n_entries > 0 && !entries_dev) ||
-      (prm.atlas_bytes > 0 && !atlas_dev))
-    return fail(CTD_ERR_INVALID, "null pointer");
-  if (prm.n_tiles == 0 || prm.n_layers == 0) return CTD_OK;
-  HIP_TRY(hipMemsetAsync(rows_dev, 0, (size_t)prm.n_layers * sizeof(ctd_typeset_row), (hipStream_t)stream));
-  HIP_TRY(launch_typeset_tilted(pages_dev, layers_dev, places_dev, glyphs_dev, tiles_dev, entries_dev, atlas_dev, prm, rows_dev,
+  bool launch;
+  const int rc = glyph_checks(pages_dev, layers_dev, places_dev, glyphs_dev, tiles_dev, entries_dev, atlas_dev, params, rows_dev, stream,
+                              launch);
+  if (!launch) return rc;
+  HIP_TRY(launch_typeset_tilted(pages_dev, layers_dev, places_dev, glyphs_dev, tiles_dev, entries_dev, atlas_dev, *params, rows_dev,
                                 (hipStream_t)stream));
   return CTD_OK;
 }

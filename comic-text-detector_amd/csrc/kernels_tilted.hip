@@ -1,36 +1,26 @@
 // Typeset from a glyph atlas in a block's own frame (`ctd_typeset_tilted`; the rule is stated in include/ctd_hip.h, "tilted
-// text", and restated in numpy in tests/tilt_ref.py): glyphs_kernel's twin.  A layer carries a pivot and a 16.16 (c, s) pair;
-// its placements are in FRAME coordinates, U is their upright max-paste over frame pixels, and the layer's coverage at page
-// pixel p is U resampled bilinearly (8 fraction bits) at page -> frame (p).  From there on it is the typeset rule in page
-// space: outline S = disk max of F, r <= 12, pixel = blend(blend(P, s, S), f, F).  Integers only, products in 64 bits.  The
-// tile, the outline and the blend are typeset_tile.h's as they stand; staging, the frame patch and the resampling are this
-// file's.
+// text", and restated in numpy in tests/tilt_ref.py).  A layer carries a pivot and a 16.16 (c, s) pair; its placements are in
+// FRAME coordinates, U is their upright max-paste over frame pixels, and the layer's coverage at page pixel p is U resampled
+// bilinearly (8 fraction bits) at page -> frame (p).  From there on it is the typeset rule in page space: outline S = disk max
+// of F, r <= 12, pixel = blend(blend(P, s, S), f, F).  Integers only, products in 64 bits.  The tile, the outline and the
+// blend are typeset_tile.h's; the walk over the tile's entries in groups of equal layer and chunks of NC, the staging and the
+// gather are glyph_walk.h's, shared with kernels_glyphs.hip.
 //
-// tilted_kernel, ONE launch, one workgroup of 256 threads per row of the tile table.  The tile's entries are walked in groups
-// of equal layer and chunks of NC entries exactly as glyphs_kernel walks them (no cap on the placements of a tile or of a
-// layer).  Per group:
+// tilted_kernel, ONE launch, one workgroup of 256 threads per row of the tile table: load the tile into registers, walk the
+// groups, store the tile once.  This file's own, per group:
 //   frame box  page -> frame is affine with integer coefficients, so the frame coordinates of the tile's coverage patch (the
 //           rows the clip can see, all CW columns) take their extremes at its four corners: UX0 .. and UY0 .., ubw x ubh
 //           pixels including the +1 neighbours of the bilinear taps.  (CW - 1) |c| + (CH - 1) |s| <= the patch's diagonal
-//           times sqrt(c^2 + s^2) <= 102.93 * 65537, so ubw, ubh <= 105 < UW; the kernel checks c^2 + s^2 and both sizes
-//           and a layer beyond them draws nothing.
-//   stage   as glyphs_kernel: one entry a thread, every index checked before use, a compact record to LDS.
-//   gather  a thread owns bytes of the frame box (byte i = t + 256 k) and takes the max over the staged glyphs that cover it,
-//           reading the atlas: one writer a byte whatever overlaps; the first chunk starts from 0, a later chunk from the
-//           byte's value.  GB bytes at a time, as glyphs_kernel: which glyph covers each first, then the loads together.
+//           times sqrt(c^2 + s^2) <= 102.93 * 65537, so ubw, ubh <= 105 < UW; the kernel checks the pivot, c^2 + s^2 and both
+//           sizes and a layer beyond them draws nothing.  The gather's bytes are the frame box `ubuf`, byte i at row i / ubw,
+//           every staged glyph scanned, GB bytes a thread at a time; the box's origin is in 64 bits.
 //   resample   every byte of the patch rows from four taps of the frame box; the bounding box of F > 0 by wave shuffles and LDS
-//           atomics gives the active rectangle (grown by r, cut to clip and tile).
-//   rows, blend, counts   rows_pass / blend_count of typeset_tile.h.
-//   store   the tile, once.
+//           atomics gives the active rectangle (grown by r, cut to clip and tile) of the rows pass, the blend and the counts.
 // LDS: 4928 (patch) + TS_PLANES * 3584 (planes / staged records) + 11236 (frame box) + small tables.
-#include <climits>
-
-#include "typeset_tile.h"
+#include "glyph_walk.h"
 
 namespace {
 
-constexpr int NC = TS_THREADS;                             // staged records a chunk: one a thread
-constexpr int MAX_COORD = 1 << 29;
 constexpr long long MAX_CS = 65537;                        // c^2 + s^2 <= MAX_CS^2: what rint of a unit vector times 65536 gives
 constexpr int UW = 106, UH = 106;                          // the frame box of a patch
 constexpr int GB = 8;                                      // frame-box bytes a thread resolves at a time
@@ -44,11 +34,23 @@ static_assert(sizeof(ctd_tilt_layer) == 48 && offsetof(ctd_tilt_layer, clip) == 
               offsetof(ctd_tilt_layer, radius) == 26 && offsetof(ctd_tilt_layer, ax) == 28 && offsetof(ctd_tilt_layer, c) == 36,
               "tilted typeset ABI (glyphs.py dtypes)");
 
-struct Staged {                                            // a checked placement; w == 0: contributes nothing
-  long long off;
-  int x, y, w, h;
+struct FrameBox {                                          // gather's box: ubw x ubh frame pixels, origin (UX0, UY0) = ox, oy
+  struct Addr { int x, y; };
+  unsigned char (*ubuf)[UW];
+  int ubw, n_bytes;
+  long long ox, oy;
+  __device__ Addr locate(int i) const { return {i - i / ubw * ubw, i / ubw}; }
+  __device__ int x(Addr a) const { return a.x; }
+  __device__ int y(Addr a) const { return a.y; }
+  __device__ int state(Addr) const { return -1; }
+  __device__ bool scan() const { return true; }
+  // the glyph's corner in the frame box; further out than any box or glyph reaches, it is far enough
+  __device__ void corner(const Staged& g, int& gx0, int& gy0) const {
+    gx0 = (int)max(min((long long)g.x - ox, (long long)FAR), -(long long)FAR);
+    gy0 = (int)max(min((long long)g.y - oy, (long long)FAR), -(long long)FAR);
+  }
+  __device__ unsigned char& byte(Addr a) const { return ubuf[a.y][a.x]; }
 };
-static_assert(sizeof(Staged) == 24 && NC * sizeof(Staged) <= (size_t)TS_PLANES * CH * TW, "the staged records fit the planes");
 
 __global__ __launch_bounds__(TS_THREADS) void tilted_kernel(const ctd_typeset_page* __restrict__ pages,
                                                             const ctd_tilt_layer* __restrict__ layers,
@@ -82,61 +84,28 @@ __global__ __launch_bounds__(TS_THREADS) void tilted_kernel(const ctd_typeset_pa
   // ---- groups
   int e = e_begin;
   while (e < e_end) {
-    int li = -1, r = 0, cx1 = 0, cy1 = 0, cx2 = 0, cy2 = 0;             // the group's layer and what it may write of this tile
-    int pr1 = 0, n_rows = 0, px0 = 0, py0 = 0, ubw = 0, ubh = 0, pvx = 0, pvy = 0;
+    Group G;
+    int n_rows = 0, ubw = 0, ubh = 0, pvx = 0, pvy = 0;
     long long c = 0, s = 0, UX0 = 0, UY0 = 0;
     bool first_chunk = true, more = true;
     while (more) {
       const int n = min(e_end - e, NC);
       __syncthreads();                                     // the group before is done with cov, planes, ubuf, slots and s_*
 
-      // ---- stage: entry e + t, checked against its OWN layer, so that no load waits for the group's layer to be known
-      int lay = -1;
-      Staged sg = {0, 0, 0, 0, 0};
-      if (t < n) {
-        const int pi = entries[e + t];
-        if (pi >= 0 && pi < prm.n_places) {
-          const ctd_glyph_place pl = places[pi];
-          if (pl.layer >= 0 && pl.layer < prm.n_layers) {
-            lay = pl.layer;
-            const ctd_tilt_layer* __restrict__ Lt = layers + lay;
-            if (t == 0 && first_chunk) s_layer = *Lt;
-            if (pl.glyph >= 0 && pl.glyph < prm.n_glyphs && pl.x >= -MAX_COORD && pl.x <= MAX_COORD && pl.y >= -MAX_COORD &&
-                pl.y <= MAX_COORD && Lt->page == T.page && Lt->radius <= RMAX) {
-              const ctd_glyph_record g = glyphs[pl.glyph];
-              if (g.w >= 1 && g.h >= 1 && g.w <= CTD_TYPESET_MAX_SIDE && g.h <= CTD_TYPESET_MAX_SIDE && g.off >= 0 &&
-                  g.off <= prm.atlas_bytes && (long long)g.w * g.h <= prm.atlas_bytes - g.off)
-                sg.off = g.off, sg.x = pl.x, sg.y = pl.y, sg.w = g.w, sg.h = g.h;
-            }
-          }
-        }
-        staged[t] = sg;
-      }
-      if (t == 0) {
-        if (first_chunk) s_li = lay;                       // s_layer: in the stage above, where lay names a layer
-        s_len = n;
-        s_box[0] = s_box[1] = INT_MAX, s_box[2] = s_box[3] = INT_MIN;
-      }
+      Staged sg;
+      const int lay = stage_entry(layers, places, glyphs, entries, prm, T.page, e, n, t, first_chunk, staged, &s_layer, &s_li, &s_len, sg);
+      if (t == 0) s_box[0] = s_box[1] = INT_MAX, s_box[2] = s_box[3] = INT_MIN;
       __syncthreads();
       if (first_chunk) {
-        // the group's layer, from its first entry; an entry that names nothing, or a layer that cannot write here, is passed
-        // over (block-uniform)
-        li = s_li;
-        if (li < 0) break;
-        const ctd_tilt_layer Ly = s_layer;
-        r = Ly.radius, c = Ly.c, s = Ly.s, pvx = Ly.ax, pvy = Ly.ay;
-        cx1 = max(Ly.clip[0], tx0), cy1 = max(Ly.clip[1], ty0);
-        cx2 = min(Ly.clip[2], min(tx0 + TW, P.W)), cy2 = min(Ly.clip[3], min(ty0 + TH, P.H));
-        if (Ly.page != T.page || r > RMAX || cx1 >= cx2 || cy1 >= cy2) break;
+        if (!group_layer(s_li, s_layer, T.page, P, tx0, ty0, t, slot, slot_dy, G)) break;
+        c = s_layer.c, s = s_layer.s, pvx = s_layer.ax, pvy = s_layer.ay;
         if (pvx < -MAX_COORD || pvx > MAX_COORD || pvy < -MAX_COORD || pvy > MAX_COORD || c < -MAX_CS || c > MAX_CS || s < -MAX_CS ||
             s > MAX_CS || c * c + s * s > MAX_CS * MAX_CS)
           break;
-        pr1 = cy1 - ty0;                                   // the patch rows a pixel of that rectangle can see: pr1 ..
-        n_rows = cy2 - cy1 + 2 * r;
-        px0 = tx0 - r, py0 = ty0 - r;                      // patch (0, 0) in page coordinates
+        n_rows = G.cy2 - G.cy1 + 2 * G.r;
         // the frame box: u and v at the four corners of those patch rows
-        const long long dxa = (long long)px0 - pvx, dxb = dxa + CW - 1;
-        const long long dya = (long long)py0 + pr1 - pvy, dyb = dya + n_rows - 1;
+        const long long dxa = (long long)G.px0 - pvx, dxb = dxa + CW - 1;
+        const long long dya = (long long)G.py0 + G.pr1 - pvy, dyb = dya + n_rows - 1;
         const long long u0 = c * dxa + s * dya, u1 = c * dxb + s * dya, u2 = c * dxa + s * dyb, u3 = c * dxb + s * dyb;
         const long long v0 = c * dya - s * dxa, v1 = c * dya - s * dxb, v2 = c * dyb - s * dxa, v3 = c * dyb - s * dxb;
         const long long ua = ((long long)pvx << 16) + min(min(u0, u1), min(u2, u3)), ub = ((long long)pvx << 16) + max(max(u0, u1), max(u2, u3));
@@ -145,68 +114,20 @@ __global__ __launch_bounds__(TS_THREADS) void tilted_kernel(const ctd_typeset_pa
         const long long bw = (ub >> 16) - UX0 + 2, bh = (vb >> 16) - UY0 + 2;
         if (bw > UW || bh > UH) break;                     // cannot happen within the bound on c^2 + s^2
         ubw = (int)bw, ubh = (int)bh;
-        if (t == 0 && r > 0) slot_table(r, slot, slot_dy); // read behind the barriers below
       }
-      // the group's length within the chunk: up to the first entry of another layer
-      const unsigned long long others = __ballot(t < n && lay != li);
-      if (lane == 0 && others) atomicMin(&s_len, (t & ~63) + __ffsll((long long)others) - 1);
+      run_length(t < n && lay != G.li, t, &s_len);
       __syncthreads();
       const int len = s_len;                               // >= 1 in the first chunk: entry e is of layer li
 
-      // ---- gather: this thread's bytes of the frame box, GB at a time, the max over the staged glyphs that cover them.  First
-      // which glyph covers each (a scan of the staged records: registers and LDS only), then the GB atlas loads together, one
-      // latency for all of them; bytes that two glyphs cover take the others one by one
-      for (int base = 0; base < ubw * ubh; base += GB * TS_THREADS) {
-        int where[GB], ux[GB], uy[GB];                     // where[k]: the first glyph that covers byte k, -1: none, -2: not a byte
-        unsigned several = 0;
-#pragma unroll
-        for (int k = 0; k < GB; ++k) {
-          const int i = base + k * TS_THREADS + t;
-          uy[k] = i / ubw, ux[k] = i - uy[k] * ubw;
-          where[k] = i < ubw * ubh ? -1 : -2;
-        }
-        for (int j = 0; j < len; ++j) {
-          const Staged g = staged[j];
-          if (g.w == 0) continue;
-          // the glyph's corner in the frame box; further out than any box or glyph reaches, it is far enough
-          const int gx0 = (int)max(min((long long)g.x - UX0, (long long)FAR), -(long long)FAR);
-          const int gy0 = (int)max(min((long long)g.y - UY0, (long long)FAR), -(long long)FAR);
-#pragma unroll
-          for (int k = 0; k < GB; ++k) {
-            const bool in = where[k] != -2 && (unsigned)(ux[k] - gx0) < (unsigned)g.w && (unsigned)(uy[k] - gy0) < (unsigned)g.h;
-            if (in && where[k] >= 0) several |= 1u << k;
-            if (in && where[k] == -1) where[k] = j;
-          }
-        }
-        int val[GB];
-#pragma unroll
-        for (int k = 0; k < GB; ++k) {
-          val[k] = 0;
-          if (where[k] >= 0) {
-            const Staged g = staged[where[k]];
-            val[k] = atlas[g.off + (UY0 + uy[k] - g.y) * g.w + (UX0 + ux[k] - g.x)];
-          }
-        }
-#pragma unroll
-        for (int k = 0; k < GB; ++k) {
-          if (where[k] == -2) continue;
-          int v = val[k];
-          if ((several >> k) & 1) {
-            for (int j = where[k] + 1; j < len; ++j) {
-              const Staged g = staged[j];
-              const long long bx = UX0 + ux[k] - g.x, by = UY0 + uy[k] - g.y;
-              if (bx >= 0 && bx < g.w && by >= 0 && by < g.h) v = max(v, (int)atlas[g.off + by * g.w + bx]);
-            }
-          }
-          ubuf[uy[k]][ux[k]] = (unsigned char)(first_chunk ? v : max(v, (int)ubuf[uy[k]][ux[k]]));
-        }
-      }
+      // ---- gather: this thread's bytes of the frame box, the max over the staged glyphs that cover them
+      gather<GB>(FrameBox{ubuf, ubw, ubw * ubh, UX0, UY0}, staged, len, atlas, first_chunk, t);
       e += len;
       more = len == n && n == NC && e < e_end;             // the chunk was all of this layer: it may go on
       first_chunk = false;
     }
     if (first_chunk) { ++e; continue; }                    // left by a break: nothing of entry e can be drawn here
 
+    const int r = G.r, pr1 = G.pr1, px0 = G.px0, py0 = G.py0;
     __syncthreads();                                       // the frame box is whole; the staged records are done with
 
     // ---- resample: F on the patch rows, and where it is above 0
@@ -235,8 +156,8 @@ __global__ __launch_bounds__(TS_THREADS) void tilted_kernel(const ctd_typeset_pa
       atomicMin(&s_box[0], bx1), atomicMin(&s_box[1], by1), atomicMax(&s_box[2], bx2), atomicMax(&s_box[3], by2);
     __syncthreads();                                       // cov is whole
     if (s_box[0] > s_box[2]) continue;                     // F is 0 all over the patch (block-uniform)
-    const int ax1 = max(s_box[0] - r, cx1), ay1 = max(s_box[1] - r, cy1);
-    const int ax2 = min(s_box[2] + 1 + r, cx2), ay2 = min(s_box[3] + 1 + r, cy2);
+    const int ax1 = max(s_box[0] - r, G.cx1), ay1 = max(s_box[1] - r, G.cy1);
+    const int ax2 = min(s_box[2] + 1 + r, G.cx2), ay2 = min(s_box[3] + 1 + r, G.cy2);
     if (ax1 >= ax2 || ay1 >= ay2) continue;                // nothing of the group can write here
 
     const int rr1 = ay1 - ty0, rr2 = ay2 - ty0 + 2 * r;    // the patch rows an active pixel can see (within pr1 ..)
@@ -245,7 +166,7 @@ __global__ __launch_bounds__(TS_THREADS) void tilted_kernel(const ctd_typeset_pa
       __syncthreads();                                     // the planes are whole
     }
     const ctd_tilt_layer Ly = s_layer;                     // s_layer is next written behind the next group's first barrier
-    blend_count(r, ax1, ay1, ax2, ay2, Ly.fill, Ly.stroke, cov, plane, slot_dy, tx0, ty0, t, pix, rows, li);
+    blend_count(r, ax1, ay1, ax2, ay2, Ly.fill, Ly.stroke, cov, plane, slot_dy, tx0, ty0, t, pix, rows, G.li);
   }
 
   store_tile(P, tx0, ty0, t, pix);

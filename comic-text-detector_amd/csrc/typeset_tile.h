@@ -1,7 +1,9 @@
-// The tile compositor that typeset_kernel (kernels_typeset.hip) and glyphs_kernel (kernels_glyphs.hip) share: a workgroup of
-// TS_THREADS threads owns a TW x TH tile of one page, holds it in registers (PX packed pixels a thread: column t % TW, rows
-// t / TW + LYS j) and applies coverage patches to it one after another.  The kernels differ in how a layer's coverage F gets
-// into the LDS patch `cov` (patch (0, 0) is tile (-r, -r)); from there on the rule is here, once: the outline S is the
+// The tile compositor that typeset_kernel (kernels_typeset.hip), glyphs_kernel (kernels_glyphs.hip) and tilted_kernel
+// (kernels_tilted.hip) share: a workgroup of TS_THREADS threads owns a TW x TH tile of one page, holds it in registers (PX
+// packed pixels a thread: column t % TW, rows t / TW + LYS j) and applies coverage patches to it one after another.  The
+// kernels differ in how a layer's coverage F gets into the LDS patch `cov` (patch (0, 0) is tile (-r, -r)) -- a bitmap's bytes,
+// glyphs gathered from an atlas, glyphs gathered in a layer's frame and resampled; what the two glyph kernels share of that is
+// glyph_walk.h's -- and from there on the rule is here, once: the outline S is the
 // grey-scale dilation of F by a disk of radius r <= RMAX, taken as running horizontal maxima kept for the disk's distinct
 // half-widths (at most TS_PLANES planes: 9 at r = 12) and 2 r + 1 reads down a column, and a pixel becomes
 // blend(blend(P, stroke, S), fill, F).  Integers only.  Device code only.

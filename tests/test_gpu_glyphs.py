@@ -247,21 +247,24 @@ def test_an_atlas_grown_across_two_adds_keeps_bytes_and_ids():
 
 # ---- 4. refusals ------------------------------------------------------------------------------------------------------------
 
-def _raw(p, pages, layers, places, bitmaps, atlas_bytes=None):
+def _raw(p, pages, layers, places, bitmaps, atlas_bytes=None, tilted=False):
     """One `ctd_typeset_glyphs` call through ctypes on dense device pages (in place).  The tile table lists EVERY tile of
     every page and, in each, EVERY placement in ascending order: the kernel has to refuse whatever does not belong there.
-    The atlas allocation is the packed glyphs plus 64 spare bytes; `atlas_bytes` is what the call is told.  The rows."""
+    The atlas allocation is the packed glyphs plus 64 spare bytes; `atlas_bytes` is what the call is told.  The rows.
+    tilted: the same tables to `ctd_typeset_tilted`, every layer a `ctd_tilt_layer` with (c, s) = (65536, 0) about (9, 9)."""
     L, T, G = p._lib, p.typeset, p.glyphs
     dev = pages[0].device
     shapes = [tuple(pg.shape[:2]) for pg in pages]
     nl, n = len(layers), len(places)
-    pt, lt, qt = np.zeros((len(pages),), T.PAGE_DTYPE), np.zeros((nl,), G.LAYER_DTYPE), np.zeros((n,), G.PLACE_DTYPE)
+    pt, lt, qt = np.zeros((len(pages),), T.PAGE_DTYPE), np.zeros((nl,), T.TILT_LAYER_DTYPE if tilted else G.LAYER_DTYPE), np.zeros((n,), G.PLACE_DTYPE)
     pt["page_dev"], pt["H"], pt["W"] = [pg.data_ptr() for pg in pages], [s[0] for s in shapes], [s[1] for s in shapes]
     pt["pitch"] = [pg.stride(0) for pg in pages]
     for i, ly in enumerate(layers):
         H, W = shapes[ly["page"]]
         lt[i]["page"], lt[i]["clip"], lt[i]["radius"] = ly["page"], ly.get("clip") or (0, 0, W, H), ly["r"]
         lt[i]["fill"], lt[i]["stroke"] = ly["fill"], ly["stroke"]
+    if tilted:
+        lt["ax"], lt["ay"], lt["c"], lt["s"] = 9, 9, 65536, 0
     qt["layer"], qt["glyph"], qt["x"], qt["y"] = [q[0] for q in places], [q[1] for q in places], [q[2] for q in places], [q[3] for q in places]
     rec = np.zeros((len(bitmaps),), G.RECORD_DTYPE)
     area = np.array([b.size for b in bitmaps], np.int64)
@@ -277,7 +280,8 @@ def _raw(p, pages, layers, places, bitmaps, atlas_bytes=None):
     total = int(area.sum())
     prm = L.CtdGlyphParams(nl, len(pages), len(tiles), len(entries), n, len(bitmaps), total if atlas_bytes is None else atlas_bytes)
     st = torch.cuda.current_stream(dev)
-    L.check(L.lib().ctd_typeset_glyphs(*[u.data_ptr() for u in up], C.byref(prm), rows.data_ptr(), st.cuda_stream), "ctd_typeset_glyphs")
+    what = "ctd_typeset_tilted" if tilted else "ctd_typeset_glyphs"
+    L.check(getattr(L.lib(), what)(*[u.data_ptr() for u in up], C.byref(prm), rows.data_ptr(), st.cuda_stream), what)
     st.synchronize()
     host = rows.cpu().numpy()
     assert (host[nl * 8:] == GUARD).all(), "a byte behind the row table was written"

@@ -1,4 +1,5 @@
-"""-m gpu: the group and chunk walk of `glyphs_kernel` (csrc/kernels_glyphs.hip) at its boundaries, and seeded random scenes
+"""-m gpu: the group and chunk walk (csrc/glyph_walk.h) at its boundaries, through both kernels that use it -- `glyphs_kernel`
+(csrc/kernels_glyphs.hip) and, at (c, s) = (65536, 0), `tilted_kernel` (csrc/kernels_tilted.hip) -- and seeded random scenes
 through both typeset kernels.  The material is tests/typeset_cases.py (what each case is there for is asserted without a GPU in
 tests/test_typeset_cases.py): run ends at, below and above every wave and chunk boundary, a run that ends the entries at a
 chunk's end, a max across two chunks, a chunk that contributes nothing (raw tables), a multi-chunk group over both seams with a
@@ -36,21 +37,49 @@ def test_walk_case_equals_both_oracles_in_every_byte(name):
     assert want_rows[:, 0].min() > 0
 
 
+@pytest.mark.parametrize("name", [name for name, _, _ in TC.API_CASES])
+def test_walk_case_through_the_tilted_kernel_equals_the_restatement_in_every_byte(name):
+    """The same case as one `typeset_glyphs` call that `tilted_kernel` serves at (c, s) = (65536, 0) (`TC.tilted`), where the
+    rule gives `ctd_typeset_glyphs`' bytes: every page byte, both row fields of the case's own layers and the status against the
+    same restatement.  That its tiles still hold the entry counts the case is there for: tests/test_typeset_cases.py."""
+    p = pkg()
+    pages, bitmaps, _, places = TC.case(name)
+    want, want_rows, _ = TC.reference(name)
+    layers, angle, pivot = TC.tilted(name)
+    tp = p.glyphs.typeset_glyphs(pages, GT._atlas(p, bitmaps), angle=angle, pivot=pivot, **GT._args(pages, layers, places))
+    got = tp.to_host()
+    assert not GT._same(got, want), f"pages {GT._same(got, want)} differ from the restatement"
+    rows = np.stack([tp.n_fill, tp.n_stroke], axis=1)
+    assert np.array_equal(rows[:-1], want_rows) and not rows[-1].any() and want_rows[:, 0].min() > 0
+    assert tp.status.tolist() == TC.statuses(name) + [p._lib.TYPESET_EMPTY] == [TR.OK] * (len(layers) - 1) + [TR.EMPTY]
+
+
 # ---- the raw path: a chunk that contributes nothing ----------------------------------------------------------------------------------
+
+def _idle_chunk(name, tilted):
+    p = pkg()
+    host, bitmaps, layers, places = TC.case(name)
+    want, want_rows, _ = TC.reference(name)
+    pages = [torch.from_numpy(pg).cuda() for pg in host]
+    rows = GT._raw(p, pages, layers, places, bitmaps, tilted=tilted)
+    got = [pg.cpu().numpy() for pg in pages]
+    assert not GT._same(got, want), f"pages {GT._same(got, want)} differ from the restatement"
+    assert np.array_equal(rows, want_rows) and rows[0, 1] > rows[0, 0] > 1000
+
 
 @pytest.mark.parametrize("name", [name for name, _, _ in TC.RAW_CASES])
 def test_a_chunk_that_contributes_nothing_to_its_tile(name):
     """`ctd_typeset_glyphs` through ctypes with EVERY placement listed in EVERY tile: in each tile one of the layer's two
     chunks stages nothing that contributes.  Pages and rows against the restatement; the guard bytes behind the rows are
     checked by `_raw`."""
-    p = pkg()
-    host, bitmaps, layers, places = TC.case(name)
-    want, want_rows, _ = TC.reference(name)
-    pages = [torch.from_numpy(pg).cuda() for pg in host]
-    rows = GT._raw(p, pages, layers, places, bitmaps)
-    got = [pg.cpu().numpy() for pg in pages]
-    assert not GT._same(got, want), f"pages {GT._same(got, want)} differ from the restatement"
-    assert np.array_equal(rows, want_rows) and rows[0, 1] > rows[0, 0] > 1000
+    _idle_chunk(name, tilted=False)
+
+
+@pytest.mark.parametrize("name", [name for name, _, _ in TC.RAW_CASES])
+def test_a_chunk_that_contributes_nothing_to_its_tile_through_the_tilted_kernel(name):
+    """The same through `ctd_typeset_tilted`: the same every-placement-in-every-tile tables, a `ctd_tilt_layer` table at
+    (c, s) = (65536, 0), the same guard bytes behind the rows, the same restatement."""
+    _idle_chunk(name, tilted=True)
 
 
 # ---- every radius back to back, through the bitmap kernel too ----------------------------------------------------------------------

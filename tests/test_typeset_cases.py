@@ -1,7 +1,8 @@
 """The material of tests/test_gpu_typeset_walk.py (tests/typeset_cases.py) holds what its docstrings promise, without a GPU: a
 case that has silently become vacuous fails HERE and does not pass on the GPU.  Run lengths are read from
-`glyphs.glyph_tables`, the pixel claims from the restatement tests/glyph_ref.py; and on every case and every seed the
-host tables of both calls equal the brute-force loops of the restatements."""
+`glyphs.glyph_tables` -- and, for the same cases sent through `tilted_kernel`, from `typeset.tilt_tables` -- the pixel claims
+from the restatement tests/glyph_ref.py; and on every case and every seed the host tables of both calls equal the brute-force
+loops of the restatements."""
 import numpy as np
 import pytest
 
@@ -27,6 +28,22 @@ def _tile_runs(name):
     pages, bitmaps, layers, places = TC.case(name)
     shapes, col = _columns(pages, bitmaps, layers, places)
     tiles, entries, _ = pkg().glyphs.glyph_tables(shapes, **col)
+    first = tiles["first"]
+    return {(int(t["page"]), int(t["tx"]), int(t["ty"])): [places[i][0] for i in entries[first[k]:first[k + 1]]]
+            for k, t in enumerate(tiles[:-1])}
+
+
+def _tilt_runs(name):
+    """`_tile_runs` of the call that sends the case through `tilted_kernel` (`TC.tilted`), from `typeset.tilt_tables`, which
+    bins by a box grown by one pixel and by r + 1: a tile may list more placements than on the upright path."""
+    pages, bitmaps, _, places = TC.case(name)
+    layers, angle, pivot = TC.tilted(name)
+    shapes, col = _columns(pages, bitmaps, layers, places)
+    T = pkg().typeset
+    _, pv, cs = T._tilt_args(angle, pivot, len(layers))
+    assert cs[:-1].tolist() == [[65536, 0]] * (len(layers) - 1) and cs[-1, 1] != 0
+    tiles, entries, status = T.tilt_tables(shapes, col["page_of"], col["layer_of"], col["sizes"], col["xy"], col["radius"], col["clip"], pv, cs)
+    assert status.tolist() == TC.statuses(name) + [pkg()._lib.TYPESET_EMPTY]
     first = tiles["first"]
     return {(int(t["page"]), int(t["tx"]), int(t["ty"])): [places[i][0] for i in entries[first[k]:first[k + 1]]]
             for k, t in enumerate(tiles[:-1])}
@@ -162,6 +179,27 @@ def test_radius_ladder_has_all_13_radii_on_the_same_pixels():
     assert common.sum() >= 4                                 # every glyph of every layer covers these pixels
     _, rows, _ = TC.reference("radius_ladder")
     assert (rows[:, 0] > 0).all() and all((rows[li, 1] > rows[li, 0]) == (r > 0) for li, r in enumerate(TC.LADDER))
+
+
+@pytest.mark.parametrize("name", [name for name, _, _ in TC.API_CASES])
+def test_the_tilted_binning_keeps_what_the_case_is_there_for(name):
+    """Through `tilted_kernel` the entries of a tile come from `tilt_tables`: the entry counts the case exists for still occur."""
+    pages, bitmaps, layers, places = TC.case(name)
+    up, tl = _tile_runs(name), _tilt_runs(name)
+    assert sorted(tl) == sorted(up) and all(len(tl[k]) >= len(up[k]) and tl[k] == sorted(tl[k]) for k in up)
+    fn, args = TC.CASES[name]
+    if fn is TC.run_then_other:
+        assert tl == {(0, 0, 0): [0] * args[0] + [1] * 3}
+    elif fn is TC.run_is_last:
+        assert args[0] % TC.NC == 0 and tl == {(0, 0, 0): [0] * args[0]}
+    elif fn is TC.cross_chunk_max:
+        assert tl == {(0, 0, 0): [0] * 300}                   # placement 280 is entry 280: in the second chunk
+    elif fn is TC.long_run_over_seams:
+        assert len(tl) == 4 and all(len(v) > TC.NC for v in tl.values())
+    elif fn is TC.batch_rows:
+        assert len(tl[(0, 0, 0)]) > 40                        # the bytes gathered come from the clip, which is the layer's
+    else:
+        assert fn is TC.radius_ladder and tl[(0, 0, 0)] == sorted(q[0] for q in places)
 
 
 # ---- the sweep -----------------------------------------------------------------------------------------------------------------

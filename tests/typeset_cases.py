@@ -1,5 +1,7 @@
 """TEST INFRASTRUCTURE of tests/test_gpu_typeset_walk.py and tests/test_typeset_cases.py: glyph scenes AT the boundaries of the
-group and chunk walk of `glyphs_kernel` (csrc/kernels_glyphs.hip), and seeded random scenes for both typeset kernels.
+group and chunk walk (csrc/glyph_walk.h) that `glyphs_kernel` (csrc/kernels_glyphs.hip) and `tilted_kernel`
+(csrc/kernels_tilted.hip) share, and seeded random scenes for both typeset kernels.  The sizes below are `glyphs_kernel`'s;
+`tilted` sends a case through the other kernel.
 
 The kernel walks a tile's entries in chunks of `NC` = 256 staged records, finds the end of a layer's run inside a chunk with
 one ballot a wave of 64 and an LDS atomicMin, carries a run over several chunks, maxes later chunks into the patch, resolves
@@ -19,7 +21,7 @@ import glyph_ref as GR
 import typeset_ref as TR
 
 TW, TH, RMAX = 64, 32, 12                                   # the tile and the largest radius (include/ctd_hip.h)
-NC, WAVE, CW, BATCH = 256, 64, TW + 2 * RMAX, 11 * 256      # kernels_glyphs.hip: NC, the wave, typeset_tile.h: CW, PB * TS_THREADS
+NC, WAVE, CW, BATCH = 256, 64, TW + 2 * RMAX, 11 * 256      # glyph_walk.h: NC, the wave, typeset_tile.h: CW, kernels_glyphs.hip: PB * TS_THREADS
 
 RUN_N = (63, 64, 65, 127, 128, 129, 191, 192, 193, 255, 256, 257, 511, 512, 513)
 RUN_R = (0, 12)
@@ -205,6 +207,15 @@ def reference(name):
     """`glyph_ref.typeset` on the case `name`, computed once: (pages, rows, composed bitmap layers)."""
     pages, bitmaps, layers, places = case(name)
     return GR.typeset(pages, layers, places, bitmaps)
+
+
+def tilted(name):
+    """The case `name` as a call that `tilted_kernel` (csrc/kernels_tilted.hip) serves: (layers, angle, pivot), its layers at
+    angle 0 -- (c, s) = (65536, 0), where the rule gives `ctd_typeset_glyphs`' bytes -- and one more layer on page 0, turned by
+    5 degrees and without a placement.  That layer is EMPTY and draws nothing, but a call with any non-zero angle goes to
+    `ctd_typeset_tilted` as a whole.  `reference(name)` is the answer for the case's own layers."""
+    layers = case(name)[2]
+    return layers + [GR.glayer(0, 3)], [0] * len(layers) + [5], [(9, 9)] * (len(layers) + 1)
 
 
 def sizes_of(bitmaps, places):
